@@ -10,8 +10,11 @@ forward (y and dy/dx) + backward (dL/dx and dL/dparam, one call), all inputs res
 rank (weak scaling; points are independent so there is no data-path collective) plus ONE RCCL all-reduce of
 dL/dparam per step.  Metric: whole-job Mpoints/s.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed inside the timed region) and,
-at N = 1, `cpu_baseline` (the CPU oracle -- a port, not the reference -- on a bounded sample).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): the headline (`value`, `ms_per_step`,
+per-op `kernel_ms` from the events around every timed step).  `--full` adds, after the timed steps and as separate runs, what
+the headline does not need: `roofline` (dominant kernel, HIP-event timed inside the timed region, the others on extra steps),
+the extra figures and, at N = 1, `cpu_baseline` (the CPU oracle -- a port, not the reference -- on a bounded sample); the
+timed loop is the same in both modes.  `--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy.
 """
 import argparse
 import ctypes
@@ -445,7 +448,7 @@ def lotd_large_batch_rate(log2n=24):
     """the headline workload at 2^24 points (the size BASELINE.json's target is quoted on), in a fresh process"""
     import subprocess
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--log2-points", str(log2n), "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, timeout=900)
     line = [l[len("BENCH_FULL "):] for l in r.stdout.splitlines() if l.startswith("BENCH_FULL {")]    # the full tables, not the digest
     if not line:
         return {"error": (r.stderr or r.stdout)[-300:]}
@@ -821,9 +824,32 @@ def emit(full):
     print(compact_line(full), flush=True)
 
 
+DUMP_ROWS = 1 << 15          # --dump-outputs: rows of the per-point outputs (same rows in each), 16 MiB at the default meta
+DUMP_PARAMS = 1 << 23        # entries of dL/dparam (of 12 131 648), 32 MiB
+DUMP_SEED = 20241016
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: {name: tensor} of the last timed step -> path/<name>.npy, float32.  Per-point outputs (leading axis of
+    equal length) keep one fixed seeded sample of DUMP_ROWS rows, other outputs a fixed seeded sample of DUMP_PARAMS entries
+    (sorted indices; everything when smaller): the same arguments give the same elements on every run and every build."""
+    os.makedirs(path, exist_ok=True)
+    pick = {}
+    for name, t in outputs.items():
+        a = t.reshape(-1) if t.dim() < 2 else t
+        n, k = a.shape[0], (DUMP_PARAMS if t.dim() < 2 else DUMP_ROWS)
+        if (n, k) not in pick:
+            pick[n, k] = None if n <= k else torch.from_numpy(
+                np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))).to(t.device)
+        if pick[n, k] is not None:
+            a = a.index_select(0, pick[n, k])
+        np.save(os.path.join(path, name + ".npy"), a.detach().to(torch.float32).cpu().numpy())
+
+
 def launch_ranks(args, argv):
-    """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU) through torch.distributed.run on this node and
-    become that process (the driver's own `python -m torch.distributed.run ... bench.py --gpus N` sets WORLD_SIZE and never gets here)"""
+    """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU) through torch.distributed.run on this node in a
+    child process and exit with its status (the driver's own `python -m torch.distributed.run ... bench.py --gpus N` sets WORLD_SIZE
+    and never gets here)"""
     import socket
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -834,7 +860,8 @@ def launch_ranks(args, argv):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "4")
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    import subprocess
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def plumbing_check(args, rank, world):
@@ -865,14 +892,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra figures (used when profiling the timed loop)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline (extra steps), the extra figures and the CPU baseline, "
+                         "and print the full tables (BENCH_FULL line, bench_extra.json) before the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (fixed seeded samples) to DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra figures (used when profiling the timed loop)")
     ap.add_argument("--log2-points", type=int, default=N_POINTS_LOG2)
     ap.add_argument("--no-kernel-timers", action="store_true",
                     help="no in-library HIP-event timers inside the timed region (A/B of their cost; roofline from an extra pass)")
     ap.add_argument("--plumbing-check", action="store_true",
                     help="launch path only (gloo, no GPU, no kernels): ranks start, meet, rank 0 prints a line with value null")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit(f"bench.py: --steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started bare (`python bench.py --gpus N`): be the launcher
@@ -939,7 +973,7 @@ def main():
         if record:
             for k, a, b in zip(names, e[:2], e[1:]):
                 ev[k].append((a, b))
-        return y, dx, dp
+        return {"y": y, "dy_dx": j, "dL_dx": dx, "dL_dparam": dp}
 
     # N > 1: bucketed (overlapped) or single all-reduce -- the split costs ~0.1 ms of extra kernel time, the overlap hides
     # most of the 46 MiB reduction; which one wins depends on the fabric, so both are tried on a few untimed steps
@@ -973,35 +1007,41 @@ def main():
         dist.barrier()
     # The dominant kernel (the forward gather kernel) is bracketed by a HIP-event pair on its launch stream INSIDE the timed
     # region (nr3d_prof_enable, include/nr3d_hip.h): `roofline.achieved` comes from these intervals.  Timing every kernel
-    # of the step that way costs ~2 % of the step (12 events), so the other kernels are timed on extra, untimed steps.
+    # of the step that way costs ~2 % of the step (12 events), so the other kernels are timed on extra, untimed steps (--full).
+    # A plain run keeps the same timed loop (and its timer) so that its figures compare with those of --full runs.
     live_timers = not args.no_kernel_timers
     for k in PROF_KERNELS:
         H.prof_read(k)
     H.prof_enable(*([LIVE_TIMER] if live_timers else []))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step(True)
+    last = step(True)           # held only from the last step on: every step allocates its outputs as before, from the cache
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     H.prof_enable()
-    live = H.prof_read(LIVE_TIMER) if live_timers else (0.0, 0)
-    H.prof_enable(*PROF_KERNELS)
-    n_extra = 5
-    for _ in range(n_extra):
-        step(False)
-    torch.cuda.synchronize()
-    H.prof_enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    del last
     kernel_us, kernel_launches = {}, {}
-    for k in PROF_KERNELS:
-        ms, n = H.prof_read(k)
-        if n:
-            kernel_us[k] = ms / n * 1e3
-            kernel_launches[k] = n / n_extra
-    if live[1]:
-        kernel_us[LIVE_TIMER] = live[0] / live[1] * 1e3           # the live figure replaces the extra-pass one
+    if args.full:
+        live = H.prof_read(LIVE_TIMER) if live_timers else (0.0, 0)
+        H.prof_enable(*PROF_KERNELS)
+        n_extra = 5
+        for _ in range(n_extra):
+            step(False)
+        torch.cuda.synchronize()
+        H.prof_enable()
+        for k in PROF_KERNELS:
+            ms, n = H.prof_read(k)
+            if n:
+                kernel_us[k] = ms / n * 1e3
+                kernel_launches[k] = n / n_extra
+        if live[1]:
+            kernel_us[LIVE_TIMER] = live[0] / live[1] * 1e3           # the live figure replaces the extra-pass one
     per_rank_ms = None
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -1014,7 +1054,7 @@ def main():
     # N > 1: the ray half of the metric, rays sharded like the points (every rank marches + composites its own 262 144
     # rays, no collective on the data path); whole-job rate = all rays / slowest rank
     multi_march = multi_loop = None
-    if dist is not None and not args.no_extra and (world > 1 or os.environ.get("NR3D_BENCH_FORCE_DIST") == "1"):
+    if dist is not None and args.full and not args.no_extra and (world > 1 or os.environ.get("NR3D_BENCH_FORCE_DIST") == "1"):
         try:
             r = march_composite_rate(dev, iters=5, side=512)
             ms_local, samples_local = float(r["ms_per_iter"]), float(r["samples"])
@@ -1033,32 +1073,6 @@ def main():
 
     if rank == 0:
         kms = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in ev.items()}
-        L_all = meta.n_levels
-        bpp = algorithmic_bytes_per_point(L_all, 2)
-        # dominant kernel = largest time per step; levels it serves: the LDS-staged levels belong to k_fwd_lds
-        per_step_us = {k: kernel_us[k] * kernel_launches[k] for k in kernel_us}
-        dom = max(per_step_us, key=per_step_us.get)
-        # levels the forward stages in LDS (lotd.hip: Dense, 2 features, table <= 96 KiB, N >= 2^18); one launch holds up
-        # to two of them (<= 150 KiB together)
-        lds_launches = int(round(kernel_launches.get("lotd_fwd_lds", 0)))
-        n_lds = sum(1 for t, f, sz in zip(meta.level_types, meta.level_n_feats, meta.level_sizes)
-                    if t == 0 and f == 2 and sz * 8 <= 96 * 1024) if lds_launches else 0
-        n_dir = int(H.lib().nr3d_lotd_pair_direct_levels(ctypes.byref(meta._cmeta()), ctypes.c_uint32(min(N, 1 << 22))))
-        served = {"lotd_fwd": L_all - n_lds, "lotd_fwd_lds": max(1, n_lds // max(1, lds_launches)), "lotd_contract_dx": L_all, "lotd_bin": L_all - n_dir,
-                  "lotd_accum": L_all - n_dir, "lotd_direct": max(n_dir, 1)}
-        per_kernel = {}
-        for k, us in kernel_us.items():
-            kb = kernel_algorithmic_bytes(k, served[k])
-            # bytes of ONE launch: a kernel that runs once per chunk of the batch (dL/dparam passes of 2^22 points; one
-            # launch per LDS-staged level is already in `served`) processes N / launches points each time
-            per_launch = max(1.0, kernel_launches[k] / (lds_launches if k == "lotd_fwd_lds" and lds_launches else 1))
-            ach = kb * (N / per_launch) / (us * 1e-6) / 1e9
-            per_kernel[PROF_KERNELS[k]] = {"avg_us": round(us, 2), "launches_per_step": round(kernel_launches[k], 2),
-                                           "algorithmic_bytes_per_point": kb, "achieved": round(ach, 1),
-                                           "frac": round(ach / HBM_PEAK_GBPS, 4)}
-        dom_name = PROF_KERNELS[dom]
-        launches = {PROF_KERNELS[k]: int(round(v)) for k, v in kernel_launches.items()}
-        at_default_size = args.log2_points == N_POINTS_LOG2
         out = {
             "metric": "Mpoints/s LoTD fwd+bwd (16-lvl hash) + Mrays/s march+composite, 1 & 8 GPU",
             "value": round(world * N * args.steps / elapsed / 1e6, 3),
@@ -1080,67 +1094,94 @@ def main():
                                       if dist is not None else "single GPU",
                        **({"per_rank_ms_per_step": per_rank_ms, "allreduce_mode": reduce_mode[0]} if dist is not None else {})},
             "kernel_ms": {k: round(v, 4) for k, v in kms.items()},
-            # the dominant KERNEL (largest HIP-event time per step), SURVEY 8(d) bytes of the levels one launch serves
-            "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": per_kernel[dom_name]["achieved"],
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": per_kernel[dom_name]["frac"],
-                         "traffic": pmc_traffic_bytes([dom_name]) if at_default_size else None,
-                         "avg_launch_us": per_kernel[dom_name]["avg_us"],
-                         "algorithmic_bytes": per_kernel[dom_name]["algorithmic_bytes_per_point"] * N,
-                         "algorithmic_bytes_per_point": per_kernel[dom_name]["algorithmic_bytes_per_point"],
-                         "timers": ("in-library HIP events on the launch stream; " + PROF_KERNELS[LIVE_TIMER] + (" inside" if live_timers else " after")
-                                    + " the timed region, the other kernels on 5 extra steps"),
-                         "per_kernel": per_kernel,
-                         "per_op": {k: {"ms": round(kms[k], 4), "algorithmic_bytes_per_point": bpp[k],
-                                        "achieved": round(bpp[k] * N / (kms[k] * 1e-3) / 1e9, 1),
-                                        "frac": round(bpp[k] * N / (kms[k] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                                        "kernels": [PROF_KERNELS[t] for t in OP_TIMERS[k]],
-                                        "traffic": pmc_traffic_bytes([PROF_KERNELS[t] for t in OP_TIMERS[k]], launches)
-                                        if at_default_size else None}
-                                    for k in names},
-                         # the whole step against the roofline, on the WALL clock of the timed region (ms_per_step: what `value` is
-                         # computed from); beside it the same bytes over the sum of the event-timed op times (no launch gaps)
-                         "whole_step_frac": round(sum(bpp.values()) * N / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBPS, 4),
-                         "whole_step_frac_event_sum": round(sum(bpp.values()) * N / (sum(kms.values()) * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)},
         }
-        if "lotd_fwd" in kernel_us:
-            # the forward gather kernel is not byte bound: its corner gathers are 8 useful bytes per 128-byte L2 line, and what
-            # limits it is the rate at which the L2 channels serve lines.  Its second ceiling, next to the HBM one:
-            # requests of one launch (4.25 per point and level, the counter figure) / launch time against the rate 8-byte
-            # random gathers ALONE reach on this part
-            req = FWD_REQUESTS_PER_POINT_LEVEL * served["lotd_fwd"] * N
-            greq = req / (kernel_us["lotd_fwd"] * 1e-6) / 1e9
-            out["roofline"]["request_rate"] = {"kernel": PROF_KERNELS["lotd_fwd"], "l2_read_requests": int(req),
-                                               "achieved_greq_s": round(greq, 1), "ceiling_greq_s": L2_GATHER_CEILING_GREQ_S,
-                                               "frac": round(greq / L2_GATHER_CEILING_GREQ_S, 4)}
-        if world == 1 and not args.no_extra:
-            out["extra"] = {}
-            for name, fn in (("march_composite", lambda: march_composite_rate(dev, cpu_seconds=0.0 if args.no_cpu_baseline else 4.0)),
-                             ("march_composite_shell", lambda: march_composite_rate(dev, cpu_seconds=0.0 if args.no_cpu_baseline else 2.0, occupancy="shell")),
-                             ("march_composite_262144_rays", lambda: march_composite_rate(dev, iters=20, side=512)),
-                             ("march_composite_262144_rays_shell", lambda: march_composite_rate(dev, iters=20, side=512, occupancy="shell")),
-                             ("c1_dense_fwd", lambda: c1_dense_rate(dev)),
-                             ("full_loop_1gpu", lambda: full_loop_rate(dev)),
-                             ("full_loop_1gpu_half", lambda: full_loop_rate(dev, precision="half")),
-                             ("c5_shard_1gpu", lambda: c5_shard_1gpu(dev)),
-                             ("forest_lotd", lambda: forest_lotd_rate(dev)),
-                             ("forest_lotd_by_block", lambda: forest_lotd_rate(dev, by_block=True)),
-                             ("lotd_half_params", lambda: lotd_half_rate(dev)),
-                             ("lotd_second_order", lambda: lotd_second_order_rate(dev)),
-                             ("mlp_decoder", lambda: mlp_decoder_rate(dev)),
-                             ("mlp_decoder_64", lambda: mlp_decoder_rate(dev, dims=(64, 64, 64, 64), with_torch=False)),
-                             ("c4_mixed_lotd", c4_mixed_rate),
-                             ("lotd_2p24_points", lambda: lotd_large_batch_rate(24)),
-                             ("reference_workloads", lambda: reference_workloads(dev))):
-                try:                     # an extra figure must never cost the headline line (or the other extras)
-                    torch.cuda.empty_cache()
-                    out["extra"][name] = fn()
-                except Exception as ex:
-                    out["extra"][name] = {"error": repr(ex)[:300]}
-        if multi_march is not None:
-            out.setdefault("extra", {})["march_composite_262144_rays_per_gpu"] = multi_march
-            out["extra"]["full_loop_2p21_rays_per_gpu"] = multi_loop
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg)
+        if args.full:
+            L_all = meta.n_levels
+            bpp = algorithmic_bytes_per_point(L_all, 2)
+            # dominant kernel = largest time per step; levels it serves: the LDS-staged levels belong to k_fwd_lds
+            per_step_us = {k: kernel_us[k] * kernel_launches[k] for k in kernel_us}
+            dom = max(per_step_us, key=per_step_us.get)
+            # levels the forward stages in LDS (lotd.hip: Dense, 2 features, table <= 96 KiB, N >= 2^18); one launch holds up
+            # to two of them (<= 150 KiB together)
+            lds_launches = int(round(kernel_launches.get("lotd_fwd_lds", 0)))
+            n_lds = sum(1 for t, f, sz in zip(meta.level_types, meta.level_n_feats, meta.level_sizes)
+                        if t == 0 and f == 2 and sz * 8 <= 96 * 1024) if lds_launches else 0
+            n_dir = int(H.lib().nr3d_lotd_pair_direct_levels(ctypes.byref(meta._cmeta()), ctypes.c_uint32(min(N, 1 << 22))))
+            served = {"lotd_fwd": L_all - n_lds, "lotd_fwd_lds": max(1, n_lds // max(1, lds_launches)), "lotd_contract_dx": L_all, "lotd_bin": L_all - n_dir,
+                      "lotd_accum": L_all - n_dir, "lotd_direct": max(n_dir, 1)}
+            per_kernel = {}
+            for k, us in kernel_us.items():
+                kb = kernel_algorithmic_bytes(k, served[k])
+                # bytes of ONE launch: a kernel that runs once per chunk of the batch (dL/dparam passes of 2^22 points; one
+                # launch per LDS-staged level is already in `served`) processes N / launches points each time
+                per_launch = max(1.0, kernel_launches[k] / (lds_launches if k == "lotd_fwd_lds" and lds_launches else 1))
+                ach = kb * (N / per_launch) / (us * 1e-6) / 1e9
+                per_kernel[PROF_KERNELS[k]] = {"avg_us": round(us, 2), "launches_per_step": round(kernel_launches[k], 2),
+                                               "algorithmic_bytes_per_point": kb, "achieved": round(ach, 1),
+                                               "frac": round(ach / HBM_PEAK_GBPS, 4)}
+            dom_name = PROF_KERNELS[dom]
+            launches = {PROF_KERNELS[k]: int(round(v)) for k, v in kernel_launches.items()}
+            at_default_size = args.log2_points == N_POINTS_LOG2
+            # the dominant KERNEL (largest HIP-event time per step), SURVEY 8(d) bytes of the levels one launch serves
+            out["roofline"] = {"bound": "hbm", "kernel": dom_name, "achieved": per_kernel[dom_name]["achieved"],
+                               "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": per_kernel[dom_name]["frac"],
+                               "traffic": pmc_traffic_bytes([dom_name]) if at_default_size else None,
+                               "avg_launch_us": per_kernel[dom_name]["avg_us"],
+                               "algorithmic_bytes": per_kernel[dom_name]["algorithmic_bytes_per_point"] * N,
+                               "algorithmic_bytes_per_point": per_kernel[dom_name]["algorithmic_bytes_per_point"],
+                               "timers": ("in-library HIP events on the launch stream; " + PROF_KERNELS[LIVE_TIMER] + (" inside" if live_timers else " after")
+                                          + " the timed region, the other kernels on 5 extra steps"),
+                               "per_kernel": per_kernel,
+                               "per_op": {k: {"ms": round(kms[k], 4), "algorithmic_bytes_per_point": bpp[k],
+                                              "achieved": round(bpp[k] * N / (kms[k] * 1e-3) / 1e9, 1),
+                                              "frac": round(bpp[k] * N / (kms[k] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                                              "kernels": [PROF_KERNELS[t] for t in OP_TIMERS[k]],
+                                              "traffic": pmc_traffic_bytes([PROF_KERNELS[t] for t in OP_TIMERS[k]], launches)
+                                              if at_default_size else None}
+                                          for k in names},
+                               # the whole step against the roofline, on the WALL clock of the timed region (ms_per_step: what `value` is
+                               # computed from); beside it the same bytes over the sum of the event-timed op times (no launch gaps)
+                               "whole_step_frac": round(sum(bpp.values()) * N / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBPS, 4),
+                               "whole_step_frac_event_sum": round(sum(bpp.values()) * N / (sum(kms.values()) * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
+            if "lotd_fwd" in kernel_us:
+                # the forward gather kernel is not byte bound: its corner gathers are 8 useful bytes per 128-byte L2 line, and what
+                # limits it is the rate at which the L2 channels serve lines.  Its second ceiling, next to the HBM one:
+                # requests of one launch (4.25 per point and level, the counter figure) / launch time against the rate 8-byte
+                # random gathers ALONE reach on this part
+                req = FWD_REQUESTS_PER_POINT_LEVEL * served["lotd_fwd"] * N
+                greq = req / (kernel_us["lotd_fwd"] * 1e-6) / 1e9
+                out["roofline"]["request_rate"] = {"kernel": PROF_KERNELS["lotd_fwd"], "l2_read_requests": int(req),
+                                                   "achieved_greq_s": round(greq, 1), "ceiling_greq_s": L2_GATHER_CEILING_GREQ_S,
+                                                   "frac": round(greq / L2_GATHER_CEILING_GREQ_S, 4)}
+            if world == 1 and not args.no_extra:
+                out["extra"] = {}
+                for name, fn in (("march_composite", lambda: march_composite_rate(dev, cpu_seconds=0.0 if args.no_cpu_baseline else 4.0)),
+                                 ("march_composite_shell", lambda: march_composite_rate(dev, cpu_seconds=0.0 if args.no_cpu_baseline else 2.0, occupancy="shell")),
+                                 ("march_composite_262144_rays", lambda: march_composite_rate(dev, iters=20, side=512)),
+                                 ("march_composite_262144_rays_shell", lambda: march_composite_rate(dev, iters=20, side=512, occupancy="shell")),
+                                 ("c1_dense_fwd", lambda: c1_dense_rate(dev)),
+                                 ("full_loop_1gpu", lambda: full_loop_rate(dev)),
+                                 ("full_loop_1gpu_half", lambda: full_loop_rate(dev, precision="half")),
+                                 ("c5_shard_1gpu", lambda: c5_shard_1gpu(dev)),
+                                 ("forest_lotd", lambda: forest_lotd_rate(dev)),
+                                 ("forest_lotd_by_block", lambda: forest_lotd_rate(dev, by_block=True)),
+                                 ("lotd_half_params", lambda: lotd_half_rate(dev)),
+                                 ("lotd_second_order", lambda: lotd_second_order_rate(dev)),
+                                 ("mlp_decoder", lambda: mlp_decoder_rate(dev)),
+                                 ("mlp_decoder_64", lambda: mlp_decoder_rate(dev, dims=(64, 64, 64, 64), with_torch=False)),
+                                 ("c4_mixed_lotd", c4_mixed_rate),
+                                 ("lotd_2p24_points", lambda: lotd_large_batch_rate(24)),
+                                 ("reference_workloads", lambda: reference_workloads(dev))):
+                    try:                     # an extra figure must never cost the headline line (or the other extras)
+                        torch.cuda.empty_cache()
+                        out["extra"][name] = fn()
+                    except Exception as ex:
+                        out["extra"][name] = {"error": repr(ex)[:300]}
+            if multi_march is not None:
+                out.setdefault("extra", {})["march_composite_262144_rays_per_gpu"] = multi_march
+                out["extra"]["full_loop_2p21_rays_per_gpu"] = multi_loop
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(cfg)
         result = out
     else:
         result = None
@@ -1154,7 +1195,10 @@ def main():
     except Exception:
         pass
     if result is not None:
-        emit(result)
+        if args.full:
+            emit(result)
+        else:
+            print(compact_line(result), flush=True)
 
 
 if __name__ == "__main__":

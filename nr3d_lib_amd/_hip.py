@@ -31,7 +31,8 @@ _lock = threading.Lock()
 
 def build(verbose=False, jobs=None):
     """hipcc --offload-arch=gfx950 build of nr3d_lib_amd/libnr3d_hip.so (incremental, via make)."""
-    jobs = jobs or os.cpu_count() or 4
+    # MAX_JOBS when set, else one job per usable CPU up to 16 (os.cpu_count() is the host's, not the container's share)
+    jobs = jobs or int(os.environ.get("MAX_JOBS") or 0) or min(len(os.sched_getaffinity(0)), 16)
     cmd = ["make", "-C", CSRC, f"-j{jobs}"]
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if verbose or res.returncode != 0:

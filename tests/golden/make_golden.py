@@ -104,7 +104,12 @@ def main():
             param = torch.from_numpy(out[f"{tag}_params"].astype(np.float32))
             ref = helpers.param_interpolate(param.view(1, *([R] * D), F), (x * 2 - 1).view(1, -1, D), R)[0]
         out[f"{tag}_y"] = ref.numpy()[keep]
-    np.savez_compressed(os.path.join(HERE, "ref_param_interpolate.npz"), **out)
+    # configs[0]'s points and values in files of their own: every committed file stays under 1 MiB
+    # (tests/util.py: load_golden_param_interpolate merges them)
+    big = ("c1_x", "c1_y")
+    np.savez_compressed(os.path.join(HERE, "ref_param_interpolate.npz"), **{k: v for k, v in out.items() if k not in big})
+    for k in big:
+        np.savez_compressed(os.path.join(HERE, f"ref_param_interpolate_{k}.npz"), **{k: out[k]})
 
     # ---- gen_ngp_cfg ---------------------------------------------------------------------------------
     cfgs = {}

@@ -94,3 +94,34 @@ def test_gpus_mismatch_is_an_error_not_an_assert():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--plumbing-check"], capture_output=True,
                        text=True, timeout=120, env=env, cwd=str(ROOT))
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr and "AssertionError" not in r.stderr
+
+
+def test_dump_outputs_is_a_fixed_float32_sample_within_64_mb(tmp_path):
+    """--dump-outputs on what one step of the default workload returns (2^20 points, 32 encoded dims, 12 131 648 params):
+    float32 .npy files of at most 64 MB together, the same rows of every per-point output, the same elements on every call.
+    Every element holds its own index, so the sample can be read back from the values."""
+    import numpy as np
+    import torch
+    N, E, P = 1 << 20, 32, 12131648
+    row = torch.arange(N, dtype=torch.float32)
+    outputs = {"y": row[:, None].expand(N, E), "dy_dx": row[:, None, None].expand(N, E, 3), "dL_dx": row[:, None].expand(N, 3),
+               "dL_dparam": torch.arange(P, dtype=torch.float32)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outputs)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["dL_dparam.npy", "dL_dx.npy", "dy_dx.npy", "y.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), got[f[:-4]])
+        assert got[f[:-4]].dtype == np.float32
+    rows = got["y"][:, 0]
+    assert rows.shape == (bench.DUMP_ROWS,) and np.all(np.diff(rows) > 0)
+    assert got["y"].shape == (bench.DUMP_ROWS, E) and got["dy_dx"].shape == (bench.DUMP_ROWS, E, 3)
+    for name in ("y", "dy_dx", "dL_dx"):
+        assert np.array_equal(got[name].reshape(bench.DUMP_ROWS, -1), np.repeat(rows[:, None], got[name][0].size, 1))
+    p = got["dL_dparam"]
+    assert p.shape == (bench.DUMP_PARAMS,) and np.all(np.diff(p) > 0) and p[-1] < P
+    # smaller outputs are written whole
+    bench.dump_outputs(str(tmp_path / "c"), {"y": row[:100, None].expand(100, E), "dL_dparam": torch.arange(7.0)})
+    assert np.array_equal(np.load(tmp_path / "c" / "y.npy")[:, 0], np.arange(100)) and np.load(tmp_path / "c" / "dL_dparam.npy").size == 7

@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from util import load_golden_param_interpolate
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -21,7 +23,7 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 @pytest.mark.parametrize("tag,D", [("c1", 3), ("d2", 2)])
 def test_dense_forward_against_reference_param_interpolate(dev, tag, D):
     from nr3d_lib_amd.bindings import _lotd
-    z = np.load(os.path.join(GOLD, "ref_param_interpolate.npz"))
+    z = load_golden_param_interpolate()
     R, F = int(z[f"{tag}_res"]), int(z[f"{tag}_feats"])
     x, p, want = z[f"{tag}_x"], z[f"{tag}_params"].astype(np.float32), z[f"{tag}_y"]
     if tag == "c1":            # configs[0] exactly as BASELINE.json states it: Dense 32^3 x 4, all 65 536 points

@@ -113,3 +113,13 @@ def random_packs(rng, n_packs, lo, hi, empty_frac=0.0):
         n[rng.random(n_packs) < empty_frac] = 0
     cs = np.cumsum(n)
     return np.ascontiguousarray(np.stack([cs - n, n], 1)), int(cs[-1])
+
+
+def load_golden_param_interpolate():
+    """tests/golden/ref_param_interpolate*.npz as one dict: configs[0]'s 65 536 points and the reference's values at them are
+    stored in files of their own so that every committed file stays under 1 MiB (tests/golden/make_golden.py)"""
+    import os
+    out = {}
+    for part in ("", "_c1_x", "_c1_y"):
+        out.update(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", f"ref_param_interpolate{part}.npz")))
+    return out

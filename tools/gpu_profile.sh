@@ -11,7 +11,7 @@ rm -rf /tmp/prof_k && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_
 DB=$(find /tmp/prof_k -name '*.db' | head -1)
 python $ROOT/tools/prof_summary.py "$DB" > "$OUT/bench_kernel_stats.txt" 2>&1
 # second pass: the extra figures only (march + composite at 4096 / 262144 rays, full loop); headline loop reduced to 1 step
-rm -rf /tmp/prof_x && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_x -o p -- python $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
+rm -rf /tmp/prof_x && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_x -o p -- python $ROOT/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline > /dev/null 2>&1
 python $ROOT/tools/prof_summary.py "$(find /tmp/prof_x -name '*.db' | head -1)" > "$OUT/bench_extra_kernel_stats.txt" 2>&1
 if [ -n "$PMC" ]; then
   rm -f "$OUT/pmc_traffic.json"
