@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 9
+#define NR3D_ABI_VERSION 10
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -468,6 +468,20 @@ int nr3d_mlp_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, i
                       int64_t gx_feature_stride, float *const *dL_dW, float *const *dL_db, void *stream);
 int nr3d_mlp_forward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, int64_t x_stride, int64_t x_feature_stride,
                      const float *packed, float *y, int64_t y_stride, void *stream);
+/* Double backward (ABI 10) -- the create_graph route of an SDF decoder's nablas = dL/dx and the eikonal loss on them (the reference
+ * differentiates its GEMM chain twice, or points users at a tiny-cuda-nn fork with a double-backward fused MLP).  Given u = dL_dy
+ * (rows, gy_stride 0 allowed: an expanded ones) and v = ddL_dx = dL/d(dL/dx) (layouts as x: row-major or feature-major), with r_l
+ * the first backward's dL/d(pre-activation of layer l) and t_l = m_l W_l t_{l-1} (t_{-1} = v, m_l the ReLU masks) the tangent of v:
+ *   dL_dW[l] += sum over samples of r_l t_{l-1}^T (fp32 atomics as nr3d_mlp_backward: zero them first);
+ *   dL_ddLdy [n, out] rows (ggy_stride; NULL: not wanted) = t_L, fully written;
+ *   dL/db_l and dL/dx are zero (the network is piecewise linear) and are not produced.
+ * packed comes from nr3d_mlp_pack(..., with_backward = 1); the forward is recomputed with nr3d_mlp_backward's route under the same
+ * options (NR3D_OPT_MLP_X3), so the masks are bit for bit the ones its dL/dx used.  nr3d_mlp_backward_backward_ok: 1 when the
+ * fused double backward applies (the shapes of nr3d_mlp_backward), else 0: the caller differentiates its unfused path. */
+int nr3d_mlp_backward_backward_ok(const nr3d_mlp_desc_t *desc);
+int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, int64_t x_stride, int64_t x_feature_stride,
+                               const float *dL_dy, int64_t gy_stride, const float *ddL_dx, int64_t v_stride, int64_t v_feature_stride,
+                               const float *packed, float *dL_ddLdy, int64_t ggy_stride, float *const *dL_dW, void *stream);
 
 /* LoTD encode + this decoder's FORWARD in one kernel (csrc/lotd_mlp.hip; no reference counterpart -- the reference runs lod_fwd and
  * the decoder as separate ops): for the no-grad density query of the ray driver (nr3d_lib/graphics/nerf/nerf_ray_query.py:105-127),

@@ -38,6 +38,8 @@ class MLPDesc:
         # the half-precision twin (csrc/mlp_half.hip, f16 MFMA): sizes in bytes
         self.half_packed_bytes = int(l.nr3d_mlp_half_packed_bytes(C.byref(c))) if c.n_layers else 0
         self.half_backward_bytes = int(l.nr3d_mlp_half_backward_packed_bytes(C.byref(c))) if self.half_packed_bytes else 0
+        # the fused double backward (nr3d_mlp_backward_backward) on the fp32 packed buffer
+        self.second_order_ok = bool(l.nr3d_mlp_backward_backward_ok(C.byref(c))) if self.backward_floats else False
 
     @property
     def fusable(self) -> bool:
@@ -46,6 +48,10 @@ class MLPDesc:
     @property
     def backward_fusable(self) -> bool:
         return self.backward_floats > 0
+
+    @property
+    def second_order_fusable(self) -> bool:
+        return self.second_order_ok
 
     @property
     def half_fusable(self) -> bool:
@@ -140,6 +146,42 @@ def backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, packed: torch.
             H.i64(g2.stride(0) if n > 1 else desc.dims[-1]), H.ptr(packed), H.ptr(dx), H.i64(gxs), H.i64(gxf), _ptr_array(dWs),
             _ptr_array(dbs), H.stream_of(x)))
     return (None if dx is None else dx.reshape(x.shape)), dWs, dbs
+
+
+def backward_backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, ddL_dx: torch.Tensor, packed: torch.Tensor, need_dgy=True,
+                      has_bias=None):
+    """The double backward: gradients of <dL/dx, ddL_dx> (dL/dx = backward()'s, a function of the parameters and dL_dy) ->
+    (dL/d(dL_dy) | None, [dL/dW_l], [dL/db_l | None]).  dL/dx and dL/db_l are zero (the network is piecewise linear): dL/dx is not
+    produced, dL/db_l are zero views of the dW pool for the layers has_bias marks (default: none).  x and ddL_dx row-major with any
+    row stride or feature-major, dL_dy rows with any row stride (0 included: an expanded ones); `packed` from
+    pack(..., with_backward=True).  dL/d(dL_dy) has dL_dy's shape."""
+    H.require_gpu(x, dL_dy, ddL_dx, packed)
+    if not desc.second_order_fusable:
+        raise RuntimeError("mlp.backward_backward: the fused double backward does not apply to this network")
+    n_layers = len(desc.dims) - 1
+    x2 = x.reshape(-1, desc.dims[0])
+    v2 = ddL_dx.reshape(-1, desc.dims[0])
+    g2 = dL_dy.reshape(-1, desc.dims[-1])
+    if (x2.dtype != torch.float32 or g2.dtype != torch.float32 or v2.dtype != torch.float32 or x2.shape[0] != g2.shape[0]
+            or v2.shape[0] != x2.shape[0]):
+        raise RuntimeError("mlp.backward_backward: expected fp32 x [n, in], dL_dy [n, out] and ddL_dx [n, in]")
+    x2, xs, xf = _layout(x2)
+    v2, vs, vf = _layout(v2)
+    g2 = g2 if (g2.stride(-1) == 1 or g2.shape[1] == 1) else g2.contiguous()
+    n, dev = x2.shape[0], x.device
+    # accumulated into by the kernel (atomics): views of one zero-filled buffer, as in backward()
+    has_bias = [False] * n_layers if has_bias is None else list(has_bias)
+    sizes = [desc.dims[l + 1] * desc.dims[l] for l in range(n_layers)] + [desc.dims[l + 1] if has_bias[l] else 0 for l in range(n_layers)]
+    parts = torch.zeros(sum(sizes), dtype=torch.float32, device=dev).split(sizes)
+    dWs = [parts[l].view(desc.dims[l + 1], desc.dims[l]) for l in range(n_layers)]
+    dbs = [parts[n_layers + l] if has_bias[l] else None for l in range(n_layers)]
+    dgy = H.empty((n, desc.dims[-1]), dtype=torch.float32, device=dev) if need_dgy else None
+    with H.on_device(dev):
+        H.check(H.lib().nr3d_mlp_backward_backward(
+            C.byref(desc._c), C.c_uint64(n), H.ptr(x2), H.i64(xs), H.i64(xf), H.ptr(g2),
+            H.i64(g2.stride(0) if n > 1 else desc.dims[-1]), H.ptr(v2), H.i64(vs), H.i64(vf), H.ptr(packed), H.ptr(dgy),
+            H.i64(desc.dims[-1]), _ptr_array(dWs), H.stream_of(x)))
+    return (None if dgy is None else dgy.view(dL_dy.shape)), dWs, dbs
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // nr3d_lib_amd/csrc/mlp.hip -- fused fully-connected decoder (gfx950), C-ABI entry points
-// nr3d_mlp_packed_floats / nr3d_mlp_pack / nr3d_mlp_forward / nr3d_mlp_backward.
+// nr3d_mlp_packed_floats / nr3d_mlp_pack / nr3d_mlp_forward / nr3d_mlp_backward / nr3d_mlp_backward_backward.
 //
 // The step right after the encoder: nr3d_lib/models/blocks/mlp.py:27-127 (`MLP` / `FCBlock`: D hidden
 // DenseLayers of width W + an output layer, nr3d_lib/models/layers.py:228-300) -- in the reference a chain of
@@ -488,6 +488,247 @@ __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T, NH>::kMaxWaves * 64)) voi
 	reduce_layer<OUT_T, W_T>(dWo, dbo, R, a.dW[NH], a.db[NH], a.dims[NH + 1], a.dims[NH], lane, wave, nw);
 }
 
+// =============================================================================================
+// double backward (second order, the eikonal term of an SDF decoder): the network is piecewise linear, so with the ReLU masks m_l of
+// the forward, r_l the first backward's dL/d(pre-activation of layer l) (r_L = m_L u, r_{l-1} = m_{l-1} W_l^T r_l) and the TANGENT of
+// the incoming v = dL/d(dL/dx) through the same masks (t_{-1} = v, t_l = m_l W_l t_{l-1}, no bias):
+//   dL/dW_l = sum over samples of r_l t_{l-1}^T,   dL/d(dL/dy) = t_L,   dL/db_l = 0,   dL/dx = 0 (sigma'' = 0 almost everywhere).
+// k_mlp_bwd2 is k_mlp_bwd with the activation tiles H_l replaced by the tangent tiles t_l (same rows, same LDS, same waves) and the
+// masks kept as one bit per register-map element instead of being read back from H_l > 0: the forward recomputation runs the same
+// dense / dense_x3 as k_mlp_bwd (same X3 rule), so the masks are bit for bit the ones nr3d_mlp_backward used.  No db, no dL/dx.
+// =============================================================================================
+struct Bwd2Args {
+	uint64_t n;
+	const float *x; int64_t xs;
+	const float *gy; int64_t gys;
+	const float *v; int64_t vs;                // dL/d(dL/dx)
+	float *ggy; int64_t ggys;                  // dL/d(dL/dy) [n, out] rows; NULL: not wanted
+	uint32_t x_fm, v_fm;                       // x / v feature-major (xs / vs = feature stride)
+	const float *packed;                       // the forward layers: f32, or their x3 planes
+	uint32_t total_floats;                     // of their padded LDS copy
+	float *dW[NR3D_MLP_MAX_LAYERS];            // accumulated into (atomics): zero them for plain gradients
+	uint32_t dims[NR3D_MLP_MAX_LAYERS + 1];
+	uint32_t n_layers;
+	int hidden_act, out_act;
+	uint32_t x_vec, gy_vec, v_vec, ggy_vec;
+	uint32_t tile_floats;                      // per wave
+};
+
+// the ReLU mask of a register-map tile set as bits (bit 16 t + j = element j of tile t is positive), and its application: one
+// v_bfe_i32 (0 or all ones) and one v_and_b32 per element -- +0.0 where the unit is off, as the "? g : 0.0f" of bwd_layer
+template <int NT>
+__device__ __forceinline__ uint32_t relu_bits(const f16v (&r)[NT]) {
+	static_assert(NT <= 2, "16 bits per tile, 32 per lane");
+	uint32_t m = 0;
+#pragma unroll
+	for (int t = 0; t < NT; ++t)
+#pragma unroll
+		for (int j = 0; j < 16; ++j) m |= (r[t][j] > 0.0f ? 1u : 0u) << (16 * t + j);
+	return m;
+}
+template <int NT>
+__device__ __forceinline__ void mask_bits(f16v (&r)[NT], uint32_t m) {
+#pragma unroll
+	for (int t = 0; t < NT; ++t)
+#pragma unroll
+		for (int j = 0; j < 16; ++j) {
+			const int keep = (int)(m << (31 - (16 * t + j))) >> 31;
+			const float v = r[t][j];                   // (a copy: __builtin_bit_cast of a vector element reads element 0)
+			r[t][j] = __builtin_bit_cast(float, __builtin_bit_cast(int, v) & keep);
+		}
+}
+
+// bwd_layer's contraction without the bias sums: dW += dPre^T . T over the wave's 32 samples, TG holding dPre (NO tiles), TB the
+// tangent of the layer's input (NI tiles), both as [feature][sample]
+template <int NO, int NI, bool X3>
+__device__ __forceinline__ void contract_tiles(const float *__restrict__ TG, const float *__restrict__ TB, f16v (&dW)[NO][NI],
+                                               int r, int h) {
+	if constexpr (X3) {
+		constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PX[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+		for (int st = 0; st < 2; ++st) {
+			bf8 ap[NO][3], bp[NI][3];
+			float dummy = 0.0f;
+#pragma unroll
+			for (int ot = 0; ot < NO; ++ot) split3_row8(TG + (32 * ot + r) * kTS + 16 * st + 8 * h, ap[ot], dummy);
+#pragma unroll
+			for (int it = 0; it < NI; ++it) split3_row8(TB + (32 * it + r) * kTS + 16 * st + 8 * h, bp[it], dummy);
+#pragma unroll
+			for (int t = 0; t < 6; ++t)
+#pragma unroll
+				for (int ot = 0; ot < NO; ++ot)
+#pragma unroll
+					for (int it = 0; it < NI; ++it)
+						dW[ot][it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[ot][PW[t]], bp[it][PX[t]], dW[ot][it], 0, 0, 0);
+		}
+	} else {
+		float bv[NI][16];
+#pragma unroll
+		for (int it = 0; it < NI; ++it) read_row16(TB, 32 * it + r, h, bv[it]);
+#pragma unroll
+		for (int ot = 0; ot < NO; ++ot) {
+			float av[16];
+			read_row16(TG, 32 * ot + r, h, av);
+#pragma unroll
+			for (int it = 0; it < NI; ++it)
+#pragma unroll
+				for (int t = 0; t < 16; ++t) dW[ot][it] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bv[it][t], dW[ot][it], 0, 0, 0);
+		}
+	}
+}
+
+// bwd_layer of the double backward: TB holds the tangent of the layer's input, the mask of dL/d(input) comes from bits
+template <int NO, int NI, bool PREV, bool MASK, bool X3>
+__device__ __forceinline__ void bwd2_layer(const f16v (&g)[NO], float *__restrict__ TG, const float *__restrict__ TB,
+                                           const float *__restrict__ wT, f16v (&dW)[NO][NI], f16v (&gp)[NI], uint32_t mbits, int lane) {
+	const int r = lane & 31, h = lane >> 5;
+	write_tile<NO>(TG, NO, g, lane);
+	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+	contract_tiles<NO, NI, X3>(TG, TB, dW, r, h);
+	if (PREV) {
+		if constexpr (X3) dense_x3_t<NO, NI>(wT, g, gp, lane);
+		else dense_t<NO, NI>(wT, g, gp, lane);
+		if (MASK) mask_bits<NI>(gp, mbits);
+	}
+	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+}
+
+// x / v: row-major (any alignment: load_rows) or feature-major (load_cols_fast); no prefetch variants -- the x and v of the SDF step
+// come in different layouts (x feature-major from the LoTD forward or 35-float rows, v whatever the eikonal term's backward made)
+template <int NT>
+__device__ __forceinline__ void load_xv(const float *__restrict__ p, int64_t s, uint32_t fm, uint32_t vec, uint32_t dim, uint64_t row,
+                                        uint64_t n, int lane, f16v (&r)[NT]) {
+	if (fm) load_cols_fast<NT>(p, s, dim, row < n ? row : n - 1, lane, r);     // rows past n: dL/dy (hence every r_l) is zero there
+	else load_rows<NT>(p, s, dim, row, row < n, vec != 0, lane, r);
+}
+
+template <int IN_T, int W_T, int OUT_T, int NH, bool X3 = false>
+__global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T, NH>::kMaxWaves * 64)) void k_mlp_bwd2(Bwd2Args a) {
+	extern __shared__ __attribute__((aligned(16))) float lds[];
+	{
+		// the padded copy of the forward layers, as k_mlp_bwd
+		constexpr int GPP = X3 ? 6 : 4;
+		constexpr uint32_t s0 = IN_T * W_T * GPP * 256 + W_T * 32, sh = W_T * W_T * GPP * 256 + W_T * 32;
+		constexpr uint32_t GS = X3 ? kGS3 : kGS;
+		constexpr uint32_t d0 = IN_T * W_T * GPP * GS + W_T * 32, dh = W_T * W_T * GPP * GS + W_T * 32;
+		stage_layer_padded<IN_T, W_T, GPP>(a.packed, lds);
+#pragma unroll
+		for (int l = 1; l < NH; ++l) stage_layer_padded<W_T, W_T, GPP>(a.packed + s0 + (l - 1) * sh, lds + d0 + (l - 1) * dh);
+		stage_layer_padded<W_T, OUT_T, GPP>(a.packed + s0 + (NH - 1) * sh, lds + d0 + (NH - 1) * dh);
+		__syncthreads();
+	}
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+	const int r = lane & 31;
+	float *tiles = lds + a.total_floats + (size_t)wave * a.tile_floats;
+	// tile rows as k_mlp_bwd: V (= t_{-1}) or G_out | T_1 .. T_NH (the tangents of the hidden layers' outputs, where k_mlp_bwd keeps H_l)
+	constexpr int XG_T = IN_T > OUT_T ? IN_T : OUT_T;
+	float *TV = tiles;
+	float *TGO = tiles;
+	float *TT1 = tiles + 32 * XG_T * kTS;
+	constexpr uint32_t f0 = X3 ? layer_x3_floats_pad(IN_T, W_T) : layer_floats_pad(IN_T, W_T);
+	constexpr uint32_t fh = X3 ? layer_x3_floats_pad(W_T, W_T) : layer_floats_pad(W_T, W_T);
+	const float *wl = lds;
+
+	f16v dW0[W_T][IN_T], dWh[NH > 1 ? NH - 1 : 1][W_T][W_T], dWo[OUT_T][W_T];
+#pragma unroll
+	for (int ot = 0; ot < W_T; ++ot) zero_tiles<IN_T>(dW0[ot]);
+#pragma unroll
+	for (int l = 0; l < (NH > 1 ? NH - 1 : 1); ++l)
+#pragma unroll
+		for (int ot = 0; ot < W_T; ++ot) zero_tiles<W_T>(dWh[l][ot]);
+#pragma unroll
+	for (int ot = 0; ot < OUT_T; ++ot) zero_tiles<W_T>(dWo[ot]);
+
+	const bool relu = a.hidden_act == NR3D_MLP_ACT_RELU;
+	const uint64_t n_tiles = (a.n + 31) / 32, step = (uint64_t)gridDim.x * nw;
+	for (uint64_t tile = (uint64_t)blockIdx.x * nw + wave; tile < n_tiles; tile += step) {
+		const uint64_t row = tile * 32 + r;
+		const bool valid = row < a.n;
+		f16v vin[IN_T], g_out[OUT_T], tcur[W_T];
+		load_xv<IN_T>(a.v, a.vs, a.v_fm, a.v_vec, a.dims[0], row, a.n, lane, vin);
+		// ---- forward: the masks only (one bit per element), the activations die layer by layer ----
+		uint32_t mk[NH], mo = ~0u;
+		{
+			f16v xin[IN_T], hcur[W_T];
+			load_xv<IN_T>(a.x, a.xs, a.x_fm, a.x_vec, a.dims[0], row, a.n, lane, xin);
+			if constexpr (X3) dense_x3<IN_T, W_T, true, true>(wl, xin, hcur, a.hidden_act, lane);
+			else dense<IN_T, W_T, true, true>(wl, xin, hcur, a.hidden_act, lane);
+			mk[0] = relu ? relu_bits<W_T>(hcur) : 0u;
+#pragma unroll
+			for (int l = 1; l < NH; ++l) {
+				f16v hn[W_T];
+				if constexpr (X3) dense_x3<W_T, W_T, true, true>(wl + f0 + (l - 1) * fh, hcur, hn, a.hidden_act, lane);
+				else dense<W_T, W_T, true, true>(wl + f0 + (l - 1) * fh, hcur, hn, a.hidden_act, lane);
+				mk[l] = relu ? relu_bits<W_T>(hn) : 0u;
+#pragma unroll
+				for (int t = 0; t < W_T; ++t) hcur[t] = hn[t];
+			}
+			if (a.out_act == NR3D_MLP_ACT_RELU) {
+				f16v yo[OUT_T];
+				if constexpr (X3) dense_x3<W_T, OUT_T, true, true>(wl + f0 + (NH - 1) * fh, hcur, yo, NR3D_MLP_ACT_NONE, lane);
+				else dense<W_T, OUT_T, true, true>(wl + f0 + (NH - 1) * fh, hcur, yo, NR3D_MLP_ACT_NONE, lane);
+				mo = relu_bits<OUT_T>(yo);
+			}
+		}
+		load_rows<OUT_T>(a.gy, a.gys, a.dims[NH + 1], row, valid, a.gy_vec != 0, lane, g_out);      // (under the tangent chain)
+		// ---- the tangent of v through the same masks, T_l into the tiles ----
+		if constexpr (X3) dense_x3<IN_T, W_T, false, true>(wl, vin, tcur, NR3D_MLP_ACT_NONE, lane);
+		else dense<IN_T, W_T, false, true>(wl, vin, tcur, NR3D_MLP_ACT_NONE, lane);
+		if (relu) mask_bits<W_T>(tcur, mk[0]);
+		write_tile<W_T>(TT1, W_T, tcur, lane);
+#pragma unroll
+		for (int l = 1; l < NH; ++l) {
+			f16v tn[W_T];
+			if constexpr (X3) dense_x3<W_T, W_T, false, true>(wl + f0 + (l - 1) * fh, tcur, tn, NR3D_MLP_ACT_NONE, lane);
+			else dense<W_T, W_T, false, true>(wl + f0 + (l - 1) * fh, tcur, tn, NR3D_MLP_ACT_NONE, lane);
+			if (relu) mask_bits<W_T>(tn, mk[l]);
+#pragma unroll
+			for (int t = 0; t < W_T; ++t) tcur[t] = tn[t];
+			write_tile<W_T>(TT1 + l * 32 * W_T * kTS, W_T, tcur, lane);
+		}
+		// ---- output layer: r_L = m_L u, dL/d(dL/dy) = t_L = m_L W_L t ----
+		const float *wo = wl + f0 + (NH - 1) * fh;
+		if (a.out_act == NR3D_MLP_ACT_RELU) mask_bits<OUT_T>(g_out, mo);
+		if (a.ggy) {
+			f16v to[OUT_T];
+			if constexpr (X3) dense_x3<W_T, OUT_T, false, true>(wo, tcur, to, NR3D_MLP_ACT_NONE, lane);
+			else dense<W_T, OUT_T, false, true>(wo, tcur, to, NR3D_MLP_ACT_NONE, lane);
+			if (a.out_act == NR3D_MLP_ACT_RELU) mask_bits<OUT_T>(to, mo);
+			store_rows<OUT_T>(a.ggy, a.ggys, a.dims[NH + 1], row, valid, a.ggy_vec != 0, lane, to);
+		}
+		// ---- adjoint sweep: dW_l += r_l t_{l-1}^T ----
+		f16v g[W_T];
+		if (relu) bwd2_layer<OUT_T, W_T, true, true, X3>(g_out, TGO, TT1 + (NH - 1) * 32 * W_T * kTS, wo, dWo, g, mk[NH - 1], lane);
+		else bwd2_layer<OUT_T, W_T, true, false, X3>(g_out, TGO, TT1 + (NH - 1) * 32 * W_T * kTS, wo, dWo, g, 0u, lane);
+		write_tile<IN_T>(TV, IN_T, vin, lane);                           // into G_out's rows (as x in k_mlp_bwd)
+#pragma unroll
+		for (int l = NH - 1; l >= 1; --l) {
+			f16v gp[W_T];
+			float *TG = TT1 + l * 32 * W_T * kTS;                       // T_{l+1} was last read by the step above
+			const float *TB = TT1 + (l - 1) * 32 * W_T * kTS;
+			if (relu) bwd2_layer<W_T, W_T, true, true, X3>(g, TG, TB, wl + f0 + (l - 1) * fh, dWh[l - 1], gp, mk[l - 1], lane);
+			else bwd2_layer<W_T, W_T, true, false, X3>(g, TG, TB, wl + f0 + (l - 1) * fh, dWh[l - 1], gp, 0u, lane);
+#pragma unroll
+			for (int t = 0; t < W_T; ++t) g[t] = gp[t];
+		}
+		f16v unused[IN_T];
+		bwd2_layer<W_T, IN_T, false, false, X3>(g, TT1, TV, wl, dW0, unused, 0u, lane);
+	}
+
+	// ---- reduce the waves' dW in LDS, one atomic per element (no db: the bias gradients of the double backward are zero) ----
+	__syncthreads();
+	float *R = lds + a.total_floats;
+	float zb0[W_T], zbh[W_T], zbo[OUT_T];
+#pragma unroll
+	for (int t = 0; t < W_T; ++t) { zb0[t] = 0.0f; zbh[t] = 0.0f; }
+#pragma unroll
+	for (int t = 0; t < OUT_T; ++t) zbo[t] = 0.0f;
+	reduce_layer<W_T, IN_T>(dW0, zb0, R, a.dW[0], nullptr, a.dims[1], a.dims[0], lane, wave, nw);
+#pragma unroll
+	for (int l = 1; l < NH; ++l) reduce_layer<W_T, W_T>(dWh[l - 1], zbh, R, a.dW[l], nullptr, a.dims[l + 1], a.dims[l], lane, wave, nw);
+	reduce_layer<OUT_T, W_T>(dWo, zbo, R, a.dW[NH], nullptr, a.dims[NH + 1], a.dims[NH], lane, wave, nw);
+}
+
 }  // namespace mlp
 }  // namespace nr3d
 
@@ -750,6 +991,69 @@ extern "C" int nr3d_mlp_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const 
 	BWD_CASE(2, 2, 1, 1) BWD_CASE(2, 2, 1, 2) BWD_CASE(2, 2, 2, 1) BWD_CASE(2, 2, 2, 2)
 	rc = ::nr3d::fail("mlp_backward: no kernel for this shape");
 #undef BWD_CASE
+	if (rc) return rc;
+	NR3D_LAUNCH_CHECK();
+	return 0;
+}
+
+// the double backward runs on every shape the fused backward runs on (same LDS plan, same waves)
+extern "C" int nr3d_mlp_backward_backward_ok(const nr3d_mlp_desc_t *desc) { return nr3d_mlp_backward_packed_floats(desc) != 0 ? 1 : 0; }
+
+extern "C" int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, int64_t x_stride, int64_t x_feature_stride,
+                                          const float *dL_dy, int64_t gy_stride, const float *ddL_dx, int64_t v_stride,
+                                          int64_t v_feature_stride, const float *packed, float *dL_ddLdy, int64_t ggy_stride,
+                                          float *const *dL_dW, void *stream) {
+	Shape s;
+	NR3D_CHECK(shape_of(desc, s) && nr3d_mlp_backward_backward_ok(desc), "mlp_backward_backward: the fused double backward does not apply to this network");
+	if (n == 0) return 0;
+	NR3D_CHECK(x && dL_dy && ddL_dx && packed && dL_dW, "mlp_backward_backward: NULL pointer");
+	Bwd2Args a;
+	const bool x_fm = x_feature_stride != 1, v_fm = v_feature_stride != 1;
+	NR3D_CHECK(!x_fm || x_stride == 1, "mlp_backward_backward: x must be row-major (feature stride 1) or feature-major (row stride 1)");
+	NR3D_CHECK(!v_fm || v_stride == 1, "mlp_backward_backward: ddL_dx must be row-major (feature stride 1) or feature-major (row stride 1)");
+	a.n = n; a.x = x; a.xs = x_fm ? x_feature_stride : x_stride; a.gy = dL_dy; a.gys = gy_stride;
+	a.v = ddL_dx; a.vs = v_fm ? v_feature_stride : v_stride; a.ggy = dL_ddLdy; a.ggys = ggy_stride;
+	a.x_fm = x_fm ? 1u : 0u; a.v_fm = v_fm ? 1u : 0u;
+	// the route of nr3d_mlp_backward under the same option state: the masks of the forward recomputation are bit for bit its masks
+	const bool x3 = x3_enabled() && backward_x3(s);
+	a.packed = x3 ? packed + packed_floats(s) : packed;
+	a.total_floats = (uint32_t)bwd_weight_floats(s, x3);
+	for (uint32_t l = 0; l < desc->n_layers; ++l) {
+		NR3D_CHECK(dL_dW[l] != nullptr, "mlp_backward_backward: dL_dW[%u] is NULL", l);
+		a.dW[l] = dL_dW[l];
+	}
+	for (uint32_t l = 0; l <= desc->n_layers; ++l) a.dims[l] = desc->dims[l];
+	a.n_layers = desc->n_layers;
+	a.hidden_act = (int)desc->hidden_activation; a.out_act = (int)desc->output_activation;
+	a.x_vec = ((uintptr_t)x % 16 == 0 && x_stride % 4 == 0) ? 1u : 0u;
+	a.v_vec = ((uintptr_t)ddL_dx % 16 == 0 && v_stride % 4 == 0) ? 1u : 0u;
+	a.gy_vec = ((uintptr_t)dL_dy % 16 == 0 && gy_stride % 4 == 0) ? 1u : 0u;
+	a.ggy_vec = (dL_ddLdy && (uintptr_t)dL_ddLdy % 16 == 0 && ggy_stride % 4 == 0) ? 1u : 0u;
+	a.tile_floats = bwd_tile_floats(s);
+	const uint32_t nw = bwd_waves(s, x3);
+	NR3D_CHECK(nw != 0, "mlp_backward_backward: no wave fits LDS");
+	const uint64_t reduce = ((uint64_t)s.w_t * s.w_t * 1024 + (uint64_t)s.w_t * 64) * 4;
+	const uint64_t tbytes = (uint64_t)nw * a.tile_floats * 4;
+	const size_t lds = (size_t)a.total_floats * 4 + (size_t)(tbytes > reduce ? tbytes : reduce);
+	const uint64_t n_tiles = (n + 31) / 32;
+	const uint32_t grid = (uint32_t)(n_tiles / nw + 1 < 256 ? n_tiles / nw + 1 : 256);     // one workgroup per CU: dW lives in registers
+	const uint32_t nh = desc->n_layers - 1;
+	auto launch = [&](auto kern) -> int {
+		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBwd));
+		hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, (hipStream_t)stream, a);
+		return 0;
+	};
+	int rc = 0;
+#define BWD2_CASE(I, W, O, H) if (s.in_t == I && s.w_t == W && s.out_t == O && nh == H) { \
+		if (x3) { if constexpr (!(W == 2 && ((H == 2 && I + O >= 3) || I + O >= 4))) /* (= backward_x3()) */ \
+		              rc = launch(k_mlp_bwd2<I, W, O, H, true>); \
+		          else rc = ::nr3d::fail("mlp_backward_backward: no bf16 MFMA kernel for this shape"); } \
+		else rc = launch(k_mlp_bwd2<I, W, O, H>); } else
+	BWD2_CASE(1, 1, 1, 1) BWD2_CASE(1, 1, 1, 2) BWD2_CASE(1, 1, 1, 3)
+	BWD2_CASE(1, 2, 1, 1) BWD2_CASE(1, 2, 1, 2) BWD2_CASE(1, 2, 2, 1) BWD2_CASE(1, 2, 2, 2)
+	BWD2_CASE(2, 2, 1, 1) BWD2_CASE(2, 2, 1, 2) BWD2_CASE(2, 2, 2, 1) BWD2_CASE(2, 2, 2, 2)
+	rc = ::nr3d::fail("mlp_backward_backward: no kernel for this shape");
+#undef BWD2_CASE
 	if (rc) return rc;
 	NR3D_LAUNCH_CHECK();
 	return 0;

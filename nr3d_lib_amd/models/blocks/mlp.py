@@ -7,7 +7,13 @@ runs the whole network in ONE kernel on the fp32 MFMA (csrc/mlp.hip) -- or, for 
 layers / its tcnn FullyFusedMLP), on the f16 MFMA (csrc/mlp_half.hip) -- whenever it can: on a GPU, ReLU / no
 activations, no skips / weight norm / equal_lr, every width <= 128.  Forward: activations stay in registers.  Backward
 (hidden width <= 64): the forward is recomputed from x inside the backward kernel, so autograd keeps x and nothing else.
-Everything else takes the layer-by-layer torch path below, with identical semantics."""
+Everything else takes the layer-by-layer torch path below, with identical semantics.
+
+Second order (``create_graph=True``: nablas = d sdf / dx and an eikonal loss on them, LoTDSDF.forward_sdf_nablas): the first
+backward is the same fused kernel, wrapped as ``FusedMLPBackwardFunction``, and the loss's backward through the nablas runs the fused
+double backward (csrc/mlp.hip k_mlp_bwd2, ``FUSED_SECOND_ORDER``) for both the fp32 and the half block (the half block's second order
+is evaluated in fp32 from the fp32 parameters, as its torch route does).  The double backward gives x no gradient (ReLU / linear
+networks: it is zero), so ``x.grad`` stays None when the eikonal term is x's only consumer."""
 from typing import List, Union
 
 import torch
@@ -16,9 +22,12 @@ import torch.nn as nn
 from nr3d_lib_amd.models.layers import DenseLayer, get_nonlinearity
 from nr3d_lib_amd.profile import profile
 
-__all__ = ['MLP', 'FCBlock', 'FusedMLPFunction', 'FusedMLPHalfFunction']
+__all__ = ['MLP', 'FCBlock', 'FusedMLPFunction', 'FusedMLPHalfFunction', 'FusedMLPBackwardFunction']
 
 USE_FUSED = True                       # False: always the layer-by-layer path (A/B measurements, debugging)
+# False: a create_graph backward of a fused block differentiates the layer-by-layer torch evaluation (the route before the fused double
+# backward; A/B measurements, tests)
+FUSED_SECOND_ORDER = True
 # Reuse of the MFMA-ordered weight copy between calls.  OFF by default: packing is one ~3 us kernel, and the only cheap
 # change detector -- the parameters' (data_ptr, _version) -- does not see in-place edits made through `.data`
 # (EMA swaps `p.data.copy_(shadow)`, weight clipping, `.data.normal_()` re-initialisation), after which a cached copy
@@ -32,9 +41,10 @@ class FusedMLPFunction(torch.autograd.Function):
     args: desc, need (bool: a gradient may be asked for -> also pack the transposed layers), x, W_0, b_0 | None, W_1, ...
 
     Higher order (``create_graph=True``, e.g. the eikonal term on nablas = d sdf / dx): backward() then runs with grad
-    mode on; in that case the gradients are produced by differentiating a layer-by-layer PyTorch evaluation of the
-    same network on the saved inputs, which autograd can differentiate again.  First-order training never takes that
-    branch."""
+    mode on and returns the outputs of ``FusedMLPBackwardFunction`` -- the same fused kernel, whose own backward is the fused
+    double backward (or, with ``FUSED_SECOND_ORDER = False`` / outside its range, the gradients of a layer-by-layer PyTorch
+    evaluation of the same network on the saved inputs, which autograd can differentiate again).  First-order training never
+    takes that branch."""
 
     @staticmethod
     def forward(ctx, desc, need, x, *params):
@@ -63,6 +73,9 @@ class FusedMLPFunction(torch.autograd.Function):
         x, packed, *flat = ctx.saved_tensors
         n_layers = len(ctx.has_bias)
         if torch.is_grad_enabled():
+            if FUSED_SECOND_ORDER and ctx.desc.second_order_fusable:
+                return (None, None, *FusedMLPBackwardFunction.apply(ctx.desc, packed, tuple(ctx.has_bias), tuple(ctx.needs_input_grad[2:]),
+                                                                    x, dL_dy.float(), *flat))
             return (None, None, *FusedMLPFunction._differentiable_backward(ctx, x, flat, dL_dy))
         dx, dWs, dbs = _mlp.backward(ctx.desc, x, dL_dy.float(), packed, need_dx=ctx.needs_input_grad[2], has_bias=ctx.has_bias)
         grads = []
@@ -131,8 +144,15 @@ class FusedMLPHalfFunction(torch.autograd.Function):
         n_layers = len(ctx.has_bias)
         if torch.is_grad_enabled():
             # differentiable form: ONE dtype for x, the (fp32) parameters and dL/dy -- F.linear(half, float) raises outside
-            # autocast; the casts are differentiable, so the graph reaches the caller's x whatever its dtype
-            out = FusedMLPFunction._differentiable_backward(ctx, x.float(), flat, dL_dy.float())
+            # autocast; the casts are differentiable, so the graph reaches the caller's x whatever its dtype.  Fused: the same fp32
+            # network through the fp32 kernels (the fp32 parameters packed here), so the semantics do not change
+            if FUSED_SECOND_ORDER and ctx.desc.second_order_fusable:
+                ws, bs = FusedMLPBackwardFunction._params(ctx.has_bias, flat)
+                packed32 = _mlp.pack(ctx.desc, ws, bs, with_backward=True)
+                out = list(FusedMLPBackwardFunction.apply(ctx.desc, packed32, tuple(ctx.has_bias), tuple(ctx.needs_input_grad[2:]),
+                                                          x.float(), dL_dy.float(), *flat))
+            else:
+                out = FusedMLPFunction._differentiable_backward(ctx, x.float(), flat, dL_dy.float())
             out[0] = None if out[0] is None else out[0].to(ctx.x_dtype)
             return (None, None, *out)
         xh = x if x.dtype == torch.float16 else x.half()
@@ -142,6 +162,102 @@ class FusedMLPHalfFunction(torch.autograd.Function):
             grads += [dWs[i] if ctx.needs_input_grad[3 + 2 * i] else None,
                       dbs[i] if (dbs[i] is not None and ctx.needs_input_grad[4 + 2 * i]) else None]
         return (None, None, None if dx is None else dx.to(ctx.x_dtype), *grads)
+
+
+class FusedMLPBackwardFunction(torch.autograd.Function):
+    """The fused first backward as a differentiable op: (dL/dx, dL/dW_0, dL/db_0, ...) = nr3d_mlp_backward(x, dL/dy) -- what the
+    create_graph branches of FusedMLPFunction / FusedMLPHalfFunction return (bit-identical to their first-order dL/dx).
+    args: desc, packed (fp32, with_backward), has_bias, need (needs_input_grad of x, W_0, b_0, ...: None for the others), x, dL_dy,
+    then the parameters that exist (W_0, b_0 if any, W_1, ...).
+
+    backward: the fused double backward (nr3d_mlp_backward_backward) when ONLY dL/dx receives a gradient (the eikonal term), no
+    third order is asked for (grad mode off) and desc.second_order_fusable -- dL/dW_l from the kernel, dL/db_l zeros (views of the
+    same pool, as the torch route's), dL/d(dL/dy) when asked for, and None for x: its gradient is zero (piecewise linear network), and
+    an [n, in] tensor of zeros would cost a full write for nothing -- so x.grad stays None when the eikonal term is x's only
+    consumer.  Every other case differentiates the layer-by-layer torch evaluation of the network, as the route before this one."""
+
+    @staticmethod
+    def _params(has_bias, flat):
+        it = iter(flat)
+        ws, bs = [], []
+        for hb in has_bias:
+            ws.append(next(it))
+            bs.append(next(it) if hb else None)
+        return ws, bs
+
+    @staticmethod
+    def forward(ctx, desc, packed, has_bias, need, x, dL_dy, *flat):
+        from nr3d_lib_amd.bindings import _mlp
+        ctx.set_materialize_grads(False)
+        dx, dWs, dbs = _mlp.backward(desc, x, dL_dy, packed, need_dx=need[0], has_bias=list(has_bias))
+        ctx.save_for_backward(x, dL_dy, packed, *flat)
+        ctx.desc, ctx.has_bias = desc, list(has_bias)
+        out = [dx]
+        for l in range(len(has_bias)):
+            out += [dWs[l] if need[1 + 2 * l] else None, dbs[l] if (dbs[l] is not None and need[2 + 2 * l]) else None]
+        ctx.produced = [o is not None for o in out]
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        from nr3d_lib_amd.bindings import _mlp
+        x, dL_dy, packed, *flat = ctx.saved_tensors
+        if all(g is None for g in grads):
+            return (None,) * (6 + len(flat))
+        need_gy, need_p = ctx.needs_input_grad[5], ctx.needs_input_grad[6:]
+        if (grads[0] is not None and all(g is None for g in grads[1:]) and not torch.is_grad_enabled()
+                and ctx.desc.second_order_fusable):
+            dgy, dWs, dbs = _mlp.backward_backward(ctx.desc, x, dL_dy, grads[0].float(), packed, need_dgy=need_gy,
+                                                   has_bias=ctx.has_bias)
+            # b_l reaches dL/dx only through the ReLU masks of layer l and above: zeros where the torch route has them, None where it
+            # has no path (a network without ReLU behind layer l)
+            n_l, relu = len(ctx.has_bias), _mlp.ACT_RELU
+            gp = []
+            for l, hb in enumerate(ctx.has_bias):
+                reach = ctx.desc.output_activation == relu or (l + 1 < n_l and ctx.desc.hidden_activation == relu)
+                gp += [dWs[l], dbs[l] if reach else None] if hb else [dWs[l]]
+            return (None, None, None, None, None, dgy, *[g if n else None for g, n in zip(gp, need_p)])
+        return (None, None, None, None, *FusedMLPBackwardFunction._torch_backward(ctx, x, dL_dy, flat, grads))
+
+    @staticmethod
+    def _torch_backward(ctx, x, dL_dy, flat, grads):
+        """gradients of sum_k <output_k, grads_k> w.r.t. (x, dL_dy, *flat) through the layer-by-layer torch evaluation of the first
+        backward.  x and dL_dy enter as detached leaves: both are downstream of the parameters (dL_dy of a loss on y), and a gradient
+        taken through the originals would run into their graph -- counting the parameters' path through them a second time (the
+        engine propagates the dL_dy gradient returned here itself) and freeing that graph.  Third order (grad mode on): the result is
+        differentiable w.r.t. the parameters; terms through x vanish for these piecewise linear networks, terms through dL_dy are
+        not propagated."""
+        from nr3d_lib_amd.bindings import _mlp
+        create = torch.is_grad_enabled()
+        need_x, need_gy = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        with torch.enable_grad():
+            xi = x.detach().requires_grad_(True)
+            gi = dL_dy.detach().requires_grad_(need_gy)
+            ws, bs = FusedMLPBackwardFunction._params(ctx.has_bias, flat)
+            h = xi
+            for l, (W, b) in enumerate(zip(ws, bs)):
+                h = torch.nn.functional.linear(h, W, b)
+                act = ctx.desc.hidden_activation if l + 1 < len(ws) else ctx.desc.output_activation
+                if act == _mlp.ACT_RELU:
+                    h = torch.relu(h)
+            slots = [xi]
+            for W, b in zip(ws, bs):
+                slots += [W, b]
+            # the first backward's outputs that exist and receive a gradient, as functions of x, the parameters and dL/dy
+            idx = [k for k, (p, g) in enumerate(zip(ctx.produced, grads)) if p and g is not None]
+            firsts = torch.autograd.grad(h, [slots[k] for k in idx], gi, create_graph=True, allow_unused=True)
+            pairs = [(f, grads[k]) for f, k in zip(firsts, idx) if f is not None]
+            inputs = [xi, gi, *flat]
+            wanted = [k for k, n in enumerate(ctx.needs_input_grad[4:]) if n]
+            got = [None] * len(inputs)
+            if pairs and wanted:
+                res = torch.autograd.grad([f for f, _ in pairs], [inputs[k] for k in wanted], [g for _, g in pairs],
+                                          create_graph=create, allow_unused=True)
+                for k, r in zip(wanted, res):
+                    got[k] = r
+        if not need_x:
+            got[0] = None
+        return got
 
 
 class MLP(nn.Module):
