@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 10
+#define NR3D_ABI_VERSION 11
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -756,6 +756,70 @@ uint64_t nr3d_sort_pairs_u32_tmp_bytes(uint32_t n_max, int batch);
 int nr3d_sort_pairs_u32(void *tmp, int batch, const uint32_t *kin0, const uint32_t *vin0, uint32_t *kout0, uint32_t *vout0,
                         const uint32_t *kin1, const uint32_t *vin1, uint32_t *kout1, uint32_t *vout1, uint32_t n_max,
                         const uint32_t *n_dev, int bits, void *stream);
+
+/* =================================================================================================
+ * Permutohedral-lattice encoder (ABI 11) -- replaces nr3d_lib.bindings._permuto
+ *   pybind surface   csrc/permuto/src/permuto.cpp:30-75
+ *   host API         csrc/permuto/include/permuto/permuto.h:87-180, csrc/permuto/src/permuto_cuda.cu
+ *   kernels          csrc/permuto/include/permuto/permuto_cuda.h:124-1030
+ * ============================================================================================== */
+#define NR3D_PERMUTO_MAX_LEVELS 24
+#define NR3D_PERMUTO_MAX_PSEUDO 512       /* n_encoded_dims <= 1024, pseudo levels of >= 2 features */
+#define NR3D_PERMUTO_N_SUPPORTED_DIMS 27
+
+typedef struct nr3d_permuto_meta {
+	double level_scales0[NR3D_PERMUTO_MAX_LEVELS];        /* res_list */
+	uint32_t level_n_feats[NR3D_PERMUTO_MAX_LEVELS];
+	uint32_t level_n_params[NR3D_PERMUTO_MAX_LEVELS];     /* hashmap_size * n_feats */
+	uint32_t level_offsets[NR3D_PERMUTO_MAX_LEVELS + 1];  /* elements, inside one table set */
+	uint32_t level_sizes[NR3D_PERMUTO_MAX_LEVELS];        /* hashmap_size (entries) */
+	uint32_t level_cols[NR3D_PERMUTO_MAX_LEVELS];         /* first output column of each level (no reference field) */
+	uint16_t map_levels[NR3D_PERMUTO_MAX_PSEUDO];         /* level of each pseudo level */
+	uint16_t map_cnt[NR3D_PERMUTO_MAX_PSEUDO];            /* index of the pseudo level inside its level */
+	uint32_t n_levels;
+	uint32_t n_pseudo_levels;
+	uint32_t n_feat_per_pseudo_lvl;  /* 4 if every width divides by 4, else 2 */
+	uint32_t n_dims_to_encode;
+	uint32_t n_encoded_dims;
+	uint32_t n_params;               /* == level_offsets[n_levels] */
+} nr3d_permuto_meta_t;
+
+/* supported_n_input_dims (permuto_cuda.cu:44): writes NR3D_PERMUTO_N_SUPPORTED_DIMS values into dims (if not NULL), returns their number */
+int nr3d_permuto_supported_n_input_dims(int32_t *dims);
+/* PermutoEncMeta::create_meta (permuto_cuda.cu:46-150).  Host only.  level_scales_multidim: optional host float [n_levels, n_input_dim]
+ * out, res / sqrt((d+1)(d+2)) computed in double.  Errors: unsupported n_input_dim, n_levels > 24, a width not divisible by 2,
+ * more than UINT32_MAX / 2 parameters, more than 1024 encoded dims. */
+int nr3d_permuto_meta_create(int32_t n_input_dim, int32_t hashmap_size, uint32_t n_levels, const double *res_list,
+                             const int32_t *n_feats_list, nr3d_permuto_meta_t *out, float *level_scales_multidim);
+
+/* Common arguments (permuto_cuda.cu:152-526):
+ *   x             float [N, D] contiguous (already multiplied by pos_scale)
+ *   params        param_dtype (NR3D_F32 | NR3D_F16) 1-D: one or more table sets of n_params elements
+ *   level_scales  DEVICE float [n_levels, D] (the meta's level_scales_multidim); level_random_shifts DEVICE float [n_levels, D] or NULL
+ *   batch_inds    int64 [N] or NULL (< 0: point skipped, its outputs 0); batch_offsets int64 [B] or NULL (element offset of each
+ *                 table set, a multiple of n_feat_per_pseudo_lvl; default b * n_params); batch_data_size > 0: b = i / batch_data_size
+ *   max_level     levels > max_level contribute 0; <= -1: nothing is launched (the bindings return zeros / None)
+ *   strides in ELEMENTS; dL_dy has the params dtype.
+ * fp16 tables are read as half and used as float; y and dL_ddLdy are fp32 sums rounded once to half; dL_dparam is always fp32. */
+
+/* permuto_enc_fwd: y[i*y_sn + e*y_se] (params dtype), fully written (skipped levels / points: 0). */
+int nr3d_permuto_fwd(const nr3d_permuto_meta_t *meta, uint32_t n_points, int param_dtype, const float *x, const void *params,
+                     const float *level_scales, const float *level_random_shifts, const int64_t *batch_inds,
+                     const int64_t *batch_offsets, uint32_t batch_data_size, int32_t max_level, void *y, int64_t y_sn, int64_t y_se,
+                     void *stream);
+/* permuto_enc_bwd: dL_dx float [N, D] contiguous, fully written (columns >= max_pos_dims and skipped points: 0), or NULL;
+ * dL_dparam float, numel of params, ZERO-INIT by the caller (hardware f32 atomics), or NULL. */
+int nr3d_permuto_bwd(const nr3d_permuto_meta_t *meta, uint32_t n_points, int param_dtype, const void *dL_dy, int64_t dldy_sn,
+                     int64_t dldy_se, const float *x, const void *params, const float *level_scales, const float *level_random_shifts,
+                     const int64_t *batch_inds, const int64_t *batch_offsets, uint32_t batch_data_size, int32_t max_level,
+                     uint32_t max_pos_dims, float *dL_dx, float *dL_dparam, void *stream);
+/* permuto_enc_bwd_bwd_input: from dL_ddLdx float [N, D] contiguous to dL_ddLdy (params dtype, [i*sn + e*se], fully written, or NULL)
+ * and dL_dparam (float, ZERO-INIT, or NULL).  x receives no second-order gradient (as in the reference). */
+int nr3d_permuto_bwd_bwd_input(const nr3d_permuto_meta_t *meta, uint32_t n_points, int param_dtype, const float *dL_ddLdx,
+                               const void *dL_dy, int64_t dldy_sn, int64_t dldy_se, const float *x, const void *params,
+                               const float *level_scales, const float *level_random_shifts, const int64_t *batch_inds,
+                               const int64_t *batch_offsets, uint32_t batch_data_size, int32_t max_level, void *dL_ddLdy,
+                               int64_t ddldy_sn, int64_t ddldy_se, float *dL_dparam, void *stream);
 
 #ifdef __cplusplus
 }
