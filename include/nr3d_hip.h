@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 11
+#define NR3D_ABI_VERSION 12
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -94,7 +94,10 @@ enum {
 	                                  * x3 route (inf - bf16(inf) = NaN in the split) where the f32 MFMA gives +-inf or NaN (inf * 0); finite rows of the
 	                                  * same batch are unaffected on both.  A ReLU pre-activation within ~1 ulp of zero may be masked differently by a
 	                                  * forward on one route and a backward recomputation on the other (the gradient of that unit at that sample only). */
-	NR3D_OPT_COUNT = 22
+	NR3D_OPT_PAIR_FOLD = 22,         /* 1: a dL/dparam call on the pair path that follows nr3d_lotd_bwd_dx_fold takes the fixed-point scale from that kernel and
+	                                  * runs as stage A, k_pair_direct (with the replica plan folded in) and stage B (with the replica sums folded in); 0: the
+	                                  * separate gmax fill, k_pair_plan and k_pair_reduce launches */
+	NR3D_OPT_COUNT = 23
 };
 int nr3d_set_option(int id, int64_t value);
 int64_t nr3d_get_option(int id);
@@ -250,6 +253,23 @@ int nr3d_lotd_bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_de
                                const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
                                int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
                                void *stream);
+/* (ABI 12) One backward call with both gradients on the pair path, in fewer launches (NR3D_OPT_PAIR_FOLD): the dL/dx kernel
+ * hands the dL/dparam launches that follow it on the same stream what they used to make in launches of their own -- the
+ * max |dL/dy| of the levels up to max_level (the fixed-point scale, bit for bit) and zeroed tickets.
+ * nr3d_lotd_pair_fold_bytes: size of that device buffer for n_points and max_level; 0 when the folded route does not apply (option
+ * off, not a pair-path meta, more points than one dL/dparam pass, levels up to max_level not the leading pseudo levels).
+ * nr3d_lotd_bwd_dx_fold: nr3d_lotd_bwd_dx (row-major dL_dy) that also fills `fold` (uninitialised, >= that many bytes; NULL or
+ * a size of 0: plain nr3d_lotd_bwd_dx).  nr3d_lotd_bwd_dparam_typed_fold: nr3d_lotd_bwd_dparam_typed with the same n_points,
+ * max_level and `fold`, enqueued after it on the same stream, before any other call that uses `fold`; results are bit for bit
+ * those of the unfolded calls. */
+uint64_t nr3d_lotd_pair_fold_bytes(const nr3d_lotd_meta_t *meta, uint32_t n_points, int32_t max_level);
+int nr3d_lotd_bwd_dx_fold(const nr3d_lotd_meta_t *meta, uint32_t n_points, int x_dtype, int param_dtype, const void *dL_dy,
+                          int64_t dldy_sn, int64_t dldy_se, const void *dy_dx, int64_t dydx_sn, int64_t dydx_se, void *dL_dx,
+                          void *dL_dy_T, int32_t max_level, void *fold, void *stream);
+int nr3d_lotd_bwd_dparam_typed_fold(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t n_points, int grad_dtype,
+                                    const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
+                                    int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
+                                    void *fold, void *stream);
 
 /* lod_bwd_bwd_input (lotd_torch_api.cu:575-729), three independent outputs:
  * (i)  dL_ddLdy[i, e] = sum_d dL_ddLdx[i, d] * dy_dx[i, e, d]      (lotd_encoding.h:1703-1727) */

@@ -510,7 +510,7 @@ def lod_bwd(lod_meta, dL_dy, input, params, dy_dx=None, batch_inds=None, batch_o
         st = H.stream_of(input)
         tag = ("dx" if need_input_grad else "") + ("dp" if need_param_grad else "")
         with _Prof(m, f"LoTD{D}-bwd-{tag}", N):
-            gT = None
+            gT = fold = None
             if need_input_grad and N > 0:
                 j, jsn, jse = _jac_view(dy_dx.detach(), N, E, D)
                 # both gradients wanted: the dL/dx kernel stages dL_dy through LDS anyway and leaves the feature-major
@@ -518,17 +518,25 @@ def lod_bwd(lod_meta, dL_dy, input, params, dy_dx=None, batch_inds=None, batch_o
                 if (need_param_grad and not batched and USE_BINNED_DPARAM and gse == 1 and gsn == E
                         and g32.data_ptr() % 16 == 0):
                     gT = H.empty((E, N), dtype=torch.float32, device=dev)
-                H.check(H.lib().nr3d_lotd_bwd_dx(
+                    # ... and, on the pair path, the fixed-point scale and zeroed tickets of the dL/dparam launches
+                    # (nr3d_lotd_pair_fold_bytes: 0 when that route does not apply)
+                    if typed:
+                        fb = H.lib().nr3d_lotd_pair_fold_bytes
+                        fb.restype = C.c_uint64
+                        nfold = int(fb(C.byref(m._cmeta()), H.u32(N), H.i32(max_level)))
+                        if nfold:
+                            fold = H.empty(((nfold + 3) // 4,), dtype=torch.int32, device=dev)
+                H.check(H.lib().nr3d_lotd_bwd_dx_fold(
                     C.byref(m._cmeta()), H.u32(N), C.c_int(H.F32), C.c_int(gcode), H.ptr(g32), H.i64(gsn),
-                    H.i64(gse), H.ptr(j), H.i64(jsn), H.i64(jse), H.ptr(dL_dx), H.ptr(gT), st))
+                    H.i64(gse), H.ptr(j), H.i64(jsn), H.i64(jse), H.ptr(dL_dx), H.ptr(gT), H.i32(max_level), H.ptr(fold), st))
             if need_param_grad and N > 0 and typed:
                 ws, wsb = _dparam_workspace(m, N, dev, 1)
                 if gT is not None:
                     g32, gsn, gse, gcode = gT, 1, N, H.F32
-                H.check(H.lib().nr3d_lotd_bwd_dparam_typed(
+                H.check(H.lib().nr3d_lotd_bwd_dparam_typed_fold(
                     C.byref(m._cmeta()), H.ptr(m._dev(dev)), H.u32(N), C.c_int(gcode), H.ptr(g32), H.i64(gsn), H.i64(gse),
                     H.ptr(_f32c(input.detach())), H.i32(max_level), C.c_int(H.F16 if native else H.F32), C.c_int(1),
-                    H.ptr(dL_dparam), H.ptr(ws), C.c_uint64(wsb), st))
+                    H.ptr(dL_dparam), H.ptr(ws), C.c_uint64(wsb), H.ptr(fold), st))
             elif need_param_grad and N > 0:
                 x32, (p32, pcode) = _f32c(input.detach()), _ptab(params)
                 nbat = _n_batches(m, p32, batch_offsets, batched)

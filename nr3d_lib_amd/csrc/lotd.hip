@@ -1427,15 +1427,24 @@ __global__ __launch_bounds__(kBlock) void k_contract_dx(uint32_t N, uint32_t E, 
 // Same contraction for a row-major dL/dy ([N, E], the layout autograd hands over): a lane reading its own row
 // touches one cache line per lane and instruction, so the block first transposes its 256 x 32 tile of dL/dy through
 // LDS (coalesced 16-byte reads), then streams the feature-major Jacobian.  Same summation order as above.
+// fold != NULL (nr3d_lotd_bwd_dx_fold): the block also writes the max |dL/dy| of its tile over the columns < gcols, as float
+// bits, to fold[slot_off + blockIdx.x], and block 0 zeroes fold[0, n_zero) -- the tickets of the pair path's dL/dparam
+// launches of the same call (lotd_pair.hip, pair_fold_layout)
 template <int D, typename GT>
 __global__ __launch_bounds__(kBlock) void k_contract_dx_rowmajor(uint32_t N, uint32_t E, const GT *__restrict__ dL_dy,
                                                                  const float *__restrict__ dydx, int64_t d_sn,
                                                                  int64_t d_se, float *__restrict__ dL_dx,
-                                                                 float *__restrict__ dL_dy_T) {
+                                                                 float *__restrict__ dL_dy_T, uint32_t *__restrict__ fold,
+                                                                 uint32_t gcols, uint32_t n_zero, uint32_t slot_off) {
 	constexpr int TE = 32;
 	__shared__ float tile[TE][kBlock + 1];
+	__shared__ uint32_t gred[kBlock / 64];
 	const uint32_t i0 = blockIdx.x * kBlock, i = i0 + threadIdx.x;
 	const uint32_t n_here = min((uint32_t)kBlock, N - i0);
+	uint32_t gbits = 0;
+	auto gm = [&](uint32_t e, float v) { if (e < gcols) gbits = max(gbits, __float_as_uint(v) & 0x7FFFFFFFu); };
+	if (fold && blockIdx.x == 0)
+		for (uint32_t k = threadIdx.x; k < n_zero; k += kBlock) fold[k] = 0u;
 	float acc[D];
 #pragma unroll
 	for (int d = 0; d < D; ++d) acc[d] = 0.0f;
@@ -1455,12 +1464,16 @@ __global__ __launch_bounds__(kBlock) void k_contract_dx_rowmajor(uint32_t N, uin
 						t = make_float4(a.x, a.y, b.x, b.y);
 					}
 					tile[e4][p] = t.x; tile[e4 + 1][p] = t.y; tile[e4 + 2][p] = t.z; tile[e4 + 3][p] = t.w;
+					if (fold) { gm(e0 + e4, t.x); gm(e0 + e4 + 1, t.y); gm(e0 + e4 + 2, t.z); gm(e0 + e4 + 3, t.w); }
 				}
 			}
 		} else {
 			for (uint32_t v = threadIdx.x; v < kBlock * te; v += kBlock) {
 				const uint32_t p = v / te, e = v - p * te;
-				if (p < n_here) tile[e][p] = to_f32<GT>(dL_dy[(size_t)(i0 + p) * E + e0 + e]);
+				if (p < n_here) {
+					tile[e][p] = to_f32<GT>(dL_dy[(size_t)(i0 + p) * E + e0 + e]);
+					if (fold) gm(e0 + e, tile[e][p]);
+				}
 			}
 		}
 		__syncthreads();
@@ -1483,6 +1496,17 @@ __global__ __launch_bounds__(kBlock) void k_contract_dx_rowmajor(uint32_t N, uin
 	if (i < N) {
 #pragma unroll
 		for (int d = 0; d < D; ++d) dL_dx[(size_t)i * D + d] = acc[d];
+	}
+	if (fold) {
+#pragma unroll
+		for (int off = 32; off >= 1; off >>= 1) gbits = max(gbits, (uint32_t)__shfl_xor((int)gbits, off, 64));
+		if ((threadIdx.x & 63u) == 0) gred[threadIdx.x >> 6] = gbits;
+		__syncthreads();
+		if (threadIdx.x == 0) {
+#pragma unroll
+			for (int k = 1; k < kBlock / 64; ++k) gbits = max(gbits, gred[k]);
+			fold[slot_off + blockIdx.x] = gbits;
+		}
 	}
 }
 
@@ -1954,9 +1978,9 @@ static int fwd_generic(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md,
 	return 0;
 }
 
-extern "C" int nr3d_lotd_bwd_dx(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int param_dtype,
-                                const void *dL_dy, int64_t g_sn, int64_t g_se, const void *dy_dx, int64_t d_sn,
-                                int64_t d_se, void *dL_dx, void *dL_dy_T, void *stream) {
+static int bwd_dx(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int param_dtype, const void *dL_dy, int64_t g_sn,
+                  int64_t g_se, const void *dy_dx, int64_t d_sn, int64_t d_se, void *dL_dx, void *dL_dy_T, int32_t max_level,
+                  void *fold_buf, void *stream) {
 	NR3D_CHECK(meta != nullptr, "LoTD: meta is NULL");
 	NR3D_CHECK(x_dtype == NR3D_F32 && (param_dtype == NR3D_F32 || param_dtype == NR3D_F16), "LoTD::bwd_dx: f32 x, f32 / f16 dL_dy");
 	if (N == 0) return 0;
@@ -1966,20 +1990,43 @@ extern "C" int nr3d_lotd_bwd_dx(const nr3d_lotd_meta_t *meta, uint32_t N, int x_
 	const bool row_major = (g_se == 1 && g_sn == (int64_t)E && ((uintptr_t)dL_dy % (g_half ? 8 : 16)) == 0);
 	NR3D_CHECK(dL_dy_T == nullptr || row_major, "LoTD::bwd_dx: dL_dy_T needs a contiguous, 16-byte aligned [N, E] dL_dy");
 	NR3D_CHECK(!g_half || (row_major && (E & 3u) == 0u), "LoTD::bwd_dx: half dL_dy must be a contiguous [N, E] tensor, E % 4 == 0");
+	// the folded dL/dparam route's hand-over buffer (pair_fold_layout; not filled when that route does not apply)
+	uint32_t gcols = 0, n_zero = 0, slot_off = 0;
+	uint32_t *fold = (fold_buf && pair_fold_layout(meta, N, max_level, gcols, n_zero, slot_off) != 0) ? (uint32_t *)fold_buf : nullptr;
+	NR3D_CHECK(!fold || row_major, "LoTD::bwd_dx_fold: the hand-over buffer needs a contiguous, 16-byte aligned [N, E] dL_dy");
 	prof::Scope ps(NR3D_PROF_LOTD_CONTRACT_DX, (hipStream_t)stream);
 	DISPATCH_D(meta->n_dims_to_encode, {
 		if (row_major && g_half)
 			hipLaunchKernelGGL((k_contract_dx_rowmajor<D, __half>), dim3(div_up(N, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, N, E,
-			                   (const __half *)dL_dy, (const float *)dy_dx, d_sn, d_se, (float *)dL_dx, (float *)dL_dy_T);
+			                   (const __half *)dL_dy, (const float *)dy_dx, d_sn, d_se, (float *)dL_dx, (float *)dL_dy_T, fold, gcols,
+			                   n_zero, slot_off);
 		else if (row_major)
 			hipLaunchKernelGGL((k_contract_dx_rowmajor<D, float>), dim3(div_up(N, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, N, E,
-			                   (const float *)dL_dy, (const float *)dy_dx, d_sn, d_se, (float *)dL_dx, (float *)dL_dy_T);
+			                   (const float *)dL_dy, (const float *)dy_dx, d_sn, d_se, (float *)dL_dx, (float *)dL_dy_T, fold, gcols,
+			                   n_zero, slot_off);
 		else
 			hipLaunchKernelGGL(k_contract_dx<D>, dim3(div_up(N, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, N, E,
 			                   (const float *)dL_dy, g_sn, g_se, (const float *)dy_dx, d_sn, d_se, (float *)dL_dx);
 	});
 	NR3D_LAUNCH_CHECK();
 	return 0;
+}
+
+extern "C" int nr3d_lotd_bwd_dx(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int param_dtype,
+                                const void *dL_dy, int64_t g_sn, int64_t g_se, const void *dy_dx, int64_t d_sn,
+                                int64_t d_se, void *dL_dx, void *dL_dy_T, void *stream) {
+	return bwd_dx(meta, N, x_dtype, param_dtype, dL_dy, g_sn, g_se, dy_dx, d_sn, d_se, dL_dx, dL_dy_T, 0, nullptr, stream);
+}
+
+extern "C" uint64_t nr3d_lotd_pair_fold_bytes(const nr3d_lotd_meta_t *meta, uint32_t N, int32_t max_level) {
+	uint32_t gcols, n_zero, slot_off;
+	return meta ? pair_fold_layout(meta, N, max_level, gcols, n_zero, slot_off) : 0;
+}
+
+extern "C" int nr3d_lotd_bwd_dx_fold(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int param_dtype, const void *dL_dy,
+                                     int64_t g_sn, int64_t g_se, const void *dy_dx, int64_t d_sn, int64_t d_se, void *dL_dx,
+                                     void *dL_dy_T, int32_t max_level, void *fold, void *stream) {
+	return bwd_dx(meta, N, x_dtype, param_dtype, dL_dy, g_sn, g_se, dy_dx, d_sn, d_se, dL_dx, dL_dy_T, max_level, fold, stream);
 }
 
 static int launch_bwd_dparam(bool second, const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N,
@@ -2050,10 +2097,9 @@ extern "C" int nr3d_lotd_pair_direct_levels(const nr3d_lotd_meta_t *meta, uint32
 	return (meta && pair_applies(meta)) ? (int)pair_direct_levels(meta, n_points) : 0;
 }
 
-extern "C" int nr3d_lotd_bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int grad_dtype,
-                                          const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
-                                          int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
-                                          void *stream) {
+static int bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int grad_dtype, const void *dL_dy,
+                            int64_t g_sn, int64_t g_se, const void *x, int32_t max_level, int out_dtype, int assign, void *dL_dparam,
+                            void *workspace, uint64_t workspace_bytes, void *fold, void *stream) {
 	if (int rc = check_common(meta, meta_dev, NR3D_F32, NR3D_F32)) return rc;
 	NR3D_CHECK((grad_dtype == NR3D_F32 || grad_dtype == NR3D_F16) && (out_dtype == NR3D_F32 || out_dtype == NR3D_F16),
 	           "LoTD::bwd_dparam_typed: f32 / f16 only");
@@ -2067,10 +2113,26 @@ extern "C" int nr3d_lotd_bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const vo
 	const Batch bb{nullptr, nullptr, 0u, meta->n_params};
 	if (int rc = dparam_binned(false, meta, meta_dev, N, nullptr, (const float *)dL_dy, g_sn, g_se, (const float *)x, nullptr, bb,
 	                           1u, max_level, (float *)dL_dparam, workspace, workspace_bytes, (hipStream_t)stream, handled, nullptr,
-	                           0, grad_dtype == NR3D_F16, out_dtype == NR3D_F16, assign != 0))
+	                           0, grad_dtype == NR3D_F16, out_dtype == NR3D_F16, assign != 0, false, (uint32_t *)fold))
 		return rc;
 	NR3D_CHECK(handled, "LoTD::bwd_dparam_typed: the pair-record path does not apply to this meta / workspace");
 	return 0;
+}
+
+extern "C" int nr3d_lotd_bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int grad_dtype,
+                                          const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
+                                          int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
+                                          void *stream) {
+	return bwd_dparam_typed(meta, meta_dev, N, grad_dtype, dL_dy, g_sn, g_se, x, max_level, out_dtype, assign, dL_dparam, workspace,
+	                        workspace_bytes, nullptr, stream);
+}
+
+extern "C" int nr3d_lotd_bwd_dparam_typed_fold(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int grad_dtype,
+                                               const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
+                                               int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
+                                               void *fold, void *stream) {
+	return bwd_dparam_typed(meta, meta_dev, N, grad_dtype, dL_dy, g_sn, g_se, x, max_level, out_dtype, assign, dL_dparam, workspace,
+	                        workspace_bytes, fold, stream);
 }
 
 extern "C" int nr3d_lotd_bwd_dparam_levels(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int x_dtype,

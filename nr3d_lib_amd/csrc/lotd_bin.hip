@@ -1100,6 +1100,7 @@ static uint32_t chunk_points(uint32_t n) {
 	const uint32_t chunk = 1u << (g_chunk_log2 ? g_chunk_log2 : 22);
 	return n < chunk ? n : chunk;
 }
+bool dparam_one_pass(uint32_t n) { return chunk_points(n) >= n; }
 
 // -------------------------------------------------------------------------------------------------
 // CP levels without records (round 3).  A 3-D CP level is three LINE tables, sum_d R_d entries in all (configs[3]: 2304 /
@@ -1793,7 +1794,7 @@ int dparam_binned(bool second, const nr3d_lotd_meta_t *meta, const void *meta_de
                   const float *dL_dy, int64_t g_sn, int64_t g_se, const float *x, const float *params, const Batch &batch,
                   uint32_t n_batches, int32_t max_level, float *dparam, void *workspace, uint64_t workspace_bytes,
                   hipStream_t st, bool &handled, const ForestDev *forest, int32_t min_level, bool g_half, bool out_half, bool assign,
-                  bool p_half) {
+                  bool p_half, uint32_t *fold) {
 	handled = false;
 	BinLayout lay;
 	const uint32_t nc = chunk_points(N);
@@ -1854,7 +1855,7 @@ int dparam_binned(bool second, const nr3d_lotd_meta_t *meta, const void *meta_de
 			need_gt();
 			if (int rc = pair_chunk(meta, md, n, xc, gc, sn, se, min_level, max_level, work_units(), dparam,
 			                        (out_half ? 1u : 0u) | (assign_now ? 2u : 0u), rec, offs, plan_buf, partial, st,
-			                        second ? vc : nullptr))
+			                        second ? vc : nullptr, (N <= nc && !second) ? fold : nullptr))
 				return rc;
 			continue;
 		}

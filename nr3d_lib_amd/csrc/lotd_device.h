@@ -736,7 +736,8 @@ int dparam_binned(bool second, const nr3d_lotd_meta_t *meta, const void *meta_de
                   const float *dL_dy, int64_t g_sn, int64_t g_se, const float *x, const float *params, const Batch &batch,
                   uint32_t n_batches, int32_t max_level, float *dparam, void *workspace, uint64_t workspace_bytes,
                   hipStream_t st, bool &handled, const ForestDev *forest = nullptr, int32_t min_level = 0, bool g_half = false,
-                  bool out_half = false, bool assign = false, bool p_half = false);
+                  bool out_half = false, bool assign = false, bool p_half = false, uint32_t *fold = nullptr);
+bool dparam_one_pass(uint32_t n_points);     // the pass covers all n_points (one chunk)
 // p_half: `params` points to __half tables (the product-type levels read their other factors from them)
 // g_half: dL_dy is __half; out_half: dparam is __half (pair path only); assign: dparam arrives UNINITIALISED -- the pair
 // path writes every element when one pass covers all levels, every other case zero-fills it first
@@ -750,7 +751,10 @@ int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_
                int64_t g_sn, int64_t g_se, int32_t min_level, int32_t max_level, uint32_t units, float *dparam,
                uint32_t out_flags /* bit 0: dparam is __half; bit 1: assign (dparam uninitialised, every element of the
                plan's levels is written) */, void *rec, uint32_t *offs, uint32_t *plan_buf, float *partial, hipStream_t st,
-               const float *vin = nullptr /* second order: dL_ddLdx [n, 3] */);
+               const float *vin = nullptr /* second order: dL_ddLdx [n, 3] */,
+               uint32_t *fold = nullptr /* hand-over buffer of the folded route (pair_fold_layout), filled by the dL/dx kernel */);
+uint64_t pair_fold_layout(const nr3d_lotd_meta_t *m, uint32_t n, int32_t max_level, uint32_t &gcols, uint32_t &zero_words,
+                          uint32_t &slot_off);
 
 }  // namespace lotd
 }  // namespace nr3d

@@ -454,20 +454,42 @@ __global__ __launch_bounds__(kPBP, kPBP == 768 ? 6 : 8) /* <= 64 VGPRs: two 64 K
 	}
 }
 
+// max of the dL/dx kernel's per-workgroup |dL/dy| maxima (float bits, nr3d_lotd_bwd_dx_fold) over a 1024-thread workgroup:
+// a max does not depend on the order, so this is bit for bit the atomicMax of pair_gmax.  `red` holds >= 16 words.
+__device__ __forceinline__ uint32_t gmax_slots(const uint32_t *__restrict__ slots, uint32_t n_slots, uint32_t *red) {
+	uint32_t m = 0;
+	for (uint32_t k = threadIdx.x; k < n_slots; k += 1024u) m = max(m, slots[k]);
+#pragma unroll
+	for (int off = 32; off >= 1; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off, 64));
+	__syncthreads();
+	if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = m;
+	__syncthreads();
+	m = 0;
+#pragma unroll
+	for (int k = 0; k < 16; ++k) m = max(m, red[k]);
+	__syncthreads();
+	return m;
+}
+
 // Records per bucket over all point blocks (one wave per bucket), and -- in the LAST workgroup to finish -- the stage-B work
 // plan: a bucket with more than total / n_units records is split into replicas over its point blocks, empty buckets
 // get no workgroup (item_start = exclusive prefix of the replica counts).  One launch instead of a totals kernel and a
 // single-workgroup planning kernel; `ticket` (zeroed with gmax) counts finished workgroups.
-__global__ __launch_bounds__(1024) void k_pair_plan(PairPlan plan, const uint32_t *__restrict__ offs_g, uint32_t n_units,
-                                                    uint32_t *__restrict__ tot, uint32_t *__restrict__ rep,
-                                                    uint32_t *__restrict__ item_start, uint32_t *__restrict__ ticket) {
+// Folded route (NR3D_OPT_PAIR_FOLD): the same work as extra workgroups of the k_pair_direct launch (`bid` of `nblk`), and the
+// last workgroup also reduces the dL/dx kernel's per-workgroup max |dL/dy| (`slots`) to the call's gmax for stage B; an empty
+// bucket then gets one work item when `empty_one` (assign mode: stage B writes its zeros, there is no k_pair_reduce).
+__device__ __forceinline__ void pair_plan_block(const PairPlan &plan, const uint32_t *__restrict__ offs_g, uint32_t n_units,
+                                                uint32_t *__restrict__ tot, uint32_t *__restrict__ rep,
+                                                uint32_t *__restrict__ item_start, uint32_t *__restrict__ ticket, uint32_t bid,
+                                                uint32_t nblk, const uint32_t *__restrict__ slots, uint32_t n_slots,
+                                                uint32_t *__restrict__ gmax_out, bool empty_one) {
 	__shared__ uint64_t red[16];
 	__shared__ uint64_t carry_s;
 	__shared__ uint32_t last_s;
 	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const uint32_t NB = plan.bucket_base[plan.n_pseudo];
 	{
-		const uint32_t fb = blockIdx.x * 16 + wave;
+		const uint32_t fb = bid * 16 + wave;
 		if (fb < NB) {
 			uint32_t q = 0;
 			while (q + 1 < plan.n_pseudo && plan.bucket_base[q + 1] <= fb) ++q;
@@ -484,11 +506,15 @@ __global__ __launch_bounds__(1024) void k_pair_plan(PairPlan plan, const uint32_
 	if (threadIdx.x == 0) {
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		last_s = (atomicAdd(ticket, 1u) == gridDim.x - 1u) ? 1u : 0u;
+		last_s = (atomicAdd(ticket, 1u) == nblk - 1u) ? 1u : 0u;
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 	}
 	__syncthreads();
 	if (!last_s) return;
+	if (slots) {
+		const uint32_t gb = gmax_slots(slots, n_slots, reinterpret_cast<uint32_t *>(red));
+		if (threadIdx.x == 0) gmax_out[0] = gb;
+	}
 	auto ld_tot = [&](uint32_t fb) { return (uint64_t)__hip_atomic_load(tot + fb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
 	uint64_t part = 0;
 	for (uint32_t fb = threadIdx.x; fb < NB; fb += 1024) part += ld_tot(fb);
@@ -507,7 +533,7 @@ __global__ __launch_bounds__(1024) void k_pair_plan(PairPlan plan, const uint32_
 		uint32_t r = 0;
 		if (fb < NB) {
 			const uint64_t t = ld_tot(fb);
-			r = t == 0 ? 0u : (uint32_t)((t + unit / 2) / unit);
+			r = t == 0 ? (empty_one ? 1u : 0u) : (uint32_t)((t + unit / 2) / unit);
 			if (t != 0 && r < 1) r = 1;
 			if (r > plan.n_blk) r = plan.n_blk;
 			rep[fb] = r;
@@ -528,6 +554,13 @@ __global__ __launch_bounds__(1024) void k_pair_plan(PairPlan plan, const uint32_
 		__syncthreads();
 	}
 	if (threadIdx.x == 0) item_start[NB] = (uint32_t)carry_s;
+}
+__global__ __launch_bounds__(1024) void k_pair_plan(PairPlan plan, const uint32_t *__restrict__ offs_g, uint32_t n_units,
+                                                    uint32_t *__restrict__ tot, uint32_t *__restrict__ rep,
+                                                    uint32_t *__restrict__ item_start, uint32_t *__restrict__ ticket,
+                                                    const uint32_t *__restrict__ slots, uint32_t n_slots, uint32_t *__restrict__ gmax_out,
+                                                    uint32_t empty_one) {
+	pair_plan_block(plan, offs_g, n_units, tot, rep, item_start, ticket, blockIdx.x, gridDim.x, slots, n_slots, gmax_out, empty_one != 0u);
 }
 
 // accumulator slot t (feature-major: t = f * 2^lg + el) of bucket b -> element of dL/dparam, nullptr outside the level
@@ -554,9 +587,8 @@ __device__ __forceinline__ void pair_st(float *p, float v, bool out_half) {
 // max|g| * 2^-min(59 - log2 n, 44) -- far below an fp32 ulp of any non-negligible entry -- and the sum is exact, so the result
 // does not depend on the order of the updates at all.  Non-finite gradients fall back to fp64 accumulation (uniform).
 struct PairFix { double scale, inv; bool on; };
-__device__ __forceinline__ PairFix pair_fix(const uint32_t *__restrict__ gmax, uint32_t sum_log2) {
+__device__ __forceinline__ PairFix pair_fix_bits(uint32_t bits, uint32_t sum_log2) {
 	PairFix f;
-	const uint32_t bits = ((cu32_t)gmax)[0];
 	f.on = bits < 0x7F800000u;
 	const int e = max((int)(bits >> 23), 1) - 126;                    // max|g| < 2^e
 	// single values stay below 2^51 (rounding trick below) -- and a "single value" may be the fp32 sum of up to 64 merged
@@ -568,9 +600,44 @@ __device__ __forceinline__ PairFix pair_fix(const uint32_t *__restrict__ gmax, u
 	f.inv = __longlong_as_double((long long)(1023 - sc) << 52);
 	return f;
 }
+__device__ __forceinline__ PairFix pair_fix(const uint32_t *__restrict__ gmax, uint32_t sum_log2) {
+	return pair_fix_bits(((cu32_t)gmax)[0], sum_log2);
+}
 __device__ __forceinline__ unsigned long long to_fix(float v, double scale) {
 	const double t = __fma_rn((double)v, scale, 0x1.8p52);            // round to nearest integer in the low mantissa bits
 	return (unsigned long long)(__double_as_longlong(t) - 0x4338000000000000LL);
+}
+
+// element t of R consecutive partial tables (stride kPLds), summed in fp32 in replica order: k_pair_reduce and the folded
+// stage B use this one sum, so both routes give the same bits
+__device__ __forceinline__ float pair_replica_sum(const float *__restrict__ part_t, uint32_t R, uint32_t kPLds) {
+	float sum = 0.0f;
+	uint32_t r0 = 0;
+	for (; r0 + 8 <= R; r0 += 8) {
+		float v[8];
+#pragma unroll
+		for (int j = 0; j < 8; ++j) v[j] = part_t[(size_t)(r0 + j) * kPLds];
+#pragma unroll
+		for (int j = 0; j < 8; ++j) sum += v[j];
+	}
+	for (; r0 < R; ++r0) sum += part_t[(size_t)r0 * kPLds];
+	return sum;
+}
+// accumulator t of direct bucket fb: dL/dparam element = (assign) or += the sum of the bucket's dp.R replica tables
+__device__ __forceinline__ void pair_direct_sum(const DirectPlan &dp, const nr3d_lotd_meta_t *__restrict__ md,
+                                                const float *__restrict__ dpart, float *__restrict__ dparam, uint32_t out_half,
+                                                uint32_t fb, uint32_t t) {
+	const bool half_out = (out_half & 1u) != 0, assign = (out_half & 2u) != 0;
+	uint32_t e = 0;
+	while (e + 1 < dp.n && dp.bucket_base[e + 1] <= fb) ++e;
+	const uint32_t b = fb - dp.bucket_base[e], q = dp.qmap[e];
+	const Lvl L = load_level(md, meta_level_of(md, q));
+	const uint32_t foff0 = meta_cnt_of(md, q) * 2u, kPLds = 2u << dp.lg;
+	if (t >= kPLds) return;
+	float *p = pair_target(L, dp.epb[e], dp.lg, foff0, b, t, dparam, half_out);
+	if (!p) return;
+	const float sum = pair_replica_sum(dpart + (size_t)fb * dp.R * kPLds + t, dp.R, kPLds);
+	pair_st(p, (assign ? 0.0f : pair_ld(p, half_out)) + sum, half_out);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -584,16 +651,27 @@ __global__ __launch_bounds__(kPAccThreads, 8) /* 8 waves per SIMD: two 64 KiB wo
                                                              const uint32_t *__restrict__ item_start,
                                                              const uint32_t *__restrict__ gmax,
                                                              float *__restrict__ partial, float *__restrict__ dparam NR3D_DBG_PARAM,
-                                                             uint32_t out_half) {
+                                                             uint32_t out_half, uint32_t *__restrict__ bticket, uint32_t n_dred,
+                                                             DirectPlan dp, const float *__restrict__ dpart) {
+	// Folded route (bticket != NULL): the first n_dred workgroups sum the direct levels' replica tables, one row of kPAccThreads
+	// accumulators each (k_pair_reduce's second branch; k_pair_direct has finished), and the last replica of a split bucket to
+	// finish sums the bucket's partial tables itself (per-bucket ticket)
 	NR3D_DBG_DECL
 	extern __shared__ __attribute__((aligned(16))) unsigned long long acc_raw[];   // [2][2^lg] 8-byte accumulators, feature-major
+	__shared__ uint32_t last_s;
+	if (blockIdx.x < n_dred) {
+		const uint32_t rows = (2u << dp.lg) / kPAccThreads;
+		pair_direct_sum(dp, md, dpart, dparam, out_half, blockIdx.x / rows, (blockIdx.x % rows) * kPAccThreads + threadIdx.x);
+		return;
+	}
+	const uint32_t item = blockIdx.x - n_dred;
 	double *acc = reinterpret_cast<double *>(acc_raw);
 	const uint32_t NB = plan.bucket_base[plan.n_pseudo];
 	const cu32_t istart = (cu32_t)item_start, irep = (cu32_t)rep_g;
-	if (blockIdx.x >= istart[NB]) return;
+	if (item >= istart[NB]) return;
 	uint32_t lo = 0, hi = NB;
-	while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (istart[mid] <= blockIdx.x) lo = mid; else hi = mid; }
-	const uint32_t fb = lo, R = irep[fb], r = blockIdx.x - istart[fb];
+	while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (istart[mid] <= item) lo = mid; else hi = mid; }
+	const uint32_t fb = lo, R = irep[fb], r = item - istart[fb];
 	uint32_t q = 0;
 	while (q + 1 < plan.n_pseudo && plan.bucket_base[q + 1] <= fb) ++q;
 	const uint32_t b = fb - plan.bucket_base[q];
@@ -702,10 +780,31 @@ __global__ __launch_bounds__(kPAccThreads, 8) /* 8 waves per SIMD: two 64 KiB wo
 		return fix ? (float)((double)(long long)acc_raw[t] * fx.inv) : (float)acc[t];
 	};
 	// flush: the only workgroup of a bucket adds its slice to dL/dparam itself; replicas store fp32 partial tables that
-	// k_pair_reduce adds in replica order (no global atomic anywhere)
+	// k_pair_reduce -- or, folded, the bucket's last replica -- adds in replica order (no float atomic anywhere)
 	if (R > 1) {
-		float *mine = partial + (size_t)blockIdx.x * kPLds;
+		float *mine = partial + (size_t)item * kPLds;
 		for (uint32_t t = threadIdx.x; t < kPLds; t += kPAccThreads) mine[t] = value(t);
+		if (!bticket) return;
+		// release (every storing wave drained, then one agent release and the ticket) / acquire in the last replica
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			last_s = (atomicAdd(bticket + fb, 1u) == R - 1u) ? 1u : 0u;
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		}
+		__syncthreads();
+		if (!last_s) return;
+		const bool half_out = (out_half & 1u) != 0, assign = (out_half & 2u) != 0;
+		const float *part0 = partial + (size_t)istart[fb] * kPLds;
+		for (uint32_t t = threadIdx.x; t < kPLds; t += kPAccThreads) {
+			float *p = pair_target(L, epb, plan.lg, foff0, b, t, dparam, half_out);
+			if (!p) continue;
+			const float sum = pair_replica_sum(part0 + t, R, kPLds);
+			pair_st(p, (assign ? 0.0f : pair_ld(p, half_out)) + sum, half_out);
+		}
 		return;
 	}
 	constexpr int kFlush = 8;
@@ -734,9 +833,22 @@ __global__ __launch_bounds__(kPAccThreads, 8) void k_pair_direct(DirectPlan dp, 
                                                                  int32_t max_level, uint32_t smooth, const float *__restrict__ x,
                                                                  const float *__restrict__ g, int64_t g_sn, int64_t g_se,
                                                                  const uint32_t *__restrict__ gmax, float *__restrict__ partial,
-                                                                 const float *__restrict__ vin_) {
+                                                                 const float *__restrict__ vin_, uint32_t plan_rows, PairPlan plan,
+                                                                 const uint32_t *__restrict__ offs_g, uint32_t n_units,
+                                                                 uint32_t *__restrict__ tot, uint32_t *__restrict__ rep,
+                                                                 uint32_t *__restrict__ item_start, uint32_t *__restrict__ ticket,
+                                                                 const uint32_t *__restrict__ slots, uint32_t n_slots,
+                                                                 uint32_t *__restrict__ gmax_out, uint32_t empty_one) {
+	// Folded route (plan_rows > 0): the last plan_rows grid rows are k_pair_plan's workgroups (stage A has finished; they run
+	// beside the second, partial round of direct workgroups -- nbk x R > two per CU -- instead of as a launch of their own), and
+	// the fixed-point scale comes from the dL/dx kernel's per-workgroup maxima (`slots`) instead of stage A's gmax word
 	extern __shared__ __attribute__((aligned(16))) unsigned long long acc_raw[];   // [2][2^lg]
 	__shared__ uint32_t queue[kPAccThreads / 64][128];                              // per wave: points waiting for the full arithmetic
+	if (blockIdx.y >= gridDim.y - plan_rows) {
+		const uint32_t bid = (blockIdx.y - (gridDim.y - plan_rows)) * gridDim.x + blockIdx.x, nblk = (plan.bucket_base[plan.n_pseudo] + 15u) / 16u;
+		if (bid < nblk) pair_plan_block(plan, offs_g, n_units, tot, rep, item_start, ticket, bid, nblk, slots, n_slots, gmax_out, empty_one != 0u);
+		return;
+	}
 	double *acc = reinterpret_cast<double *>(acc_raw);
 	const uint32_t r = blockIdx.x, fb = blockIdx.y;
 	uint32_t e = 0;
@@ -746,7 +858,7 @@ __global__ __launch_bounds__(kPAccThreads, 8) void k_pair_direct(DirectPlan dp, 
 	const Lvl L = load_level(md, level);
 	const uint32_t kPEpb = 1u << dp.lg, kPLds = 2u << dp.lg;
 	PairFix fx = {1.0, 1.0, false};
-	if constexpr (FIX) fx = pair_fix(gmax, dp.sum_log2);
+	if constexpr (FIX) fx = slots ? pair_fix_bits(gmax_slots(slots, n_slots, &queue[0][0]), dp.sum_log2) : pair_fix(gmax, dp.sum_log2);
 	const bool fix = FIX && fx.on;
 	for (uint32_t t = threadIdx.x; t < kPLds; t += kPAccThreads) acc_raw[t] = 0ull;
 	__syncthreads();
@@ -922,27 +1034,7 @@ __global__ __launch_bounds__(kPAccThreads) void k_pair_reduce(PairPlan plan, con
 		// a direct bucket has ~100 replicas to add per element: one 256-element row per workgroup (kRedRows workgroups in x per
 		// bucket and grid row), not kRedRows rows in sequence like the sparsely replicated buckets below
 		const uint32_t fb = (blockIdx.x - NB) / kRedRows, sub = (blockIdx.x - NB) % kRedRows;
-		uint32_t e = 0;
-		while (e + 1 < dp.n && dp.bucket_base[e + 1] <= fb) ++e;
-		const uint32_t b = fb - dp.bucket_base[e], q = dp.qmap[e];
-		const Lvl L = load_level(md, meta_level_of(md, q));
-		const uint32_t foff0 = meta_cnt_of(md, q) * 2u, kPLds = 2u << dp.lg;
-		const uint32_t t = (blockIdx.y * kRedRows + sub) * kPAccThreads + threadIdx.x;
-		if (t >= kPLds) return;
-		float *p = pair_target(L, dp.epb[e], dp.lg, foff0, b, t, dparam, half_out);
-		if (!p) return;
-		const float *part0 = dpart + (size_t)fb * dp.R * kPLds + t;
-		float sum = 0.0f;
-		uint32_t r0 = 0;
-		for (; r0 + 8 <= dp.R; r0 += 8) {
-			float v[8];
-#pragma unroll
-			for (int j = 0; j < 8; ++j) v[j] = part0[(size_t)(r0 + j) * kPLds];
-#pragma unroll
-			for (int j = 0; j < 8; ++j) sum += v[j];
-		}
-		for (; r0 < dp.R; ++r0) sum += part0[(size_t)r0 * kPLds];
-		pair_st(p, (assign ? 0.0f : pair_ld(p, half_out)) + sum, half_out);
+		pair_direct_sum(dp, md, dpart, dparam, out_half, fb, (blockIdx.y * kRedRows + sub) * kPAccThreads + threadIdx.x);
 		return;
 	}
 	const uint32_t fb = blockIdx.x;
@@ -962,16 +1054,7 @@ __global__ __launch_bounds__(kPAccThreads) void k_pair_reduce(PairPlan plan, con
 		if (t >= kPLds) return;
 		float *p = pair_target(L, plan.epb[q], plan.lg, foff0, b, t, dparam, half_out);
 		if (!p) continue;
-		float sum = 0.0f;
-		uint32_t r0 = 0;
-		for (; r0 + 8 <= R; r0 += 8) {
-			float v[8];
-#pragma unroll
-			for (int j = 0; j < 8; ++j) v[j] = part0[(size_t)(r0 + j) * kPLds + t];
-#pragma unroll
-			for (int j = 0; j < 8; ++j) sum += v[j];
-		}
-		for (; r0 < R; ++r0) sum += part0[(size_t)r0 * kPLds + t];
+		const float sum = pair_replica_sum(part0 + t, R, kPLds);
 		pair_st(p, (assign ? 0.0f : pair_ld(p, half_out)) + sum, half_out);
 	}
 }
@@ -1100,11 +1183,41 @@ void pair_layout(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t units, ui
 void launch_plan_items(uint32_t NB, uint32_t n_blk, uint32_t units, const uint32_t *tot, uint32_t *rep, uint32_t *item_start,
                        hipStream_t st);      // lotd_bin.hip
 
+// Hand-over buffer of the folded route (NR3D_OPT_PAIR_FOLD), words: [0] the call's gmax (written by the plan's last workgroup) |
+// [1] the plan's ticket | [kFoldHead, kFoldHead + NB) stage B's per-bucket tickets | from slot_off: max |dL/dy| of each dL/dx
+// workgroup (kBlock points) as float bits.  The dL/dx kernel fills the slots and zeroes words [0, zero_words); the dL/dparam
+// launches of the same call follow it in stream order, so no memset is needed.  Applies to a first-order call that runs the pair
+// path in ONE pass (the scale is per pass) and whose levels up to max_level are a prefix of the pseudo levels (gcols columns of
+// dL_dy: exactly what stage A's gmax covered, direct levels included); returns the buffer's bytes, 0 when it does not apply.
+constexpr uint32_t kFoldHead = 64;
+uint64_t pair_fold_layout(const nr3d_lotd_meta_t *m, uint32_t n, int32_t max_level, uint32_t &gcols, uint32_t &zero_words,
+                          uint32_t &slot_off) {
+	gcols = zero_words = slot_off = 0;
+	if (!opt::on(NR3D_OPT_PAIR_FOLD) || !m || !pair_applies(m) || n == 0 || max_level < 0 || !dparam_one_pass(n)) return 0;
+	if (2u * m->n_pseudo_levels != m->n_encoded_dims) return 0;
+	uint32_t nq = 0;
+	while (nq < m->n_pseudo_levels && (int32_t)m->map_levels[nq] <= max_level) ++nq;
+	for (uint32_t q = nq; q < m->n_pseudo_levels; ++q)
+		if ((int32_t)m->map_levels[q] <= max_level) return 0;
+	if (nq == 0) return 0;
+	PairPlan pl;
+	uint64_t ow;
+	pair_plan(m, n, 0, max_level, pl, ow);
+	gcols = 2u * nq;
+	zero_words = kFoldHead + pl.bucket_base[pl.n_pseudo];
+	slot_off = (zero_words + 63u) & ~63u;
+	return (uint64_t)(slot_off + div_up(n, (uint32_t)kBlock)) * 4u;
+}
+
 // one chunk of points: dL_dy given feature-major or with any strides (g_sn, g_se)
 int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_t n, const float *x, const float *g,
                int64_t g_sn, int64_t g_se, int32_t min_level, int32_t max_level, uint32_t units, float *dparam, uint32_t out_flags,
-               void *rec, uint32_t *offs, uint32_t *plan_buf, float *partial, hipStream_t st, const float *vin) {
-	// vin != NULL: second order (d(dL/dx)/dparam for dL_ddLdx = vin, [n, 3])
+               void *rec, uint32_t *offs, uint32_t *plan_buf, float *partial, hipStream_t st, const float *vin, uint32_t *fold) {
+	// vin != NULL: second order (d(dL/dx)/dparam for dL_ddLdx = vin, [n, 3]); fold != NULL: the folded route (pair_fold_layout)
+	uint32_t f_gcols = 0, f_zero = 0, f_slot = 0;
+	if (fold && (vin || min_level > 0 || pair_fold_layout(meta, n, max_level, f_gcols, f_zero, f_slot) == 0)) fold = nullptr;
+	const uint32_t *slots = fold ? fold + f_slot : nullptr;
+	const uint32_t n_slots = div_up(n, (uint32_t)kBlock);
 	PairPlan pl;
 	uint64_t ow;
 	pair_plan(meta, n, min_level, max_level, pl, ow);
@@ -1121,7 +1234,9 @@ int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_
 	for (uint32_t q = 0; q < pl.n_pseudo; ++q) nb_max = nb_max > pl.nb[q] ? nb_max : pl.nb[q];
 	const uint32_t NB = pl.bucket_base[pl.n_pseudo];
 	uint32_t *tot = plan_buf, *rep = plan_buf + NB, *item_start = plan_buf + 2 * (size_t)NB;
-	uint32_t *gmax = plan_buf + 3 * (size_t)NB + 2;                  // two spare words of the plan region: gmax | ticket
+	// gmax | plan ticket: two spare words of the plan region, or the hand-over buffer's head (zeroed by the dL/dx kernel)
+	uint32_t *gmax = fold ? fold : plan_buf + 3 * (size_t)NB + 2;
+	uint32_t *bticket = fold ? fold + kFoldHead : nullptr;
 	units = pair_units();
 	const size_t bin_lds_max = (size_t)1024 * 4 * 16 + (size_t)(kPMaxNb + 2) * 8;
 	static bool attr_set_dev[64] = {};
@@ -1146,14 +1261,14 @@ int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_
 		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_accum<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
 		attr_set_dev[dev_id & 63] = true;
 	}
-	NR3D_HIP_CHECK(hipMemsetAsync(gmax, 0, 2 * sizeof(uint32_t), st));      // gmax | ticket of k_pair_plan
+	if (!fold) NR3D_HIP_CHECK(hipMemsetAsync(gmax, 0, 2 * sizeof(uint32_t), st));      // gmax | ticket of k_pair_plan
 	const uint32_t bp = pair_bp();
 	const size_t bin_lds = (size_t)bp * 4 * 16 + (size_t)(nb_max + 1) * 4;     // stage | hist
 	// first order: the Dense levels' records in quad form (NR3D_PAIR_QUAD=0: pair records only)
 	const uint32_t quad_on = (!vin && pair_quad_enabled()) ? 1u : 0u;
 #define NR3D_PAIR_BIN(BP) if (vin) NR3D_PAIR_BIN_(BP, true); else NR3D_PAIR_BIN_(BP, false)
 #define NR3D_PAIR_BIN_(BP, SEC) hipLaunchKernelGGL((k_pair_bin<BP, SEC>), dim3(pl.n_blk, pl.n_pseudo), dim3(BP), bin_lds, st, pl, md, n, max_level, \
-	meta->interpolation_type, x, g, g_sn, g_se, (u32x4 *)rec, offs, gmax, dp, vin, quad_on)
+	meta->interpolation_type, x, g, g_sn, g_se, (u32x4 *)rec, offs, fold ? nullptr : gmax, dp, vin, quad_on)
 	{
 		prof::Scope ps(NR3D_PROF_LOTD_BIN, st);
 #ifdef NR3D_EXPERIMENTS
@@ -1167,11 +1282,16 @@ int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_
 	// and its replicas are summed together with stage B's (one launch less)
 	float *dpart = partial + (size_t)(units + NB_full) * (2u << pl.lg);       // behind stage B's partial tables
 	const uint32_t nbk_direct = dp.n ? dp.bucket_base[dp.n] : 0u;
+	// folded: the replica plan rides in the direct launch (grid rows behind the direct buckets)
+	const bool plan_in_direct = fold && dp.n && pl.n_pseudo;
+	const uint32_t plan_rows = plan_in_direct ? div_up(div_up(NB, 16u), dp.R) : 0u;
+	const uint32_t empty_one = (fold && (out_flags & 2u)) ? 1u : 0u;
 	if (dp.n) {
 		prof::Scope ps(NR3D_PROF_LOTD_DIRECT, st);
 		auto direct = [&](auto kern) {
-			hipLaunchKernelGGL(kern, dim3(dp.R, nbk_direct), dim3(kPAccThreads), (size_t)(16u << pl.lg), st, dp, md, n, max_level,
-			                   meta->interpolation_type, x, g, g_sn, g_se, gmax, dpart, vin);
+			hipLaunchKernelGGL(kern, dim3(dp.R, nbk_direct + plan_rows), dim3(kPAccThreads), (size_t)(16u << pl.lg), st, dp, md, n, max_level,
+			                   meta->interpolation_type, x, g, g_sn, g_se, gmax, dpart, vin, plan_rows, pl, offs, units, tot, rep, item_start,
+			                   gmax + 1, slots, n_slots, fold, empty_one);
 		};
 		if (vin) { if (pair_fixed()) direct(k_pair_direct<true, true>); else direct(k_pair_direct<false, true>); }
 		else     { if (pair_fixed()) direct(k_pair_direct<true, false>); else direct(k_pair_direct<false, false>); }
@@ -1183,9 +1303,13 @@ int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_
 		NR3D_LAUNCH_CHECK();
 		return 0;
 	}
-	hipLaunchKernelGGL(k_pair_plan, dim3(div_up(NB, 16)), dim3(1024), 0, st, pl, offs, units, tot, rep, item_start, gmax + 1);
-#define NR3D_PAIR_ACC(U, F) hipLaunchKernelGGL((k_pair_accum<U, F>), dim3(units + NB), dim3(kPAccThreads), (size_t)(16u << pl.lg), st, pl, md, \
-	(const u32x4 *)rec, offs, rep, item_start, gmax, partial, dparam NR3D_DBG_ARG(NR3D_XOPT(PAIR_DEBUG, 0)), out_flags)
+	if (!plan_in_direct)
+		hipLaunchKernelGGL(k_pair_plan, dim3(div_up(NB, 16)), dim3(1024), 0, st, pl, offs, units, tot, rep, item_start, gmax + 1, slots, n_slots,
+		                   fold, empty_one);
+	// folded: stage B also sums the direct buckets (n_dred rows of kPAccThreads accumulators, in front) and its split buckets
+	const uint32_t n_dred = fold ? nbk_direct * ((2u << pl.lg) / kPAccThreads) : 0u;
+#define NR3D_PAIR_ACC(U, F) hipLaunchKernelGGL((k_pair_accum<U, F>), dim3(n_dred + units + NB), dim3(kPAccThreads), (size_t)(16u << pl.lg), st, pl, md, \
+	(const u32x4 *)rec, offs, rep, item_start, gmax, partial, dparam NR3D_DBG_ARG(NR3D_XOPT(PAIR_DEBUG, 0)), out_flags, bticket, n_dred, dp, dpart)
 	{
 		prof::Scope ps(NR3D_PROF_LOTD_ACCUM, st);
 #ifdef NR3D_EXPERIMENTS
@@ -1194,9 +1318,10 @@ int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_
 		{ if (pair_fixed()) NR3D_PAIR_ACC(4, true); else NR3D_PAIR_ACC(4, false); }
 	}
 #undef NR3D_PAIR_ACC
-	// the replicated buckets of the record path and the direct levels' buckets are summed in ONE launch
-	hipLaunchKernelGGL(k_pair_reduce, dim3(NB + nbk_direct * kRedRows, div_up((2u << pl.lg) / kPAccThreads, kRedRows)), dim3(kPAccThreads), 0, st, pl, md, rep,
-	                   item_start, partial, dparam, out_flags, NB, dp, dpart);
+	// the replicated buckets of the record path and the direct levels' buckets are summed in ONE launch (folded: in stage B)
+	if (!fold)
+		hipLaunchKernelGGL(k_pair_reduce, dim3(NB + nbk_direct * kRedRows, div_up((2u << pl.lg) / kPAccThreads, kRedRows)), dim3(kPAccThreads), 0, st, pl, md, rep,
+		                   item_start, partial, dparam, out_flags, NB, dp, dpart);
 	NR3D_LAUNCH_CHECK();
 	return 0;
 }
