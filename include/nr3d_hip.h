@@ -80,7 +80,8 @@ enum {
 	NR3D_OPT_PACK_SCAN = 14,         /* 1: fused composite on wave prefix products; 0: serial replay */
 	NR3D_OPT_VM_LINES_DIRECT = 15,   /* 1: VM line-table gradients accumulated in LDS inside stage A, plane updates as records only (default 0: measured
 	                                  * slower -- the fp64 LDS atomics cost stage A what the smaller records save stage B) */
-	NR3D_OPT_FWD_CELL_MAJOR = 16,    /* 1: forward reads a cell-major replica of the mid Dense levels when the caller supplies one */
+	NR3D_OPT_FWD_CELL_MAJOR = 16,    /* 1: forward reads a cell-major replica of the mid Dense levels when the caller supplies one (read by no
+	                                  * kernel at present: no test sets it) */
 	NR3D_OPT_SORT_WAVE = 17,         /* 1: packed_sort with one wave per pack (bitonic); 0: one lane per pack (heapsort) */
 	NR3D_OPT_VM_DIRECT = 18,         /* 1: VM levels whose planes split into <= 4 LDS-sized bands accumulate their dL/dparam in LDS without records (k_vm_direct) */
 	NR3D_OPT_DIRECT_FIXED = 19,      /* 1: k_cp_direct and k_vm_sorted accumulate in 64-bit fixed point (scale from the workgroup's own bound on its updates); 2: k_vm_direct

@@ -82,10 +82,11 @@ static uint32_t pair_fixed() { return opt::on(NR3D_OPT_PAIR_FIXED) ? 1u : 0u; } 
 //     W'(lower) = (1 - wp) C_m - E_m,   W'(upper) = wp C_m + E_m,     C_m = a_A s_A w_B + a_B s_B w_A,  E_m = a_P w_A w_B
 // which is the SAME record form with A_f = g_f C_m and wp'_m = wp + E_m / C_m (one more weight per record, no fifth word).
 // C_m = 0 exactly (or 1e18 times smaller than E_m) is replaced by a C of that size: the products A_f (1 - wp') and A_f wp'
-// then still give -+ g_f E_m to fp32 rounding, and what is lost of g_f C_m is below 1e-18 of it.
+// then still give -+ g_f E_m to fp32 rounding, and what is lost of g_f C_m is below 1e-18 of it.  A NaN C_m (a NaN in a
+// component of dL_ddLdx) is kept, so that A_f and wp' carry it: replaced by the floor it would give a finite record.
 __device__ __forceinline__ float pair_wp2(float wp, float Cm, float Em, float &Cuse) {
 	const float floor_c = fmaxf(1e-18f * fabsf(Em), 1e-30f);
-	Cuse = fabsf(Cm) >= floor_c ? Cm : copysignf(floor_c, Cm);
+	Cuse = !(fabsf(Cm) < floor_c) ? Cm : copysignf(floor_c, Cm);
 	return __fmaf_rn(Em, __builtin_amdgcn_rcpf(Cuse), wp);   // v_rcp_f32 (1 ulp) + fma, no division sequence: 1e-7 of wp', far inside the contract
 }
 // Quad records (first order, Dense levels, quad_on): the pairs (x, y) and (x, y + 1) of a Dense level are neighbours in memory
@@ -431,8 +432,10 @@ __global__ __launch_bounds__(kPBP, kPBP == 768 ? 6 : 8) /* <= 64 VGPRs: two 64 K
 					gbits = max(gbits, __float_as_uint(g[(int64_t)i * g_sn + (int64_t)(qd * 2 + 1) * g_se]) & 0x7FFFFFFFu);
 				}
 		} else {
+			// max of |ga|, |gb| in float bits, as above: a NaN in ONE feature must win (fmaxf would return the other one, and
+			// the NaN would then go through to_fix as a large finite number instead of switching the call to fp64)
 			auto bound = [&](const Lvl &Lq, float ga, float gb) {
-				const float m = fmaxf(fabsf(ga), fabsf(gb)) * 1.5f *
+				const float m = __uint_as_float(max(__float_as_uint(ga) & 0x7FFFFFFFu, __float_as_uint(gb) & 0x7FFFFFFFu)) * 1.5f *
 				                ((float)(Lq.res[0] - 2u) * fabsf(vin[0]) + (float)(Lq.res[1] - 2u) * fabsf(vin[1]) + (float)(Lq.res[2] - 2u) * fabsf(vin[2]));
 				return __float_as_uint(m) & 0x7FFFFFFFu;
 			};
