@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 12
+#define NR3D_ABI_VERSION 13
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -69,8 +69,7 @@ enum {
 	NR3D_OPT_PAIR_FIXED = 4,         /* 1: 64-bit fixed-point LDS accumulators; 0: fp64 */
 	NR3D_OPT_FWD_PAIRLANE = 5,       /* 1: two-lane forward / Hessian kernels for 3-D Dense/Hash metas; 0: k_fwd (corner sum) */
 	NR3D_OPT_FWD_SPLIT = 6,          /* 1: mixed metas launch per level type */
-	NR3D_OPT_FWD_LDS_STAGE = 7,      /* 1: coarse Dense levels whose whole table fits LDS are served from it (k_fwd_lds); 2: also tables that fit in <= 8 slabs of
-	                                  * x-planes, from 2^19 points on (k_fwd_lds_slab: round-5 experiment, bit-identical, slower: off); 0: none */
+	NR3D_OPT_FWD_LDS_STAGE = 7,      /* 1: coarse Dense levels whose whole table fits LDS are served from it (k_fwd_lds); 0: none */
 	NR3D_OPT_HVP_LEVELS = 8,         /* 1: d(dL/dx)/dx with one lane per (point, level) when a workspace is given */
 	NR3D_OPT_HVP_PAIRLANE = 9,       /* 1: ... through the two-lane gather */
 	NR3D_OPT_HVP_SPLIT = 10,         /* 1: lane-serial d(dL/dx)/dx launches per level type */
@@ -78,27 +77,22 @@ enum {
 	NR3D_OPT_CP_DIRECT = 12,         /* 1: CP levels' dL/dparam accumulated in LDS without records */
 	NR3D_OPT_MARCH_GROUP = 13,       /* 0: lanes per ray chosen from the ray count; 1 | 16 | 32 | 64 forces */
 	NR3D_OPT_PACK_SCAN = 14,         /* 1: fused composite on wave prefix products; 0: serial replay */
-	NR3D_OPT_VM_LINES_DIRECT = 15,   /* 1: VM line-table gradients accumulated in LDS inside stage A, plane updates as records only (default 0: measured
-	                                  * slower -- the fp64 LDS atomics cost stage A what the smaller records save stage B) */
-	NR3D_OPT_FWD_CELL_MAJOR = 16,    /* 1: forward reads a cell-major replica of the mid Dense levels when the caller supplies one (read by no
-	                                  * kernel at present: no test sets it) */
-	NR3D_OPT_SORT_WAVE = 17,         /* 1: packed_sort with one wave per pack (bitonic); 0: one lane per pack (heapsort) */
-	NR3D_OPT_VM_DIRECT = 18,         /* 1: VM levels whose planes split into <= 4 LDS-sized bands accumulate their dL/dparam in LDS without records (k_vm_direct) */
-	NR3D_OPT_DIRECT_FIXED = 19,      /* 1: k_cp_direct and k_vm_sorted accumulate in 64-bit fixed point (scale from the workgroup's own bound on its updates); 2: k_vm_direct
-	                                  * too (measured slower there, twice: it is not bound by its LDS atomics); 0: fp64 */
-	NR3D_OPT_VM_SORTED = 20,         /* 1: a dL/dparam pass with a VM level of >= 2^20 entries (over its blocks) and >= 2^19 points -- or any VM level and >= 2^21 points -- sorts the POINTS by
+	NR3D_OPT_SORT_WAVE = 15,         /* 1: packed_sort with one wave per pack (bitonic); 0: one lane per pack (heapsort) */
+	NR3D_OPT_VM_DIRECT = 16,         /* 1: VM levels whose planes split into <= 4 LDS-sized bands accumulate their dL/dparam in LDS without records (k_vm_direct) */
+	NR3D_OPT_DIRECT_FIXED = 17,      /* 1: k_cp_direct and k_vm_sorted accumulate in 64-bit fixed point (scale from the workgroup's own bound on its updates); 0: fp64 */
+	NR3D_OPT_VM_SORTED = 18,         /* 1: a dL/dparam pass with a VM level of >= 2^20 entries (over its blocks) and >= 2^19 points -- or any VM level and >= 2^21 points -- sorts the POINTS by
 	                                  * (block, coordinate) and accumulates every VM level band by band in LDS, without records (lotd_sorted.hip;
 	                                  * single tables, batches and forests; a forest's small Dense levels ride along as slices); 2: whenever the geometry allows (tests); 3: as 1, VM levels only; 0: records */
-	NR3D_OPT_MLP_X3 = 21,            /* 1: the fp32 fused MLP forward runs on the bf16 MFMA with every value split into three bf16 pieces (six piece products,
+	NR3D_OPT_MLP_X3 = 19,            /* 1: the fp32 fused MLP forward runs on the bf16 MFMA with every value split into three bf16 pieces (six piece products,
 	                                  * fp32 accumulation: fp32-grade results at 2.7x the matrix rate of the f32 MFMA); 0: v_mfma_f32_32x32x2_f32.
 	                                  * Non-finite inputs: a row holding +-inf (or a magnitude above the bf16 maximum, 3.39e38) comes out as NaN on the
 	                                  * x3 route (inf - bf16(inf) = NaN in the split) where the f32 MFMA gives +-inf or NaN (inf * 0); finite rows of the
 	                                  * same batch are unaffected on both.  A ReLU pre-activation within ~1 ulp of zero may be masked differently by a
 	                                  * forward on one route and a backward recomputation on the other (the gradient of that unit at that sample only). */
-	NR3D_OPT_PAIR_FOLD = 22,         /* 1: a dL/dparam call on the pair path that follows nr3d_lotd_bwd_dx_fold takes the fixed-point scale from that kernel and
+	NR3D_OPT_PAIR_FOLD = 20,         /* 1: a dL/dparam call on the pair path that follows nr3d_lotd_bwd_dx_fold takes the fixed-point scale from that kernel and
 	                                  * runs as stage A, k_pair_direct (with the replica plan folded in) and stage B (with the replica sums folded in); 0: the
 	                                  * separate gmax fill, k_pair_plan and k_pair_reduce launches */
-	NR3D_OPT_COUNT = 23
+	NR3D_OPT_COUNT = 21
 };
 int nr3d_set_option(int id, int64_t value);
 int64_t nr3d_get_option(int id);
@@ -247,9 +241,9 @@ int nr3d_lotd_pair_path_ok(const nr3d_lotd_meta_t *meta);
  * records (levels with <= 4 buckets; 0 when the pair path does not apply or NR3D_OPT_PAIR_DIRECT is 0).  Informational: which
  * kernel serves which level (bench.py's per-kernel byte model). */
 int nr3d_lotd_pair_direct_levels(const nr3d_lotd_meta_t *meta, uint32_t n_points);
-/* which pseudo levels (bit q) nr3d_lotd_fwd serves from LDS for a batch of n_points: whole Dense tables and (*by_slab, ABI 5) Dense
- * tables staged slab by slab; 0 when the two-lane forward does not apply.  bench.py prices the forward kernels on the levels each serves. */
-uint64_t nr3d_lotd_fwd_lds_levels(const nr3d_lotd_meta_t *meta, uint32_t n_points, uint64_t *by_slab);
+/* which pseudo levels (bit q) nr3d_lotd_fwd serves from LDS for a batch of n_points: Dense levels whose whole table fits; 0 when the
+ * two-lane forward does not apply.  bench.py prices the forward kernels on the levels each serves. */
+uint64_t nr3d_lotd_fwd_lds_levels(const nr3d_lotd_meta_t *meta, uint32_t n_points);
 int nr3d_lotd_bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t n_points, int grad_dtype,
                                const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
                                int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
@@ -503,20 +497,6 @@ int nr3d_mlp_backward_backward_ok(const nr3d_mlp_desc_t *desc);
 int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, int64_t x_stride, int64_t x_feature_stride,
                                const float *dL_dy, int64_t gy_stride, const float *ddL_dx, int64_t v_stride, int64_t v_feature_stride,
                                const float *packed, float *dL_ddLdy, int64_t ggy_stride, float *const *dL_dW, void *stream);
-
-/* LoTD encode + this decoder's FORWARD in one kernel (csrc/lotd_mlp.hip; no reference counterpart -- the reference runs lod_fwd and
- * the decoder as separate ops): for the no-grad density query of the ray driver (nr3d_lib/graphics/nerf/nerf_ray_query.py:105-127),
- * which needs ONE number per marched sample.  out[i, c] for c < out_cols = column c of decoder(encode(x[i])) -- the SAME values as
- * nr3d_lotd_forward followed by nr3d_mlp_forward (bit-identical when both take the two-lane forward, i.e. with the fwd_lds_stage option off; to fp32
- * rounding of the interpolation otherwise), without the [N, n_encoded_dims] features ever reaching memory.  x [N, 3] float contiguous
- * (already in the encoder's [0, 1] range), params / param_dtype / max_level / meta_dev as nr3d_lotd_forward, packed = the decoder's
- * packed buffer (nr3d_mlp_pack), out float with row stride out_stride.  nr3d_lotd_mlp_forward_ok: 1 when the pair is inside the
- * kernel's range (3-D meta of Dense / Hash levels, 2-feature pseudo levels, <= 32 encoded dims = the decoder's input width; hidden
- * width <= 64, <= 32 outputs), else 0: the caller keeps the two calls. */
-int nr3d_lotd_mlp_forward_ok(const nr3d_lotd_meta_t *meta, const nr3d_mlp_desc_t *desc);
-int nr3d_lotd_mlp_forward(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint64_t n_points, const float *x, const void *params,
-                          int param_dtype, int32_t max_level, const nr3d_mlp_desc_t *desc, const float *packed, float *out,
-                          int64_t out_stride, uint32_t out_cols, void *stream);
 
 /* The same decoder in HALF precision on the f16 MFMA (csrc/mlp_half.hip) -- the contract of the reference's fast decoder,
  * tiny-cuda-nn's FullyFusedMLP behind nr3d_lib/models/tcnn_adapter.py:37-51,74-146 (`use_tcnn_backend`,

@@ -480,45 +480,29 @@ __device__ __forceinline__ uint32_t emit_forest(const ForestDev &fo, const Batch
 // its 72 KB stage allows two 256-thread workgroups per CU: 2 waves per SIMD against ~1 us gathers (profiles/
 // r03k_c4_counters_before_cp16.txt: VALU 30 %, LDS 17 %, L2 requests 55 % of their ceilings).  Threads are component-major
 // (a wave holds 64 consecutive points of ONE component), so the coherent-lane merge sees what it saw.
-// LINES (round 4, VM levels with SPLIT == 3): the two LINE updates of a component are not records -- a VM level's three line
-// tables are sum_d R_d entries (configs[3]: 288 / 576 / 1152), G fp64 accumulators each fit LDS many times over -- they are added
-// to a per-workgroup LDS table with ds_add_f64, exactly as k_cp_direct does for CP lines; only the component's four PLANE updates
-// are sorted and written out: 12 instead of 18 records per (point, pseudo level).  For the table to be worth flushing the
-// workgroup must see many points, so the grid is (replicas, pseudo levels) and a workgroup walks the point blocks r, r + R, ...
-// (the record slots stay indexed by block: stage B does not change); its line table goes to `lines_out` as fp32 and
-// k_vm_lines_reduce adds the replicas in order.
-constexpr uint32_t kLinesRecPerPoint = 12;
-template <int D, int G, bool SECOND, int NR, bool DH, bool FO, typename PT, int SPLIT = 1, bool LINES = false>
+template <int D, int G, bool SECOND, int NR, bool DH, bool FO, typename PT, int SPLIT = 1>
 __device__ __forceinline__ void bin_body(const BinPlan &plan, const nr3d_lotd_meta_t *__restrict__ md, uint32_t n,
                                          int32_t max_level, uint32_t smooth, const float *__restrict__ x,
                                          const float *__restrict__ vin_, const float *__restrict__ g,
                                          int64_t g_sn, int64_t g_se, const PT *__restrict__ params,
                                          const Batch &ba, const ForestDev &fo, uint32_t *__restrict__ rec,
-                                         uint32_t *__restrict__ offs_g, float *__restrict__ lines_out = nullptr,
-                                         uint32_t line_stride = 0) {
+                                         uint32_t *__restrict__ offs_g) {
 	constexpr int BP = BinCfg<G, NR>::BP;                 // points per workgroup
 	constexpr int kThr = BP * SPLIT;                      // threads per workgroup
 	constexpr int NRT = NR / SPLIT;                       // record slots per thread
-	constexpr uint32_t cap = LINES ? (uint32_t)BP * kLinesRecPerPoint : BinCfg<G, NR>::cap;
+	constexpr uint32_t cap = BinCfg<G, NR>::cap;
 	constexpr int C = 1 << D;
-	static_assert(!LINES || (SPLIT == 3 && D == 3), "line tables in LDS: the three-threads-per-point VM stage A");
-	extern __shared__ __attribute__((aligned(16))) uint32_t smem[];   // [LINES: fp64 line table |] stage[(1+G)*cap] | hist[nb + 1]
+	extern __shared__ __attribute__((aligned(16))) uint32_t smem[];   // stage[(1+G)*cap] | hist[nb + 1]
 	__shared__ uint64_t scan_lds[kThr / 64 > 0 ? kThr / 64 : 1];
 	const uint32_t ql = blockIdx.y;
 	const uint32_t q = plan.qmap[ql];
 	const uint32_t nb = plan.nb[ql];
 	const uint32_t level = meta_level_of(md, q);
 	const Lvl L = load_level(md, level);
-	const uint32_t n_line = LINES ? (L.res[0] + L.res[1] + L.res[2]) * (uint32_t)G : 0u;     // fp64 accumulators of the line table
-	double *lines = reinterpret_cast<double *>(smem);
-	uint32_t *stage = smem + 2u * (size_t)n_line;
+	uint32_t *stage = smem;
 	uint32_t *hist = stage + (size_t)(1 + G) * cap;
 	const uint32_t comp = SPLIT == 1 ? 0u : threadIdx.x / (uint32_t)BP;      // wave-uniform (BP is a multiple of 64)
-	if (LINES) for (uint32_t t = threadIdx.x; t < n_line; t += kThr) lines[t] = 0.0;
-	// (!LINES: exactly one trip, and in a form the compiler folds -- `blk < blockIdx.x + 1` kept the loop, and its invariants in
-	// 27 more registers: k_bin_vm3 went from 68 to 95 VGPRs and lost its second workgroup per CU)
-#pragma unroll 1
-	for (uint32_t blk = blockIdx.x, once = 1u; LINES ? blk < plan.n_blk : once != 0u; blk += gridDim.x, once = 0u) {
+	const uint32_t blk = blockIdx.x;
 	const uint32_t i = blk * BP + (SPLIT == 1 ? threadIdx.x : threadIdx.x % (uint32_t)BP);
 
 	for (uint32_t b = threadIdx.x; b <= nb; b += kThr) hist[b] = 0;
@@ -652,16 +636,6 @@ __device__ __forceinline__ void bin_body(const BinPlan &plan, const nr3d_lotd_me
 			if (same) n_rec = 0;                                         // merged into the head of the run
 		}
 	}
-	if constexpr (LINES) {
-		// records 4 and 5 of a component are its line's two entries: into the LDS table (merged runs: the head lane carries the sum)
-		if (active && n_rec == 6u) {
-#pragma unroll
-			for (uint32_t r = 4; r < 6; ++r)
-#pragma unroll
-				for (int f = 0; f < G; ++f) atomicAdd(&lines[(size_t)ent[r] * G + f], (double)val[r][f]);
-			n_rec = 4u;
-		}
-	}
 	if (nb <= kBallotRankBuckets) {
 		// A coarse level's table is one to four buckets: every record of the block would hit the same few histogram
 		// counters (LDS atomics on one address serialise).  Rank through ballots instead: per distinct bucket in the wave
@@ -748,13 +722,6 @@ __device__ __forceinline__ void bin_body(const BinPlan &plan, const nr3d_lotd_me
 	}
 	uint32_t *ob = offs_g + plan.offs_base[ql];
 	for (uint32_t b = threadIdx.x; b <= nb; b += kThr) ob[(size_t)b * plan.n_blk + blk] = hist[b];
-	if (LINES) __syncthreads();                          // the next block's histogram reset must not overtake these reads
-	}
-	if constexpr (LINES) {
-		__syncthreads();
-		float *mine = lines_out + ((size_t)ql * gridDim.x + blockIdx.x) * line_stride;
-		for (uint32_t t = threadIdx.x; t < n_line; t += kThr) mine[t] = (float)lines[t];
-	}
 }
 
 // PT: storage type of the tables the product-type levels read their other factors from (DH instantiations read none)
@@ -777,33 +744,6 @@ __global__ __launch_bounds__((BinCfg<G, 24>::BP * 3)) void k_bin_vm3(BinPlan pla
                                                                      Batch ba, uint32_t *__restrict__ rec,
                                                                      uint32_t *__restrict__ offs_g) {
 	bin_body<3, G, SECOND, 24, false, false, PT, 3>(plan, md, n, max_level, smooth, x, vin_, g, g_sn, g_se, params, ba, ForestDev{}, rec, offs_g);
-}
-
-// ... and with the line updates accumulated in LDS (bin_body, LINES): grid = (replicas, pseudo levels), each workgroup walks the
-// point blocks r, r + R, ...; 12 plane records per (point, pseudo level), lines_out [pseudo level][replica][line entries x G] fp32
-template <int G, bool SECOND, typename PT>
-__global__ __launch_bounds__((BinCfg<G, 24>::BP * 3), 6) /* 6 waves per SIMD = two workgroups per CU */ void k_bin_vm3l(BinPlan plan, const nr3d_lotd_meta_t *__restrict__ md, uint32_t n,
-                                                                      int32_t max_level, uint32_t smooth, const float *__restrict__ x,
-                                                                      const float *__restrict__ vin_, const float *__restrict__ g,
-                                                                      int64_t g_sn, int64_t g_se, const PT *__restrict__ params,
-                                                                      Batch ba, uint32_t *__restrict__ rec,
-                                                                      uint32_t *__restrict__ offs_g, float *__restrict__ lines_out,
-                                                                      uint32_t line_stride) {
-	bin_body<3, G, SECOND, 24, false, false, PT, 3, true>(plan, md, n, max_level, smooth, x, vin_, g, g_sn, g_se, params, ba, ForestDev{}, rec,
-	                                                      offs_g, lines_out, line_stride);
-}
-// dL/dparam of the line tables += the replicas' partial tables, replica 0 first (one thread per (line entry, feature))
-template <int G>
-__global__ __launch_bounds__(256) void k_vm_lines_reduce(BinPlan plan, const nr3d_lotd_meta_t *__restrict__ md, uint32_t R, uint32_t line_stride,
-                                                         const float *__restrict__ lines_part, float *__restrict__ dparam) {
-	const uint32_t ql = blockIdx.y, q = plan.qmap[ql];
-	const Lvl L = load_level(md, meta_level_of(md, q));
-	const uint32_t n_line = (L.res[0] + L.res[1] + L.res[2]) * (uint32_t)G, t = blockIdx.x * 256u + threadIdx.x;
-	if (t >= n_line) return;
-	const float *p0 = lines_part + (size_t)ql * R * line_stride + t;
-	float sum = 0.0f;
-	for (uint32_t r = 0; r < R; ++r) sum += p0[(size_t)r * line_stride];
-	dparam[L.off + (size_t)(t / G) * L.F + meta_cnt_of(md, q) * G + (t % G)] += sum;
 }
 
 // stage A for a forest of blocks (3-D): same sort, corner owners resolved through the octree; NR = 8 Dense / Hash,
@@ -1349,7 +1289,7 @@ template <bool SECOND, typename PT>
 __global__ __launch_bounds__(kVmDirectThreads) void k_vm_direct(VmPlan vp, const nr3d_lotd_meta_t *__restrict__ md, uint32_t n, uint32_t smooth,
                                                                 const float *__restrict__ x, const float *__restrict__ vin_,
                                                                 const float *__restrict__ g, int64_t g_sn, int64_t g_se,
-                                                                const PT *__restrict__ params, float *__restrict__ partial, uint32_t opt_fix) {
+                                                                const PT *__restrict__ params, float *__restrict__ partial) {
 	extern __shared__ __attribute__((aligned(16))) double vm_acc[];            // plane band [<= 8192 entries][2] | line d [Rd][2]
 	constexpr uint32_t kEnt = 1u << kVmDirectLg;
 	const uint32_t r = blockIdx.x, item = blockIdx.y;
@@ -1364,50 +1304,6 @@ __global__ __launch_bounds__(kVmDirectThreads) void k_vm_direct(VmPlan vp, const
 	const auto grid = make_tab(params + L.off);
 	const uint32_t band_lo = gm.plane_lo + row0 * gm.Rb;                       // first entry of this workgroup's band
 	const uint32_t i_lo = r * vp.pts_per_rep, i_hi = min(n, i_lo + vp.pts_per_rep);
-	// optional fixed-point accumulators from the workgroup's own bound, as k_cp_direct: |update| <= gmax pmax (first order),
-	// <= gmax pmax 7.5 max R vmax (second order: plane g (wo a_d dl + C_m LI) <= 4 |a| pmax, line g (w PC -+ a PI) <= 5 |a| pmax, |a| <= 1.5 R |v|)
-	double fscale = 0.0, finv = 0.0;
-	bool fix = false;
-	if (opt_fix) {
-		__shared__ uint32_t s_bound[3];
-		if (threadIdx.x < 3) s_bound[threadIdx.x] = 0u;
-		__syncthreads();
-		uint32_t gb = 0u, pb = 0u, vb = 0u;
-		for (uint32_t i = i_lo + threadIdx.x; i < i_hi; i += kVmDirectThreads) {
-#pragma unroll
-			for (uint32_t f = 0; f < 2u; ++f) gb = max(gb, __float_as_uint(g[(int64_t)i * g_sn + (int64_t)(col0 + f) * g_se]) & 0x7FFFFFFFu);
-			if (SECOND)
-#pragma unroll
-				for (int d = 0; d < 3; ++d) vb = max(vb, __float_as_uint(vin_[(size_t)i * 3 + d]) & 0x7FFFFFFFu);
-		}
-		for (uint32_t t = threadIdx.x; t < 2u * L.size; t += kVmDirectThreads)
-			pb = max(pb, __float_as_uint((float)grid[(t >> 1) * L.F + foff + (t & 1u)]) & 0x7FFFFFFFu);
-#pragma unroll
-		for (int off = 32; off >= 1; off >>= 1) {
-			gb = max(gb, (uint32_t)__shfl_xor((int)gb, off, 64)); pb = max(pb, (uint32_t)__shfl_xor((int)pb, off, 64));
-			vb = max(vb, (uint32_t)__shfl_xor((int)vb, off, 64));
-		}
-		if ((threadIdx.x & 63u) == 0u) { atomicMax(&s_bound[0], gb); atomicMax(&s_bound[1], pb); atomicMax(&s_bound[2], vb); }
-		__syncthreads();
-		float B = __uint_as_float(s_bound[0]) * __uint_as_float(s_bound[1]);
-		if (SECOND) B *= 8.0f * fmaxf((float)L.res[0], fmaxf((float)L.res[1], (float)L.res[2])) * __uint_as_float(s_bound[2]);
-		const uint32_t bb = __float_as_uint(B);
-		if (bb != 0u && bb < 0x7F000000u && B >= 1e-30f) {
-			const int e = (int)(bb >> 23) - 126;
-			uint32_t lg = 0;
-			while ((1u << lg) < vp.pts_per_rep) ++lg;
-			const int sc = min(62 - (int)lg - 3, 44) - e;
-			if (sc > -1000 && sc < 1000) {
-				fscale = __longlong_as_double((long long)(sc + 1023) << 52);
-				finv = __longlong_as_double((long long)(1023 - sc) << 52);
-				fix = true;
-			}
-		}
-	}
-	auto add = [&](double *dst, float v) {                                             // block-uniform branch
-		if (fix) atomicAdd(reinterpret_cast<unsigned long long *>(dst), (unsigned long long)(__double_as_longlong(__fma_rn((double)v, fscale, 0x1.8p52)) - 0x4338000000000000LL));
-		else atomicAdd(dst, (double)v);
-	};
 	for (uint32_t i = i_lo + threadIdx.x; i < i_hi; i += kVmDirectThreads) {
 		float xp[3], a[3], grad[2];
 #pragma unroll
@@ -1431,20 +1327,19 @@ __global__ __launch_bounds__(kVmDirectThreads) void k_vm_direct(VmPlan vp, const
 #pragma unroll
 		for (int k = 0; k < 4; ++k) {
 			double *dst = &vm_acc[(size_t)(ent[k] - band_lo) * 2u];
-			add(dst, val[k][0]);
-			add(dst + 1, val[k][1]);
+			atomicAdd(dst, (double)val[k][0]);
+			atomicAdd(dst + 1, (double)val[k][1]);
 		}
 #pragma unroll
 		for (int k = 4; k < 6; ++k) {
 			double *dst = &ln_acc[(size_t)(ent[k] - gm.line_lo) * 2u];
-			add(dst, val[k][0]);
-			add(dst + 1, val[k][1]);
+			atomicAdd(dst, (double)val[k][0]);
+			atomicAdd(dst + 1, (double)val[k][1]);
 		}
 	}
 	__syncthreads();
 	float *mine = partial + ((size_t)item * vp.R + r) * vp.stride;
-	const unsigned long long *vm_fix = reinterpret_cast<const unsigned long long *>(vm_acc);
-	for (uint32_t t = threadIdx.x; t < n_acc; t += kVmDirectThreads) mine[t] = fix ? (float)((double)(long long)vm_fix[t] * finv) : (float)vm_acc[t];
+	for (uint32_t t = threadIdx.x; t < n_acc; t += kVmDirectThreads) mine[t] = (float)vm_acc[t];
 }
 
 // dL/dparam += the replicas' tables, replica 0 first.  A band's extra row belongs to the NEXT band of the same plane: that band's
@@ -1529,14 +1424,11 @@ static uint64_t vm_direct_plan(const nr3d_lotd_meta_t *m, uint32_t n, int32_t mi
 // (the sorted-points path of large VM levels: lotd_sorted.hip, its own translation unit)
 
 // plan for the pseudo levels of record class `cls` (0 levels => n_pseudo == 0)
-// only != 0: exactly the pseudo levels of that mask, whatever their class, in blocks of `only_bp` points with `only_nr` records per
-// point (the VM levels whose line updates stay in LDS: k_bin_vm3l)
 static bool make_plan(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t n_batches, uint32_t cls, BinPlan &plan,
                       uint64_t &offs_words, int32_t min_level = 0, int32_t max_level = 0x7fffffff, bool forest = false,
-                      uint64_t skip = 0, uint64_t only = 0, uint32_t only_bp = 0, uint32_t only_nr = 0) {
+                      uint64_t skip = 0) {
 	const uint32_t D = m->n_dims_to_encode, G = m->n_feat_per_pseudo_lvl;
-	const uint32_t kBinPts = only ? only_bp : bin_points(G, cls);
-	if (only) cls = only_nr;
+	const uint32_t kBinPts = bin_points(G, cls);
 	if (m->n_pseudo_levels > kMaxPlanLevels) return false;
 	uint32_t lg = 0;
 	while ((1u << (lg + 1)) <= (uint32_t)kLdsDoubles / G) ++lg;
@@ -1548,8 +1440,7 @@ static bool make_plan(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t n_ba
 	uint64_t base = 0;
 	for (uint32_t q = 0; q < m->n_pseudo_levels; ++q) {
 		const nr3d_lotd_level_t &L = m->levels[m->map_levels[q]];
-		if (only) { if (q >= 64u || !((only >> q) & 1ull)) continue; }
-		else if (rec_class(rec_count(L.type, D, forest)) != cls) continue;
+		if (rec_class(rec_count(L.type, D, forest)) != cls) continue;
 		if (q < 64u && ((skip >> q) & 1ull)) continue;          // served without records (k_cp_direct) or by another plan
 		// levels outside the requested range get no stage-A blocks, offsets or work items (max_level schedules, the
 		// level-bucket calls of the data-parallel path)
@@ -1929,11 +1820,11 @@ int dparam_binned(bool second, const nr3d_lotd_meta_t *meta, const void *meta_de
 				need_gt();
 				auto vd_launch = [&](auto kern, auto *tab) {
 					hipLaunchKernelGGL(kern, dim3(vp.R, vp.n_items), dim3(kVmDirectThreads), (size_t)vp.stride * 8, st, vp, md, n, meta->interpolation_type, xc, vc,
-					                   gc, sn, se, tab, partial, opt::get(NR3D_OPT_DIRECT_FIXED) == 2 ? 1u : 0u);
+					                   gc, sn, se, tab, partial);
 				};
-				// (fixed-point accumulators pay in k_cp_direct, which is LDS bound: 1.29 -> 0.98 ms on configs[3]; in k_vm_direct the
-				// bound scan and the conversions cost more than they save -- slice-major 1.28 -> 1.48 ms, plane-major 5.13 -> 5.21 ms per
-				// pass: it keeps fp64 unless NR3D_OPT_DIRECT_FIXED is 2)
+				// (fp64 accumulators: fixed point pays in k_cp_direct, which is LDS bound -- 1.29 -> 0.98 ms on configs[3] -- but in
+				// k_vm_direct the bound scan and the conversions cost more than they save: slice-major 1.28 -> 1.48 ms, plane-major
+				// 5.13 -> 5.21 ms per pass)
 				{
 					prof::Scope ps(NR3D_PROF_LOTD_DIRECT, st);
 					if (p_half) {
@@ -1945,78 +1836,6 @@ int dparam_binned(bool second, const nr3d_lotd_meta_t *meta, const void *meta_de
 				hipLaunchKernelGGL(k_vm_direct_reduce, dim3(div_up(vp.stride, 256u), vp.n_items), dim3(256), 0, st, vp, md, partial, dparam);
 				NR3D_LAUNCH_CHECK();
 				cp_mask |= vmask;
-			}
-		}
-		// VM levels: the line tables' gradients accumulate in LDS inside stage A, only the plane updates travel as records
-		// (k_bin_vm3l; 12 instead of 18 records per point and pseudo level), then the usual stage B over those records
-		if (!forest && n_batches <= 1 && !batch.inds && !batch.offsets && !batch.data_size && D == 3 && G == 2 &&
-		    opt::on(NR3D_OPT_VM_LINES_DIRECT) && vm_split_enabled() && meta->n_pseudo_levels <= 64u) {
-			uint64_t vm_mask = 0;
-			uint32_t line_stride = 0;
-			for (uint32_t q = 0; q < meta->n_pseudo_levels; ++q) {
-				const nr3d_lotd_level_t &Lq = meta->levels[meta->map_levels[q]];
-				if (Lq.type != NR3D_LOD_VectorMatrix || (int32_t)meta->map_levels[q] < min_level || (int32_t)meta->map_levels[q] > max_level) continue;
-				if ((cp_mask >> q) & 1ull) continue;                        // served by k_vm_direct
-				const uint32_t nl = (Lq.res[0] + Lq.res[1] + Lq.res[2]) * G;
-				if ((uint64_t)nl * 8u > 32u * 1024u) continue;              // fp64 line table <= 32 KiB: two workgroups still share a CU
-				vm_mask |= 1ull << q;
-				line_stride = nl > line_stride ? nl : line_stride;
-			}
-			if (vm_mask) {
-				constexpr int BPL = BinCfg<2, 24>::BP;
-				BinPlan pl;
-				uint64_t ow;
-				make_plan(meta, n, n_batches, 0, pl, ow, min_level, max_level, false, cp_mask, vm_mask, (uint32_t)BPL, kLinesRecPerPoint);
-				// replicas: about four workgroups per CU in all (two are resident), never more than there are point blocks
-				uint32_t R = (4u * 256u) / pl.n_pseudo;
-				R = R < 1u ? 1u : (R > pl.n_blk ? pl.n_blk : R);
-				while (R > 1u && (uint64_t)R * pl.n_pseudo * line_stride * 4u > lay.part_bytes) --R;
-				if (pl.n_pseudo && (uint64_t)R * pl.n_pseudo * line_stride * 4u <= lay.part_bytes) {
-					uint32_t nb_max = 0;
-					for (uint32_t q = 0; q < pl.n_pseudo; ++q) nb_max = nb_max > pl.nb[q] ? nb_max : pl.nb[q];
-					const uint32_t NB = pl.bucket_base[pl.n_pseudo];
-					uint32_t *tot = plan_buf, *rep = plan_buf + NB, *item_start = plan_buf + 2 * (size_t)NB;
-					const size_t bin_lds = (size_t)line_stride * 8 + ((size_t)(1 + G) * BPL * kLinesRecPerPoint + nb_max + 1) * sizeof(uint32_t);
-					static bool lattr[64] = {};
-					int dev_id = 0;
-					NR3D_HIP_CHECK(hipGetDevice(&dev_id));
-					if (!lattr[dev_id & 63]) {
-						NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_vm3l<2, true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-						NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_vm3l<2, false, float>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-						NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_vm3l<2, true, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-						NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_vm3l<2, false, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-						NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_accum<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsDoubles * 8));
-						lattr[dev_id & 63] = true;
-					}
-					NR3D_CHECK(bin_lds <= (size_t)kBinLdsDyn, "LoTD::bwd: VM line tables do not fit the stage-A LDS budget");
-					need_gt();
-					auto vm_launch = [&](auto kern, auto *tab) {
-						hipLaunchKernelGGL(kern, dim3(R, pl.n_pseudo), dim3(BPL * 3), bin_lds, st, pl, md, n, max_level, meta->interpolation_type,
-						                   xc, vc, gc, sn, se, tab, ba, rec, offs, partial, line_stride);
-					};
-					{
-						prof::Scope ps(NR3D_PROF_LOTD_BIN, st);
-						if (p_half) {
-							if (second) vm_launch(k_bin_vm3l<2, true, __half>, (const __half *)params); else vm_launch(k_bin_vm3l<2, false, __half>, (const __half *)params);
-						} else {
-							if (second) vm_launch(k_bin_vm3l<2, true, float>, params); else vm_launch(k_bin_vm3l<2, false, float>, params);
-						}
-					}
-					// the line tables first: stage B's replicas reuse the partial-table region afterwards
-					hipLaunchKernelGGL(k_vm_lines_reduce<2>, dim3(div_up(line_stride, 256u), pl.n_pseudo), dim3(256), 0, st, pl, md, R, line_stride,
-					                   partial, dparam);
-					hipLaunchKernelGGL(k_bucket_totals, dim3(div_up(NB, 4)), dim3(256), 0, st, pl, offs, tot);
-					hipLaunchKernelGGL(k_plan_items, dim3(1), dim3(1024), 0, st, NB, pl.n_blk, work_units(), tot, rep, item_start);
-					{
-						prof::Scope ps(NR3D_PROF_LOTD_ACCUM, st);
-						hipLaunchKernelGGL((k_accum<3, 2>), dim3(work_units() + NB), dim3(kAccThreads), kLdsDoubles * 8, st, pl, md, rec, offs, rep,
-						                   item_start, ba, partial, dparam);
-					}
-					hipLaunchKernelGGL((k_reduce_partials<3, 2>), dim3(NB, kLdsDoubles / kAccThreads), dim3(kAccThreads), 0, st, pl, md, rep, item_start, ba,
-					                   partial, dparam);
-					NR3D_LAUNCH_CHECK();
-					cp_mask |= vm_mask;                          // the record classes below leave these levels out
-				}
 			}
 		}
 		for (uint32_t cls : kClasses) {

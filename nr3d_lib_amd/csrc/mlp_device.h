@@ -1,7 +1,6 @@
-// nr3d_lib_amd/csrc/mlp_device.h -- device side of the fused fp32 decoder shared between translation units (round 6): the register
-// map, the dense layers on the f32 MFMA and on the bf16 MFMA with three-piece splits, row / column loads and stores.  mlp.hip holds
-// the kernels and the host side of the decoder; lotd_mlp.hip runs the same layers behind the LoTD encoder inside one kernel.  See
-// mlp.hip's header comment for the layout.
+// nr3d_lib_amd/csrc/mlp_device.h -- device side of the fused fp32 decoder (round 6): the register map, the dense layers on the f32
+// MFMA and on the bf16 MFMA with three-piece splits, row / column loads and stores.  mlp.hip holds the kernels and the host side of
+// the decoder.  See mlp.hip's header comment for the layout.
 #pragma once
 #include "common.h"
 #include <type_traits>
@@ -452,11 +451,6 @@ __device__ __forceinline__ void prefetch_x(const float *__restrict__ p, int64_t 
 	if constexpr (XF == 2) load_cols_fast<NT>(p, stride, dim, row_clamped, lane, r);
 	else load_rows_fast<NT>(p, stride, dim, row_clamped, lane, r);
 }
-
-// host side (mlp.hip): the region of a packed decoder (nr3d_mlp_pack) the forward kernels stage in LDS -- the x3 planes when the bf16
-// route is on and they exist, else the f32 layers -- and the decoder's tile counts.  false: outside the fused kernels' range.
-bool forward_region(const nr3d_mlp_desc_t *desc, const float *packed, bool &x3, const float *&region, uint32_t &region_floats,
-                    uint32_t &in_t, uint32_t &w_t, uint32_t &out_t);
 
 }  // namespace mlp
 }  // namespace nr3d

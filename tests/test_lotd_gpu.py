@@ -167,12 +167,10 @@ def test_vm_stage_a_three_threads_per_point(oracle, dev, case, coherent, hip_opt
         x = np.clip(base + (np.linspace(0, 3e-3, x.shape[0], dtype=np.float32)[:, None] % 2e-4), 1e-6, 1 - 1e-6).astype(np.float32)
         xt = torch.from_numpy(x).to(dev)
     outs = {}
-    # "lines": three threads per point, the line tables' gradients accumulated in LDS, 12 plane records (round 4, default);
-    # "1": three threads, 18 records; "0": one thread, 18 records
+    # "1": three threads per point, 18 records; "0": one thread, 18 records
     # "direct": VM levels of <= 4 LDS-sized slices (every VM level of these small metas) accumulate in LDS without records
-    for mode, (split, lines, direct) in (("direct", (1, 1, 1)), ("lines", (1, 1, 0)), ("1", (1, 0, 0)), ("0", (0, 0, 0))):
+    for mode, (split, direct) in (("direct", (1, 1)), ("1", (1, 0)), ("0", (0, 0))):
         hip_option("vm_split", split)
-        hip_option("vm_lines_direct", lines)
         hip_option("vm_direct", direct)
         dp = _lotd.lod_bwd(m, gt, xt, pt, None, need_input_grad=False, need_param_grad=True)[1]
         dp2 = _lotd.lod_bwd_bwd_input(m, vt, gt, xt, pt, None, need_dLdinput_ddLdoutput=False, need_dLdinput_dparams=True,
@@ -181,16 +179,12 @@ def test_vm_stage_a_three_threads_per_point(oracle, dev, case, coherent, hip_opt
         outs[mode] = (dp, dp2, dpm)
     assert_close(outs["1"][0], outs["0"][0].cpu().numpy(), rel=1e-6, name="dL/dparam, 3 threads vs 1", levels=m_ref)
     assert_close(outs["1"][1], outs["0"][1].cpu().numpy(), rel=1e-6, name="d(dL/dx)/dparam, 3 threads vs 1", levels=m_ref)
-    for k, nm in enumerate(("dL/dparam", "d(dL/dx)/dparam", "dL/dparam, max_level")):
-        assert_close(outs["lines"][k], outs["1"][k].cpu().numpy(), rel=1e-6, name=f"{nm}, line tables in LDS vs records", levels=m_ref)
     assert_close(outs["1"][0], oracle.lotd_bwd_dparam(m_ref, g, x, p, accum_double=True), name="dL/dparam", levels=m_ref)
     assert_close(outs["1"][1], oracle.lotd_bwd_bwd_dparam(m_ref, v, g, x, p, accum_double=True), name="d(dL/dx)/dparam", levels=m_ref)
     for k, nm in enumerate(("dL/dparam", "d(dL/dx)/dparam", "dL/dparam, max_level")):
         assert_close(outs["direct"][k], outs["1"][k].cpu().numpy(), rel=1e-6, name=f"{nm}, VM levels without records vs records", levels=m_ref)
     assert_close(outs["direct"][0], oracle.lotd_bwd_dparam(m_ref, g, x, p, accum_double=True), name="dL/dparam (VM direct)", levels=m_ref)
     assert_close(outs["direct"][1], oracle.lotd_bwd_bwd_dparam(m_ref, v, g, x, p, accum_double=True), name="d(dL/dx)/dparam (VM direct)", levels=m_ref)
-    assert_close(outs["lines"][0], oracle.lotd_bwd_dparam(m_ref, g, x, p, accum_double=True), name="dL/dparam (lines in LDS)", levels=m_ref)
-    assert_close(outs["lines"][1], oracle.lotd_bwd_bwd_dparam(m_ref, v, g, x, p, accum_double=True), name="d(dL/dx)/dparam (lines in LDS)", levels=m_ref)
 
 
 @pytest.mark.parametrize("case", ["ngp_small", "ngp_smooth", "ngp_pair", "pair_f4"])
@@ -935,7 +929,7 @@ def test_cp_and_vm_levels_without_records(oracle, dev, case, scale, hip_option):
     g = (g * scale).astype(np.float32)
     gt = torch.from_numpy(g).to(dev)
     outs = {}
-    for mode, (direct, fixed) in (("fixed", (1, 2)), ("fp64", (1, 0)), ("records", (0, 0))):     # 2: k_vm_direct in fixed point too
+    for mode, (direct, fixed) in (("fixed", (1, 1)), ("fp64", (1, 0)), ("records", (0, 0))):
         hip_option("cp_direct", direct)
         hip_option("vm_direct", direct)
         hip_option("direct_fixed", fixed)
@@ -957,11 +951,11 @@ def test_cp_and_vm_levels_without_records(oracle, dev, case, scale, hip_option):
 
 
 @pytest.mark.parametrize("smooth,half", [(False, False), (True, False), (False, True)])
-def test_forward_lds_slabs_bit_identical(dev, hip_option, smooth, half):
-    """the three forward routes of a 3-D Dense / Hash meta -- two lanes per (point, level) through L2 (fwd_lds_stage = 0), coarse
-    Dense tables whole in LDS (1, default), and the round-5 experiment that also serves the next Dense levels from LDS slab by slab
-    (2) -- give the same bits: which route a level takes depends on the batch size, so it must never show in the result.
-    N = 2^19 + 77: above both staging thresholds, a ragged last workgroup; levels of 2 and 6 slabs (30^3, 42^3) and a cuboid one."""
+def test_forward_lds_stage_bit_identical(dev, hip_option, smooth, half):
+    """the two forward routes of a 3-D Dense / Hash meta -- two lanes per (point, level) through L2 (fwd_lds_stage = 0) and coarse
+    Dense tables whole in LDS (1, default) -- give the same bits: which route a level takes depends on the batch size, so it must
+    never show in the result.  N = 2^19 + 77: above the staging threshold, a ragged last workgroup; Dense levels too large to stage
+    (30^3, 42^3) and a cuboid one."""
     from nr3d_lib_amd.bindings import _lotd
     res = [16, 22, 30, 42, [36, 20, 50], 58, 111, 212]
     meta = _lotd.LoDMeta(3, res, [2] * 8, ["Dense"] * 6 + ["Hash"] * 2, 2 ** 16, smooth)
@@ -973,22 +967,20 @@ def test_forward_lds_slabs_bit_identical(dev, hip_option, smooth, half):
     if half:
         params = params.half()
     out = {}
-    for mode in (0, 1, 2):
+    for mode in (0, 1):
         hip_option("fwd_lds_stage", mode)
         y, j = _lotd.lod_fwd(meta, x, params, need_input_grad=True)
         y0, _ = _lotd.lod_fwd(meta, x, params, need_input_grad=False)
         assert torch.equal(y, y0), "with and without the Jacobian"
         out[mode] = (y.clone(), j.clone())
-    for mode in (1, 2):
-        assert torch.equal(out[mode][0], out[0][0]), f"y, fwd_lds_stage = {mode}"
-        assert torch.equal(out[mode][1], out[0][1]), f"dy_dx, fwd_lds_stage = {mode}"
+    assert torch.equal(out[1][0], out[0][0]), "y, fwd_lds_stage = 1"
+    assert torch.equal(out[1][1], out[0][1]), "dy_dx, fwd_lds_stage = 1"
     import ctypes
     from nr3d_lib_amd import _hip as H
     H.lib().nr3d_lotd_fwd_lds_levels.restype = ctypes.c_uint64
-    by_slab = ctypes.c_uint64(0)
-    hip_option("fwd_lds_stage", 2)
-    mask = H.lib().nr3d_lotd_fwd_lds_levels(ctypes.byref(meta._cmeta()), ctypes.c_uint32(n), ctypes.byref(by_slab))
-    assert mask == 0b011111 and by_slab.value == 0b011100, (bin(mask), bin(by_slab.value))    # 58^3 needs 15 slabs: left to the two-lane kernel
+    hip_option("fwd_lds_stage", 1)
+    mask = H.lib().nr3d_lotd_fwd_lds_levels(ctypes.byref(meta._cmeta()), ctypes.c_uint32(n))
+    assert mask == 0b000011, bin(mask)                 # 16^3 and 22^3 fit LDS whole; 30^3 and up take the two-lane kernel
 
 
 @pytest.mark.parametrize("case", ["ngp_pair", "ngp_small"])
@@ -1046,64 +1038,11 @@ def test_loss_scale_changes_no_bit(dev, monkeypatch):
     assert float((a - b).abs().max()) <= 2.0 ** -24, "dL/dgrid: subnormal results differ by at most one subnormal step (double rounding of the scaled protocol)"
 
 
-@pytest.mark.parametrize("case,dims", [("ngp_small", (32, 16)), ("ngp_smooth", (64, 64, 1)), ("pair_f4", (32, 32, 16)),
-                                       ("hash_npow2_f2", (48, 5)), ("ngp_pair", (32, 16))])
-@pytest.mark.parametrize("ptype", ["float", "half"])
-def test_encode_and_decode_in_one_kernel(oracle, dev, hip_option, case, dims, ptype):
-    """round 6: nr3d_lotd_mlp_forward (encode -> decoder forward, only the asked columns leave) against the two calls it replaces.
-    With the two-lane forward serving every level (fwd_lds_stage = 0) the features are the same bits and so is the decoder's output,
-    on both decoder routes (f32 MFMA / bf16 x3); against the oracle's features + a float64 decoder to 1e-5 of the column scale."""
-    from nr3d_lib_amd.bindings import _lotd, _mlp
-    # (a hash table whose size is not a power of two, 2-feature levels: the % path of the gather)
-    D, res, nf, types, T, smooth = (3, [9, 17, 33], [2, 2, 2], ["Dense", "Hash", "Hash"], 3001, False) if case == "hash_npow2_f2" else LOTD_CASES[case]
-    m_ref = oracle.lotd_create_meta(D, res, nf, types, T, smooth)
-    m = _lotd.LoDMeta(D, res, nf, types, T, smooth)
-    E = m.n_encoded_dims
-    n = 70001                                               # not a multiple of 64: a ragged last round
-    x, p, _, _ = lotd_inputs(m_ref.as_dict(), n, 5)
-    rng = np.random.default_rng(9)
-    widths = [E, *dims]
-    ws = [torch.from_numpy((rng.standard_normal((b, a)) / np.sqrt(a)).astype(np.float32)).to(dev) for a, b in zip(widths[:-1], widths[1:])]
-    bs = [torch.from_numpy((rng.standard_normal(b) * 0.1).astype(np.float32)).to(dev) for b in widths[1:]]
-    desc = _mlp.MLPDesc(widths, _mlp.ACT_RELU, _mlp.ACT_NONE)
-    assert _lotd.lod_mlp_fwd_ok(m, desc)
-    packed = _mlp.pack(desc, ws, bs)
-    xt = torch.from_numpy(x).to(dev)
-    pt = torch.from_numpy(p).to(dev)
-    pt = pt.half() if ptype == "half" else pt
-    hip_option("fwd_lds_stage", 0)
-    for x3 in (1, 0):
-        hip_option("mlp_x3", x3)
-        y, _ = _lotd.lod_fwd(m, xt, pt)
-        want = _mlp.forward(desc, y.float(), packed)
-        for cols in (None, 1):
-            got = _lotd.lod_mlp_fwd(m, xt, pt, desc, packed, out_cols=cols)
-            assert got.shape == (n, widths[-1] if cols is None else 1)
-            assert_equal(got, want[:, :got.shape[1]], f"x3={x3} cols={cols}: fused vs two calls")
-    # and against the oracle chain in float64
-    feat = oracle.lotd_fwd(m_ref, x, pt.float().cpu().numpy())[0].astype(np.float64)
-    h = feat
-    for l, (w, b) in enumerate(zip(ws, bs)):
-        h = h @ w.double().cpu().numpy().T + b.double().cpu().numpy()
-        if l + 1 < len(ws):
-            h = np.maximum(h, 0)
-    got = _lotd.lod_mlp_fwd(m, xt, pt, desc, packed)
-    assert_close(got, h, rel=2e-5 if ptype == "float" else 2e-3, name="fused encode + decode vs oracle + float64 decoder")
-
-
 def test_encode_and_decode_range_and_module(dev):
-    """outside the kernel's range the check says no and the module takes the two ops; inside, LoTD.forward_decoded == decoder(encoding)"""
-    from nr3d_lib_amd.bindings import _lotd, _mlp
+    """LoTD.forward_decoded == decoder(encoding), sliced to the asked columns, without gradients"""
     from nr3d_lib_amd.models.blocks import MLP
     from nr3d_lib_amd.models.grid_encodings.lotd import LoTD
-    from nr3d_lib_amd.models.grid_encodings.lotd import lotd as lotd_mod
-    D, res, nf, types, T, smooth = LOTD_CASES["mixed"]
-    m = _lotd.LoDMeta(D, res, nf, types, T, smooth)
-    assert not _lotd.lod_mlp_fwd_ok(m, _mlp.MLPDesc([m.n_encoded_dims, 32, 4]))          # VM / CP levels
     D, res, nf, types, T, smooth = LOTD_CASES["ngp_small"]
-    m = _lotd.LoDMeta(D, res, nf, types, T, smooth)
-    assert not _lotd.lod_mlp_fwd_ok(m, _mlp.MLPDesc([m.n_encoded_dims, 128, 4]))         # hidden width 128
-    assert not _lotd.lod_mlp_fwd_ok(m, _mlp.MLPDesc([m.n_encoded_dims + 1, 32, 4]))      # not the encoder's width
     enc = LoTD(3, res, nf, types, hashmap_size=T, dtype=torch.float)
     torch.manual_seed(3)
     grid = (torch.randn(enc.n_params) * 0.1).to(dev)
@@ -1111,12 +1050,6 @@ def test_encode_and_decode_range_and_module(dev):
     x = torch.rand(3, 1111, 3, device=dev)
     with torch.no_grad():
         want = dec(enc(x, grid))
-    assert lotd_mod.FUSE_DECODED is False              # measured slower on the full loop (round 6): the two ops are the default
-    for fuse in (True, False):
-        lotd_mod.FUSE_DECODED = fuse
-        try:
-            got = enc.forward_decoded(x, grid, dec, out_cols=2)
-        finally:
-            lotd_mod.FUSE_DECODED = False
-        assert got.shape == (3, 1111, 2) and not got.requires_grad
-        assert_close(got.reshape(-1, 2), want[..., :2].reshape(-1, 2).cpu().numpy(), rel=1e-5, name=f"forward_decoded fuse={fuse}")
+    got = enc.forward_decoded(x, grid, dec, out_cols=2)
+    assert got.shape == (3, 1111, 2) and not got.requires_grad
+    assert_close(got.reshape(-1, 2), want[..., :2].reshape(-1, 2).cpu().numpy(), rel=1e-5, name="forward_decoded")

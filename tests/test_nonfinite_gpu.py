@@ -49,7 +49,7 @@ def _metas(oracle, case):
         from nr3d_lib_amd.models.grid_encodings.lotd import gen_ngp_cfg
         cfg = gen_ngp_cfg()
         args = (3, cfg["lod_res"], cfg["lod_n_feats"], cfg["lod_types"], cfg["hashmap_size"], False)
-    elif case == "lds_slabs":           # test_lotd_gpu.py test_forward_lds_slabs_bit_identical's meta
+    elif case == "lds_stage":           # test_lotd_gpu.py test_forward_lds_stage_bit_identical's meta
         args = (3, [16, 22, 30, 42, [36, 20, 50], 58, 111, 212], [2] * 8, ["Dense"] * 6 + ["Hash"] * 2, 2 ** 16, False)
     else:
         args = LOTD_CASES[case]
@@ -183,7 +183,7 @@ def test_generic_dparam(oracle, inputs, dev, monkeypatch, case, binned, kind):
 
 
 # (cp_direct, vm_direct, direct_fixed, vm_sorted)
-DIRECT_ROUTES = [(1, 1, 0, 0), (1, 1, 1, 0), (1, 1, 2, 0), (0, 0, 1, 0), (0, 0, 0, 0), (1, 1, 1, 2), (1, 1, 0, 2)]
+DIRECT_ROUTES = [(1, 1, 0, 0), (1, 1, 1, 0), (0, 0, 1, 0), (0, 0, 0, 0), (1, 1, 1, 2), (1, 1, 0, 2)]
 
 
 @pytest.mark.parametrize("case", ["mixed", "mixed_smooth"])
@@ -378,27 +378,24 @@ def _lds_levels(m, n):
     from nr3d_lib_amd import _hip as H
     f = H.lib().nr3d_lotd_fwd_lds_levels
     f.restype = ctypes.c_uint64
-    by_slab = ctypes.c_uint64(0)
-    mask = int(f(ctypes.byref(m._cmeta()), ctypes.c_uint32(n), ctypes.byref(by_slab)))
-    return mask, int(by_slab.value)
+    return int(f(ctypes.byref(m._cmeta()), ctypes.c_uint32(n)))
 
 
 def test_forward_nan_table_entry_lds_staged(oracle, inputs, dev, hip_option):
-    """the LDS-staged forward (fwd_lds_stage 1: coarse Dense tables whole in LDS; 2: also the next ones slab by slab) engages
-    from 2^18 / 2^19 points on: at 2^19 + 77 points the staged levels read their NaN entry from LDS, checked to be the case"""
+    """the LDS-staged forward (fwd_lds_stage 1: coarse Dense tables whole in LDS) engages from 2^18 points on: at 2^19 + 77
+    points the staged levels read their NaN entry from LDS, checked to be the case"""
     n = (1 << 19) + 77
-    _lotd, m_ref, m, (x, p, g, v), _ = inputs("lds_slabs", n=n)
+    _lotd, m_ref, m, (x, p, g, v), _ = inputs("lds_stage", n=n)
     pp = _nan_per_level(m, p)
     xt, pt = _t(dev, x, pp)
     masks = {}
-    for lds in (0, 1, 2):
+    for lds in (0, 1):
         hip_option("fwd_lds_stage", lds)
         masks[lds] = _lds_levels(m, n)
-    assert masks[0] == (0, 0)
-    assert masks[2] == (0b011111, 0b011100), masks[2]                 # levels 0-1 whole, 2-4 in slabs
-    assert masks[1] == (masks[2][0] & ~masks[2][1], 0) and masks[1][0] != 0, masks[1]
+    assert masks[0] == 0
+    assert masks[1] == 0b000011, bin(masks[1])                        # levels 0-1 whole
     outs = {}
-    for lds in (0, 1, 2):
+    for lds in (0, 1):
         hip_option("fwd_lds_stage", lds)
         outs[lds] = _lotd.lod_fwd(m, xt, pt, need_input_grad=True)
     chunk = 1 << 17

@@ -71,8 +71,8 @@ class DemoField(nn.Module):
 
     def query_density(self, x, **kw):
         if not torch.is_grad_enabled() and isinstance(self.density, MLP):
-            # the pruning query (no grad): only the density column leaves the decoder (LoTD.forward_decoded: in one kernel with the
-            # encoder when lotd.FUSE_DECODED is on, else the two calls with the decoder's last layer cut to that column)
+            # the pruning query (no grad): only the density column leaves the decoder (LoTD.forward_decoded: the two calls with the
+            # decoder's last layer cut to that column)
             h0 = self.encoding.forward_decoded(torch.addcmul(self._half, x, self._half), self.grid, self.density, out_cols=1)
             return torch.nn.functional.softplus(h0[..., 0].float()) * 20.0
         return self._h(x)[0]
