@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 13
+#define NR3D_ABI_VERSION 14
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -821,6 +821,68 @@ int nr3d_permuto_bwd_bwd_input(const nr3d_permuto_meta_t *meta, uint32_t n_point
                                const float *level_scales, const float *level_random_shifts, const int64_t *batch_inds,
                                const int64_t *batch_offsets, uint32_t batch_data_size, int32_t max_level, void *dL_ddLdy,
                                int64_t ddldy_sn, int64_t ddldy_se, float *dL_dparam, void *stream);
+
+/* =================================================================================================
+ * Sphere tracer (ABI 14) -- replaces nr3d_lib.bindings._sphere_trace
+ *   pybind surface   csrc/sphere_trace/src/entry.cu:14-47
+ *   segment march    csrc/sphere_trace/include/sphere_trace/dense_grid.cuh:38-67,117-200, csrc/sphere_trace/src/ray_march.cu:11-129
+ *   tracer           csrc/sphere_trace/src/sphere_tracer.cu:11-121,177-399, include/sphere_trace/sphere_tracer.cuh
+ * Common arguments: rays_o / rays_d float [n_rays, 3], rays_near / rays_far float [n_rays], all contiguous; grid_occ bool (one byte)
+ * [res0, res1, res2] over [-1, 1]^3; segs float [n_segs, 2] (t_enter, t_exit).  Status codes: ALIVE 0, HIT 1, OUT 2.
+ * The tracer's state is a structure of arrays inside ONE caller-allocated block of nr3d_sphere_trace_state_bytes(cap) bytes per
+ * buffer side (the caller keeps two and swaps them at every compaction), the hit list one block of nr3d_sphere_trace_hits_bytes(cap)
+ * bytes; cap = the number of rays given to nr3d_sphere_trace_init, the same in every later call.  Neither needs initialising.  tmp:
+ * nr3d_sphere_trace_tmp_bytes(n) bytes of device scratch.  `totals` / `total`: int64 words the last kernel stores with system scope
+ * (pinned host memory + nr3d_wait_host_words, or device memory).  n == 0 is an ordinary input everywhere: nothing is launched, totals
+ * are zeroed.  Not ported: the segs_endpoint_distances variant of init / advance and the debug outputs of ray_march. */
+uint64_t nr3d_sphere_trace_state_bytes(uint32_t cap);
+uint64_t nr3d_sphere_trace_hits_bytes(uint32_t cap);
+uint64_t nr3d_sphere_trace_tmp_bytes(uint32_t n);
+/* ray_march phase 1 + the compaction of the rays with >= 1 segment: valid_rays_idx int64 [n_rays] (the first totals[1] rows written,
+ * ascending), pack_infos int64 [n_rays, 2] (begin, count) of those rays (same rows), totals = {segments, valid rays}. */
+int nr3d_sphere_trace_march_count(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *rays_near,
+                                  const float *rays_far, const int32_t grid_res[3], const uint8_t *grid_occ, int64_t *valid_rays_idx,
+                                  int64_t *pack_infos, int64_t *totals, void *tmp, void *stream);
+/* ray_march phase 2 over the n_valid compacted rays: segs_pack_info int32 [n_valid, 2] (offset, count), segs float [total_segs, 2],
+ * segs_endpoints float [total_segs, 2, 3] or NULL; all fully written. */
+int nr3d_sphere_trace_march_write(uint32_t n_valid, const float *rays_o, const float *rays_d, const float *rays_near,
+                                  const float *rays_far, const int32_t grid_res[3], const uint8_t *grid_occ,
+                                  const int64_t *valid_rays_idx, const int64_t *pack_infos, int64_t total_segs, int32_t *segs_pack_info,
+                                  float *segs, float *segs_endpoints, void *stream);
+/* init_rays: n rows of (valid_rays_idx int64, segs_pack_info int32 [n, 2]) -> state rows [0, n), query positions included.  A row with
+ * a ray index outside [0, n_rays), an empty pack or one outside [0, n_segs) starts as OUT. */
+int nr3d_sphere_trace_init(uint32_t n, uint32_t n_rays, int64_t n_segs, const float *rays_o, const float *rays_d,
+                           const int64_t *valid_rays_idx, const int32_t *segs_pack_info, const float *segs, void *state, uint32_t cap,
+                           void *stream);
+/* advance_rays: one step of the n buffered rays from distances float [n] (rows that are not ALIVE are left alone), and the next query
+ * positions (inside the state block) in the same launch.  A non-finite distance ends its ray as OUT. */
+int nr3d_sphere_trace_advance(uint32_t n, const float *rays_o, const float *rays_d, const float *distances, const float *segs, void *state,
+                              uint32_t cap, float zero_offset, float distance_scale, float min_step, float hit_threshold, void *stream);
+/* compact_rays: ALIVE rows of state_in move to state_out in their order, HIT rows are appended to hits at row n_hit in their order;
+ * totals = {alive rows, new hits}. */
+int nr3d_sphere_trace_compact(uint32_t n, void *state_in, void *state_out, uint32_t cap, void *hits, uint32_t n_hit, int64_t *totals,
+                              void *tmp, void *stream);
+/* get_rays(HIT) / get_rays(ALIVE): pos, dir float [n, 3], idx int64 [n], t float [n], n_steps int32 [n]; ALIVE also status uint8,
+ * debug_flag int8, hit_region_infos float [n, 4], hit_seg_regions int32 [n, 2], seg_idxs / seg_end_idxs int32 [n]; fully written. */
+int nr3d_sphere_trace_gather_hit(uint32_t n_hit, const float *rays_o, const float *rays_d, const void *hits, uint32_t cap, float *pos,
+                                 float *dir, int64_t *idx, float *t, int32_t *n_steps, void *stream);
+int nr3d_sphere_trace_gather_alive(uint32_t n, const float *rays_o, const float *rays_d, const void *state, uint32_t cap, float *pos,
+                                   float *dir, int64_t *idx, float *t, int32_t *n_steps, uint8_t *status, int8_t *debug_flag,
+                                   float *hit_region_infos, int32_t *hit_seg_regions, int32_t *seg_idxs, int32_t *seg_end_idxs,
+                                   void *stream);
+/* sample_on_segments phase 1 + the scan: pack_info int32 [n, 2] (offset, count), total[0] = samples; phase 2: samples_offset /
+ * n_samples int32 [n], sample_depths float [total], sample_positions float [total, 3]; fully written. */
+int nr3d_sphere_trace_sample_count(uint32_t n, float step_size, const float *segs, const void *state, uint32_t cap, int32_t *pack_info,
+                                   int64_t *total, void *tmp, void *stream);
+int nr3d_sphere_trace_sample_write(uint32_t n, float step_size, const float *rays_o, const float *rays_d, const float *segs,
+                                   const void *state, uint32_t cap, const int32_t *pack_info, int64_t total, int32_t *samples_offset,
+                                   int32_t *n_samples, float *sample_depths, float *sample_positions, void *stream);
+/* trace_on_samples: the first (d >= 0, d <= 0) bracket of every buffered ray's samples becomes a hit, appended at row n_hit in the
+ * rays' order (n_hit + n <= cap); totals = {0, new hits}. */
+int nr3d_sphere_trace_trace_on_samples(uint32_t n, const void *state, uint32_t cap, const int32_t *samples_offset,
+                                       const int32_t *n_samples, int64_t total, const float *sample_depths,
+                                       const float *sample_distances, void *hits, uint32_t n_hit, int64_t *totals, void *tmp,
+                                       void *stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@ from types import SimpleNamespace
 from typing import Dict, List, Tuple
 
 import torch
+import torch.nn.functional as F
 
 from nr3d_lib_amd.graphics.nerf.nerf_utils import packed_alpha_to_vw
 from nr3d_lib_amd.graphics.neus.neus_utils import (neus_packed_sdf_to_alpha, neus_packed_sdf_to_upsample_alpha,
@@ -24,7 +25,7 @@ from nr3d_lib_amd.graphics.raysample import (batch_sample_step_linear, batch_sam
                                              batch_sample_step_wrt_sqrt_depth, packed_sample_cdf)
 from nr3d_lib_amd.profile import profile
 
-__all__ = ['neus_ray_query_march_occ_multi_upsample', 'neus_ray_query_march_occ_multi_upsample_compressed',
+__all__ = ['neus_ray_query_sphere_trace', 'neus_ray_query_march_occ_multi_upsample', 'neus_ray_query_march_occ_multi_upsample_compressed',
            'neus_ray_query_march_occ_multi_upsample_compressed_strategy']
 
 _RAY_ATTRS = (('ts', 'rays_ts'), ('fidx', 'rays_fidx'), ('bidx', 'rays_bidx'), ('pix', 'rays_pix'),
@@ -363,3 +364,65 @@ def neus_ray_query_march_occ_multi_upsample_compressed_strategy(model, ray_teste
     """declared but unimplemented in the reference as well (neus_ray_query.py:1106-1117 raises after resolving inv_s)"""
     _ = model.forward_inv_s() if kwargs.get('forward_inv_s') is None else kwargs['forward_inv_s']
     raise NotImplementedError
+
+
+def neus_ray_query_sphere_trace(
+        model, ray_tested: Dict[str, torch.Tensor], *,
+        # Common params
+        with_rgb: bool = True, with_normal: bool = True, perturb: bool = False, nablas_has_grad: bool = False,
+        # Distinct params
+        debug: bool = False, **sphere_trace_cfg) -> Tuple[dict, dict]:
+    """Surface rendering by sphere tracing: one hit per ray instead of volume samples (nr3d_lib/graphics/neus/neus_ray_query.py:41-130).
+    The model's occupancy grid (``model.accel.occ.resolution`` / ``.occ_grid``) becomes the tracer's ``DenseGrid``, ``model.forward_sdf``
+    its distance function; ``sphere_trace_cfg`` goes to ``graphics.sphere_trace.SphereTracer``.  The volume buffer is batched with
+    ``num_per_hit=1``: ``t``, ``opacity_alpha`` (1 on the hit rays), ``net_x`` (the hit points), ``nablas`` / ``rgb`` from
+    ``model.forward`` at the hit points, ``rays_bidx_hit`` for batched models.
+    With zero rays, and with no ray hit, the result is the ``(empty_buffer, {})`` pair -- the reference returns the bare buffer from
+    the first of its two early exits, which its callers cannot unpack."""
+    _check_model(model)
+    use_ts, use_fidx, use_bidx = _flag(model, 'use_ts'), _flag(model, 'use_fidx'), _flag(model, 'use_bidx')
+    use_pix = (_flag(model, 'use_pix') and with_rgb) or _flag(model, 'fwd_sdf_use_pix')
+    use_h_appear = (_flag(model, 'use_h_appear') and with_rgb) or _flag(model, 'fwd_sdf_use_h_appear')
+    use_view_dirs = (_flag(model, 'use_view_dirs') and with_rgb) or _flag(model, 'fwd_sdf_use_view_dirs')
+
+    empty_buffer = dict(type="empty", rays_inds_hit=[])
+    if ray_tested["num_rays"] == 0:
+        return empty_buffer, {}
+    assert ray_tested["rays_o"].dim() == 2
+
+    from nr3d_lib_amd.graphics.sphere_trace import DenseGrid, SphereTracer
+    model.tracer = SphereTracer(DenseGrid(*model.accel.occ.resolution, model.accel.occ.occ_grid), **sphere_trace_cfg)
+    rays_to_trace = {"rays_o": ray_tested["rays_o"], "rays_d": ray_tested["rays_d"], "near": ray_tested["near"],
+                     "far": ray_tested["far"]}
+    ret_st = model.tracer.trace(rays_to_trace, model.forward_sdf, print_debug_log=debug)
+    hit = ret_st["idx"]
+    if hit.numel() == 0:
+        return empty_buffer, {}
+
+    with profile("Acquire volume buffer"):
+        near, rays_o = ray_tested["near"], ray_tested["rays_o"]
+        volume_buffer = dict(type="batched", rays_inds_hit=ray_tested["rays_inds"], num_per_hit=1,
+                             t=torch.zeros_like(near)[:, None], opacity_alpha=torch.zeros_like(near)[:, None])
+        volume_buffer["opacity_alpha"][hit] = 1.
+        if use_bidx:
+            volume_buffer['rays_bidx_hit'] = torch.full_like(near, -1)[:, None]
+            volume_buffer['rays_bidx_hit'][hit] = ray_tested['rays_bidx'][hit]
+        if with_rgb or with_normal:
+            fwd_kwargs = dict(x=ret_st["pos"], nablas_has_grad=nablas_has_grad, with_rgb=with_rgb, with_normal=with_normal)
+            # Extra infos attached to each ray
+            for on, (arg, key) in zip((use_ts, use_fidx, use_bidx, use_pix, use_h_appear), _RAY_ATTRS):
+                if on:
+                    fwd_kwargs[arg] = ray_tested[key][hit]
+            if use_view_dirs:
+                fwd_kwargs['v'] = F.normalize(ret_st["dir"], 2, -1)
+            net_out = model.forward(**fwd_kwargs)
+            volume_buffer["net_x"] = torch.zeros_like(rays_o)[:, None]
+            volume_buffer["net_x"][hit] = ret_st["pos"][:, None]
+            if "nablas" in net_out:
+                volume_buffer["nablas"] = torch.zeros_like(rays_o)[:, None]
+                volume_buffer["nablas"][hit] = net_out["nablas"][:, None].to(volume_buffer["nablas"].dtype)
+            if "rgb" in net_out:
+                volume_buffer["rgb"] = rays_o.new_zeros(rays_o.shape[0], 1, net_out["rgb"].shape[-1])
+                volume_buffer["rgb"][hit] = net_out["rgb"][:, None].to(volume_buffer["rgb"].dtype)
+        details = {'render.num_per_ray': 1}
+    return volume_buffer, details
