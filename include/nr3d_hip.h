@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 14
+#define NR3D_ABI_VERSION 15
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -883,6 +883,37 @@ int nr3d_sphere_trace_trace_on_samples(uint32_t n, const void *state, uint32_t c
                                        const int32_t *n_samples, int64_t total, const float *sample_depths,
                                        const float *sample_distances, void *hits, uint32_t n_hit, int64_t *totals, void *tmp,
                                        void *stream);
+
+/* =================================================================================================
+ * Embedders -- replace nr3d_lib.bindings._shencoder and nr3d_lib.bindings._freqencoder
+ *   pybind surfaces   externals/shencoder/bindings.cpp, externals/freqencoder/bindings.cpp
+ *   kernels           externals/shencoder/shencoder.cu, externals/freqencoder/freqencoder.cu
+ * Element-wise, one launch each, no workspace, no atomics, no host wait.  B == 0 is a no-op.
+ * ============================================================================================== */
+
+/* Real spherical harmonics of x [B, 3] as polynomials on all of R^3 (no normalisation): y[b, l*l + l + m], l < degree, degree 1..8,
+ * D must be 3.  dtype NR3D_F32 or NR3D_F16 for every tensor of the call; arithmetic in fp32, one rounding at the store.
+ * y: rows of degree^2 elements, y_stride elements apart (>= degree^2: a column slice of a wider row-major buffer is a valid output; the
+ * other columns are not touched).  dy_dx: NULL, or [B, 3, degree^2] (the reference's layout) to also store the Jacobian. */
+int nr3d_sh_encode_fwd(uint64_t B, uint32_t D, uint32_t degree, int dtype, const void *x, void *y, int64_t y_stride, void *dy_dx, void *stream);
+/* grad_x[b, d] = sum_c grad[b, c] dY_c/dx_d (accumulate != 0: added to what grad_x holds).  dy_dx == NULL: the derivatives are
+ * recomputed from x; otherwise they are read from the stored Jacobian and x may be NULL.  grad rows grad_stride elements apart. */
+int nr3d_sh_encode_bwd(uint64_t B, uint32_t D, uint32_t degree, int dtype, const void *grad, int64_t grad_stride, const void *x,
+                       const void *dy_dx, void *grad_x, int accumulate, void *stream);
+
+/* Sinusoidal embedding of x [B, D], float32, D >= 1, C = D + 2 D n_freq, n_freq <= 24 (from f = 24 on, 2^f x + pi/2 has no phase left
+ * in fp32), B * C < 2^31: y[b, c] = x[b, c] for c < D, else sin(2^f x[b, d] + k pi/2) with col = c / D - 1, d = c % D, f = col / 2,
+ * k = col % 2, the argument formed in fp32.  y rows y_stride (>= C) elements apart. */
+int nr3d_freq_encode_fwd(uint64_t B, uint32_t D, uint32_t n_freq, uint32_t C, const float *x, float *y, int64_t y_stride, void *stream);
+/* grad_x [B, D] (overwritten) from grad [B, C] and the forward's outputs y, no trigonometry:
+ * grad_x[d] = g[d] + sum_f 2^f (g[f,0,d] y[f,1,d] - g[f,1,d] y[f,0,d]). */
+int nr3d_freq_encode_bwd(uint64_t B, uint32_t D, uint32_t n_freq, uint32_t C, const float *grad, const float *y, int64_t y_stride,
+                         float *grad_x, void *stream);
+/* The backward of nr3d_freq_encode_bwd.  v = dL/d(grad_x) [B, D]; outputs, each optional (NULL) and overwritten:
+ * d_grad [B, C] = dL/dgrad:  v[d];  v[d] 2^f y[f,1,d];  -v[d] 2^f y[f,0,d]
+ * d_x [B, D]    = dL/dx:     -v[d] sum_f 4^f (g[f,0,d] y[f,0,d] + g[f,1,d] y[f,1,d])      (needs grad). */
+int nr3d_freq_encode_bwd_bwd(uint64_t B, uint32_t D, uint32_t n_freq, uint32_t C, const float *v, const float *grad, const float *y,
+                             int64_t y_stride, float *d_grad, float *d_x, void *stream);
 
 #ifdef __cplusplus
 }

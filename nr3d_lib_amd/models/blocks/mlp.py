@@ -19,10 +19,11 @@ from typing import List, Union
 import torch
 import torch.nn as nn
 
+from nr3d_lib_amd.models.embedders import get_embedder
 from nr3d_lib_amd.models.layers import DenseLayer, get_nonlinearity
 from nr3d_lib_amd.profile import profile
 
-__all__ = ['MLP', 'FCBlock', 'FusedMLPFunction', 'FusedMLPHalfFunction', 'FusedMLPBackwardFunction']
+__all__ = ['MLP', 'FCBlock', 'MLPNet', 'FusedMLPFunction', 'FusedMLPHalfFunction', 'FusedMLPBackwardFunction']
 
 USE_FUSED = True                       # False: always the layer-by-layer path (A/B measurements, debugging)
 # False: a create_graph backward of a fused block differentiates the layer-by-layer torch evaluation (the route before the fused double
@@ -398,3 +399,20 @@ class MLP(nn.Module):
 
 
 FCBlock = MLP
+
+
+class MLPNet(MLP):
+    """``MLP`` behind an input embedder (nr3d_lib/models/blocks/mlp.py:130-165): ``embed_cfg`` goes to ``get_embedder``, the network
+    takes the embedded width.  The embedding is a contiguous fp32 tensor, so the block still runs on the fused decoder kernels."""
+
+    def __init__(self, in_features: int, out_features: int, *, embed_cfg: dict = {'type': 'identity'}, D: int = 4,
+                 W: Union[int, List[int]] = 128, skips: List[int] = [], activation: Union[str, dict] = 'relu',
+                 output_activation: Union[str, dict] = None, weight_norm=False, dtype: Union[str, torch.dtype] = None,
+                 device: torch.device = None):
+        embedder, embedded_in_ch = get_embedder(embed_cfg, in_features)
+        super().__init__(embedded_in_ch, out_features, D=D, W=W, skips=skips, activation=activation, output_activation=output_activation,
+                         weight_norm=weight_norm, dtype=dtype, device=device)
+        self.embedder = embedder
+
+    def forward(self, x: torch.Tensor, return_last: bool = False):
+        return super().forward(self.embedder(x), return_last=return_last)
