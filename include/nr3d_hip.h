@@ -60,7 +60,8 @@ int nr3d_prof_read(int id, double *total_ms, uint32_t *n_intervals, int reset);
  * entries are relaxed atomics, so a concurrent set/launch is not a data race, but two host threads that A/B DIFFERENT values at the
  * same time see each other's choice -- results stay correct (both implementations give the same result), measurements do not.
  * Production callers never set one: every default is the measured-fastest path.
- * Measurement knobs and timing experiments are NOT options: they exist only in a -DNR3D_EXPERIMENTS build. */
+ * The library has no build-time variants and reads nothing from the environment; the timing decompositions of the past are
+ * recorded under profiles/. */
 enum {
 	NR3D_OPT_LOTD_PAIR = 0,          /* 1: pair / quad records for dL/dparam of 3-D Dense/Hash metas (lotd_pair.hip); 0: corner records */
 	NR3D_OPT_PAIR_QUAD = 1,          /* 1: Dense levels of the pair path as quad records */

@@ -1,8 +1,6 @@
 // nr3d_lib_amd/csrc/host_api.hip -- host-only parts of the C ABI: error string, ABI version and the
 // LoTD meta builder (reference: LoDMeta::create_meta, csrc/lotd/src/lotd_torch_api.cu:29-230).
 #include "common.h"
-#include <stdlib.h>
-#include <utility>
 #include <string.h>
 #include <limits>
 #include <chrono>
@@ -61,20 +59,6 @@ static const bool g_val_init = [] {                 // the defaults are written 
 	for (int i = 0; i < NR3D_OPT_COUNT; ++i) g_val[i].store(kDefault[i], std::memory_order_relaxed);
 	return true;
 }();
-
-#ifdef NR3D_EXPERIMENTS
-// measurement knobs of the experiments build: NR3D_<NAME> from the environment, looked up once per name
-int64_t experiment_env(const char *name, int64_t dflt) {
-	static std::mutex mu;
-	static std::vector<std::pair<const char *, int64_t>> seen;
-	std::lock_guard<std::mutex> lk(mu);
-	for (const auto &kv : seen) if (kv.first == name) return kv.second;        // string literals: pointer identity
-	const char *e = getenv(name);
-	const int64_t v = e ? (int64_t)atoll(e) : dflt;
-	seen.emplace_back(name, v);
-	return v;
-}
-#endif
 }  // namespace opt
 
 }  // namespace nr3d

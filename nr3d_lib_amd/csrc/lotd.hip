@@ -309,7 +309,7 @@ template <> __device__ __forceinline__ void store_nt<__half>(__half *p, float v)
 // =============================================================================================
 // The kernel (round 3 form).
 //
-// Measured on the round-2 kernel (tools/exp_fwd_variants.py, profiles/r03a_fwd_experiments.txt): with its gathers REMOVED
+// Measured on the round-2 kernel (profiles/r03a_fwd_experiments.txt): with its gathers REMOVED
 // it still took 236 of its 355 us -- 201 VALU instructions per wave at 4 cycles each (160 us of SIMD time) plus 64-bit
 // address arithmetic for every access.  This form keeps the gather pattern (4.25 requests per point and level) and cuts
 // the instruction stream to about a third (the no-gather time drops to 131 us, the no-gather-no-store time to 106):
@@ -331,8 +331,6 @@ template <> __device__ __forceinline__ void store_nt<__half>(__half *p, float v)
 // the same channels -- the times add instead of overlapping.  More groups in flight (SUB 1 / 2 / 4 / 8: 358 / 352 / 358
 // / 355 us at 2^20), plain instead of non-temporal stores (373), a row pitch that is not a power of two (no change), x
 // through the scalar cache (+14 us on the round-2 kernel) do not move it.
-// `dbg` exists in a -DNR3D_EXPERIMENTS build only (timing experiments, results wrong by design): bit 0 no stores, bit 1 no
-// gathers, bit 2 no x loads; in the production build it is the constant 0 and these branches fold away.
 // =============================================================================================
 constexpr int kPlSub = 2;                          // 32-point groups per wave
 // one work item = pseudo level q x the block's `chunk` of kPlPts * SUB points
@@ -340,8 +338,7 @@ template <bool DYDX, typename PT, int SUB>
 __device__ __forceinline__ void pl_item(uint32_t q, uint32_t chunk, const nr3d_lotd_meta_t *__restrict__ md, uint32_t N,
                                         int32_t max_level, uint32_t smooth, const float *__restrict__ x,
                                         const PT *__restrict__ params, PT *__restrict__ y, int64_t y_sn, int64_t y_se,
-                                        float *__restrict__ dydx, int64_t d_sn, int64_t d_se NR3D_DBG_PARAM) {
-	NR3D_DBG_DECL
+                                        float *__restrict__ dydx, int64_t d_sn, int64_t d_se) {
 	constexpr uint32_t kGroup = 32;                        // points per wave and sub-step
 	constexpr uint32_t kPts = kPlPts * SUB;                // points per block
 	const uint32_t lane = threadIdx.x & 63u, side = lane & 1u, pl = lane >> 1;
@@ -371,11 +368,7 @@ __device__ __forceinline__ void pl_item(uint32_t q, uint32_t chunk, const nr3d_l
 		uint32_t off = pl * 12u;
 		if (gc + kGroup > N) { const uint32_t i = gc + pl; off = ((i < N ? i : N - 1u) - gc) * 12u; }
 		const float *px = reinterpret_cast<const float *>(xb + off);
-		if (dbg & 4u) {
-			uint32_t h = (gc + pl) * 2654435761u + 12345u;
-#pragma unroll
-			for (int d = 0; d < 3; ++d) { h ^= h >> 16; h *= 0x7feb352dU; h ^= h >> 15; h *= 0x846ca68bU; h ^= h >> 16; xp[u][d] = (float)(h >> 8) * (1.0f / 16777216.0f); }
-		} else { xp[u][0] = px[0]; xp[u][1] = px[1]; xp[u][2] = px[2]; }
+		xp[u][0] = px[0]; xp[u][1] = px[1]; xp[u][2] = px[2];
 	}
 	float yv[SUB], gx[SUB], gy[SUB], gz[SUB];
 #pragma unroll
@@ -428,20 +421,8 @@ __device__ __forceinline__ void pl_item(uint32_t q, uint32_t chunk, const nr3d_l
 #pragma unroll
 				for (int m = 0; m < 4; ++m) off[m] = e[m] * stride;
 			}
-			if ((dbg & 8u) && dense) {
-				// timing experiment (round 4, results wrong): what a CELL-MAJOR replica of the Dense levels would issue -- a
-				// lane's four corner pairs are 32 contiguous bytes of the cell's 64-byte record, two 16-byte loads
-				const uint32_t cb = (off[0] & ~63u) + 32u * side;
-				const float4 lo4 = *reinterpret_cast<const float4 *>(base + cb), hi4 = *reinterpret_cast<const float4 *>(base + cb + 16u);
-				t[u][0] = make_float2(lo4.x, lo4.y); t[u][1] = make_float2(lo4.z, lo4.w);
-				t[u][2] = make_float2(hi4.x, hi4.y); t[u][3] = make_float2(hi4.z, hi4.w);
-			} else {
 #pragma unroll
-			for (int m = 0; m < 4; ++m) {
-				if (dbg & 2u) t[u][m] = make_float2(__int_as_float(off[m] | 0x3f000000u), __int_as_float(off[m] ^ 0x3f123456u));
-				else t[u][m] = load_pair<PT>(base + off[m]);
-			}
-			}
+			for (int m = 0; m < 4; ++m) t[u][m] = load_pair<PT>(base + off[m]);
 		}
 		// ---- phase 3: pair-dim lerps (the partner gets the feature it interpolates, this lane keeps its own; the true
 		// (v1 - v0) along P is sgn * d), then dims A and B
@@ -476,7 +457,6 @@ __device__ __forceinline__ void pl_item(uint32_t q, uint32_t chunk, const nr3d_l
 #pragma unroll
 	for (int u = 0; u < SUB; ++u) {
 		const uint32_t g0 = w0 + (uint32_t)u * kGroup;
-		if ((dbg & 1u) && yv[u] + gx[u] + gy[u] + gz[u] != 1234.56789f) continue;
 		if (g0 + pl < N) {
 			char *yb = reinterpret_cast<char *>(y) + ((int64_t)g0 * y_sn + (int64_t)(q * 2u) * y_se) * (int64_t)sizeof(PT);
 			store_nt<PT>(reinterpret_cast<PT *>(yb + y_lane), yv[u]);
@@ -495,10 +475,10 @@ template <bool DYDX, typename PT, int SUB>
 __global__ __launch_bounds__(kBlock) void k_fwd_pairlane(Sched s, const nr3d_lotd_meta_t *__restrict__ md, uint32_t N,
                                                    int32_t max_level, uint32_t smooth, const float *__restrict__ x,
                                                    const PT *__restrict__ params, PT *__restrict__ y, int64_t y_sn,
-                                                   int64_t y_se, float *__restrict__ dydx, int64_t d_sn, int64_t d_se NR3D_DBG_PARAM) {
+                                                   int64_t y_se, float *__restrict__ dydx, int64_t d_sn, int64_t d_se) {
 	uint32_t q, chunk;
 	if (!decode_block(s, blockIdx.x, q, chunk)) return;
-	pl_item<DYDX, PT, SUB>(q, chunk, md, N, max_level, smooth, x, params, y, y_sn, y_se, dydx, d_sn, d_se NR3D_DBG_ARG(dbg));
+	pl_item<DYDX, PT, SUB>(q, chunk, md, N, max_level, smooth, x, params, y, y_sn, y_se, dydx, d_sn, d_se);
 }
 
 // Tried and dropped (round 3, profiles/r03e_dynamic_handout_experiment.txt): handing the items out dynamically -- resident
@@ -518,6 +498,7 @@ constexpr int kLdsThreads = 1024;
 constexpr uint32_t kLdsPts = 4096;                 // points per workgroup
 constexpr uint32_t kLdsMaxBytes = 96 * 1024;       // table bytes a level may have to be staged
 constexpr uint32_t kLdsGroupBytes = 150 * 1024;    // ... and the tables one launch holds together (160 KiB of LDS per CU)
+constexpr uint32_t kLdsMinPoints = 1u << 18;       // points from which the staging launch pays for itself
 
 // NL levels per launch (round 3): the two coarsest NGP levels (32 + 85 KiB) share one workgroup -- x is read once, one
 // launch instead of two (2 x 13 us -> <see DESIGN>).  q[l] = pseudo level, its table at float2 offset lds_off[l].
@@ -983,7 +964,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_bwd_dx_lv(Sched s, const nr3d_lo
 // out = (H v) * dL_dy[feature s]; the partners add their two features through one more DPP swap and lane 0 stores.  Same
 // polynomial as hvp_from_sdot (the oracle's corner sum), other association: agreement to fp32 rounding of the level's values.
 // dL_dy [N, 2 P] (any strides) -> g_pairs [P][N][2]: a level's pass of the kernel below reads its two columns as one
-// contiguous stream.  Reading them in place costs as much as the table gathers (measured, tools/exp_hvp_variants.py,
+// contiguous stream.  Reading them in place costs as much as the table gathers (measured,
 // profiles/r03i_hvp_experiments.txt: 673 -> 401 us per 2^20 points without the dL_dy loads): 8 of every row's 128 bytes per
 // level, and every level's XCD pulls the whole line across the fabric.
 constexpr int kGpPts = 128, kGpLv = 16;            // tile: points x pseudo levels
@@ -1021,8 +1002,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_bwd_dx_pl(Sched s, const nr3d_lo
                                                           int32_t max_level, uint32_t smooth, const float *__restrict__ dL_ddLdx,
                                                           const float *__restrict__ g_pairs, int64_t g_fm,
                                                           const float *__restrict__ x, const PT *__restrict__ params,
-                                                          float *__restrict__ partial NR3D_DBG_PARAM) {
-	NR3D_DBG_DECL
+                                                          float *__restrict__ partial) {
 	// g_fm == 0: g_pairs is the [pseudo level][point][2] copy of k_hvp_pairs; > 0: the caller's dL_dy is feature-major already
 	// (element (i, e) at e * g_fm + i, e.g. the copy the dL/dparam pass of the same step uses) and is read in place
 	uint32_t q, chunk;
@@ -1058,9 +1038,8 @@ __global__ __launch_bounds__(kBlock) void k_bwd_bwd_dx_pl(Sched s, const nr3d_lo
 		                       : ((size_t)q * N + gc) * 8u);                             // [pseudo level][point][2]
 		const uint32_t g_lane = g_fm ? pi * 4u : pi * 8u + side * 4u;
 		xp[u][0] = px[0]; xp[u][1] = px[1]; xp[u][2] = px[2];
-		if (dbg & 8u) { vp[u][0] = xp[u][1]; vp[u][1] = xp[u][2]; vp[u][2] = xp[u][0]; }
-		else { vp[u][0] = pv[0]; vp[u][1] = pv[1]; vp[u][2] = pv[2]; }
-		gs[u] = (dbg & 4u) ? 1.0f + (float)side : *reinterpret_cast<const float *>(gb + g_lane);
+		vp[u][0] = pv[0]; vp[u][1] = pv[1]; vp[u][2] = pv[2];
+		gs[u] = *reinterpret_cast<const float *>(gb + g_lane);
 	}
 	float ox[SUB], oy[SUB], oz[SUB];
 #pragma unroll
@@ -1116,10 +1095,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_bwd_dx_pl(Sched s, const nr3d_lo
 				for (int m = 0; m < 4; ++m) off[m] = e[m] * stride;
 			}
 #pragma unroll
-			for (int m = 0; m < 4; ++m) {
-				if (dbg & 2u) t[u][m] = make_float2(__int_as_float(off[m] | 0x3f000000u), __int_as_float(off[m] ^ 0x3f123456u));
-				else t[u][m] = load_pair<PT>(base + off[m]);
-			}
+			for (int m = 0; m < 4; ++m) t[u][m] = load_pair<PT>(base + off[m]);
 		}
 		// ---- phase 3: the lerp tree's differences -> gradient and mixed second differences -> H v
 #pragma unroll
@@ -1167,7 +1143,6 @@ __global__ __launch_bounds__(kBlock) void k_bwd_bwd_dx_pl(Sched s, const nr3d_lo
 #pragma unroll
 	for (int u = 0; u < SUB; ++u) {
 		const uint32_t g0 = w0 + (uint32_t)u * kGroup;
-		if ((dbg & 1u) && ox[u] + oy[u] + oz[u] != 1234.56789f) continue;
 		if (side == 0u && g0 + pl < N) {
 			float *dst = reinterpret_cast<float *>(reinterpret_cast<char *>(partial) + ((size_t)q * N + g0) * 12u + pl * 12u);
 			__builtin_nontemporal_store(ox[u], &dst[0]);
@@ -1358,11 +1333,6 @@ __global__ __launch_bounds__(kBlock) void k_grid_index(Sched s, const nr3d_lotd_
 // =============================================================================================
 // Host side
 // =============================================================================================
-// knobs of the experiments build (options.h): the schedule mode, and LOTD_SCHED_EXCL = 0 for the cost-balanced work line in the
-// two-lane forward like every other kernel (A/B)
-static uint32_t sched_mode_default() { const int64_t m = NR3D_XOPT(LOTD_SCHED, 3); return (m < 0 || m > 3) ? 3u : (uint32_t)m; }
-static bool sched_exclusive_enabled() { return NR3D_XOPT(LOTD_SCHED_EXCL, 1) != 0; }
-
 // estimated cost of one (point, pseudo level) item, in half L2 requests (see lotd_device.h, mode 3)
 static uint32_t level_cost(const nr3d_lotd_meta_t *m, uint32_t q, bool pairlane = false) {
 	const nr3d_lotd_level_t &L = m->levels[m->map_levels[q]];
@@ -1386,10 +1356,10 @@ static Sched make_sched(uint32_t N, const nr3d_lotd_meta_t *m, uint32_t &n_block
 	const uint32_t n_pseudo = m->n_pseudo_levels;
 	s.n_chunks = div_up(N, pts_per_block);
 	s.n_pseudo = n_pseudo;
-	s.mode = sched_mode_default();
+	s.mode = 3;                                                       // cost-balanced (lotd_device.h); 1 below when that does not fit
 	s.n_slots = div_up(n_pseudo, 8);
 	auto skipped = [&](uint32_t q) { return q < 64u && ((skip >> q) & 1ull); };
-	if (s.mode == 3 && pairlane && sched_exclusive_enabled()) {
+	if (pairlane) {
 		// Two-lane forward (every level costs the same for spread-out points).  The 8 * floor(L / 8) LARGEST tables (ties: the
 		// finer level) are "owned": they are paired finest with least fine, and a pair of levels belongs to a pair of XCDs,
 		// each of which walks ITS half of the chunks of both levels -- one 4 MiB Hash table at a time in an XCD's L2, loaded by
@@ -1435,69 +1405,66 @@ static Sched make_sched(uint32_t N, const nr3d_lotd_meta_t *m, uint32_t &n_block
 			return s;
 		}
 	}
-	if (s.mode == 3) {
-		// work line: level q occupies n_chunks items of cost c_q each; XCD x takes the items that START in
-		// [x, x + 1) * total / 8
-		uint64_t total = 0;
-		for (uint32_t q = 0; q < n_pseudo; ++q) if (!skipped(q)) total += (uint64_t)level_cost(m, q, pairlane) * s.n_chunks;
-		uint32_t max_blocks = 0;
-		bool ok = total > 0;
-		uint64_t pos = 0;                                             // start of level q on the line
-		uint32_t nseg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-		for (int x = 0; x < 8; ++x) s.seg_cum[x][0] = 0;
-		// Order of the levels on the line: coarsest, finest, second coarsest, second finest, ...  The cost model prices
-		// every level alike, which is right for spread-out points; samples along rays coalesce in the coarse levels (several
-		// consecutive samples per cell) and not in the fine ones, so with the levels in natural order the XCDs that own the
-		// coarse end finish early (full loop, 262 144 rays: 6.94 ms per iteration against 6.52 with each XCD owning one
-		// coarse and one fine level, profiles/r03c_full_loop_sched.txt).  Alternating ends gives every XCD a mix.
-		std::vector<uint32_t> order;
-		{
-			std::vector<uint32_t> live;
-			for (uint32_t q = 0; q < n_pseudo; ++q) if (!skipped(q)) live.push_back(q);
-			for (size_t lo = 0, hi = live.size(); lo < hi;) {
-				order.push_back(live[lo++]);
-				if (lo < hi) order.push_back(live[--hi]);
-			}
+	// work line: level q occupies n_chunks items of cost c_q each; XCD x takes the items that START in
+	// [x, x + 1) * total / 8
+	uint64_t total = 0;
+	for (uint32_t q = 0; q < n_pseudo; ++q) if (!skipped(q)) total += (uint64_t)level_cost(m, q, pairlane) * s.n_chunks;
+	uint32_t max_blocks = 0;
+	bool ok = total > 0;
+	uint64_t pos = 0;                                             // start of level q on the line
+	uint32_t nseg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	for (int x = 0; x < 8; ++x) s.seg_cum[x][0] = 0;
+	// Order of the levels on the line: coarsest, finest, second coarsest, second finest, ...  The cost model prices
+	// every level alike, which is right for spread-out points; samples along rays coalesce in the coarse levels (several
+	// consecutive samples per cell) and not in the fine ones, so with the levels in natural order the XCDs that own the
+	// coarse end finish early (full loop, 262 144 rays: 6.94 ms per iteration against 6.52 with each XCD owning one
+	// coarse and one fine level, profiles/r03c_full_loop_sched.txt).  Alternating ends gives every XCD a mix.
+	std::vector<uint32_t> order;
+	{
+		std::vector<uint32_t> live;
+		for (uint32_t q = 0; q < n_pseudo; ++q) if (!skipped(q)) live.push_back(q);
+		for (size_t lo = 0, hi = live.size(); lo < hi;) {
+			order.push_back(live[lo++]);
+			if (lo < hi) order.push_back(live[--hi]);
 		}
-		for (size_t oi = 0; oi < order.size() && ok; ++oi) {
-			const uint32_t q = order[oi];
-			const uint64_t c = level_cost(m, q, pairlane);
-			uint32_t ch = 0;
-			while (ch < s.n_chunks) {
-				const uint64_t start = pos + (uint64_t)ch * c;
-				uint32_t x = (uint32_t)((start * 8) / total);
-				x = x > 7 ? 7 : x;
-				// last chunk of this level that still starts inside XCD x's share
-				const uint64_t bound = ((uint64_t)(x + 1) * total + 7) / 8;          // first position owned by x + 1
-				uint64_t ch_end = (bound > pos) ? (bound - pos + c - 1) / c : 0;      // chunks with start < bound
-				if (x == 7 || ch_end > s.n_chunks) ch_end = s.n_chunks;
-				if (ch_end <= ch) ch_end = ch + 1;
-				if (nseg[x] >= (uint32_t)kSchedSegs) { ok = false; break; }
-				const uint32_t i = nseg[x]++;
-				s.seg_q[x][i] = q;
-				s.seg_begin[x][i] = ch;
-				s.seg_cum[x][i + 1] = s.seg_cum[x][i] + (uint32_t)(ch_end - ch);
-				ch = (uint32_t)ch_end;
-			}
-			pos += c * s.n_chunks;
-		}
-		if (ok) {
-			for (int x = 0; x < 8; ++x) {
-				for (int i = nseg[x]; i < kSchedSegs; ++i) { s.seg_cum[x][i + 1] = s.seg_cum[x][i]; s.seg_q[x][i] = 0; s.seg_begin[x][i] = 0; }
-				max_blocks = s.seg_cum[x][kSchedSegs] > max_blocks ? s.seg_cum[x][kSchedSegs] : max_blocks;
-			}
-			n_blocks = 8u * max_blocks;
-			return s;
-		}
-		s.mode = 1;                                                   // too fragmented: plain XCD-affine
 	}
-	n_blocks = (s.mode == 1) ? 8u * s.n_slots * s.n_chunks : n_pseudo * s.n_chunks;
+	for (size_t oi = 0; oi < order.size() && ok; ++oi) {
+		const uint32_t q = order[oi];
+		const uint64_t c = level_cost(m, q, pairlane);
+		uint32_t ch = 0;
+		while (ch < s.n_chunks) {
+			const uint64_t start = pos + (uint64_t)ch * c;
+			uint32_t x = (uint32_t)((start * 8) / total);
+			x = x > 7 ? 7 : x;
+			// last chunk of this level that still starts inside XCD x's share
+			const uint64_t bound = ((uint64_t)(x + 1) * total + 7) / 8;          // first position owned by x + 1
+			uint64_t ch_end = (bound > pos) ? (bound - pos + c - 1) / c : 0;      // chunks with start < bound
+			if (x == 7 || ch_end > s.n_chunks) ch_end = s.n_chunks;
+			if (ch_end <= ch) ch_end = ch + 1;
+			if (nseg[x] >= (uint32_t)kSchedSegs) { ok = false; break; }
+			const uint32_t i = nseg[x]++;
+			s.seg_q[x][i] = q;
+			s.seg_begin[x][i] = ch;
+			s.seg_cum[x][i + 1] = s.seg_cum[x][i] + (uint32_t)(ch_end - ch);
+			ch = (uint32_t)ch_end;
+		}
+		pos += c * s.n_chunks;
+	}
+	if (ok) {
+		for (int x = 0; x < 8; ++x) {
+			for (int i = nseg[x]; i < kSchedSegs; ++i) { s.seg_cum[x][i + 1] = s.seg_cum[x][i]; s.seg_q[x][i] = 0; s.seg_begin[x][i] = 0; }
+			max_blocks = s.seg_cum[x][kSchedSegs] > max_blocks ? s.seg_cum[x][kSchedSegs] : max_blocks;
+		}
+		n_blocks = 8u * max_blocks;
+		return s;
+	}
+	s.mode = 1;                                                       // too fragmented: plain XCD-affine
+	n_blocks = 8u * s.n_slots * s.n_chunks;
 	return s;
 }
 
 static bool pairlane_enabled() { return opt::on(NR3D_OPT_FWD_PAIRLANE); }
 static bool lds_stage_enabled() { return opt::on(NR3D_OPT_FWD_LDS_STAGE); }
-static uint32_t lds_stage_min_points() { const int64_t v = NR3D_XOPT(LOTD_LDS_MIN_POINTS, 1 << 18); return v < 1 ? 1u : (uint32_t)v; }
 
 static int check_common(const nr3d_lotd_meta_t *m, const void *meta_dev, int x_dtype, int p_dtype, bool half_params_ok = false) {
 	NR3D_CHECK(m != nullptr, "LoTD: meta is NULL");
@@ -1555,7 +1522,7 @@ static bool pairlane_meta_ok(const nr3d_lotd_meta_t *meta) {
 // result = pseudo level q
 static uint64_t fwd_lds_levels(const nr3d_lotd_meta_t *meta, uint32_t N, int32_t max_level) {
 	uint64_t staged = 0;
-	if (lds_stage_enabled() && N >= lds_stage_min_points() && meta->n_pseudo_levels <= 64)
+	if (lds_stage_enabled() && N >= kLdsMinPoints && meta->n_pseudo_levels <= 64)
 		for (uint32_t q = 0; q < meta->n_pseudo_levels; ++q) {
 			const uint32_t lv = meta->map_levels[q];
 			const nr3d_lotd_level_t &L = meta->levels[lv];
@@ -1580,7 +1547,7 @@ static int fwd_fast_path(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *m
 	if (!lane_span_ok(y_sn, y_se, (int64_t)sizeof(PT)) || (dy_dx && !lane_span_ok(d_sn, d_se, 4))) return 0;
 	served = true;
 	uint64_t staged = 0;
-	if (lds_stage_enabled() && N >= lds_stage_min_points() && meta->n_pseudo_levels <= 64) {
+	if (lds_stage_enabled() && N >= kLdsMinPoints && meta->n_pseudo_levels <= 64) {
 		static bool attr_set_dev[64] = {};
 		int dev_id = 0;
 		NR3D_HIP_CHECK(hipGetDevice(&dev_id));
@@ -1591,7 +1558,6 @@ static int fwd_fast_path(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *m
 			NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_fwd_lds<false, PT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsGroupBytes));
 			attr_set_dev[dev_id & 63] = true;
 		}
-		const bool pair_levels = NR3D_XOPT(LOTD_LDS_PAIR, 1) != 0;     // experiments build: 0 = one launch per staged level (A/B)
 		LdsLevels grp;
 		uint32_t n_grp = 0, grp_bytes = 0;
 		auto flush = [&]() {
@@ -1610,27 +1576,22 @@ static int fwd_fast_path(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *m
 			const nr3d_lotd_level_t &L = meta->levels[meta->map_levels[q]];
 			staged |= 1ull << q;
 			const uint32_t bytes = (L.size * 8u + 15u) & ~15u;     // staged as float pairs whatever the storage type
-			if (n_grp == 2 || (n_grp == 1 && (!pair_levels || grp_bytes + bytes > kLdsGroupBytes))) flush();
+			if (n_grp == 2 || (n_grp == 1 && grp_bytes + bytes > kLdsGroupBytes)) flush();
 			grp.q[n_grp] = q; grp.lds_off[n_grp] = grp_bytes / 8u;
 			++n_grp; grp_bytes += bytes;
 		}
 		flush();
 	}
-	// timing experiments (experiments build only; results wrong by design): FWD_DBG bit 0 no stores, 1 no gathers, 2 no x loads;
-	// FWD_ONLY_LEVEL = one pseudo level
-	const int64_t dbg = NR3D_XOPT(FWD_DBG, 0), only = NR3D_XOPT(FWD_ONLY_LEVEL, -1);
-	(void)dbg;
-	if (only >= 0) for (uint32_t q = 0; q < meta->n_pseudo_levels && q < 64u; ++q) if ((int)q != only) staged |= 1ull << q;
 	uint32_t n_blocks;
 	const Sched s = make_sched(N, meta, n_blocks, staged, (uint32_t)(kPlPts * kPlSub), true);
 	if (n_blocks != 0) {
 		prof::Scope ps(NR3D_PROF_LOTD_FWD, st);
 		if (dy_dx)
 			hipLaunchKernelGGL((k_fwd_pairlane<true, PT, kPlSub>), dim3(n_blocks), dim3(kBlock), 0, st, s, md, N, max_level,
-			                   meta->interpolation_type, x, params, y, y_sn, y_se, dy_dx, d_sn, d_se NR3D_DBG_ARG(dbg));
+			                   meta->interpolation_type, x, params, y, y_sn, y_se, dy_dx, d_sn, d_se);
 		else
 			hipLaunchKernelGGL((k_fwd_pairlane<false, PT, kPlSub>), dim3(n_blocks), dim3(kBlock), 0, st, s, md, N, max_level,
-			                   meta->interpolation_type, x, params, y, y_sn, y_se, dy_dx, d_sn, d_se NR3D_DBG_ARG(dbg));
+			                   meta->interpolation_type, x, params, y, y_sn, y_se, dy_dx, d_sn, d_se);
 	}
 	NR3D_LAUNCH_CHECK();
 	return 0;
@@ -1959,8 +1920,6 @@ static int launch_bwd_bwd_dx_t(const nr3d_lotd_meta_t *meta, const void *meta_de
 	if (workspace && need && workspace_bytes >= need && opt::on(NR3D_OPT_HVP_LEVELS)) {
 		uint32_t n_blocks;
 		const bool batched = batch_inds || batch_offsets || batch_data_size;
-		const int64_t hvp_dbg = NR3D_XOPT(HVP_DBG, 0);                 // timing experiments only (experiments build; results wrong by design)
-		(void)hvp_dbg;
 		const bool pl = !batched && pairlane_enabled() && pairlane_meta_ok(meta) && ((uintptr_t)params % (2 * sizeof(PT))) == 0 &&
 		                opt::on(NR3D_OPT_HVP_PAIRLANE);
 		const Sched s = pl ? make_sched(N, meta, n_blocks, 0, (uint32_t)(kPlPts * kHvpSub), true) : make_sched(N, meta, n_blocks);
@@ -1982,7 +1941,7 @@ static int launch_bwd_bwd_dx_t(const nr3d_lotd_meta_t *meta, const void *meta_de
 				}
 				hipLaunchKernelGGL((k_bwd_bwd_dx_pl<kHvpSub, PT>), dim3(n_blocks), dim3(kBlock), 0, (hipStream_t)stream, s, md, N, max_level,
 				                   meta->interpolation_type, (const float *)dL_ddLdx, g_pairs, g_fm,
-				                   (const float *)x, (const PT *)params, (float *)workspace NR3D_DBG_ARG(hvp_dbg));
+				                   (const float *)x, (const PT *)params, (float *)workspace);
 			}
 			else if (dh) launch(k_bwd_bwd_dx_lv<D, G, true, PT>); else launch(k_bwd_bwd_dx_lv<D, G, false, PT>);
 			hipLaunchKernelGGL(k_sum_levels<D>, dim3(div_up(N, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, N,

@@ -1026,10 +1026,7 @@ __global__ __launch_bounds__(kAccThreads) void k_reduce_partials(BinPlan plan, c
 // target number of stage-B work items (a bucket holding more than total / units records is split into replicas).
 // Measured on the NGP config, 2^20 points (backward ms): 512: 0.904, 768: 0.884, 900: 0.884, 960: 0.880, 1000: 0.897,
 // 1024: 0.901, 1280: 0.913, 2048: 0.937.
-static uint32_t work_units() {                  // knob of the experiments build only (options.h)
-	const int64_t v = NR3D_XOPT(LOTD_ACC_UNITS, 960);
-	return (uint32_t)(v < 256 ? 256 : (v > 8192 ? 8192 : v));
-}
+constexpr uint32_t kWorkUnits = 960;
 
 // Points per pass of the binned path: the record workspace grows with it (1.6 GB per 2^20 points for the 16-level
 // NGP config), larger passes amortise the per-bucket zero / flush better (2^22 points: backward 3.74 -> 3.51 ms with
@@ -1489,12 +1486,12 @@ static bool layout(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t n_batch
 		const uint64_t pb = (((uint64_t)plan.bucket_base[plan.n_pseudo] * 3 + 4) * 4 + 255) / 256 * 256;   // tot | rep | item_start
 		l.plan_bytes = pb > l.plan_bytes ? pb : l.plan_bytes;
 		// one fp32 partial table per possible stage-B work item (only replicas write theirs)
-		const uint64_t qb = (uint64_t)(work_units() + plan.bucket_base[plan.n_pseudo]) * kLdsDoubles * 4;
+		const uint64_t qb = (uint64_t)(kWorkUnits + plan.bucket_base[plan.n_pseudo]) * kLdsDoubles * 4;
 		l.part_bytes = qb > l.part_bytes ? qb : l.part_bytes;
 	}
 	if (!forest && n_batches <= 1 && pair_applies(m)) {       // lotd_pair.hip runs in the same regions
 		uint64_t rb, ob, pb, qb;
-		pair_layout(m, n_chunk, work_units(), rb, ob, pb, qb);
+		pair_layout(m, n_chunk, kWorkUnits, rb, ob, pb, qb);
 		l.rec_bytes = rb > l.rec_bytes ? rb : l.rec_bytes;
 		l.offs_bytes = ob > l.offs_bytes ? ob : l.offs_bytes;
 		l.plan_bytes = pb > l.plan_bytes ? pb : l.plan_bytes;
@@ -1638,11 +1635,11 @@ static int launch_class(bool second, const BinPlan &pl, const nr3d_lotd_meta_t *
 		                   meta->interpolation_type, xc, vc, gc, sn, se, params, ba, rec, offs);
 	prof::end(NR3D_PROF_LOTD_BIN, st);
 	hipLaunchKernelGGL(k_bucket_totals, dim3(div_up(NB, 4)), dim3(256), 0, st, pl, offs, tot);
-	hipLaunchKernelGGL(k_plan_items, dim3(1), dim3(1024), 0, st, NB, pl.n_blk, work_units(), tot, rep, item_start);
-	// sum of replicas <= work_units() (rounded shares of the total) + one per non-empty bucket
+	hipLaunchKernelGGL(k_plan_items, dim3(1), dim3(1024), 0, st, NB, pl.n_blk, kWorkUnits, tot, rep, item_start);
+	// sum of replicas <= kWorkUnits (rounded shares of the total) + one per non-empty bucket
 	{
 		prof::Scope ps(NR3D_PROF_LOTD_ACCUM, st);
-		hipLaunchKernelGGL((k_accum<D, G>), dim3(work_units() + NB), dim3(kAccThreads), kLdsDoubles * 8, st, pl, md, rec, offs, rep,
+		hipLaunchKernelGGL((k_accum<D, G>), dim3(kWorkUnits + NB), dim3(kAccThreads), kLdsDoubles * 8, st, pl, md, rec, offs, rep,
 		                   item_start, ba, partial, dparam);
 	}
 	hipLaunchKernelGGL((k_reduce_partials<D, G>), dim3(NB, kLdsDoubles / kAccThreads), dim3(kAccThreads), 0, st, pl, md, rep, item_start, ba, partial, dparam);
@@ -1744,7 +1741,7 @@ int dparam_binned(bool second, const nr3d_lotd_meta_t *meta, const void *meta_de
 		};
 		if (use_pair) {
 			need_gt();
-			if (int rc = pair_chunk(meta, md, n, xc, gc, sn, se, min_level, max_level, work_units(), dparam,
+			if (int rc = pair_chunk(meta, md, n, xc, gc, sn, se, min_level, max_level, kWorkUnits, dparam,
 			                        (out_half ? 1u : 0u) | (assign_now ? 2u : 0u), rec, offs, plan_buf, partial, st,
 			                        second ? vc : nullptr, (N <= nc && !second) ? fold : nullptr))
 				return rc;

@@ -26,10 +26,12 @@ constexpr uint32_t kPrimes[7] = {1u, 2654435761u, 805459861u, 3674653429u, 20971
 //                               levels {xcd, xcd+8, ...} one after another, so one 4 MiB hash table
 //                               at a time is live in that XCD's private 4 MiB L2.
 //   mode 2  chunk-major       : q = b % n_pseudo (all levels of a chunk back to back)
-//   mode 3  XCD-affine, cost-balanced (default): the (level, chunk) items laid out level after level are cut into
+//   mode 3  XCD-affine, cost-balanced: the (level, chunk) items laid out level after level are cut into
 //                               8 contiguous pieces of equal estimated COST (L2 gather requests per point differ
 //                               between levels: 4 for Dense, 6 for Hash with the paired 16-byte gathers, half of
 //                               that when the table fits the L1).  An XCD still walks few tables, one at a time.
+// The host (make_sched, lotd.hip) produces mode 3, and mode 1 when the work line needs more than kSchedSegs segments on
+// one XCD.  Modes 0 and 2 are decoded here but nothing produces them.
 // ---------------------------------------------------------------------------------------------
 constexpr int kSchedSegs = 16;             // max (level, chunk range) segments per XCD in mode 3
 struct Sched {

@@ -25,7 +25,7 @@ namespace nr3d {
 namespace lotd {
 
 constexpr uint32_t kPEpbMax = 8192;                  // accumulator entries per bucket: 2 features x 8192 x 8 B = 128 KiB (1 workgroup
-                                                     // per CU) or x 4096 = 64 KiB (2 per CU); plan.lg = log2 of it, NR3D_PAIR_EPB_LOG2
+                                                     // per CU) or x 4096 = 64 KiB (2 per CU); plan.lg = log2 of it
 constexpr int kPAccThreads = 1024;
 constexpr int kPLdsMax = 2 * (int)kPEpbMax;          // fp64 accumulators per stage-B workgroup (upper bound)
 constexpr int kPMaxLv = 32;                          // pseudo levels per plan
@@ -54,18 +54,14 @@ struct DirectPlan {
 	uint32_t qmap[kDirectMaxLv], nb[kDirectMaxLv], epb[kDirectMaxLv], shift[kDirectMaxLv];
 	uint32_t bucket_base[kDirectMaxLv + 1];
 	uint32_t lg, sum_log2, R, pts_per_rep;    // replicas per bucket, points per replica
-	uint32_t merge_min;                       // lanes continuing their neighbour's cell from which a wave rotates its update order (experiments build: knob)
+	uint32_t merge_min;                       // lanes continuing their neighbour's cell from which a wave rotates its update order
 };
 
 
-// Measurement knobs (only a -DNR3D_EXPERIMENTS build reads them, options.h): points per stage-A workgroup 512 | 768 | 1024,
-// log2 of the entries per bucket 12 | 13, loads in flight per wave in stage B 4 | 8, stage-B work items (measured, NGP config,
-// 2^20 points, 64 KiB buckets, backward ms: 768: 0.679, 1024: 0.669, 1536: 0.657, 2048: 0.671), and the timing experiment
-// PAIR_DEBUG (results wrong by design: bit 0 = no LDS atomics, bit 1 = every lane re-reads one record).
-static uint32_t pair_bp() { const int64_t x = NR3D_XOPT(PAIR_BP, 1024); return (x == 512 || x == 768) ? (uint32_t)x : 1024u; }
-static uint32_t pair_lg() { return NR3D_XOPT(PAIR_EPB_LOG2, 12) == 13 ? 13u : 12u; }
-static uint32_t pair_unroll() { return NR3D_XOPT(PAIR_UNROLL, 4) == 8 ? 8u : 4u; }
-static uint32_t pair_units() { const int64_t x = NR3D_XOPT(PAIR_UNITS, 1536); return (uint32_t)(x < 256 ? 256 : (x > 8192 ? 8192 : x)); }
+// Points per stage-A workgroup, log2 of the accumulator entries per bucket, loads in flight per wave in stage B, rotation
+// threshold of k_pair_direct (DirectPlan::merge_min) and stage-B work items (measured, NGP config, 2^20 points, 64 KiB buckets,
+// backward ms: 768: 0.679, 1024: 0.669, 1536: 0.657, 2048: 0.671).
+constexpr uint32_t kPairBp = 1024, kPairLg = 12, kPairUnroll = 4, kDirectRotate = 8, kPairUnits = 1536;
 // selectable paths (nr3d_set_option; the tests compare both forms in one process)
 static bool pair_quad_enabled() { return opt::on(NR3D_OPT_PAIR_QUAD); }
 static uint32_t pair_fixed() { return opt::on(NR3D_OPT_PAIR_FIXED) ? 1u : 0u; }      // stage-B accumulators: 64-bit fixed point | fp64
@@ -653,13 +649,12 @@ __global__ __launch_bounds__(kPAccThreads, 8) /* 8 waves per SIMD: two 64 KiB wo
                                                              const uint32_t *__restrict__ rep_g,
                                                              const uint32_t *__restrict__ item_start,
                                                              const uint32_t *__restrict__ gmax,
-                                                             float *__restrict__ partial, float *__restrict__ dparam NR3D_DBG_PARAM,
+                                                             float *__restrict__ partial, float *__restrict__ dparam,
                                                              uint32_t out_half, uint32_t *__restrict__ bticket, uint32_t n_dred,
                                                              DirectPlan dp, const float *__restrict__ dpart) {
 	// Folded route (bticket != NULL): the first n_dred workgroups sum the direct levels' replica tables, one row of kPAccThreads
 	// accumulators each (k_pair_reduce's second branch; k_pair_direct has finished), and the last replica of a split bucket to
 	// finish sums the bucket's partial tables itself (per-bucket ticket)
-	NR3D_DBG_DECL
 	extern __shared__ __attribute__((aligned(16))) unsigned long long acc_raw[];   // [2][2^lg] 8-byte accumulators, feature-major
 	__shared__ uint32_t last_s;
 	if (blockIdx.x < n_dred) {
@@ -737,11 +732,11 @@ __global__ __launch_bounds__(kPAccThreads, 8) /* 8 waves per SIMD: two 64 KiB wo
 					for (int u = 1; u < kGroup; ++u) at = (pos >= pre[u]) ? rbase[u] : at;
 					// branch-free (a load under an `if` makes the compiler drain all outstanding loads at the join): lanes
 					// past the end re-read the group's first slot and drop it
-					rv[v] = __builtin_nontemporal_load(rec_b + (size_t)((pos < total && !(dbg & 2u)) ? at + pos : rbase[0]));
+					rv[v] = __builtin_nontemporal_load(rec_b + (size_t)(pos < total ? at + pos : rbase[0]));
 				}
 #pragma unroll
 				for (int v = 0; v < kUnroll; ++v)
-					if (p0 + 64u * (uint32_t)v + lane < total && !(dbg & 1u)) {
+					if (p0 + 64u * (uint32_t)v + lane < total) {
 						const uint32_t h = rv[v].x, fl = (h >> 26) & 7u;
 						const uint32_t i0 = h & 8191u, i1 = (h >> 13) & 8191u;
 						const float w = __uint_as_float(rv[v].y), a0 = __uint_as_float(rv[v].z), a1 = __uint_as_float(rv[v].w);
@@ -1073,7 +1068,7 @@ bool pair_applies(const nr3d_lotd_meta_t *m) {
 	if (m->n_pseudo_levels > (uint32_t)kPMaxLv) return false;
 	for (uint32_t l = 0; l < m->n_levels; ++l) {
 		const nr3d_lotd_level_t &L = m->levels[l];
-		const uint32_t kPEpb = 1u << pair_lg();
+		const uint32_t kPEpb = 1u << kPairLg;
 		if (L.type == NR3D_LOD_Dense) {
 			if (L.res[2] > kPEpb) return false;
 			const uint64_t rows = (uint64_t)L.res[0] * L.res[1];
@@ -1083,7 +1078,7 @@ bool pair_applies(const nr3d_lotd_meta_t *m) {
 		} else if (L.type == NR3D_LOD_Hash) {
 			if (L.size <= kPEpb) continue;
 			if ((L.size & (L.size - 1u)) != 0u || L.res[0] > kPEpb) return false;
-			if ((L.size >> pair_lg()) > kPMaxNb) return false;
+			if ((L.size >> kPairLg) > kPMaxNb) return false;
 		} else {
 			return false;
 		}
@@ -1097,9 +1092,9 @@ bool pair_applies(const nr3d_lotd_meta_t *m) {
 
 static void pair_plan(const nr3d_lotd_meta_t *m, uint32_t n_chunk, int32_t min_level, int32_t max_level, PairPlan &plan,
                       uint64_t &offs_words, uint64_t skip_pseudo = 0) {
-	plan.n_blk = div_up(n_chunk, pair_bp());
-	plan.cap = pair_bp() * 4u;
-	plan.lg = pair_lg();
+	plan.n_blk = div_up(n_chunk, kPairBp);
+	plan.cap = kPairBp * 4u;
+	plan.lg = kPairLg;
 	plan.sum_log2 = 3;
 	while ((1ull << (plan.sum_log2 - 3)) < n_chunk) ++plan.sum_log2;
 	const uint32_t kPEpb = 1u << plan.lg;
@@ -1136,14 +1131,12 @@ static bool pair_direct_enabled() { return opt::on(NR3D_OPT_PAIR_DIRECT); }
 // when nothing would be left for the record path, whose stage A carries the fixed-point scale)
 static uint64_t pair_direct_plan(const PairPlan &full, uint32_t n, DirectPlan &dp) {
 	dp.n = 0; dp.lg = full.lg; dp.sum_log2 = full.sum_log2; dp.R = 1; dp.pts_per_rep = n;
-	dp.merge_min = (uint32_t)NR3D_XOPT(PAIR_DIRECT_ROTATE, 8);
+	dp.merge_min = kDirectRotate;
 	dp.bucket_base[0] = 0;
 	if (!pair_direct_enabled()) return 0;
 	uint64_t mask = 0;
-	const int64_t nb_x = NR3D_XOPT(PAIR_DIRECT_NB, kDirectNb);  // buckets up to which a level goes direct (knob: experiments build)
-	const uint32_t nb_lim = nb_x < 0 ? 0u : (uint32_t)nb_x;
 	for (uint32_t ql = 0; ql < full.n_pseudo && dp.n < kDirectMaxLv; ++ql) {
-		if (full.nb[ql] > nb_lim || full.qmap[ql] >= 64u) continue;
+		if (full.nb[ql] > kDirectNb || full.qmap[ql] >= 64u) continue;
 		if (dp.bucket_base[dp.n] + full.nb[ql] > kDirectMaxWg) break;      // pair_layout reserves kDirectMaxWg partial tables
 		const uint32_t e = dp.n++;
 		dp.qmap[e] = full.qmap[ql]; dp.nb[e] = full.nb[ql]; dp.epb[e] = full.epb[ql]; dp.shift[e] = full.shift[ql];
@@ -1180,7 +1173,7 @@ void pair_layout(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t units, ui
 	rec_bytes = (uint64_t)plan.n_pseudo * plan.n_blk * plan.cap * 16;
 	offs_bytes = ((ow * 4 + 255) / 256) * 256;
 	plan_bytes = (((uint64_t)NB * 3 + 4) * 4 + 255) / 256 * 256;
-	part_bytes = (uint64_t)(pair_units() + NB + kDirectMaxWg) * (2u << plan.lg) * 4;   // the pair path's own item count, not `units`; + k_pair_direct
+	part_bytes = (uint64_t)(kPairUnits + NB + kDirectMaxWg) * (2u << plan.lg) * 4;   // the pair path's own item count, not `units`; + k_pair_direct
 }
 
 void launch_plan_items(uint32_t NB, uint32_t n_blk, uint32_t units, const uint32_t *tot, uint32_t *rep, uint32_t *item_start,
@@ -1240,33 +1233,24 @@ int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_
 	// gmax | plan ticket: two spare words of the plan region, or the hand-over buffer's head (zeroed by the dL/dx kernel)
 	uint32_t *gmax = fold ? fold : plan_buf + 3 * (size_t)NB + 2;
 	uint32_t *bticket = fold ? fold + kFoldHead : nullptr;
-	units = pair_units();
-	const size_t bin_lds_max = (size_t)1024 * 4 * 16 + (size_t)(kPMaxNb + 2) * 8;
+	units = kPairUnits;
+	const size_t bin_lds_max = (size_t)kPairBp * 4 * 16 + (size_t)(kPMaxNb + 2) * 8;
 	static bool attr_set_dev[64] = {};
 	int dev_id = 0;
 	NR3D_HIP_CHECK(hipGetDevice(&dev_id));
 	if (!attr_set_dev[dev_id & 63]) {
-#ifdef NR3D_EXPERIMENTS
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_bin<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds_max));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_bin<768>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds_max));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_bin<512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds_max));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_bin<768, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds_max));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_accum<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_accum<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
-#endif
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_bin<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds_max));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_bin<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds_max));
+		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_bin<kPairBp>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds_max));
+		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_bin<kPairBp, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds_max));
 		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_direct<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
 		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_direct<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
 		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_direct<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
 		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_direct<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_accum<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_accum<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
+		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_accum<kPairUnroll, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
+		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_accum<kPairUnroll, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
 		attr_set_dev[dev_id & 63] = true;
 	}
 	if (!fold) NR3D_HIP_CHECK(hipMemsetAsync(gmax, 0, 2 * sizeof(uint32_t), st));      // gmax | ticket of k_pair_plan
-	const uint32_t bp = pair_bp();
-	const size_t bin_lds = (size_t)bp * 4 * 16 + (size_t)(nb_max + 1) * 4;     // stage | hist
+	const size_t bin_lds = (size_t)kPairBp * 4 * 16 + (size_t)(nb_max + 1) * 4;     // stage | hist
 	// first order: the Dense levels' records in quad form (NR3D_PAIR_QUAD=0: pair records only)
 	const uint32_t quad_on = (!vin && pair_quad_enabled()) ? 1u : 0u;
 #define NR3D_PAIR_BIN(BP) if (vin) NR3D_PAIR_BIN_(BP, true); else NR3D_PAIR_BIN_(BP, false)
@@ -1274,10 +1258,7 @@ int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_
 	meta->interpolation_type, x, g, g_sn, g_se, (u32x4 *)rec, offs, fold ? nullptr : gmax, dp, vin, quad_on)
 	{
 		prof::Scope ps(NR3D_PROF_LOTD_BIN, st);
-#ifdef NR3D_EXPERIMENTS
-		if (bp == 512) { NR3D_PAIR_BIN(512); } else if (bp == 768) { NR3D_PAIR_BIN(768); } else
-#endif
-		{ NR3D_PAIR_BIN(1024); }
+		NR3D_PAIR_BIN(kPairBp);
 	}
 #undef NR3D_PAIR_BIN
 #undef NR3D_PAIR_BIN_
@@ -1312,13 +1293,10 @@ int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_
 	// folded: stage B also sums the direct buckets (n_dred rows of kPAccThreads accumulators, in front) and its split buckets
 	const uint32_t n_dred = fold ? nbk_direct * ((2u << pl.lg) / kPAccThreads) : 0u;
 #define NR3D_PAIR_ACC(U, F) hipLaunchKernelGGL((k_pair_accum<U, F>), dim3(n_dred + units + NB), dim3(kPAccThreads), (size_t)(16u << pl.lg), st, pl, md, \
-	(const u32x4 *)rec, offs, rep, item_start, gmax, partial, dparam NR3D_DBG_ARG(NR3D_XOPT(PAIR_DEBUG, 0)), out_flags, bticket, n_dred, dp, dpart)
+	(const u32x4 *)rec, offs, rep, item_start, gmax, partial, dparam, out_flags, bticket, n_dred, dp, dpart)
 	{
 		prof::Scope ps(NR3D_PROF_LOTD_ACCUM, st);
-#ifdef NR3D_EXPERIMENTS
-		if (pair_unroll() == 8) { if (pair_fixed()) NR3D_PAIR_ACC(8, true); else NR3D_PAIR_ACC(8, false); } else
-#endif
-		{ if (pair_fixed()) NR3D_PAIR_ACC(4, true); else NR3D_PAIR_ACC(4, false); }
+		if (pair_fixed()) NR3D_PAIR_ACC(kPairUnroll, true); else NR3D_PAIR_ACC(kPairUnroll, false);
 	}
 #undef NR3D_PAIR_ACC
 	// the replicated buckets of the record path and the direct levels' buckets are summed in ONE launch (folded: in stage B)

@@ -500,7 +500,7 @@ struct VsCtx {
 // VEC: the level's entries are one 2-feature pseudo level and the table is aligned to two entries -- three loads of two whole entries
 // per point (emit_vm_component_f2) instead of twelve scalar ones
 template <bool SECOND, bool FO, bool FIX, bool VEC, typename TB>
-__device__ __forceinline__ bool vs_own_point(const VsCtx<TB> &cx, const float (&xp)[3], const float (&grad)[2], const float (&vv)[3], uint32_t dbg) {
+__device__ __forceinline__ bool vs_own_point(const VsCtx<TB> &cx, const float (&xp)[3], const float (&grad)[2], const float (&vv)[3]) {
 	const Lvl &L = cx.L;
 	float a[3];
 	Cell<3> c;
@@ -531,10 +531,8 @@ __device__ __forceinline__ bool vs_own_point(const VsCtx<TB> &cx, const float (&
 				for (int d = 0; d < 3; ++d) { const float t = face_weight<3>(c, k, d, a[d]); wk += ((k >> d) & 1u) ? t : -t; }
 			}
 			const uint32_t slot = (p[0] * L.res[1] + p[1]) * L.res[2] + p[2] - cx.band_lo;
-			if (!(dbg & 4u)) {
-				vs_add<FIX>(cx.acc, slot, grad[0] * wk, cx.scale);
-				vs_add<FIX>(cx.acc, kVsAcc + slot, grad[1] * wk, cx.scale);
-			}
+			vs_add<FIX>(cx.acc, slot, grad[0] * wk, cx.scale);
+			vs_add<FIX>(cx.acc, kVsAcc + slot, grad[1] * wk, cx.scale);
 		}
 		return true;
 	}
@@ -549,7 +547,6 @@ __device__ __forceinline__ bool vs_own_point(const VsCtx<TB> &cx, const float (&
 		else if (cx.dc == 1u) emit_vm_component<2, 1, 6, SECOND>(L, c, a, grad, cx.grid, cx.foff, ent, val);
 		else emit_vm_component<2, 2, 6, SECOND>(L, c, a, grad, cx.grid, cx.foff, ent, val);
 	}
-	if (dbg & 4u) return val[0][0] + val[1][1] + val[2][0] + val[3][1] + val[4][0] + val[5][1] == 1.2345f;
 #pragma unroll
 	for (int k = 0; k < 6; ++k) {
 		const uint32_t slot = k < 4 ? ent[k] - cx.band_lo : cx.n_plane + (ent[k] - cx.gm.line_lo);
@@ -656,14 +653,12 @@ __global__ __launch_bounds__(kVsThreads) void k_vm_sorted(const VsPlan *__restri
                                                           const float *__restrict__ x, const float *__restrict__ vin_,
                                                           const float *__restrict__ g, int64_t g_sn, int64_t g_se,
                                                           const PT *__restrict__ params, Batch ba, ForestDev fo, float *__restrict__ dparam,
-                                                          uint32_t opt_fix NR3D_DBG_PARAM) {
-	NR3D_DBG_DECL   // timing experiments (experiments build only; results wrong by design): 1 no boundary pass, 2 no write-out, 4 no LDS adds, 8 no own points
+                                                          uint32_t opt_fix) {
 	extern __shared__ __attribute__((aligned(16))) double vs_acc[];            // [2 features][kVsAcc slots]: plane band (nrows + 1) Rb | line d Rd
 	__shared__ uint8_t s_rank[kVsThreads];                                       // per wave: the lanes of its surviving candidates, by rank
 	const uint32_t w = blockIdx.x;
 	const VsUnit un = dv.units[w];
 	if (un.item == kVsNoUnit) return;
-	if (dbg & 64u) return;
 	const uint32_t gmax_bits = dv.stats[0], vmax_bits = SECOND ? dv.stats[1] : 0u;
 	const uint32_t item = un.item, rep = un.rep, n_rep = un.n_rep;
 	Lvl L;                                                                         // (everything the unit needs came with its record)
@@ -720,10 +715,10 @@ __global__ __launch_bounds__(kVsThreads) void k_vm_sorted(const VsPlan *__restri
 	cx.foff = foff; cx.col0 = col0; cx.b = un.b; cx.last = last; cx.grid = grid; cx.acc = vs_acc; cx.scale = fx.scale;
 	const int o = dc == 0u ? 1 : 0;
 	const uint32_t p_lo = un.own_lo + rep * kVsPmax, p_end = un.own_lo + own_cnt;
-	const uint32_t n_own = (dbg & 8u) ? 0u : ((p_end - p_lo) < kVsPmax ? p_end - p_lo : kVsPmax);
+	const uint32_t n_own = (p_end - p_lo) < kVsPmax ? p_end - p_lo : kVsPmax;
 	uint32_t c_lo[3] = {0u, 0u, 0u}, c_n[3] = {0u, 0u, 0u};
 	int kb[3] = {0, 0, 0};
-	if (FO && !(dbg & 1u)) {
+	if (FO) {
 #pragma unroll
 		for (uint32_t rg = 0; rg < 3u; ++rg) {
 			const uint32_t r_cnt = un.sub_cnt[rg], per = (r_cnt + n_rep - 1u) / n_rep;
@@ -758,7 +753,7 @@ __global__ __launch_bounds__(kVsThreads) void k_vm_sorted(const VsPlan *__restri
 	const uint32_t own = 2u * (last ? nrows + 1u : nrows) * gm.Rb;
 	float *dst = dparam + (boff + L.off) + (size_t)band_lo * L.F + foff;
 	float old[kPre][4];
-	if (n_rep == 1u && !(dbg & 2u)) {
+	if (n_rep == 1u) {
 #pragma unroll
 		for (uint32_t k = 0; k < kPre; ++k)
 #pragma unroll
@@ -778,7 +773,7 @@ __global__ __launch_bounds__(kVsThreads) void k_vm_sorted(const VsPlan *__restri
 			for (int d = 0; d < 3; ++d) { cxp[d] = nx[d]; cv[d] = nv[d]; }
 			cg[0] = ng[0]; cg[1] = ng[1];
 			fetch(idx + kVsThreads);
-			if (idx >= cnd_pad) any |= vs_own_point<SECOND, FO, FIX, VEC>(cx, cxp, cg, cv, dbg);
+			if (idx >= cnd_pad) any |= vs_own_point<SECOND, FO, FIX, VEC>(cx, cxp, cg, cv);
 			else if constexpr (FO) {
 				// (cnd_pad is a multiple of 64: a wave is on candidates with all its lanes)
 				float bx[3] = {0.5f, 0.5f, 0.5f};
@@ -841,7 +836,6 @@ __global__ __launch_bounds__(kVsThreads) void k_vm_sorted(const VsPlan *__restri
 	if (fx.on) { if (vec) run(std::true_type{}, std::true_type{}); else run(std::true_type{}, std::false_type{}); }
 	else { if (vec) run(std::false_type{}, std::true_type{}); else run(std::false_type{}, std::false_type{}); }
 	const int touched = __syncthreads_or(any ? 1 : 0);
-	if (dbg & 2u) return;
 	// ---- write-out.  Rows 0 .. nrows - 1 of the band belong to this item alone (the last band: nrows as well); row nrows is the
 	// next band's row 0 and travels through `handoff`; line d through `lines` (k_vs_reduce adds both, and the replicas, in order).
 	// Element t of a table = (slot t >> 1, feature t & 1), the layout of dL/dparam and of the three buffers.
@@ -1219,7 +1213,7 @@ int vm_sorted_run(bool second, const VsPlan &vp, const nr3d_lotd_meta_t *meta, c
 	}
 	auto launch = [&](auto kern, auto *tab) {
 		hipLaunchKernelGGL(kern, dim3(vp.w_max), dim3(kVsThreads), (size_t)kVsLds, st, vpd, vp.rb_max, vp.rd_max, dv, n, meta->interpolation_type, x, vin, g, g_sn, g_se,
-		                   tab, ba, fo, dparam, opt_fix NR3D_DBG_ARG(NR3D_XOPT(VS_DBG, 0)));
+		                   tab, ba, fo, dparam, opt_fix);
 	};
 	{
 		prof::Scope ps(NR3D_PROF_LOTD_DIRECT, st);

@@ -828,15 +828,15 @@ __global__ __launch_bounds__(kBlock) void k_alpha_bwd_lpp(uint32_t P, const floa
 	for (uint32_t j = 4 * n4; j < len; ++j) grad_alphas[begin + j] = one(alphas[begin + j], grad_weights[begin + j], weights[begin + j]);
 }
 
-// wave-per-pack for few packs; from 2048 packs on (32 waves of lanes) one lane per pack is faster at every pack
+// wave-per-pack for few packs; from kLanePerPackMin packs on (32 waves of lanes) one lane per pack is faster at every pack
 // length measured (4096 packs x 61 samples: 8 / 23 us vs 27 / 42 us forward / backward)
 // NR3D_OPT_PACK_SCAN = 0: the fused composite replays the transmittance serially (vw bit-identical to packed_alpha_to_vw)
-// instead of the prefix-product kernels.  Knobs of the experiments build: PACK_SCAN_MAX = packs up to which wave-per-pack +
-// scan is preferred over one lane per pack (default: always -- 4096 packs x <= 512: 8.5 / 11 us against 38 / 77 us forward /
-// backward, 262144 packs: 148 / 289 against 302 / 837), PACK_LPP_MIN.
+// instead of the prefix-product kernels.  With the option on, wave-per-pack + scan is preferred over one lane per pack at
+// every pack count (4096 packs x <= 512: 8.5 / 11 us against 38 / 77 us forward / backward, 262144 packs: 148 / 289 against
+// 302 / 837).
+constexpr uint32_t kLanePerPackMin = 2048;
 static inline bool composite_scan() { return opt::on(NR3D_OPT_PACK_SCAN); }
-static inline uint32_t composite_scan_max() { return (uint32_t)NR3D_XOPT(PACK_SCAN_MAX, 0xFFFFFFFFll); }
-static inline bool lane_per_pack(uint32_t P) { return P >= (uint32_t)NR3D_XOPT(PACK_LPP_MIN, 2048); }
+static inline bool lane_per_pack(uint32_t P) { return P >= kLanePerPackMin; }
 
 // ------------------------------------------------------------------------------------------------
 // Fused alpha composite of a packed volume buffer: the renderer's chain
@@ -1729,7 +1729,7 @@ extern "C" int nr3d_pack_composite_fwd(uint32_t P, const float *alphas, const fl
 	if (P == 0) return 0;
 	NR3D_CHECK(alphas && t && pack_infos && vw && mask && depth, "pack_composite_fwd: NULL pointer");
 	NR3D_CHECK(!rgb || rgb_out, "pack_composite_fwd: rgb given without rgb_out");
-	const bool scan = pk::composite_scan() && P <= pk::composite_scan_max();
+	const bool scan = pk::composite_scan();
 	const bool lpp = !scan && pk::lane_per_pack(P);
 	const dim3 g = lpp ? dim3(div_up(P, pk::kBlock)) : pk::grid_for(P), b(pk::kBlock);
 #define NR3D_COMP_FWD(K) hipLaunchKernelGGL(K, g, b, 0, (hipStream_t)stream, P, alphas, t, rgb, pack_infos, ray_index, \
@@ -1750,7 +1750,7 @@ extern "C" int nr3d_pack_composite_bwd(uint32_t P, const float *alphas, const fl
                                        float *grad_alphas, float *grad_t, float *grad_rgb, void *stream) {
 	if (P == 0) return 0;
 	NR3D_CHECK(alphas && vw && t && pack_infos && mask && depth && grad_alphas, "pack_composite_bwd: NULL pointer");
-	const bool scan = pk::composite_scan() && P <= pk::composite_scan_max();
+	const bool scan = pk::composite_scan();
 	const bool lpp = !scan && pk::lane_per_pack(P);
 	const dim3 g = lpp ? dim3(div_up(P, pk::kBlock)) : pk::grid_for(P), b(pk::kBlock);
 #define NR3D_COMP_BWD(K) hipLaunchKernelGGL(K, g, b, 0, (hipStream_t)stream, P, alphas, vw, t, rgb, pack_infos, ray_index, \

@@ -247,5 +247,13 @@ def test_option_table_round_trip(hiplib):
     assert hiplib.nr3d_set_option(C.c_int(count), C.c_int64(1)) != 0
     # nothing in the shipped library reads the environment
     blob = open(_hip.LIB_PATH, "rb").read()
-    assert b"getenv" not in blob or b"NR3D_FWD_DBG" not in blob
+    for name in (b"NR3D_FWD_DBG", b"NR3D_HVP_DBG", b"NR3D_VS_DBG", b"NR3D_PAIR_DEBUG"):
+        assert name not in blob, name
     assert blob.count(b"NR3D_LOTD_") == 0 and blob.count(b"NR3D_PAIR_") == 0 and blob.count(b"NR3D_PACK_") == 0
+    # ... and the sources have no second build flavour that could
+    for top in (os.path.join(ROOT, "nr3d_lib_amd", "csrc"), os.path.join(ROOT, "include")):
+        for d, _, files in os.walk(top):
+            for f in files:
+                text = open(os.path.join(d, f), "rb").read()
+                for word in (b"NR3D_EXPERIMENTS", b"NR3D_XOPT", b"NR3D_DBG_"):
+                    assert word not in text, (os.path.join(d, f), word)

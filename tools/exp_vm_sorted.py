@@ -1,9 +1,8 @@
 """tools/exp_vm_sorted.py -- time of k_vm_sorted on the reference's forest workload.
-   python tools/exp_vm_sorted.py levels     : production build; the kernel's time with the levels up to max_level = 2 .. 8 (differences = per level)
-   NR3D_VS_DBG=<bits> python tools/exp_vm_sorted.py   : experiments build only (1 no boundary pass, 2 no write-out, 4 no LDS adds,
-                                                       8 no own points; results wrong by design)"""
+   python tools/exp_vm_sorted.py            : the kernel's time and the pass's wall time
+   python tools/exp_vm_sorted.py levels     : the kernel's time with the levels up to max_level = 2 .. 8 (differences = per level)"""
 import os, sys, torch
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nr3d_lib_amd import _hip
 from nr3d_lib_amd.bindings import _lotd
 from nr3d_lib_amd.models.spatial import ForestBlockSpace
@@ -35,7 +34,7 @@ def run(max_level=None, tag=""):
     wall = (time.perf_counter() - t0) / 5 * 1e3
     _hip.prof_enable()
     ms, k = _hip.prof_read("lotd_direct")
-    print(f"{tag}NR3D_VS_DBG={os.environ.get('NR3D_VS_DBG', '0')} max_level={max_level}: k_vm_sorted {ms / max(k, 1):.3f} ms ({k} launches), pass {wall:.3f} ms", flush=True)
+    print(f"{tag}max_level={max_level}: k_vm_sorted {ms / max(k, 1):.3f} ms ({k} launches), pass {wall:.3f} ms", flush=True)
     return ms / max(k, 1)
 
 
