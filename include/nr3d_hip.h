@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 15
+#define NR3D_ABI_VERSION 16
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -90,7 +90,7 @@ enum {
 	                                  * x3 route (inf - bf16(inf) = NaN in the split) where the f32 MFMA gives +-inf or NaN (inf * 0); finite rows of the
 	                                  * same batch are unaffected on both.  A ReLU pre-activation within ~1 ulp of zero may be masked differently by a
 	                                  * forward on one route and a backward recomputation on the other (the gradient of that unit at that sample only). */
-	NR3D_OPT_PAIR_FOLD = 20,         /* 1: a dL/dparam call on the pair path that follows nr3d_lotd_bwd_dx_fold takes the fixed-point scale from that kernel and
+	NR3D_OPT_PAIR_FOLD = 20,         /* 1: a dL/dparam call on the pair path that follows nr3d_lotd_bwd_dx (with `fold`) takes the fixed-point scale from that kernel and
 	                                  * runs as stage A, k_pair_direct (with the replica plan folded in) and stage B (with the replica sums folded in); 0: the
 	                                  * separate gmax fill, k_pair_plan and k_pair_reduce launches */
 	NR3D_OPT_COUNT = 21
@@ -185,6 +185,8 @@ int nr3d_lotd_bwd_dx(const nr3d_lotd_meta_t *meta, uint32_t n_points, int x_dtyp
                      void *dL_dy_T /* optional out, f32 [n_encoded_dims, n_points]: feature-major copy of a contiguous
                                       dL_dy; pass it to nr3d_lotd_bwd_dparam as dL_dy with strides (1, n_points) and
                                       the scatter skips its own transposition */,
+                     int32_t max_level, void *fold /* optional out, the hand-over buffer of the folded pair path (see
+                                      nr3d_lotd_pair_fold_bytes below); NULL: max_level is not used */,
                      void *stream);
 
 /* lod_bwd, parameter-gradient half (kernel_lod[_hashonly]_backward_grid, lotd_encoding.h:467-711,
@@ -219,7 +221,7 @@ int nr3d_lotd_bwd_dparam_levels(const nr3d_lotd_meta_t *meta, const void *meta_d
 /* dL_dy [N, E] (element (i, e) at i * g_sn + e * g_se; grad_dtype NR3D_F32 | NR3D_F16) -> out float [E][N], feature-major:
  * the layout the level-major kernels read.  The dL/dparam entry points make this copy themselves when handed a row-major
  * dL_dy; a caller that runs several of them on one dL_dy (d(dL/dx)/dparam and d(dL/dx)/dx of one second-order step) makes it
- * once and passes it with strides (1, N) to nr3d_lotd_bwd_bwd_dparam and nr3d_lotd_bwd_bwd_dx_ws. */
+ * once and passes it with strides (1, N) to nr3d_lotd_bwd_bwd_dparam and nr3d_lotd_bwd_bwd_dx. */
 int nr3d_lotd_dLdy_feature_major(uint32_t n_points, uint32_t n_encoded_dims, int grad_dtype, const void *dL_dy,
                                  int64_t g_sn, int64_t g_se, float *out, void *stream);
 
@@ -236,7 +238,8 @@ int nr3d_lotd_half_params_ok(const nr3d_lotd_meta_t *meta, int batched);
  * strides; F32 for the feature-major copy that nr3d_lotd_bwd_dx leaves), out_dtype of dL_dparam.  assign == 0:
  * dL_dparam is ZERO-INIT by the caller and accumulated into, like nr3d_lotd_bwd_dparam; assign != 0: dL_dparam arrives
  * UNINITIALISED and is fully defined on return (the flush writes instead of read-modify-writing when one pass covers
- * all levels; the library zero-fills it itself otherwise).  workspace as nr3d_lotd_bwd_dparam. */
+ * all levels; the library zero-fills it itself otherwise).  workspace as nr3d_lotd_bwd_dparam; fold: NULL, or see
+ * nr3d_lotd_pair_fold_bytes below. */
 int nr3d_lotd_pair_path_ok(const nr3d_lotd_meta_t *meta);
 /* pseudo levels of a pair-path meta whose dL/dparam is accumulated straight from (x, dL_dy) in LDS instead of through
  * records (levels with <= 4 buckets; 0 when the pair path does not apply or NR3D_OPT_PAIR_DIRECT is 0).  Informational: which
@@ -248,24 +251,16 @@ uint64_t nr3d_lotd_fwd_lds_levels(const nr3d_lotd_meta_t *meta, uint32_t n_point
 int nr3d_lotd_bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t n_points, int grad_dtype,
                                const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
                                int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
-                               void *stream);
+                               void *fold, void *stream);
 /* (ABI 12) One backward call with both gradients on the pair path, in fewer launches (NR3D_OPT_PAIR_FOLD): the dL/dx kernel
  * hands the dL/dparam launches that follow it on the same stream what they used to make in launches of their own -- the
  * max |dL/dy| of the levels up to max_level (the fixed-point scale, bit for bit) and zeroed tickets.
  * nr3d_lotd_pair_fold_bytes: size of that device buffer for n_points and max_level; 0 when the folded route does not apply (option
  * off, not a pair-path meta, more points than one dL/dparam pass, levels up to max_level not the leading pseudo levels).
- * nr3d_lotd_bwd_dx_fold: nr3d_lotd_bwd_dx (row-major dL_dy) that also fills `fold` (uninitialised, >= that many bytes; NULL or
- * a size of 0: plain nr3d_lotd_bwd_dx).  nr3d_lotd_bwd_dparam_typed_fold: nr3d_lotd_bwd_dparam_typed with the same n_points,
- * max_level and `fold`, enqueued after it on the same stream, before any other call that uses `fold`; results are bit for bit
- * those of the unfolded calls. */
+ * nr3d_lotd_bwd_dx (row-major dL_dy) fills `fold` (uninitialised, >= that many bytes; NULL or a size of 0: the route is not
+ * taken).  nr3d_lotd_bwd_dparam_typed takes the same n_points, max_level and `fold`, enqueued after it on the same stream,
+ * before any other call that uses `fold`; results are bit for bit those of the calls with fold == NULL. */
 uint64_t nr3d_lotd_pair_fold_bytes(const nr3d_lotd_meta_t *meta, uint32_t n_points, int32_t max_level);
-int nr3d_lotd_bwd_dx_fold(const nr3d_lotd_meta_t *meta, uint32_t n_points, int x_dtype, int param_dtype, const void *dL_dy,
-                          int64_t dldy_sn, int64_t dldy_se, const void *dy_dx, int64_t dydx_sn, int64_t dydx_se, void *dL_dx,
-                          void *dL_dy_T, int32_t max_level, void *fold, void *stream);
-int nr3d_lotd_bwd_dparam_typed_fold(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t n_points, int grad_dtype,
-                                    const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
-                                    int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
-                                    void *fold, void *stream);
 
 /* lod_bwd_bwd_input (lotd_torch_api.cu:575-729), three independent outputs:
  * (i)  dL_ddLdy[i, e] = sum_d dL_ddLdx[i, d] * dy_dx[i, e, d]      (lotd_encoding.h:1703-1727) */
@@ -279,24 +274,18 @@ int nr3d_lotd_bwd_bwd_dparam(const nr3d_lotd_meta_t *meta, const void *meta_dev,
                              const void *params, const int64_t *batch_inds, const int64_t *batch_offsets,
                              uint32_t batch_data_size, uint32_t n_batches, int32_t max_level, void *dL_dparam,
                              void *workspace, uint64_t workspace_bytes, void *stream);
-/* (iii) d(dL/dx)/dx (lotd_encoding.h:1157-1298, lotd_hash_only.h:576-695); dL_dx [N, D] fully written. */
+/* (iii) d(dL/dx)/dx (lotd_encoding.h:1157-1298, lotd_hash_only.h:576-695); dL_dx [N, D] fully written.
+ * workspace: optional device scratch of nr3d_lotd_bwd_bwd_dx_workspace_bytes(meta, n_points) bytes (0: not served -- Dense /
+ * Hash metas only).  With it the pseudo levels of a point are worked on side by side (one lane per (point, pseudo level), the
+ * forward's level-major schedule) and summed in level order afterwards; NULL / 0 / too short: one after another in one lane.
+ * Same values (the same bits for 2-feature pseudo levels). */
+uint64_t nr3d_lotd_bwd_bwd_dx_workspace_bytes(const nr3d_lotd_meta_t *meta, uint32_t n_points);
 int nr3d_lotd_bwd_bwd_dx(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t n_points,
                          int x_dtype, int param_dtype, const void *dL_ddLdx,
                          const void *dL_dy, int64_t dldy_sn, int64_t dldy_se, const void *x,
                          const void *params, const int64_t *batch_inds, const int64_t *batch_offsets,
-                         uint32_t batch_data_size, int32_t max_level, void *dL_dx, void *stream);
-/* the same with a scratch buffer of nr3d_lotd_bwd_bwd_dx_workspace_bytes(meta, n_points) bytes (0: not served -- Dense /
- * Hash metas only): the
- * pseudo levels of a point are then worked on side by side (one lane per (point, pseudo level), the forward's level-major
- * schedule) and summed in level order afterwards, instead of one after another in one lane.  Same values (the same bits
- * for 2-feature pseudo levels).  A NULL / short workspace falls back to nr3d_lotd_bwd_bwd_dx. */
-uint64_t nr3d_lotd_bwd_bwd_dx_workspace_bytes(const nr3d_lotd_meta_t *meta, uint32_t n_points);
-int nr3d_lotd_bwd_bwd_dx_ws(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t n_points,
-                            int x_dtype, int param_dtype, const void *dL_ddLdx,
-                            const void *dL_dy, int64_t dldy_sn, int64_t dldy_se, const void *x,
-                            const void *params, const int64_t *batch_inds, const int64_t *batch_offsets,
-                            uint32_t batch_data_size, int32_t max_level, void *dL_dx, void *workspace,
-                            uint64_t workspace_bytes, void *stream);
+                         uint32_t batch_data_size, int32_t max_level, void *dL_dx, void *workspace,
+                         uint64_t workspace_bytes, void *stream);
 
 /* lod_get_grid_index (lotd_torch_api.cu:771-855; kernel lotd_encoding.h:1300-1433):
  * grid_inds int64 [N, n_encoded_dims, 2^D] contiguous, ZERO-INIT.  Dense/Hash levels only. */
@@ -640,23 +629,19 @@ int nr3d_pack_composite_bwd(uint32_t P, const float *alphas, const float *vw, co
 int nr3d_tau_to_alpha_fwd(uint64_t S, const float *sigma, const float *delta, float *alpha, void *stream);
 int nr3d_tau_to_alpha_bwd(uint64_t S, const float *sigma, const float *delta, const float *grad_alpha, float *grad_sigma,
                           void *stream);
-/* Post-processing of the marcher's outputs (nr3d_lib/graphics/raymarch/occgrid_raymarch.py:87-112: nonzero on the counts,
- * index, .long()): packed_info int32 [n_rays, 2] -> the rays with >= 1 sample, ascending: ridx_hit int64 [n_hit],
- * pack_infos int64 [n_hit, 2]; totals int64 [2] = {samples, n_hit} (the caller reads n_hit back; outputs sized n_rays).
- * scan_tmp >= nr3d_scan_tmp_bytes(n_rays).
- * Range of the three compacting entry points (this one, nr3d_ray_marching_count_finished, nr3d_prune_compact_packs): one scan
- * carries the running sample count (36 bits) and the rank among the non-empty packs (28 bits) -- fewer than 2^28 packs /
- * rays per call (checked: nonzero status above that), fewer than 2^36 samples in all (more than a 288 GB device can hold). */
-int nr3d_march_finish_rays(uint32_t n_rays, const int32_t *packed_info, int64_t *ridx_hit, int64_t *pack_infos,
-                           int64_t *totals, void *scan_tmp, void *stream);
-/* ... and per sample (same lines): ridx64 = (int64) ridx, deltas = t_ends - t_starts, samples [S, 3] =
- * fma(rays_d[ridx], t_starts, rays_o[ridx]) (torch.addcmul).  Any output may be NULL. */
+/* Post-processing of the marcher's outputs per sample (nr3d_lib/graphics/raymarch/occgrid_raymarch.py:87-112): ridx64 =
+ * (int64) ridx, deltas = t_ends - t_starts, samples [S, 3] = fma(rays_d[ridx], t_starts, rays_o[ridx]) (torch.addcmul).  Any
+ * output may be NULL. */
 int nr3d_march_finish_samples(uint64_t S, const float *rays_o, const float *rays_d, const int32_t *ridx,
                               const float *t_starts, const float *t_ends, int64_t *ridx64, float *deltas, float *samples,
                               void *stream);
-/* nr3d_ray_marching_count AND nr3d_march_finish_rays with ONE scan of the counts: packed_info as nr3d_ray_marching_count,
- * ridx_hit [n_rays] / pack_infos [n_rays, 2] (their first n_hit rows are written) as nr3d_march_finish_rays,
- * totals = {number of samples, n_hit}. */
+/* nr3d_ray_marching_count AND the per-ray post-processing of the same lines (nonzero on the counts, index, .long()) with ONE
+ * scan of the counts: packed_info int32 [n_rays, 2] as nr3d_ray_marching_count -> the rays with >= 1 sample, ascending:
+ * ridx_hit int64 [n_rays] / pack_infos int64 [n_rays, 2] (their first n_hit rows are written); totals int64 [2] = {number of
+ * samples, n_hit} (the caller reads n_hit back).  scan_tmp >= nr3d_scan_tmp_bytes(n_rays).
+ * Range of the compacting entry points (this one, nr3d_prune_compact_packs): one scan carries the running sample count (36
+ * bits) and the rank among the non-empty packs (28 bits) -- fewer than 2^28 packs / rays per call (checked: nonzero status
+ * above that), fewer than 2^36 samples in all (more than a 288 GB device can hold). */
 int nr3d_ray_marching_count_finished(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
                                      const float *t_max, const float *roi, const int32_t grid_res[3],
                                      const uint8_t *grid_binary, int type, float step_size, float max_step_size,

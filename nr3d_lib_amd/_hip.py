@@ -82,9 +82,13 @@ _CTYPE = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t
 
 def _declare(l):
     """argtypes / restype of EVERY entry point, from the table tools/gen_abi.py generated out of include/nr3d_hip.h at build time
-    (nr3d_lib_amd/_abi.py -- inside the package: a vendored copy needs no header).  With them the bindings pass plain Python
-    ints / floats -- ``ptr()`` is ``tensor.data_ptr()``, no ctypes object per argument (a launch-bound op spent ~10 us per iteration
-    wrapping ~50 arguments) -- and a Python int can no longer be taken for a 32-bit C int where a pointer is meant: every pointer
+    (nr3d_lib_amd/_abi.py -- inside the package: a vendored copy needs no header).  This is the ONLY place that sets either.  With
+    them every call through ``lib()`` passes plain Python values: scalars as int / float / bool, tensor addresses through ``ptr()``
+    (``tensor.data_ptr()``), streams through ``stream_of()``, structs and out-parameters as ``byref()`` results or ctypes arrays --
+    no ctypes object per scalar argument (a launch-bound op spent ~10 us per iteration wrapping ~50 arguments).  ctypes converts
+    by the declared type, takes Python numbers only (a numpy or torch scalar is a TypeError: a binding converts what its own caller
+    handed it with int() / float() / bool(), nothing else) and does not range-check.  A Python int can not be taken for a 32-bit C
+    int where a pointer is meant: every pointer
     parameter is declared c_void_p (which also takes None, ctypes arrays and byref() results).  An entry point of the table that
     the library does not export is an error here, not a crash later; that the table matches the header one to one, and the
     library's exports match both, is tests/test_boundary_cpu.py's job (it regenerates the table and runs nm)."""
@@ -146,13 +150,13 @@ def prof_enable(*names):
     mask = 0
     for n in names:
         mask |= 1 << PROF_IDS[n]
-    lib().nr3d_prof_enable(C.c_uint32(mask))
+    lib().nr3d_prof_enable(mask)
 
 
 def prof_read(name, reset=True):
     """(total ms, number of intervals) recorded for `name` since the last reset; synchronises on the events"""
     ms, n = C.c_double(0.0), C.c_uint32(0)
-    check(lib().nr3d_prof_read(C.c_int(PROF_IDS[name]), C.byref(ms), C.byref(n), C.c_int(1 if reset else 0)))
+    check(lib().nr3d_prof_read(PROF_IDS[name], C.byref(ms), C.byref(n), 1 if reset else 0))
     return float(ms.value), int(n.value)
 
 
@@ -224,8 +228,7 @@ def sort_pairs_u32(keys, values=None, bits=32, n_dev=None):
     assert all(v is None or (v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and v.shape == ks[0].shape) for v in vs)
     n, dev = ks[0].numel(), ks[0].device
     l = lib()
-    l.nr3d_sort_pairs_u32_tmp_bytes.restype = C.c_uint64
-    tmp = torch.empty(int(l.nr3d_sort_pairs_u32_tmp_bytes(C.c_uint32(n), C.c_int(len(ks)))) or 1, dtype=torch.uint8, device=dev)
+    tmp = torch.empty(int(l.nr3d_sort_pairs_u32_tmp_bytes(n, len(ks))) or 1, dtype=torch.uint8, device=dev)
     ko, vo = [empty(n, dtype=torch.int32, device=dev) for _ in ks], [empty(n, dtype=torch.int32, device=dev) for _ in ks]
     a = []
     for i in range(2):
@@ -233,7 +236,7 @@ def sort_pairs_u32(keys, values=None, bits=32, n_dev=None):
         a += [ptr(ks[j]) if j is not None else None, ptr(vs[j]) if j is not None else None,
               ptr(ko[j]) if j is not None else None, ptr(vo[j]) if j is not None else None]
     with on_device(dev):
-        check(l.nr3d_sort_pairs_u32(ptr(tmp), C.c_int(len(ks)), *a, C.c_uint32(n), ptr(n_dev), C.c_int(int(bits)), stream_of(ks[0])))
+        check(l.nr3d_sort_pairs_u32(ptr(tmp), len(ks), *a, n, ptr(n_dev), int(bits), stream_of(ks[0])))
     return (ko, vo) if pair else (ko[0], vo[0])
 
 
@@ -243,12 +246,11 @@ def spatial_order(x, bits_per_dim=6):
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()
     n, dev = x.shape[0], x.device
     l = lib()
-    l.nr3d_spatial_order_tmp_bytes.restype = C.c_uint64
     order = empty(n, dtype=torch.int32, device=dev)
     if n:
-        tmp = torch.empty(int(l.nr3d_spatial_order_tmp_bytes(C.c_uint32(n))), dtype=torch.uint8, device=dev)
+        tmp = torch.empty(int(l.nr3d_spatial_order_tmp_bytes(n)), dtype=torch.uint8, device=dev)
         with on_device(dev):
-            check(l.nr3d_spatial_order(C.c_uint32(n), ptr(x), C.c_uint32(int(bits_per_dim)), ptr(order), ptr(tmp), stream_of(x)))
+            check(l.nr3d_spatial_order(n, ptr(x), int(bits_per_dim), ptr(order), ptr(tmp), stream_of(x)))
     return order
 
 
@@ -263,7 +265,7 @@ def order_gather_inputs(order, x, ridx=None, dirs=None):
     r_s = empty(n, dtype=torch.int64, device=dev) if ridx is not None else None
     d_s = empty((n, 3), dtype=torch.float32, device=dev) if dirs is not None else None
     with on_device(dev):
-        check(lib().nr3d_order_gather_inputs(C.c_uint32(n), ptr(order), ptr(x), ptr(ridx), ptr(dirs), ptr(x_s), ptr(r_s), ptr(d_s), stream_of(x)))
+        check(lib().nr3d_order_gather_inputs(n, ptr(order), ptr(x), ptr(ridx), ptr(dirs), ptr(x_s), ptr(r_s), ptr(d_s), stream_of(x)))
     return x_s, r_s, d_s
 
 
@@ -280,9 +282,24 @@ def order_move_rows(order, a, b=None, scatter=True):
         wb = b.numel() // max(n, 1)
         b_out = empty(b.shape, dtype=torch.float32, device=dev)
     with on_device(dev):
-        check(lib().nr3d_order_move_rows(C.c_uint32(n), ptr(order), C.c_int(1 if scatter else 0), ptr(a), C.c_uint32(wa), ptr(a_out),
-                                         ptr(b), C.c_uint32(wb), ptr(b_out), stream_of(a)))
+        check(lib().nr3d_order_move_rows(n, ptr(order), 1 if scatter else 0, ptr(a), wa, ptr(a_out), ptr(b), wb, ptr(b_out),
+                                         stream_of(a)))
     return a_out, b_out
+
+
+_workspaces = {}
+
+
+def workspace(nbytes, device):
+    """uint8 scratch of at least ``nbytes`` bytes for ONE library call, grown on demand; one buffer per (device index, raw stream),
+    so calls on one stream share it in stream order and calls on different streams never do.  Contents do not survive the call."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _workspaces.get(key)
+    if ws is None or ws.numel() < nbytes:
+        _workspaces.pop(key, None)          # the short one goes back to the allocator before the larger one is asked for
+        ws = None
+        ws = _workspaces[key] = empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
 
 
 class _NoCtx:
@@ -406,20 +423,3 @@ def require_gpu(*tensors):
         if t is not None and not t.is_cuda:
             raise RuntimeError("nr3d_lib_amd: kernels run on the GPU only (got a CPU tensor); "
                                "there is no CPU fallback in the product path")
-
-
-# scalar arguments: plain Python values (the entry points' argtypes convert them, _declare)
-def i64(v):
-    return int(v)
-
-
-def u32(v):
-    return int(v)
-
-
-def i32(v):
-    return int(v)
-
-
-def f32(v):
-    return float(v)

@@ -76,7 +76,7 @@ def forest_identify(forest: ForestMeta, ks: torch.Tensor) -> torch.Tensor:
     out = H.empty(k16.shape[0], dtype=torch.int32, device=ks.device)
     with H.on_device(ks.device):
         c = forest._c()
-        H.check(H.lib().nr3d_forest_identify(C.byref(c), C.c_uint64(k16.shape[0]), H.ptr(k16), H.ptr(out), H.stream_of(ks)))
+        H.check(H.lib().nr3d_forest_identify(C.byref(c), k16.shape[0], H.ptr(k16), H.ptr(out), H.stream_of(ks)))
     return out.view(ks.shape[:-1])
 
 
@@ -97,26 +97,14 @@ def _check(fn, metas, input, params, block_inds, block_offsets, batch_data_size)
     return m, fo, N, bds
 
 
-_workspaces = {}
-
-
 def _workspace(m, fo, N, dev):
     """scratch of the atomic-free parameter-gradient path (blocks play the role of batch entries; every 3-D level type
     of the forest kernels: per-corner records, nr3d_lotd_forest_dparam_workspace_bytes); (None, 0): global atomics"""
     from . import _lotd
     if not _lotd.USE_BINNED_DPARAM:
         return None, 0
-    H.lib().nr3d_lotd_forest_dparam_workspace_bytes.restype = C.c_uint64
-    need = int(H.lib().nr3d_lotd_forest_dparam_workspace_bytes(C.byref(m._cmeta()), H.u32(N), H.u32(int(fo.n_trees))))
-    if need == 0:
-        return None, 0
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < need:
-        _workspaces.pop(key, None)
-        ws = H.empty(need, dtype=torch.uint8, device=dev)
-        _workspaces[key] = ws
-    return ws, need
+    need = H.lib().nr3d_lotd_forest_dparam_workspace_bytes(C.byref(m._cmeta()), N, int(fo.n_trees))
+    return (H.workspace(need, dev), need) if need else (None, 0)
 
 
 def lod_fwd(metas, input, params, batch_inds=None, batch_offsets=None, batch_data_size=None, max_level=None,
@@ -141,9 +129,8 @@ def lod_fwd(metas, input, params, batch_inds=None, batch_offsets=None, batch_dat
                 dy_dx, dsn, dse = H.empty((N, E * 3), dtype=torch.float32, device=dev), E * 3, 3
         c = fo._c()
         H.check(H.lib().nr3d_lotd_forest_fwd(
-            C.byref(m._cmeta()), H.ptr(m._dev(dev)), C.byref(c), H.u32(N), H.ptr(x32), H.ptr(p32), C.c_int(pcode), H.ptr(batch_inds),
-            H.ptr(batch_offsets), H.u32(bds), H.i32(max_level), H.ptr(y), H.i64(y.stride(0)), H.i64(y.stride(1)),
-            H.ptr(dy_dx), H.i64(dsn), H.i64(dse), H.stream_of(input)))
+            C.byref(m._cmeta()), H.ptr(m._dev(dev)), C.byref(c), N, H.ptr(x32), H.ptr(p32), pcode, H.ptr(batch_inds),
+            H.ptr(batch_offsets), bds, max_level, H.ptr(y), y.stride(0), y.stride(1), H.ptr(dy_dx), dsn, dse, H.stream_of(input)))
     return _lotd._cast(y, params.dtype), _lotd._cast(dy_dx, input.dtype)
 
 
@@ -175,16 +162,15 @@ def lod_bwd(metas, dL_dy, input, params, dy_dx=None, batch_inds=None, batch_offs
         if need_input_grad:
             j, jsn, jse = _lotd._jac_view(dy_dx.detach(), N, E, 3)
             H.check(H.lib().nr3d_lotd_bwd_dx(
-                C.byref(m._cmeta()), H.u32(N), C.c_int(H.F32), C.c_int(H.F32), H.ptr(g32), H.i64(E), H.i64(1),
-                H.ptr(j), H.i64(jsn), H.i64(jse), H.ptr(dL_dx), None, st))
+                C.byref(m._cmeta()), N, H.F32, H.F32, H.ptr(g32), E, 1, H.ptr(j), jsn, jse, H.ptr(dL_dx), None, max_level, None,
+                st))
         if need_param_grad:
             x32, (p32, pcode) = _lotd._f32c(input.detach()), _lotd._ptab(params)
             c = fo._c()
             ws, wsb = _workspace(m, fo, N, dev)
             H.check(H.lib().nr3d_lotd_forest_bwd_dparam(
-                C.byref(m._cmeta()), H.ptr(m._dev(dev)), C.byref(c), H.u32(N), None, H.ptr(g32), H.ptr(x32), H.ptr(p32), C.c_int(pcode),
-                H.ptr(batch_inds), H.ptr(batch_offsets), H.u32(bds), H.i32(max_level), H.ptr(dL_dparam), H.ptr(ws),
-                C.c_uint64(wsb), st))
+                C.byref(m._cmeta()), H.ptr(m._dev(dev)), C.byref(c), N, None, H.ptr(g32), H.ptr(x32), H.ptr(p32), pcode,
+                H.ptr(batch_inds), H.ptr(batch_offsets), bds, max_level, H.ptr(dL_dparam), H.ptr(ws), wsb, st))
     return _lotd._cast(dL_dx, input.dtype), _lotd._cast(dL_dparam, params.dtype)
 
 
@@ -225,17 +211,16 @@ def lod_bwd_bwd_input(metas, dL_ddLdx, dL_dy, input, params, dy_dx=None, batch_i
         if need_dLdy:
             j, jsn, jse = _lotd._jac_view(dy_dx.detach(), N, E, 3)
             H.check(H.lib().nr3d_lotd_bwd_bwd_ddLdy(
-                cm, H.u32(N), C.c_int(H.F32), C.c_int(H.F32), H.ptr(v32), H.ptr(j), H.i64(jsn), H.i64(jse),
-                H.ptr(dL_ddLdy), H.i64(E), H.i64(1), st))
+                cm, N, H.F32, H.F32, H.ptr(v32), H.ptr(j), jsn, jse, H.ptr(dL_ddLdy), E, 1, st))
         if need_dx:
             H.check(H.lib().nr3d_lotd_forest_bwd_bwd_dx(
-                cm, md, C.byref(c), H.u32(N), H.ptr(v32), H.ptr(g32), H.ptr(x32), H.ptr(p32), C.c_int(pcode), H.ptr(batch_inds),
-                H.ptr(batch_offsets), H.u32(bds), H.i32(max_level), H.ptr(dL_dx), st))
+                cm, md, C.byref(c), N, H.ptr(v32), H.ptr(g32), H.ptr(x32), H.ptr(p32), pcode, H.ptr(batch_inds),
+                H.ptr(batch_offsets), bds, max_level, H.ptr(dL_dx), st))
         if need_dp:
             ws, wsb = _workspace(m, fo, N, dev)
             H.check(H.lib().nr3d_lotd_forest_bwd_dparam(
-                cm, md, C.byref(c), H.u32(N), H.ptr(v32), H.ptr(g32), H.ptr(x32), H.ptr(p32), C.c_int(pcode), H.ptr(batch_inds),
-                H.ptr(batch_offsets), H.u32(bds), H.i32(max_level), H.ptr(dL_dparams), H.ptr(ws), C.c_uint64(wsb), st))
+                cm, md, C.byref(c), N, H.ptr(v32), H.ptr(g32), H.ptr(x32), H.ptr(p32), pcode, H.ptr(batch_inds),
+                H.ptr(batch_offsets), bds, max_level, H.ptr(dL_dparams), H.ptr(ws), wsb, st))
     return _lotd._cast(dL_ddLdy, dL_dy.dtype), _lotd._cast(dL_dparams, params.dtype), _lotd._cast(dL_dx, input.dtype)
 
 

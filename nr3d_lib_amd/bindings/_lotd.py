@@ -102,9 +102,7 @@ class LoDMeta:
         self.level_types_str = [str(t) for t in lod_types]
         tp = (C.c_int32 * L)(*[int(string_to_lod_type(t)) for t in lod_types])
         self._c = _CMeta()
-        H.check(H.lib().nr3d_lotd_meta_create(C.c_int32(D), C.c_uint32(L), res, nf, tp,
-                                              C.c_uint32(int(hashmap_size or 0)),
-                                              C.c_int(int(bool(use_smooth_step))), C.byref(self._c)))
+        H.check(H.lib().nr3d_lotd_meta_create(D, L, res, nf, tp, int(hashmap_size or 0), bool(use_smooth_step), C.byref(self._c)))
         c = self._c
         # the per-level lists (level_res_multidim, level_res, level_n_feats, level_types, level_sizes, level_n_params, level_offsets,
         # map_levels, map_cnt) are read out of the C struct on first use (__getattr__ below): building them here was half of the
@@ -139,7 +137,7 @@ class LoDMeta:
             groups = []
             for width in (8, 4, 2):
                 g = _CMeta()
-                H.check(H.lib().nr3d_lotd_meta_regroup(C.byref(self._c), C.c_uint32(width), C.c_uint32(8), C.byref(g)))
+                H.check(H.lib().nr3d_lotd_meta_regroup(C.byref(self._c), width, 8, C.byref(g)))
                 if g.n_pseudo_levels:
                     groups.append(g)
             if len(groups) > 1 or (groups and groups[0].n_feat_per_pseudo_lvl != self.n_feat_per_pseudo_lvl):
@@ -254,8 +252,6 @@ def _check_common(fn, meta, input, params, batch_inds, batch_offsets, batch_data
     return N, bds
 
 
-# scratch for the atomic-free parameter-gradient path, grown on demand, one buffer per (device, stream)
-_workspaces = {}
 USE_BINNED_DPARAM = True      # False forces the hardware-atomic scatter (debug / A-B measurements)
 
 
@@ -271,18 +267,8 @@ def _dparam_workspace(meta, n_points, device, n_batches=1):
     does not apply to this meta."""
     if not USE_BINNED_DPARAM:
         return None, 0
-    H.lib().nr3d_lotd_dparam_workspace_bytes.restype = C.c_uint64
-    need = int(H.lib().nr3d_lotd_dparam_workspace_bytes(C.byref(meta._cmeta()), H.u32(n_points), H.u32(n_batches)))
-    if need == 0:
-        return None, 0
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < need:
-        ws = None
-        _workspaces.pop(key, None)
-        ws = H.empty(need, dtype=torch.uint8, device=device)
-        _workspaces[key] = ws
-    return ws, need
+    need = H.lib().nr3d_lotd_dparam_workspace_bytes(C.byref(meta._cmeta()), n_points, n_batches)
+    return (H.workspace(need, device), need) if need else (None, 0)
 
 
 def _f32c(t):
@@ -318,7 +304,7 @@ def _native_half(meta, params, batched):
     """the kernels read __half params / dL_dy and write __half y / dL_dparam themselves ((float, half, float) type
     combination, lotd_encoding.h:1501-1504): no whole-table conversion per call"""
     return (NATIVE_HALF and params.dtype == torch.float16 and not batched and params.data_ptr() % 4 == 0
-            and bool(H.lib().nr3d_lotd_half_params_ok(C.byref(meta._cmeta()), C.c_int(0))))
+            and bool(H.lib().nr3d_lotd_half_params_ok(C.byref(meta._cmeta()), 0)))
 
 
 def _strides2(t):
@@ -398,10 +384,8 @@ def lod_fwd(lod_meta, input, params, batch_inds=None, batch_offsets=None, batch_
         with _Prof(m, f"LoTD{D}-fwd" + ("-grad" if need_input_grad else ""), N):
             for cm, md in m._calls(dev):          # one call, or one per feature width (disjoint output columns)
                 H.check(H.lib().nr3d_lotd_fwd(
-                    cm, md, H.u32(N), C.c_int(H.F32), C.c_int(pcode),
-                    H.ptr(x32), H.ptr(p32), H.ptr(batch_inds), H.ptr(batch_offsets), H.u32(bds), H.i32(max_level),
-                    H.ptr(y_store), H.i64(y.stride(0)), H.i64(y.stride(1)),
-                    H.ptr(dy_dx), H.i64(dsn), H.i64(dse), H.stream_of(input)))
+                    cm, md, N, H.F32, pcode, H.ptr(x32), H.ptr(p32), H.ptr(batch_inds), H.ptr(batch_offsets), bds, max_level,
+                    H.ptr(y_store), y.stride(0), y.stride(1), H.ptr(dy_dx), dsn, dse, H.stream_of(input)))
     if y.dtype != params.dtype:
         y = y.to(params.dtype)
     if dy_dx is not None and input.dtype != torch.float32:
@@ -479,22 +463,19 @@ def lod_bwd(lod_meta, dL_dy, input, params, dy_dx=None, batch_inds=None, batch_o
                     # ... and, on the pair path, the fixed-point scale and zeroed tickets of the dL/dparam launches
                     # (nr3d_lotd_pair_fold_bytes: 0 when that route does not apply)
                     if typed:
-                        fb = H.lib().nr3d_lotd_pair_fold_bytes
-                        fb.restype = C.c_uint64
-                        nfold = int(fb(C.byref(m._cmeta()), H.u32(N), H.i32(max_level)))
+                        nfold = H.lib().nr3d_lotd_pair_fold_bytes(C.byref(m._cmeta()), N, max_level)
                         if nfold:
                             fold = H.empty(((nfold + 3) // 4,), dtype=torch.int32, device=dev)
-                H.check(H.lib().nr3d_lotd_bwd_dx_fold(
-                    C.byref(m._cmeta()), H.u32(N), C.c_int(H.F32), C.c_int(gcode), H.ptr(g32), H.i64(gsn),
-                    H.i64(gse), H.ptr(j), H.i64(jsn), H.i64(jse), H.ptr(dL_dx), H.ptr(gT), H.i32(max_level), H.ptr(fold), st))
+                H.check(H.lib().nr3d_lotd_bwd_dx(
+                    C.byref(m._cmeta()), N, H.F32, gcode, H.ptr(g32), gsn, gse, H.ptr(j), jsn, jse, H.ptr(dL_dx), H.ptr(gT),
+                    max_level, H.ptr(fold), st))
             if need_param_grad and N > 0 and typed:
                 ws, wsb = _dparam_workspace(m, N, dev, 1)
                 if gT is not None:
                     g32, gsn, gse, gcode = gT, 1, N, H.F32
-                H.check(H.lib().nr3d_lotd_bwd_dparam_typed_fold(
-                    C.byref(m._cmeta()), H.ptr(m._dev(dev)), H.u32(N), C.c_int(gcode), H.ptr(g32), H.i64(gsn), H.i64(gse),
-                    H.ptr(_f32c(input.detach())), H.i32(max_level), C.c_int(H.F16 if native else H.F32), C.c_int(1),
-                    H.ptr(dL_dparam), H.ptr(ws), C.c_uint64(wsb), H.ptr(fold), st))
+                H.check(H.lib().nr3d_lotd_bwd_dparam_typed(
+                    C.byref(m._cmeta()), H.ptr(m._dev(dev)), N, gcode, H.ptr(g32), gsn, gse, H.ptr(_f32c(input.detach())),
+                    max_level, H.F16 if native else H.F32, 1, H.ptr(dL_dparam), H.ptr(ws), wsb, H.ptr(fold), st))
             elif need_param_grad and N > 0:
                 x32, (p32, pcode) = _f32c(input.detach()), _ptab(params)
                 nbat = _n_batches(m, p32, batch_offsets, batched)
@@ -503,10 +484,8 @@ def lod_bwd(lod_meta, dL_dy, input, params, dy_dx=None, batch_inds=None, batch_o
                     g32, gsn, gse = gT, 1, N
                 if level_buckets is None:
                     H.check(H.lib().nr3d_lotd_bwd_dparam(
-                        C.byref(m._cmeta()), H.ptr(m._dev(dev)), H.u32(N), C.c_int(H.F32), C.c_int(pcode),
-                        H.ptr(g32), H.i64(gsn), H.i64(gse), H.ptr(x32), H.ptr(p32), H.ptr(batch_inds),
-                        H.ptr(batch_offsets), H.u32(bds), H.u32(nbat), H.i32(max_level), H.ptr(dL_dparam), H.ptr(ws),
-                        C.c_uint64(wsb), st))
+                        C.byref(m._cmeta()), H.ptr(m._dev(dev)), N, H.F32, pcode, H.ptr(g32), gsn, gse, H.ptr(x32), H.ptr(p32),
+                        H.ptr(batch_inds), H.ptr(batch_offsets), bds, nbat, max_level, H.ptr(dL_dparam), H.ptr(ws), wsb, st))
                 else:
                     if batched:
                         raise RuntimeError("bwd: level_buckets need non-batched params")
@@ -519,10 +498,8 @@ def lod_bwd(lod_meta, dL_dy, input, params, dy_dx=None, batch_inds=None, batch_o
                             raise RuntimeError(f"bwd: bad or overlapping level bucket {(lo, hi)}")
                         seen |= set(range(lo, hi + 1))
                         H.check(H.lib().nr3d_lotd_bwd_dparam_levels(
-                            C.byref(m._cmeta()), H.ptr(m._dev(dev)), H.u32(N), C.c_int(H.F32), C.c_int(H.F32),
-                            H.ptr(g32), H.i64(gsn), H.i64(gse), H.ptr(x32), H.ptr(p32), None, None, H.u32(0),
-                            H.u32(nbat), H.i32(lo), H.i32(min(hi, max_level)), H.ptr(dL_dparam), H.ptr(ws),
-                            C.c_uint64(wsb), st))
+                            C.byref(m._cmeta()), H.ptr(m._dev(dev)), N, H.F32, H.F32, H.ptr(g32), gsn, gse, H.ptr(x32), H.ptr(p32),
+                            None, None, 0, nbat, lo, min(hi, max_level), H.ptr(dL_dparam), H.ptr(ws), wsb, st))
                         if on_bucket is not None:
                             on_bucket(k, dL_dparam[m.level_offsets[lo]:m.level_offsets[hi + 1]])
     return _cast(dL_dx, input.dtype), _cast(dL_dparam, params.dtype)
@@ -586,37 +563,32 @@ def lod_bwd_bwd_input(lod_meta, dL_ddLdx, dL_dy, input, params, dy_dx=None, batc
             if need_dLdy:
                 j, jsn, jse = _jac_view(dy_dx.detach(), N, E, D)
                 H.check(H.lib().nr3d_lotd_bwd_bwd_ddLdy(
-                    cm, H.u32(N), C.c_int(H.F32), C.c_int(H.F32), H.ptr(v32), H.ptr(j), H.i64(jsn), H.i64(jse),
-                    H.ptr(dL_ddLdy), H.i64(dL_ddLdy.stride(0)), H.i64(dL_ddLdy.stride(1)), st))
+                    cm, N, H.F32, H.F32, H.ptr(v32), H.ptr(j), jsn, jse, H.ptr(dL_ddLdy), dL_ddLdy.stride(0), dL_ddLdy.stride(1),
+                    st))
             batched = batch_inds is not None or batch_offsets is not None or bds != 0
             wsb = 0
             if need_dx:
                 # scratch for the level-parallel form ([n_pseudo, N, D] floats), while it stays below HVP_WORKSPACE_MAX_BYTES
-                f = H.lib().nr3d_lotd_bwd_bwd_dx_workspace_bytes
-                f.restype = C.c_uint64
-                wsb = int(f(cm, H.u32(N)))
+                wsb = H.lib().nr3d_lotd_bwd_bwd_dx_workspace_bytes(cm, N)
             if (need_dx and need_dp and not batched and 0 < wsb <= HVP_WORKSPACE_MAX_BYTES and USE_BINNED_DPARAM
                     and gse == 1 and gsn == E):
                 # both level-major passes of this step read dL_dy feature-major: ONE copy for the two of them (each would make
                 # its own: the parameter pass a [E, N] transposition, the Hessian pass its by-level pairs)
                 gT = H.empty((E, N), dtype=torch.float32, device=dev)
-                H.check(H.lib().nr3d_lotd_dLdy_feature_major(H.u32(N), H.u32(E), C.c_int(H.F32), H.ptr(g32), H.i64(gsn), H.i64(gse),
-                                                             H.ptr(gT), st))
+                H.check(H.lib().nr3d_lotd_dLdy_feature_major(N, E, H.F32, H.ptr(g32), gsn, gse, H.ptr(gT), st))
                 g32, gsn, gse = gT, 1, N
             if need_dx:
                 ws = (H.empty((wsb + 3) // 4, dtype=torch.float32, device=dev)
                       if 0 < wsb <= HVP_WORKSPACE_MAX_BYTES else None)
-                H.check(H.lib().nr3d_lotd_bwd_bwd_dx_ws(
-                    cm, md, H.u32(N), C.c_int(H.F32), C.c_int(pcode), H.ptr(v32), H.ptr(g32), H.i64(gsn),
-                    H.i64(gse), H.ptr(x32), H.ptr(p32), H.ptr(batch_inds), H.ptr(batch_offsets), H.u32(bds),
-                    H.i32(max_level), H.ptr(dL_dx), H.ptr(ws), C.c_uint64(wsb if ws is not None else 0), st))
+                H.check(H.lib().nr3d_lotd_bwd_bwd_dx(
+                    cm, md, N, H.F32, pcode, H.ptr(v32), H.ptr(g32), gsn, gse, H.ptr(x32), H.ptr(p32), H.ptr(batch_inds),
+                    H.ptr(batch_offsets), bds, max_level, H.ptr(dL_dx), H.ptr(ws), wsb if ws is not None else 0, st))
             if need_dp:
                 nbat = _n_batches(m, p32, batch_offsets, batched)
                 ws, wsb = _dparam_workspace(m, N, dev, nbat)
                 H.check(H.lib().nr3d_lotd_bwd_bwd_dparam(
-                    cm, md, H.u32(N), C.c_int(H.F32), C.c_int(pcode), H.ptr(v32), H.ptr(g32), H.i64(gsn),
-                    H.i64(gse), H.ptr(x32), H.ptr(p32), H.ptr(batch_inds), H.ptr(batch_offsets), H.u32(bds),
-                    H.u32(nbat), H.i32(max_level), H.ptr(dL_dparams), H.ptr(ws), C.c_uint64(wsb), st))
+                    cm, md, N, H.F32, pcode, H.ptr(v32), H.ptr(g32), gsn, gse, H.ptr(x32), H.ptr(p32), H.ptr(batch_inds),
+                    H.ptr(batch_offsets), bds, nbat, max_level, H.ptr(dL_dparams), H.ptr(ws), wsb, st))
     return _cast(dL_ddLdy, dL_dy.dtype), _cast(dL_dparams, params.dtype), _cast(dL_dx, input.dtype)
 
 
@@ -640,6 +612,6 @@ def lod_get_grid_index(lod_meta, input, batch_inds=None, batch_offsets=None, bat
         if max_level <= -1 or N == 0:
             return out
         H.check(H.lib().nr3d_lotd_grid_index(
-            C.byref(m._cmeta()), H.ptr(m._dev(dev)), H.u32(N), C.c_int(H.F32), H.ptr(_f32c(input.detach())),
-            H.ptr(batch_inds), H.ptr(batch_offsets), H.u32(bds), H.i32(max_level), H.ptr(out), H.stream_of(input)))
+            C.byref(m._cmeta()), H.ptr(m._dev(dev)), N, H.F32, H.ptr(_f32c(input.detach())), H.ptr(batch_inds),
+            H.ptr(batch_offsets), bds, max_level, H.ptr(out), H.stream_of(input)))
     return out

@@ -30,14 +30,11 @@ class MLPDesc:
         c.hidden_activation, c.output_activation = self.hidden_activation, self.output_activation
         self._c = c
         l = H.lib()
-        for fn in (l.nr3d_mlp_packed_floats, l.nr3d_mlp_backward_packed_floats, l.nr3d_mlp_half_packed_bytes,
-                   l.nr3d_mlp_half_backward_packed_bytes):
-            fn.restype = C.c_uint64
-        self.packed_floats = int(l.nr3d_mlp_packed_floats(C.byref(c))) if c.n_layers else 0
-        self.backward_floats = int(l.nr3d_mlp_backward_packed_floats(C.byref(c))) if self.packed_floats else 0
+        self.packed_floats = l.nr3d_mlp_packed_floats(C.byref(c)) if c.n_layers else 0
+        self.backward_floats = l.nr3d_mlp_backward_packed_floats(C.byref(c)) if self.packed_floats else 0
         # the half-precision twin (csrc/mlp_half.hip, f16 MFMA): sizes in bytes
-        self.half_packed_bytes = int(l.nr3d_mlp_half_packed_bytes(C.byref(c))) if c.n_layers else 0
-        self.half_backward_bytes = int(l.nr3d_mlp_half_backward_packed_bytes(C.byref(c))) if self.half_packed_bytes else 0
+        self.half_packed_bytes = l.nr3d_mlp_half_packed_bytes(C.byref(c)) if c.n_layers else 0
+        self.half_backward_bytes = l.nr3d_mlp_half_backward_packed_bytes(C.byref(c)) if self.half_packed_bytes else 0
         # the fused double backward (nr3d_mlp_backward_backward) on the fp32 packed buffer
         self.second_order_ok = bool(l.nr3d_mlp_backward_backward_ok(C.byref(c))) if self.backward_floats else False
 
@@ -84,7 +81,7 @@ def pack(desc: MLPDesc, weights, biases, with_backward=False) -> torch.Tensor:
         raise RuntimeError("mlp.pack: the fused backward does not apply to this network")
     packed = H.empty(desc.packed_floats + (desc.backward_floats if with_backward else 0), dtype=torch.float32, device=dev)
     with H.on_device(dev):
-        H.check(H.lib().nr3d_mlp_pack(C.byref(desc._c), _ptr_array(ws), _ptr_array(bs), H.ptr(packed), C.c_int(int(with_backward)),
+        H.check(H.lib().nr3d_mlp_pack(C.byref(desc._c), _ptr_array(ws), _ptr_array(bs), H.ptr(packed), int(with_backward),
                                       H.stream_of(packed)))
     return packed
 
@@ -109,8 +106,8 @@ def forward(desc: MLPDesc, x: torch.Tensor, packed: torch.Tensor) -> torch.Tenso
     n = x2.shape[0]
     y = H.empty((n, desc.dims[-1]), dtype=torch.float32, device=x.device)
     with H.on_device(x.device):
-        H.check(H.lib().nr3d_mlp_forward(C.byref(desc._c), C.c_uint64(n), H.ptr(x2), H.i64(xs), H.i64(xf),
-                                         H.ptr(packed), H.ptr(y), H.i64(y.shape[1]), H.stream_of(x)))
+        H.check(H.lib().nr3d_mlp_forward(C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(packed), H.ptr(y), y.shape[1],
+                                         H.stream_of(x)))
     return y.view(*x.shape[:-1], desc.dims[-1])
 
 
@@ -142,9 +139,8 @@ def backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, packed: torch.
         dx = H.empty((n, desc.dims[0]), dtype=torch.float32, device=dev)
     with H.on_device(dev):
         H.check(H.lib().nr3d_mlp_backward(
-            C.byref(desc._c), C.c_uint64(n), H.ptr(x2), H.i64(xs), H.i64(xf), H.ptr(g2),
-            H.i64(g2.stride(0) if n > 1 else desc.dims[-1]), H.ptr(packed), H.ptr(dx), H.i64(gxs), H.i64(gxf), _ptr_array(dWs),
-            _ptr_array(dbs), H.stream_of(x)))
+            C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(g2), g2.stride(0) if n > 1 else desc.dims[-1], H.ptr(packed), H.ptr(dx),
+            gxs, gxf, _ptr_array(dWs), _ptr_array(dbs), H.stream_of(x)))
     return (None if dx is None else dx.reshape(x.shape)), dWs, dbs
 
 
@@ -178,9 +174,8 @@ def backward_backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, ddL_d
     dgy = H.empty((n, desc.dims[-1]), dtype=torch.float32, device=dev) if need_dgy else None
     with H.on_device(dev):
         H.check(H.lib().nr3d_mlp_backward_backward(
-            C.byref(desc._c), C.c_uint64(n), H.ptr(x2), H.i64(xs), H.i64(xf), H.ptr(g2),
-            H.i64(g2.stride(0) if n > 1 else desc.dims[-1]), H.ptr(v2), H.i64(vs), H.i64(vf), H.ptr(packed), H.ptr(dgy),
-            H.i64(desc.dims[-1]), _ptr_array(dWs), H.stream_of(x)))
+            C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(g2), g2.stride(0) if n > 1 else desc.dims[-1], H.ptr(v2), vs, vf,
+            H.ptr(packed), H.ptr(dgy), desc.dims[-1], _ptr_array(dWs), H.stream_of(x)))
     return (None if dgy is None else dgy.view(dL_dy.shape)), dWs, dbs
 
 
@@ -203,7 +198,7 @@ def pack_half(desc: MLPDesc, weights, biases, with_backward=False) -> torch.Tens
         raise RuntimeError("mlp.pack_half: the fused backward does not apply to this network")
     packed = H.empty(desc.half_packed_bytes + (desc.half_backward_bytes if with_backward else 0), dtype=torch.uint8, device=dev)
     with H.on_device(dev):
-        H.check(H.lib().nr3d_mlp_half_pack(C.byref(desc._c), _ptr_array(ws), _ptr_array(bs), H.ptr(packed), C.c_int(int(with_backward)),
+        H.check(H.lib().nr3d_mlp_half_pack(C.byref(desc._c), _ptr_array(ws), _ptr_array(bs), H.ptr(packed), int(with_backward),
                                            H.stream_of(packed)))
     return packed
 
@@ -217,8 +212,8 @@ def forward_half(desc: MLPDesc, x: torch.Tensor, packed: torch.Tensor) -> torch.
     n = x2.shape[0]
     y = H.empty((n, desc.dims[-1]), dtype=torch.float16, device=x.device)
     with H.on_device(x.device):
-        H.check(H.lib().nr3d_mlp_half_forward(C.byref(desc._c), C.c_uint64(n), H.ptr(x2), H.i64(xs), H.i64(xf),
-                                              H.ptr(packed), H.ptr(y), H.i64(y.shape[1]), H.stream_of(x)))
+        H.check(H.lib().nr3d_mlp_half_forward(C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(packed), H.ptr(y), y.shape[1],
+                                              H.stream_of(x)))
     return y.view(*x.shape[:-1], desc.dims[-1])
 
 
@@ -247,7 +242,6 @@ def backward_half(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, packed: t
         dx = H.empty((n, desc.dims[0]), dtype=torch.float16, device=dev)
     with H.on_device(dev):
         H.check(H.lib().nr3d_mlp_half_backward(
-            C.byref(desc._c), C.c_uint64(n), H.ptr(x2), H.i64(xs), H.i64(xf), H.ptr(g2),
-            H.i64(g2.stride(0) if n > 1 else desc.dims[-1]), H.ptr(packed), H.ptr(dx), H.i64(gxs), H.i64(gxf), _ptr_array(dWs),
-            _ptr_array(dbs), H.stream_of(x)))
+            C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(g2), g2.stride(0) if n > 1 else desc.dims[-1], H.ptr(packed), H.ptr(dx),
+            gxs, gxf, _ptr_array(dWs), _ptr_array(dbs), H.stream_of(x)))
     return (None if dx is None else dx.reshape(x.shape)), dWs, dbs

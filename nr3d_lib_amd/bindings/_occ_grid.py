@@ -47,8 +47,14 @@ def _scan_tmp_bytes(n):
     """nr3d_scan_tmp_bytes(n), remembered per n (a binding call costs more than the lookup)"""
     b = _SCAN_TMP.get(n)
     if b is None:
-        b = _SCAN_TMP[n] = int(H.lib().nr3d_scan_tmp_bytes(C.c_uint64(max(n, 1))))
+        b = _SCAN_TMP[n] = int(H.lib().nr3d_scan_tmp_bytes(max(n, 1)))
     return b
+
+
+def _cache_bytes(n_rays, max_steps):
+    """size of the marcher's sample cache: what nr3d_ray_marching_cache_bytes returns, without the call (12 B per possible sample;
+    tests/test_boundary_cpu.py holds the two together)"""
+    return n_rays * max_steps * 12
 
 
 def _march(rays_o, rays_d, t_min, t_max, batch_inds, batch_data_size, roi, grid_binary, contraction_type,
@@ -83,14 +89,14 @@ def _march(rays_o, rays_d, t_min, t_max, batch_inds, batch_data_size, roi, grid_
         bds = 0
     dev = rays_o.device
     res = (C.c_int32 * 3)(*[int(s) for s in grid_binary.shape[-3:]])
-    ctype = C.c_int(int(contraction_type))
+    ctype = int(contraction_type)
     with H.on_device(dev):
         st = H.stream_of(rays_o)
         packed_info = H.empty((n, 2), dtype=torch.int32, device=dev)
         total = None if finish else H.host_i64(1, dev)      # pinned host word the scan writes into
         tmp = H.empty((_scan_tmp_bytes(n) + 7) // 8, dtype=torch.int64, device=dev)
         # sample cache: the count pass keeps every sample, the emit pass only compacts (no second march)
-        cache_bytes = n * int(max_steps) * 12
+        cache_bytes = _cache_bytes(n, int(max_steps))
         cache = (H.empty((cache_bytes + 3) // 4, dtype=torch.int32, device=dev)
                  if 0 < cache_bytes <= SAMPLE_CACHE_MAX_BYTES else None)
         if finish:
@@ -100,17 +106,16 @@ def _march(rays_o, rays_d, t_min, t_max, batch_inds, batch_data_size, roi, grid_
             pack_infos = H.empty((n, 2), dtype=torch.int64, device=dev)
             totals = H.host_i64(2, dev)
             H.check(H.lib().nr3d_ray_marching_count_finished(
-                H.u32(n), H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_binary),
-                ctype, H.f32(step_size), H.f32(max_step_size), H.f32(dt_gamma), H.u32(max_steps), C.c_int(int(batched)),
-                H.ptr(batch_inds), H.u32(bds), H.ptr(packed_info), H.ptr(ridx_hit), H.ptr(pack_infos), H.ptr(totals), H.ptr(tmp),
-                H.ptr(cache), C.c_uint64(cache_bytes if cache is not None else 0), st))
+                n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_binary), ctype,
+                float(step_size), float(max_step_size), float(dt_gamma), int(max_steps), batched, H.ptr(batch_inds), bds,
+                H.ptr(packed_info), H.ptr(ridx_hit), H.ptr(pack_infos), H.ptr(totals), H.ptr(tmp), H.ptr(cache),
+                cache_bytes if cache is not None else 0, st))
             S, n_hit = H.wait_i64(totals, dev)
         else:
             H.check(H.lib().nr3d_ray_marching_count(
-                H.u32(n), H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_binary),
-                ctype, H.f32(step_size), H.f32(max_step_size), H.f32(dt_gamma), H.u32(max_steps), C.c_int(int(batched)),
-                H.ptr(batch_inds), H.u32(bds), H.ptr(packed_info), H.ptr(total), H.ptr(tmp), H.ptr(cache),
-                C.c_uint64(cache_bytes if cache is not None else 0), st))
+                n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_binary), ctype,
+                float(step_size), float(max_step_size), float(dt_gamma), int(max_steps), batched, H.ptr(batch_inds), bds,
+                H.ptr(packed_info), H.ptr(total), H.ptr(tmp), H.ptr(cache), cache_bytes if cache is not None else 0, st))
             S = H.wait_i64(total, dev)[0]  # the single device->host sync of this op
         t_starts = H.empty((S, 1), dtype=torch.float32, device=dev)
         t_ends = H.empty((S, 1), dtype=torch.float32, device=dev)
@@ -124,23 +129,22 @@ def _march(rays_o, rays_d, t_min, t_max, batch_inds, batch_data_size, roi, grid_
             samples = H.empty((S, 3), dtype=torch.float32, device=dev)
             if S > 0:
                 H.check(H.lib().nr3d_ray_marching_emit_finished(
-                    H.u32(n), H.ptr(rays_o), H.ptr(rays_d), C.c_int(int(batched)), H.ptr(batch_inds), H.u32(bds),
-                    H.ptr(packed_info), H.ptr(cache), H.u32(max_steps), H.ptr(t_starts), H.ptr(t_ends), H.ptr(ridx), H.ptr(bidx),
-                    H.ptr(gidx), H.ptr(ridx64), H.ptr(deltas), H.ptr(samples), st))
+                    n, H.ptr(rays_o), H.ptr(rays_d), batched, H.ptr(batch_inds), bds, H.ptr(packed_info), H.ptr(cache),
+                    int(max_steps), H.ptr(t_starts), H.ptr(t_ends), H.ptr(ridx), H.ptr(bidx), H.ptr(gidx), H.ptr(ridx64),
+                    H.ptr(deltas), H.ptr(samples), st))
             return dict(n_hit=n_hit, ridx_hit=ridx_hit[:n_hit], pack_infos=H.mark_ordered(pack_infos[:n_hit], total=S), t_starts=t_starts.view(-1),
                         t_ends=t_ends.view(-1), ridx=ridx64, deltas=deltas, samples=samples, bidx=bidx, gidx=gidx)
         if S > 0:
             H.check(H.lib().nr3d_ray_marching_emit(
-                H.u32(n), H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res,
-                H.ptr(grid_binary), ctype, H.f32(step_size), H.f32(max_step_size), H.f32(dt_gamma),
-                C.c_int(int(batched)), H.ptr(batch_inds), H.u32(bds), H.ptr(packed_info), H.ptr(t_starts),
-                H.ptr(t_ends), H.ptr(ridx), H.ptr(bidx), H.ptr(gidx), H.ptr(cache), H.u32(max_steps), st))
+                n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_binary), ctype,
+                float(step_size), float(max_step_size), float(dt_gamma), batched, H.ptr(batch_inds), bds, H.ptr(packed_info),
+                H.ptr(t_starts), H.ptr(t_ends), H.ptr(ridx), H.ptr(bidx), H.ptr(gidx), H.ptr(cache), int(max_steps), st))
         if finish:
             ridx64 = H.empty(S, dtype=torch.int64, device=dev)
             deltas = H.empty(S, dtype=torch.float32, device=dev)
             samples = H.empty((S, 3), dtype=torch.float32, device=dev)
-            H.check(H.lib().nr3d_march_finish_samples(C.c_uint64(S), H.ptr(rays_o), H.ptr(rays_d), H.ptr(ridx), H.ptr(t_starts),
-                                                      H.ptr(t_ends), H.ptr(ridx64), H.ptr(deltas), H.ptr(samples), st))
+            H.check(H.lib().nr3d_march_finish_samples(S, H.ptr(rays_o), H.ptr(rays_d), H.ptr(ridx), H.ptr(t_starts), H.ptr(t_ends),
+                                                      H.ptr(ridx64), H.ptr(deltas), H.ptr(samples), st))
             return dict(n_hit=n_hit, ridx_hit=ridx_hit[:n_hit], pack_infos=H.mark_ordered(pack_infos[:n_hit], total=S), t_starts=t_starts.view(-1),
                         t_ends=t_ends.view(-1), ridx=ridx64, deltas=deltas, samples=samples, bidx=bidx, gidx=gidx)
     if batched:
@@ -207,13 +211,13 @@ def forest_ray_marching(forest, rays_o, rays_d, t_min, t_max, seg_block_inds, se
         fc = forest._c()
         packed_info = H.empty((n, 2), dtype=torch.int32, device=dev)
         total = H.host_i64(1, dev)
-        nbytes = int(H.lib().nr3d_scan_tmp_bytes(C.c_uint64(max(n, 1))))
+        nbytes = int(H.lib().nr3d_scan_tmp_bytes(max(n, 1)))
         tmp = H.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
         common = (H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(seg_block_inds), H.ptr(seg_entries),
-                  H.ptr(seg_exits), H.ptr(seg_pack_infos), res, H.ptr(grid_binary), H.f32(step_size),
-                  H.f32(max_step_size), H.f32(dt_gamma))
-        H.check(H.lib().nr3d_forest_ray_marching_count(C.byref(fc), H.u32(n), *common, H.u32(max_steps),
-                                                       H.ptr(packed_info), H.ptr(total), H.ptr(tmp), st))
+                  H.ptr(seg_exits), H.ptr(seg_pack_infos), res, H.ptr(grid_binary), float(step_size),
+                  float(max_step_size), float(dt_gamma))
+        H.check(H.lib().nr3d_forest_ray_marching_count(C.byref(fc), n, *common, int(max_steps), H.ptr(packed_info), H.ptr(total),
+                                                       H.ptr(tmp), st))
         S = H.wait_i64(total, dev)[0]  # the single device->host sync of this op
         t_starts = H.empty((S, 1), dtype=torch.float32, device=dev)
         t_ends = H.empty((S, 1), dtype=torch.float32, device=dev)
@@ -221,9 +225,8 @@ def forest_ray_marching(forest, rays_o, rays_d, t_min, t_max, seg_block_inds, se
         blidx = H.empty(S, dtype=torch.int32, device=dev)
         gidx = H.empty(S, dtype=torch.int32, device=dev) if return_gidx else None
         if S > 0:
-            H.check(H.lib().nr3d_forest_ray_marching_emit(C.byref(fc), H.u32(n), *common, H.ptr(packed_info),
-                                                          H.ptr(t_starts), H.ptr(t_ends), H.ptr(ridx), H.ptr(blidx),
-                                                          H.ptr(gidx), st))
+            H.check(H.lib().nr3d_forest_ray_marching_emit(C.byref(fc), n, *common, H.ptr(packed_info), H.ptr(t_starts),
+                                                          H.ptr(t_ends), H.ptr(ridx), H.ptr(blidx), H.ptr(gidx), st))
     return [packed_info, t_starts, t_ends, ridx, blidx, gidx]
 
 
@@ -382,7 +385,7 @@ def ray_marching_composite(rays_o, rays_d, t_min, t_max, roi, grid_binary, contr
     with H.on_device(dev):
         # ONE allocation, carved into 16-byte aligned pieces (sizes in bytes)
         scan_b = _scan_tmp_bytes(n)
-        pieces = [("packed_info", n * 8), ("ridx_hit", n * 8), ("pack_infos", n * 16), ("scan_tmp", scan_b + 8), ("cache", rows * 12),
+        pieces = [("packed_info", n * 8), ("ridx_hit", n * 8), ("pack_infos", n * 16), ("scan_tmp", scan_b + 8), ("cache", _cache_bytes(n, int(max_steps))),
                   ("t_starts", rows * 4), ("t_ends", rows * 4), ("ridx32", rows * 4), ("gidx", rows * 4 if return_gidx else 0),
                   ("ridx", rows * 8), ("deltas", rows * 4), ("samples", rows * 12), ("alpha", rows * 4), ("vw", rows * 4),
                   ("mask", n * 4), ("depth", n * 4), ("rgb_out", n * 12 if rgb is not None else 0)]
@@ -400,11 +403,10 @@ def ray_marching_composite(rays_o, rays_d, t_min, t_max, roi, grid_binary, contr
         mc._host.fill_(-1)                                   # the sentinel totals() polls against
         mc._raw_stream = H.stream_of(rays_o)
         H.check(H.lib().nr3d_march_composite_fwd(
-            n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_binary),
-            int(contraction_type), float(step_size), float(max_step_size), float(dt_gamma), int(max_steps),
-            P("packed_info"), P("ridx_hit"), P("pack_infos"), H.ptr(mc._host), P("scan_tmp"), P("cache"),
-            rows * 12, rows, P("t_starts"), P("t_ends"), P("ridx32"), P("gidx"),
-            P("ridx"), P("deltas"), P("samples"), H.ptr(sigma), sigma_rows, H.ptr(rgb),
-            float(early_stop_eps), float(alpha_thre), 1 if normalize_depth else 0, P("alpha"), P("vw"),
-            P("mask"), P("depth"), P("rgb_out"), mc._raw_stream))
+            n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_binary), int(contraction_type),
+            float(step_size), float(max_step_size), float(dt_gamma), int(max_steps), P("packed_info"), P("ridx_hit"),
+            P("pack_infos"), H.ptr(mc._host), P("scan_tmp"), P("cache"), offs["cache"][1], rows, P("t_starts"), P("t_ends"),
+            P("ridx32"), P("gidx"), P("ridx"), P("deltas"), P("samples"), H.ptr(sigma), sigma_rows, H.ptr(rgb),
+            float(early_stop_eps), float(alpha_thre), 1 if normalize_depth else 0, P("alpha"), P("vw"), P("mask"), P("depth"),
+            P("rgb_out"), mc._raw_stream))
     return mc

@@ -9,7 +9,6 @@ Same function names, positional arguments and return structure.  What differs by
   * two-phase producers keep their prefix sums on the device and read back ONE scalar (the total);
   * ``packed_sort_thrust`` is an alias of the in-tree sort (no thrust on this platform).
 """
-import ctypes as C
 
 import torch
 
@@ -61,11 +60,11 @@ def _fd(feats):
 
 
 def _code(t):
-    return C.c_int(H.DTYPE_CODE[t.dtype])
+    return H.DTYPE_CODE[t.dtype]
 
 
 def _scan_tmp(n, device):
-    nbytes = int(H.lib().nr3d_scan_tmp_bytes(C.c_uint64(max(int(n), 1))))
+    nbytes = H.lib().nr3d_scan_tmp_bytes(max(n, 1))
     return H.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
 
 
@@ -76,8 +75,7 @@ def _pack_infos_from_n(n_per_pack):
     pi = H.empty((P, 2), dtype=torch.int64, device=dev)
     total = H.host_i64(1, dev)                  # the scan's last store goes to pinned host memory: no copy launch
     tmp = _scan_tmp(P, dev)
-    H.check(H.lib().nr3d_pack_infos_from_n(H.u32(P), H.ptr(n_per_pack), H.ptr(pi), H.ptr(total), H.ptr(tmp),
-                                           H.stream_of(n_per_pack)))
+    H.check(H.lib().nr3d_pack_infos_from_n(P, H.ptr(n_per_pack), H.ptr(pi), H.ptr(total), H.ptr(tmp), H.stream_of(n_per_pack)))
     num = H.wait_i64(total, dev)[0]
     return H.mark_ordered(pi, total=num), num
 
@@ -93,8 +91,7 @@ def interleave_arange(stop, return_idx):
         pi, num = _pack_infos_from_n(stop)
         out = H.empty(num, dtype=torch.int64, device=stop.device)
         nidx = H.empty(num, dtype=torch.int64, device=stop.device) if return_idx else None
-        H.check(H.lib().nr3d_interleave_linstep(H.u32(stop.shape[0]), C.c_int(H.I64), H.ptr(pi), None, None,
-                                                C.c_double(0), C.c_double(1), H.ptr(out), H.ptr(nidx),
+        H.check(H.lib().nr3d_interleave_linstep(stop.shape[0], H.I64, H.ptr(pi), None, None, 0, 1, H.ptr(out), H.ptr(nidx),
                                                 H.stream_of(stop)))
     return out, nidx
 
@@ -120,9 +117,8 @@ def interleave_linstep(start, num_steps, step_size, return_idx):
         pi, num = _pack_infos_from_n(num_steps)
         out = H.empty(num, dtype=start.dtype, device=start.device)
         nidx = H.empty(num, dtype=torch.int64, device=start.device) if return_idx else None
-        H.check(H.lib().nr3d_interleave_linstep(H.u32(start.shape[0]), _code(start), H.ptr(pi), H.ptr(start),
-                                                H.ptr(steps_t), C.c_double(0), C.c_double(step_s), H.ptr(out),
-                                                H.ptr(nidx), H.stream_of(start)))
+        H.check(H.lib().nr3d_interleave_linstep(start.shape[0], _code(start), H.ptr(pi), H.ptr(start), H.ptr(steps_t), 0, step_s,
+                                                H.ptr(out), H.ptr(nidx), H.stream_of(start)))
     return out, nidx
 
 
@@ -142,8 +138,8 @@ def arange_num_steps(start, stop, step_size):
     start, stop = start.contiguous(), stop.contiguous()
     with H.on_device(start.device):
         n = H.empty(start.shape[0], dtype=torch.int64, device=start.device)
-        H.check(H.lib().nr3d_arange_num_steps(H.u32(start.shape[0]), _code(start), H.ptr(start), H.ptr(stop), H.ptr(steps_t),
-                                              C.c_double(step_s), H.ptr(n), H.stream_of(start)))
+        H.check(H.lib().nr3d_arange_num_steps(start.shape[0], _code(start), H.ptr(start), H.ptr(stop), H.ptr(steps_t), step_s,
+                                              H.ptr(n), H.stream_of(start)))
     return n
 
 
@@ -164,14 +160,14 @@ def interleave_sample_step_wrt_depth_clamped(near, far, max_steps, dt_gamma, min
     with H.on_device(dev):
         n = H.empty(P, dtype=torch.int64, device=dev)
         st = H.stream_of(near)
-        H.check(H.lib().nr3d_sample_step_count(H.u32(P), H.ptr(near), H.ptr(far), H.u32(max_steps), H.f32(dt_gamma),
-                                               H.f32(min_step_size), H.f32(max_step_size), H.ptr(n), st))
+        H.check(H.lib().nr3d_sample_step_count(P, H.ptr(near), H.ptr(far), int(max_steps), float(dt_gamma), float(min_step_size),
+                                               float(max_step_size), H.ptr(n), st))
         pi, num = _pack_infos_from_n(n)
         t = H.empty(num, dtype=near.dtype, device=dev)
         dt = H.empty(num, dtype=near.dtype, device=dev)
         nidx = H.empty(num, dtype=torch.int64, device=dev)
-        H.check(H.lib().nr3d_sample_step_emit(H.u32(P), H.ptr(near), H.ptr(pi), H.f32(dt_gamma), H.f32(min_step_size),
-                                              H.f32(max_step_size), H.ptr(t), H.ptr(dt), H.ptr(nidx), st))
+        H.check(H.lib().nr3d_sample_step_emit(P, H.ptr(near), H.ptr(pi), float(dt_gamma), float(min_step_size),
+                                              float(max_step_size), H.ptr(t), H.ptr(dt), H.ptr(nidx), st))
     return t, dt, nidx, pi
 
 
@@ -194,16 +190,15 @@ def interleave_sample_step_wrt_depth_in_packed_segments(near, far, entry, exit, 
     with H.on_device(dev):
         n = H.empty(P, dtype=torch.int64, device=dev)
         st = H.stream_of(near)
-        common = (H.u32(P), H.ptr(near), H.ptr(far), H.ptr(entry), H.ptr(exit), H.ptr(seg_pack_infos),
-                  H.u32(max_steps), H.f32(dt_gamma), H.f32(min_step_size), H.f32(max_step_size))
-        H.check(H.lib().nr3d_sample_step_segments(*common, C.c_int(0), H.ptr(n), None, None, None, None, None, st))
+        common = (P, H.ptr(near), H.ptr(far), H.ptr(entry), H.ptr(exit), H.ptr(seg_pack_infos),
+                  int(max_steps), float(dt_gamma), float(min_step_size), float(max_step_size))
+        H.check(H.lib().nr3d_sample_step_segments(*common, 0, H.ptr(n), None, None, None, None, None, st))
         pi, num = _pack_infos_from_n(n)
         t = H.empty(num, dtype=near.dtype, device=dev)
         dt = H.empty(num, dtype=near.dtype, device=dev)
         nidx = H.empty(num, dtype=torch.int64, device=dev)
         sidx = H.empty(num, dtype=torch.int64, device=dev)
-        H.check(H.lib().nr3d_sample_step_segments(*common, C.c_int(1), None, H.ptr(pi), H.ptr(t), H.ptr(dt),
-                                                  H.ptr(nidx), H.ptr(sidx), st))
+        H.check(H.lib().nr3d_sample_step_segments(*common, 1, None, H.ptr(pi), H.ptr(t), H.ptr(dt), H.ptr(nidx), H.ptr(sidx), st))
     return t, dt, sidx, nidx, pi
 
 
@@ -216,8 +211,8 @@ def packed_sum(feats, pack_infos):
     with H.on_device(feats.device):
         # every pack's row is written by the kernel (an empty pack gets its zero there): no zero-fill launch in front of it
         out = H.empty((P,) + tuple(feats.shape[1:]), dtype=feats.dtype, device=feats.device)
-        H.check(H.lib().nr3d_packed_sum(H.u32(P), C.c_uint64(feats.shape[0]), H.u32(_fd(feats)), _code(feats),
-                                        H.ptr(feats), H.ptr(pack_infos), H.ptr(out), H.stream_of(feats)))
+        H.check(H.lib().nr3d_packed_sum(P, feats.shape[0], _fd(feats), _code(feats), H.ptr(feats), H.ptr(pack_infos), H.ptr(out),
+                                        H.stream_of(feats)))
     return out
 
 
@@ -226,10 +221,9 @@ def _scan(fn, feats, pack_infos, mode, exclusive, reverse):
     ordered = _ordered(pack_infos)
     with H.on_device(feats.device):
         out = H.empty_like(feats) if ordered else torch.zeros_like(feats)
-        H.check(H.lib().nr3d_packed_scan(H.u32(pack_infos.shape[0]), C.c_uint64(feats.shape[0]), H.u32(_fd(feats)),
-                                         _code(feats), H.ptr(feats), H.ptr(pack_infos), C.c_int(mode),
-                                         C.c_int(int(bool(exclusive))), C.c_int(int(bool(reverse))), C.c_int(ordered),
-                                         H.ptr(out), H.stream_of(feats)))
+        H.check(H.lib().nr3d_packed_scan(pack_infos.shape[0], feats.shape[0], _fd(feats), _code(feats), H.ptr(feats),
+                                         H.ptr(pack_infos), mode, bool(exclusive), bool(reverse), ordered, H.ptr(out),
+                                         H.stream_of(feats)))
     return out
 
 
@@ -259,9 +253,8 @@ def _diff(fn, feats, pack_infos, edge_a, edge_fill, backward, names):
     ordered = _ordered(pack_infos)
     with H.on_device(feats.device):
         out = H.empty_like(feats) if ordered else torch.zeros_like(feats)
-        H.check(H.lib().nr3d_packed_diff(H.u32(P), C.c_uint64(feats.shape[0]), H.u32(_fd(feats)), _code(feats),
-                                         H.ptr(feats), H.ptr(pack_infos), H.ptr(edge_a), H.ptr(edge_fill),
-                                         C.c_int(backward), C.c_int(ordered), H.ptr(out), H.stream_of(feats)))
+        H.check(H.lib().nr3d_packed_diff(P, feats.shape[0], _fd(feats), _code(feats), H.ptr(feats), H.ptr(pack_infos),
+                                         H.ptr(edge_a), H.ptr(edge_fill), backward, ordered, H.ptr(out), H.stream_of(feats)))
     return out
 
 
@@ -304,9 +297,8 @@ def _binary(name, feats, other, pack_infos):
     ordered = _ordered(pack_infos)
     with H.on_device(feats.device):
         out = (H.empty if ordered else torch.zeros)(out_shape, dtype=out_dtype, device=feats.device)
-        H.check(H.lib().nr3d_packed_binary(H.u32(P), C.c_uint64(feats.shape[0]), H.u32(fd), H.u32(od), _code(feats),
-                                           H.ptr(feats), H.ptr(other), H.ptr(pack_infos), C.c_int(op), C.c_int(ordered),
-                                           H.ptr(out), H.stream_of(feats)))
+        H.check(H.lib().nr3d_packed_binary(P, feats.shape[0], fd, od, _code(feats), H.ptr(feats), H.ptr(other), H.ptr(pack_infos),
+                                           op, ordered, H.ptr(out), H.stream_of(feats)))
     return out
 
 
@@ -332,8 +324,8 @@ def packed_sort_qsort(vals, pack_infos, return_idx):
     _chk_feats("packed_sort_qsort", vals, pack_infos, dims=(1,))
     with H.on_device(vals.device):
         idx = torch.arange(vals.shape[0], dtype=torch.int64, device=vals.device) if return_idx else None
-        H.check(H.lib().nr3d_packed_sort(H.u32(pack_infos.shape[0]), C.c_uint64(vals.shape[0]), _code(vals),
-                                         H.ptr(vals), H.ptr(idx), H.ptr(pack_infos), H.stream_of(vals)))
+        H.check(H.lib().nr3d_packed_sort(pack_infos.shape[0], vals.shape[0], _code(vals), H.ptr(vals), H.ptr(idx),
+                                         H.ptr(pack_infos), H.stream_of(vals)))
     return idx
 
 
@@ -348,9 +340,8 @@ def packed_searchsorted(bins, vals, pack_infos):
                            "with the dtype of bins")
     with H.on_device(bins.device):
         pidx = torch.full(vals.shape, -1, dtype=torch.int64, device=bins.device)
-        H.check(H.lib().nr3d_packed_searchsorted(H.u32(pack_infos.shape[0]), _code(bins), H.ptr(bins), H.ptr(vals),
-                                                 H.ptr(pack_infos), H.u32(vals.shape[1]), None, H.ptr(pidx),
-                                                 H.stream_of(bins)))
+        H.check(H.lib().nr3d_packed_searchsorted(pack_infos.shape[0], _code(bins), H.ptr(bins), H.ptr(vals), H.ptr(pack_infos),
+                                                 vals.shape[1], None, H.ptr(pidx), H.stream_of(bins)))
     return pidx
 
 
@@ -361,9 +352,8 @@ def packed_searchsorted_packed_vals(bins, pack_infos, vals, val_pack_infos):
         raise RuntimeError("packed_searchsorted_packed_vals: vals must have the dtype of bins and one pack per bin pack")
     with H.on_device(bins.device):
         pidx = torch.full(vals.shape, -1, dtype=torch.int64, device=bins.device)
-        H.check(H.lib().nr3d_packed_searchsorted(H.u32(pack_infos.shape[0]), _code(bins), H.ptr(bins), H.ptr(vals),
-                                                 H.ptr(pack_infos), H.u32(0), H.ptr(val_pack_infos), H.ptr(pidx),
-                                                 H.stream_of(bins)))
+        H.check(H.lib().nr3d_packed_searchsorted(pack_infos.shape[0], _code(bins), H.ptr(bins), H.ptr(vals), H.ptr(pack_infos), 0,
+                                                 H.ptr(val_pack_infos), H.ptr(pidx), H.stream_of(bins)))
     return pidx
 
 
@@ -381,14 +371,14 @@ def try_merge_two_packs_sorted_aligned(vals_a, pack_infos_a, vals_b, pack_infos_
         pim = H.empty((P, 2), dtype=torch.int64, device=dev)
         if P > 0:
             tot = H.empty(1, dtype=torch.int64, device=dev)
-            H.check(H.lib().nr3d_pack_infos_from_n(H.u32(P), H.ptr(n), H.ptr(pim), H.ptr(tot), H.ptr(_scan_tmp(P, dev)),
+            H.check(H.lib().nr3d_pack_infos_from_n(P, H.ptr(n), H.ptr(pim), H.ptr(tot), H.ptr(_scan_tmp(P, dev)),
                                                    H.stream_of(vals_a)))
             H.mark_ordered(pim)
         pa = torch.zeros(vals_a.shape[0], dtype=torch.int64, device=dev)      # the merge kernel counts into it
         pb = torch.zeros(vals_b.shape[0], dtype=torch.int64, device=dev)
         H.check(H.lib().nr3d_try_merge_two_packs_sorted_aligned(
-            H.u32(pack_infos_a.shape[0]), _code(vals_a), H.ptr(vals_a), H.ptr(pack_infos_a), H.ptr(vals_b),
-            H.ptr(pack_infos_b), H.ptr(pim), C.c_int(int(bool(b_sorted))), H.ptr(pa), H.ptr(pb), H.stream_of(vals_a)))
+            pack_infos_a.shape[0], _code(vals_a), H.ptr(vals_a), H.ptr(pack_infos_a), H.ptr(vals_b), H.ptr(pack_infos_b),
+            H.ptr(pim), bool(b_sorted), H.ptr(pa), H.ptr(pb), H.stream_of(vals_a)))
     return pa, pb, pim
 
 
@@ -417,20 +407,20 @@ def merge_two_packs_sorted_general(vals_a, pack_infos_a, nidx_a, vals_b, pack_in
         out = H.empty(6 * cap, dtype=torch.int64, device=dev)                 # u | pia_u | pib_u | n_u
         u, pia_u, pib_u, n_u = out[:cap], out[cap:3 * cap].view(cap, 2), out[3 * cap:5 * cap].view(cap, 2), out[5 * cap:]
         total = H.host_i64(1, dev)
-        H.check(H.lib().nr3d_merge_pack_union(H.u32(Pa), H.ptr(nidx_a), H.ptr(pack_infos_a), H.u32(Pb), H.ptr(nidx_b),
-                                              H.ptr(pack_infos_b), H.ptr(scratch), H.ptr(scratch[Pb:]), H.ptr(_scan_tmp(Pb, dev)),
-                                              H.ptr(scratch[3 * Pb:]), H.ptr(u), H.ptr(pia_u), H.ptr(pib_u), H.ptr(n_u), H.ptr(total), st))
+        H.check(H.lib().nr3d_merge_pack_union(Pa, H.ptr(nidx_a), H.ptr(pack_infos_a), Pb, H.ptr(nidx_b), H.ptr(pack_infos_b),
+                                              H.ptr(scratch), H.ptr(scratch[Pb:]), H.ptr(_scan_tmp(Pb, dev)),
+                                              H.ptr(scratch[3 * Pb:]), H.ptr(u), H.ptr(pia_u), H.ptr(pib_u), H.ptr(n_u),
+                                              H.ptr(total), st))
         Pu = H.wait_i64(total, dev)[0]                                        # the one device->host sync
         pim = H.empty((Pu, 2), dtype=torch.int64, device=dev)
         tot = H.empty(1, dtype=torch.int64, device=dev)                       # = len(vals_a) + len(vals_b): not read back
-        H.check(H.lib().nr3d_pack_infos_from_n(H.u32(Pu), H.ptr(n_u), H.ptr(pim), H.ptr(tot), H.ptr(_scan_tmp(Pu, dev)), st))
+        H.check(H.lib().nr3d_pack_infos_from_n(Pu, H.ptr(n_u), H.ptr(pim), H.ptr(tot), H.ptr(_scan_tmp(Pu, dev)), st))
         # elements outside every pack have no position: -1, as in the reference (the kernel zeroes the rows of its packs itself
         # before it counts into them)
         pa = torch.full((vals_a.shape[0],), -1, dtype=torch.int64, device=dev)
         pb = torch.full((vals_b.shape[0],), -1, dtype=torch.int64, device=dev)
         H.check(H.lib().nr3d_try_merge_two_packs_sorted_aligned(
-            H.u32(Pu), _code(vals_a), H.ptr(vals_a), H.ptr(pia_u), H.ptr(vals_b), H.ptr(pib_u), H.ptr(pim), C.c_int(1),
-            H.ptr(pa), H.ptr(pb), st))
+            Pu, _code(vals_a), H.ptr(vals_a), H.ptr(pia_u), H.ptr(vals_b), H.ptr(pib_u), H.ptr(pim), 1, H.ptr(pa), H.ptr(pb), st))
     return pa, pb, H.mark_ordered(pim, total=vals_a.shape[0] + vals_b.shape[0])
 
 
@@ -447,9 +437,8 @@ def packed_invert_cdf(bins, cdfs, u, pack_infos):
     with H.on_device(bins.device):
         bin_idx = torch.full(u.shape, -1, dtype=torch.int64, device=bins.device)
         samples = torch.zeros_like(u)
-        H.check(H.lib().nr3d_packed_invert_cdf(H.u32(pack_infos.shape[0]), H.ptr(bins), H.ptr(cdfs), H.ptr(pack_infos),
-                                               H.ptr(u), H.u32(u.shape[1]), H.ptr(samples), H.ptr(bin_idx),
-                                               H.stream_of(bins)))
+        H.check(H.lib().nr3d_packed_invert_cdf(pack_infos.shape[0], H.ptr(bins), H.ptr(cdfs), H.ptr(pack_infos), H.ptr(u),
+                                               u.shape[1], H.ptr(samples), H.ptr(bin_idx), H.stream_of(bins)))
     return samples, bin_idx
 
 
@@ -470,17 +459,15 @@ def packed_alpha_to_vw_forward(alphas, pack_infos, early_stop_eps, alpha_thre, c
             # the kernel writes the rows of the packs; rows outside every pack are zero (at::zeros in the reference): a fill launch
             # unless the packs are known to tile [0, S) (H.tiles: a marcher's / a two-phase op's pack_infos)
             sel = (H.empty if H.tiles(pack_infos, S) else torch.zeros)(S, dtype=torch.bool, device=dev)
-            H.check(H.lib().nr3d_alpha_to_vw_forward(H.u32(P), C.c_uint64(S), H.ptr(alphas), H.ptr(pack_infos),
-                                                     H.f32(early_stop_eps), H.f32(alpha_thre), None, H.ptr(num),
-                                                     H.ptr(sel), st))
+            H.check(H.lib().nr3d_alpha_to_vw_forward(P, S, H.ptr(alphas), H.ptr(pack_infos), float(early_stop_eps),
+                                                     float(alpha_thre), None, H.ptr(num), H.ptr(sel), st))
             cpi = H.empty((P, 2), dtype=torch.int64, device=dev)
             total = H.empty(1, dtype=torch.int64, device=dev)
-            H.check(H.lib().nr3d_pack_infos_from_n(H.u32(P), H.ptr(num), H.ptr(cpi), H.ptr(total),
-                                                   H.ptr(_scan_tmp(P, dev)), st))
+            H.check(H.lib().nr3d_pack_infos_from_n(P, H.ptr(num), H.ptr(cpi), H.ptr(total), H.ptr(_scan_tmp(P, dev)), st))
             return None, H.mark_ordered(cpi), sel
         w = (H.empty if (H.tiles(pack_infos, S) and P > 0) else torch.zeros)(S, dtype=alphas.dtype, device=dev)
-        H.check(H.lib().nr3d_alpha_to_vw_forward(H.u32(P), C.c_uint64(S), H.ptr(alphas), H.ptr(pack_infos),
-                                                 H.f32(early_stop_eps), H.f32(alpha_thre), H.ptr(w), None, None, st))
+        H.check(H.lib().nr3d_alpha_to_vw_forward(P, S, H.ptr(alphas), H.ptr(pack_infos), float(early_stop_eps), float(alpha_thre),
+                                                 H.ptr(w), None, None, st))
     return w, None, None
 
 
@@ -507,14 +494,14 @@ def packed_compression_compact(alphas, pack_infos, early_stop_eps, alpha_thre, t
         st = H.stream_of(alphas)
         num = torch.zeros(P, dtype=torch.int64, device=dev)
         sel = H.empty(S, dtype=torch.bool, device=dev)
-        H.check(H.lib().nr3d_alpha_to_vw_forward(H.u32(P), C.c_uint64(S), H.ptr(alphas), H.ptr(pack_infos), H.f32(early_stop_eps),
-                                                 H.f32(alpha_thre), None, H.ptr(num), H.ptr(sel), st))
+        H.check(H.lib().nr3d_alpha_to_vw_forward(P, S, H.ptr(alphas), H.ptr(pack_infos), float(early_stop_eps), float(alpha_thre),
+                                                 None, H.ptr(num), H.ptr(sel), st))
         begin_all = H.empty(P, dtype=torch.int64, device=dev)
         idx = H.empty(P, dtype=torch.int64, device=dev)
         cpi = H.empty((P, 2), dtype=torch.int64, device=dev)
         totals = H.host_i64(2, dev)
-        H.check(H.lib().nr3d_prune_compact_packs(H.u32(P), H.ptr(num), H.ptr(tag), H.ptr(begin_all), H.ptr(idx), H.ptr(cpi),
-                                                 H.ptr(totals), H.ptr(_scan_tmp(P, dev)), st))
+        H.check(H.lib().nr3d_prune_compact_packs(P, H.ptr(num), H.ptr(tag), H.ptr(begin_all), H.ptr(idx), H.ptr(cpi), H.ptr(totals),
+                                                 H.ptr(_scan_tmp(P, dev)), st))
         S2, P2 = H.wait_i64(totals, dev)                    # the one device->host sync
         pidx = H.empty(S2, dtype=torch.int64, device=dev) if want_pidx else None
         o1 = H.empty(S2, dtype=torch.float32, device=dev) if f1 is not None else None
@@ -522,9 +509,9 @@ def packed_compression_compact(alphas, pack_infos, early_stop_eps, alpha_thre, t
         o3 = H.empty((S2, 3), dtype=torch.float32, device=dev) if f3 is not None else None
         ol = H.empty(S2, dtype=torch.int64, device=dev) if l1 is not None else None
         if S2 > 0:
-            H.check(H.lib().nr3d_prune_compact_samples(H.u32(P), H.ptr(pack_infos), H.ptr(begin_all), H.ptr(sel), H.ptr(f1),
-                                                       H.ptr(f2), H.ptr(f3), H.ptr(l1), H.ptr(pidx), H.ptr(o1), H.ptr(o2),
-                                                       H.ptr(o3), H.ptr(ol), st))
+            H.check(H.lib().nr3d_prune_compact_samples(P, H.ptr(pack_infos), H.ptr(begin_all), H.ptr(sel), H.ptr(f1), H.ptr(f2),
+                                                       H.ptr(f3), H.ptr(l1), H.ptr(pidx), H.ptr(o1), H.ptr(o2), H.ptr(o3),
+                                                       H.ptr(ol), st))
     return idx[:P2], H.mark_ordered(cpi[:P2], total=S2), pidx, o1, o2, o3, ol
 
 
@@ -537,8 +524,7 @@ def tau_to_alpha_forward(sigma, delta):
         raise RuntimeError(f"{fn}: Expected contiguous float32 sigma / delta of the same shape")
     with H.on_device(sigma.device):
         alpha = H.empty_like(sigma)
-        H.check(H.lib().nr3d_tau_to_alpha_fwd(C.c_uint64(sigma.numel()), H.ptr(sigma), H.ptr(delta), H.ptr(alpha),
-                                              H.stream_of(sigma)))
+        H.check(H.lib().nr3d_tau_to_alpha_fwd(sigma.numel(), H.ptr(sigma), H.ptr(delta), H.ptr(alpha), H.stream_of(sigma)))
     return alpha
 
 
@@ -551,7 +537,7 @@ def tau_to_alpha_backward(sigma, delta, grad_alpha):
             raise RuntimeError(f"{fn}: Expected contiguous float32 tensors of sigma's shape")
     with H.on_device(sigma.device):
         g = H.empty_like(sigma)
-        H.check(H.lib().nr3d_tau_to_alpha_bwd(C.c_uint64(sigma.numel()), H.ptr(sigma), H.ptr(delta), H.ptr(grad_alpha), H.ptr(g),
+        H.check(H.lib().nr3d_tau_to_alpha_bwd(sigma.numel(), H.ptr(sigma), H.ptr(delta), H.ptr(grad_alpha), H.ptr(g),
                                               H.stream_of(sigma)))
     return g
 
@@ -568,10 +554,9 @@ def packed_alpha_to_vw_backward(weights, grad_weights, alphas, pack_infos, early
     with H.on_device(weights.device):
         tiled = H.tiles(pack_infos, weights.shape[0]) and pack_infos.shape[0] > 0
         g = H.empty_like(alphas) if tiled else torch.zeros_like(alphas)
-        H.check(H.lib().nr3d_alpha_to_vw_backward(H.u32(pack_infos.shape[0]), C.c_uint64(weights.shape[0]),
-                                                  H.ptr(alphas), H.ptr(weights), H.ptr(grad_weights), H.ptr(pack_infos),
-                                                  H.f32(early_stop_eps), H.f32(alpha_thre), H.ptr(g),
-                                                  H.stream_of(weights)))
+        H.check(H.lib().nr3d_alpha_to_vw_backward(pack_infos.shape[0], weights.shape[0], H.ptr(alphas), H.ptr(weights),
+                                                  H.ptr(grad_weights), H.ptr(pack_infos), float(early_stop_eps), float(alpha_thre),
+                                                  H.ptr(g), H.stream_of(weights)))
     return g
 
 
@@ -611,10 +596,9 @@ def packed_composite_forward(alphas, t, rgb, pack_infos, rays_inds_hit, num_rays
         pool = (torch.zeros if rays_inds_hit is not None else H.empty)(nr * (5 if rgb is not None else 2), dtype=torch.float32, device=dev)
         mask, depth = pool[:nr], pool[nr:2 * nr]
         rgb_out = pool[2 * nr:].view(nr, 3) if rgb is not None else None
-        H.check(H.lib().nr3d_pack_composite_fwd(H.u32(P), H.ptr(alphas), H.ptr(t), H.ptr(rgb), H.ptr(pack_infos),
-                                                H.ptr(rays_inds_hit), H.f32(early_stop_eps), H.f32(alpha_thre),
-                                                C.c_int(1 if normalize_depth else 0), H.ptr(vw), H.ptr(mask), H.ptr(depth),
-                                                H.ptr(rgb_out), H.stream_of(alphas)))
+        H.check(H.lib().nr3d_pack_composite_fwd(P, H.ptr(alphas), H.ptr(t), H.ptr(rgb), H.ptr(pack_infos), H.ptr(rays_inds_hit),
+                                                float(early_stop_eps), float(alpha_thre), 1 if normalize_depth else 0, H.ptr(vw),
+                                                H.ptr(mask), H.ptr(depth), H.ptr(rgb_out), H.stream_of(alphas)))
     return vw, mask, depth, rgb_out
 
 
@@ -639,9 +623,9 @@ def packed_composite_backward(alphas, vw, t, rgb, pack_infos, rays_inds_hit, ear
         ga = alloc(S, dtype=torch.float32, device=dev)
         gt = alloc(S, dtype=torch.float32, device=dev) if need_t else None
         gr = alloc((S, 3), dtype=torch.float32, device=dev) if (need_rgb and rgb is not None) else None
-        H.check(H.lib().nr3d_pack_composite_bwd(H.u32(P), H.ptr(alphas), H.ptr(vw), H.ptr(t), H.ptr(rgb), H.ptr(pack_infos),
-                                                H.ptr(rays_inds_hit), H.f32(early_stop_eps), H.f32(alpha_thre),
-                                                C.c_int(1 if normalize_depth else 0), H.ptr(mask), H.ptr(depth), H.ptr(g_mask),
+        H.check(H.lib().nr3d_pack_composite_bwd(P, H.ptr(alphas), H.ptr(vw), H.ptr(t), H.ptr(rgb), H.ptr(pack_infos),
+                                                H.ptr(rays_inds_hit), float(early_stop_eps), float(alpha_thre),
+                                                1 if normalize_depth else 0, H.ptr(mask), H.ptr(depth), H.ptr(g_mask),
                                                 H.ptr(g_depth), H.ptr(g_rgb), H.ptr(g_vw), H.ptr(ga), H.ptr(gt), H.ptr(gr),
                                                 H.stream_of(alphas)))
     return ga, gt, gr
@@ -659,8 +643,8 @@ def mark_pack_boundaries_cuda(pack_ids):
     H.require_gpu(pack_ids)
     with H.on_device(pack_ids.device):
         b = H.empty(pack_ids.shape[0], dtype=torch.int32, device=pack_ids.device)
-        H.check(H.lib().nr3d_mark_pack_boundaries(C.c_uint64(pack_ids.shape[0]), _code(pack_ids), H.ptr(pack_ids),
-                                                  H.ptr(b), H.stream_of(pack_ids)))
+        H.check(H.lib().nr3d_mark_pack_boundaries(pack_ids.shape[0], _code(pack_ids), H.ptr(pack_ids), H.ptr(b),
+                                                  H.stream_of(pack_ids)))
     return b
 
 
@@ -675,7 +659,7 @@ def octree_mark_consecutive_segments(pidx, pack_infos, point_hierarchies):
     mark_start = torch.zeros(n, dtype=torch.bool, device=pidx.device)
     mark_end = torch.zeros(n, dtype=torch.bool, device=pidx.device)
     with H.on_device(pidx.device):
-        H.check(H.lib().nr3d_octree_mark_consecutive_segments(H.u32(pack_infos.shape[0]), H.ptr(pidx), H.ptr(pack_infos),
+        H.check(H.lib().nr3d_octree_mark_consecutive_segments(pack_infos.shape[0], H.ptr(pidx), H.ptr(pack_infos),
                                                               H.ptr(point_hierarchies), H.ptr(mark_start), H.ptr(mark_end),
                                                               H.stream_of(pidx)))
     return mark_start, mark_end

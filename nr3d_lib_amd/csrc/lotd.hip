@@ -1198,7 +1198,7 @@ __global__ __launch_bounds__(kBlock) void k_contract_dx(uint32_t N, uint32_t E, 
 // Same contraction for a row-major dL/dy ([N, E], the layout autograd hands over): a lane reading its own row
 // touches one cache line per lane and instruction, so the block first transposes its 256 x 32 tile of dL/dy through
 // LDS (coalesced 16-byte reads), then streams the feature-major Jacobian.  Same summation order as above.
-// fold != NULL (nr3d_lotd_bwd_dx_fold): the block also writes the max |dL/dy| of its tile over the columns < gcols, as float
+// fold != NULL (nr3d_lotd_bwd_dx): the block also writes the max |dL/dy| of its tile over the columns < gcols, as float
 // bits, to fold[slot_off + blockIdx.x], and block 0 zeroes fold[0, n_zero) -- the tickets of the pair path's dL/dparam
 // launches of the same call (lotd_pair.hip, pair_fold_layout)
 template <int D, typename GT>
@@ -1697,9 +1697,9 @@ static int fwd_generic(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md,
 	return 0;
 }
 
-static int bwd_dx(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int param_dtype, const void *dL_dy, int64_t g_sn,
-                  int64_t g_se, const void *dy_dx, int64_t d_sn, int64_t d_se, void *dL_dx, void *dL_dy_T, int32_t max_level,
-                  void *fold_buf, void *stream) {
+extern "C" int nr3d_lotd_bwd_dx(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int param_dtype, const void *dL_dy,
+                                int64_t g_sn, int64_t g_se, const void *dy_dx, int64_t d_sn, int64_t d_se, void *dL_dx,
+                                void *dL_dy_T, int32_t max_level, void *fold_buf, void *stream) {
 	NR3D_CHECK(meta != nullptr, "LoTD: meta is NULL");
 	NR3D_CHECK(x_dtype == NR3D_F32 && (param_dtype == NR3D_F32 || param_dtype == NR3D_F16), "LoTD::bwd_dx: f32 x, f32 / f16 dL_dy");
 	if (N == 0) return 0;
@@ -1712,7 +1712,7 @@ static int bwd_dx(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int par
 	// the folded dL/dparam route's hand-over buffer (pair_fold_layout; not filled when that route does not apply)
 	uint32_t gcols = 0, n_zero = 0, slot_off = 0;
 	uint32_t *fold = (fold_buf && pair_fold_layout(meta, N, max_level, gcols, n_zero, slot_off) != 0) ? (uint32_t *)fold_buf : nullptr;
-	NR3D_CHECK(!fold || row_major, "LoTD::bwd_dx_fold: the hand-over buffer needs a contiguous, 16-byte aligned [N, E] dL_dy");
+	NR3D_CHECK(!fold || row_major, "LoTD::bwd_dx: the hand-over buffer needs a contiguous, 16-byte aligned [N, E] dL_dy");
 	prof::Scope ps(NR3D_PROF_LOTD_CONTRACT_DX, (hipStream_t)stream);
 	DISPATCH_D(meta->n_dims_to_encode, {
 		if (row_major && g_half)
@@ -1731,21 +1731,9 @@ static int bwd_dx(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int par
 	return 0;
 }
 
-extern "C" int nr3d_lotd_bwd_dx(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int param_dtype,
-                                const void *dL_dy, int64_t g_sn, int64_t g_se, const void *dy_dx, int64_t d_sn,
-                                int64_t d_se, void *dL_dx, void *dL_dy_T, void *stream) {
-	return bwd_dx(meta, N, x_dtype, param_dtype, dL_dy, g_sn, g_se, dy_dx, d_sn, d_se, dL_dx, dL_dy_T, 0, nullptr, stream);
-}
-
 extern "C" uint64_t nr3d_lotd_pair_fold_bytes(const nr3d_lotd_meta_t *meta, uint32_t N, int32_t max_level) {
 	uint32_t gcols, n_zero, slot_off;
 	return meta ? pair_fold_layout(meta, N, max_level, gcols, n_zero, slot_off) : 0;
-}
-
-extern "C" int nr3d_lotd_bwd_dx_fold(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int param_dtype, const void *dL_dy,
-                                     int64_t g_sn, int64_t g_se, const void *dy_dx, int64_t d_sn, int64_t d_se, void *dL_dx,
-                                     void *dL_dy_T, int32_t max_level, void *fold, void *stream) {
-	return bwd_dx(meta, N, x_dtype, param_dtype, dL_dy, g_sn, g_se, dy_dx, d_sn, d_se, dL_dx, dL_dy_T, max_level, fold, stream);
 }
 
 static int launch_bwd_dparam(bool second, const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N,
@@ -1815,9 +1803,10 @@ extern "C" int nr3d_lotd_pair_direct_levels(const nr3d_lotd_meta_t *meta, uint32
 	return (meta && pair_applies(meta)) ? (int)pair_direct_levels(meta, n_points) : 0;
 }
 
-static int bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int grad_dtype, const void *dL_dy,
-                            int64_t g_sn, int64_t g_se, const void *x, int32_t max_level, int out_dtype, int assign, void *dL_dparam,
-                            void *workspace, uint64_t workspace_bytes, void *fold, void *stream) {
+extern "C" int nr3d_lotd_bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int grad_dtype,
+                                          const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
+                                          int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
+                                          void *fold, void *stream) {
 	if (int rc = check_common(meta, meta_dev, NR3D_F32, NR3D_F32)) return rc;
 	NR3D_CHECK((grad_dtype == NR3D_F32 || grad_dtype == NR3D_F16) && (out_dtype == NR3D_F32 || out_dtype == NR3D_F16),
 	           "LoTD::bwd_dparam_typed: f32 / f16 only");
@@ -1835,22 +1824,6 @@ static int bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_dev, 
 		return rc;
 	NR3D_CHECK(handled, "LoTD::bwd_dparam_typed: the pair-record path does not apply to this meta / workspace");
 	return 0;
-}
-
-extern "C" int nr3d_lotd_bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int grad_dtype,
-                                          const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
-                                          int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
-                                          void *stream) {
-	return bwd_dparam_typed(meta, meta_dev, N, grad_dtype, dL_dy, g_sn, g_se, x, max_level, out_dtype, assign, dL_dparam, workspace,
-	                        workspace_bytes, nullptr, stream);
-}
-
-extern "C" int nr3d_lotd_bwd_dparam_typed_fold(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int grad_dtype,
-                                               const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
-                                               int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
-                                               void *fold, void *stream) {
-	return bwd_dparam_typed(meta, meta_dev, N, grad_dtype, dL_dy, g_sn, g_se, x, max_level, out_dtype, assign, dL_dparam, workspace,
-	                        workspace_bytes, fold, stream);
 }
 
 extern "C" int nr3d_lotd_bwd_dparam_levels(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int x_dtype,
@@ -1993,11 +1966,11 @@ static int launch_bwd_bwd_dx_t(const nr3d_lotd_meta_t *meta, const void *meta_de
 }
 
 // float or half tables (read as float: HalfTab); dL_ddLdx, dL_dy, x and the result are float
-static int launch_bwd_bwd_dx(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int x_dtype, int param_dtype,
-                             const void *dL_ddLdx, const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x,
-                             const void *params, const int64_t *batch_inds, const int64_t *batch_offsets,
-                             uint32_t batch_data_size, int32_t max_level, void *dL_dx, void *workspace, uint64_t workspace_bytes,
-                             void *stream) {
+extern "C" int nr3d_lotd_bwd_bwd_dx(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int x_dtype,
+                                    int param_dtype, const void *dL_ddLdx, const void *dL_dy, int64_t g_sn, int64_t g_se,
+                                    const void *x, const void *params, const int64_t *batch_inds,
+                                    const int64_t *batch_offsets, uint32_t batch_data_size, int32_t max_level,
+                                    void *dL_dx, void *workspace, uint64_t workspace_bytes, void *stream) {
 	if (param_dtype == NR3D_F16)
 		return launch_bwd_bwd_dx_t<__half>(meta, meta_dev, N, x_dtype, param_dtype, dL_ddLdx, dL_dy, g_sn, g_se, x, params, batch_inds,
 		                                   batch_offsets, batch_data_size, max_level, dL_dx, workspace, workspace_bytes, stream);
@@ -2012,24 +1985,6 @@ extern "C" uint64_t nr3d_lotd_bwd_bwd_dx_workspace_bytes(const nr3d_lotd_meta_t 
 	// per (point, pseudo level): the D partial sums; + the pair-lane kernel's copy of dL_dy by level (2 floats)
 	const uint64_t per = meta->n_dims_to_encode + (pairlane_meta_ok(meta) ? 2u : 0u);
 	return (uint64_t)n_points * meta->n_pseudo_levels * per * sizeof(float);
-}
-
-extern "C" int nr3d_lotd_bwd_bwd_dx(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int x_dtype,
-                                    int param_dtype, const void *dL_ddLdx, const void *dL_dy, int64_t g_sn, int64_t g_se,
-                                    const void *x, const void *params, const int64_t *batch_inds,
-                                    const int64_t *batch_offsets, uint32_t batch_data_size, int32_t max_level,
-                                    void *dL_dx, void *stream) {
-	return launch_bwd_bwd_dx(meta, meta_dev, N, x_dtype, param_dtype, dL_ddLdx, dL_dy, g_sn, g_se, x, params, batch_inds,
-	                         batch_offsets, batch_data_size, max_level, dL_dx, nullptr, 0, stream);
-}
-
-extern "C" int nr3d_lotd_bwd_bwd_dx_ws(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int x_dtype,
-                                       int param_dtype, const void *dL_ddLdx, const void *dL_dy, int64_t g_sn, int64_t g_se,
-                                       const void *x, const void *params, const int64_t *batch_inds,
-                                       const int64_t *batch_offsets, uint32_t batch_data_size, int32_t max_level,
-                                       void *dL_dx, void *workspace, uint64_t workspace_bytes, void *stream) {
-	return launch_bwd_bwd_dx(meta, meta_dev, N, x_dtype, param_dtype, dL_ddLdx, dL_dy, g_sn, g_se, x, params, batch_inds,
-	                         batch_offsets, batch_data_size, max_level, dL_dx, workspace, workspace_bytes, stream);
 }
 
 extern "C" int nr3d_lotd_grid_index(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int x_dtype,

@@ -453,7 +453,7 @@ __global__ __launch_bounds__(kPBP, kPBP == 768 ? 6 : 8) /* <= 64 VGPRs: two 64 K
 	}
 }
 
-// max of the dL/dx kernel's per-workgroup |dL/dy| maxima (float bits, nr3d_lotd_bwd_dx_fold) over a 1024-thread workgroup:
+// max of the dL/dx kernel's per-workgroup |dL/dy| maxima (float bits, nr3d_lotd_bwd_dx with `fold`) over a 1024-thread workgroup:
 // a max does not depend on the order, so this is bit for bit the atomicMax of pair_gmax.  `red` holds >= 16 words.
 __device__ __forceinline__ uint32_t gmax_slots(const uint32_t *__restrict__ slots, uint32_t n_slots, uint32_t *red) {
 	uint32_t m = 0;

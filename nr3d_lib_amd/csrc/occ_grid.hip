@@ -607,7 +607,7 @@ extern "C" uint64_t nr3d_ray_marching_cache_bytes(uint32_t n_rays, uint32_t max_
 }
 
 // count pass + the scan of the counts.  ridx_hit == NULL: packed_info and total_steps[0] (nr3d_ray_marching_count); else the
-// same scan also compacts the rays that got samples (nr3d_march_finish_rays' outputs; total_steps is then {S, n_hit})
+// same scan also compacts the rays that got samples (ridx_hit and pack_infos of nr3d_ray_marching_count_finished; total_steps is then {S, n_hit})
 static int march_count(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
                        const float *t_max, const float *roi, const int32_t grid_res[3],
                        const uint8_t *grid_binary, int type, float step_size, float max_step_size,

@@ -5,7 +5,6 @@
 // those chains were ~110 launches and 20 % of the GPU time of an iteration (profiles/r02z_full_loop_kernel_stats.txt);
 // here each chain is one to three launches:
 //   nr3d_tau_to_alpha_fwd / _bwd     alpha = 1 - exp(-sigma * delta) and its gradient: one launch each way
-//   nr3d_march_finish_rays           rays that got samples -> (ray index, int64 pack_infos) compacted, + their number
 //   nr3d_march_finish_samples        per sample: int64 ray index, delta = t1 - t0, position o + d * t0
 //   nr3d_prune_compact_packs         kept-sample counts -> new begin of every pack, packs that keep >= 1 sample
 //                                    compacted (index, int64 pack_infos), + both totals
@@ -112,13 +111,6 @@ extern "C" int nr3d_tau_to_alpha_bwd(uint64_t S, const float *sigma, const float
 	                   (hipStream_t)stream, S, sigma, delta, grad_alpha, grad_sigma);
 	NR3D_LAUNCH_CHECK();
 	return 0;
-}
-
-extern "C" int nr3d_march_finish_rays(uint32_t n_rays, const int32_t *packed_info, int64_t *ridx_hit, int64_t *pack_infos,
-                                      int64_t *totals, void *scan_tmp, void *stream) {
-	NR3D_CHECK(totals && (n_rays == 0 || (packed_info && ridx_hit && pack_infos && scan_tmp)), "march_finish_rays: NULL tensor pointer");
-	glue::PackWriter<int32_t, 2> w{packed_info + 1, nullptr, nullptr, ridx_hit, pack_infos};
-	return glue::compact_packs<int32_t, 2>(n_rays, w, totals, scan_tmp, (hipStream_t)stream);
 }
 
 extern "C" int nr3d_march_finish_samples(uint64_t S, const float *rays_o, const float *rays_d, const int32_t *ridx,

@@ -85,13 +85,13 @@ def _scatter_max_apply(grid: torch.Tensor, n_batches: int, res, *, gidx=None, pt
     with torch.cuda.device(grid.device):
         st = H.stream_of(grid)
         vmax = torch.empty(grid.numel(), dtype=torch.float32, device=grid.device)
-        H.check(H.lib().nr3d_occ_scatter_max(C.c_uint64(n), H.ptr(gidx), H.ptr(pts), H.ptr(bidx), C.c_uint64(per_batch),
-                                             H.ptr(val), cres, H.u32(n_batches), H.ptr(vmax), st))
+        H.check(H.lib().nr3d_occ_scatter_max(n, H.ptr(gidx), H.ptr(pts), H.ptr(bidx), per_batch, H.ptr(val), cres, n_batches,
+                                             H.ptr(vmax), st))
         if group is not None and group is not False and torch.distributed.is_initialized():
             pg = None if group is True else group
             if torch.distributed.get_world_size(pg) > 1:      # ranks hold different samples of the same update
                 torch.distributed.all_reduce(vmax, op=torch.distributed.ReduceOp.MAX, group=pg)
-        H.check(H.lib().nr3d_occ_apply_max(C.c_uint64(grid.numel()), H.f32(ema_decay), H.ptr(vmax), H.ptr(grid), st))
+        H.check(H.lib().nr3d_occ_apply_max(grid.numel(), float(ema_decay), H.ptr(vmax), H.ptr(grid), st))
 
 
 def update_occ_val_grid_idx_(occ_val_grid: torch.Tensor, gidx: torch.Tensor, occ_val: torch.Tensor,

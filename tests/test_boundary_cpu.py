@@ -51,6 +51,25 @@ def test_signature_table_is_the_header():
         assert all((t is ctypes.c_void_p) == (a == "ptr") for t, a in zip(fn.argtypes, args)), name
 
 
+def test_size_queries_return_uint64(hiplib):
+    """every nr3d_*_bytes entry point is declared uint64_t -- ctypes' default result type is a C int, which would cut a size above
+    2 GiB short -- and the loader has applied it (the bindings set no restype of their own)"""
+    from nr3d_lib_amd import _abi
+    queries = [n for n in _abi.SIGNATURES if n.endswith("_bytes")]
+    assert len(queries) >= 8, queries
+    for name in queries:
+        assert _abi.SIGNATURES[name][0] == "uint64_t", name
+        assert getattr(_hip.lib(), name).restype is ctypes.c_uint64, name
+    assert _hip.lib().nr3d_ray_marching_cache_bytes(1 << 20, 1 << 10) == 12 << 30
+
+
+def test_cache_bytes_is_the_library_s(hiplib):
+    """the sample-cache size the marcher bindings compute on the host is what the library asks for"""
+    from nr3d_lib_amd.bindings import _occ_grid
+    for n, s in ((0, 0), (0, 512), (4096, 0), (1, 1), (4096, 1024), (65536, 512), (1 << 20, 1 << 10), (2 ** 32 - 1, 1024)):
+        assert _occ_grid._cache_bytes(n, s) == _hip.lib().nr3d_ray_marching_cache_bytes(n, s), (n, s)
+
+
 def test_vendored_package_needs_no_header(tmp_path):
     """a copy of nr3d_lib_amd/ ALONE (no include/, no tools/, no csrc/) imports, loads the library and resolves every entry point"""
     import shutil

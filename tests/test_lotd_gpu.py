@@ -977,9 +977,8 @@ def test_forward_lds_stage_bit_identical(dev, hip_option, smooth, half):
     assert torch.equal(out[1][1], out[0][1]), "dy_dx, fwd_lds_stage = 1"
     import ctypes
     from nr3d_lib_amd import _hip as H
-    H.lib().nr3d_lotd_fwd_lds_levels.restype = ctypes.c_uint64
     hip_option("fwd_lds_stage", 1)
-    mask = H.lib().nr3d_lotd_fwd_lds_levels(ctypes.byref(meta._cmeta()), ctypes.c_uint32(n))
+    mask = H.lib().nr3d_lotd_fwd_lds_levels(ctypes.byref(meta._cmeta()), n)
     assert mask == 0b000011, bin(mask)                 # 16^3 and 22^3 fit LDS whole; 30^3 and up take the two-lane kernel
 
 

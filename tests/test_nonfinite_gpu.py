@@ -376,9 +376,7 @@ def test_forward_nan_table_entry(oracle, inputs, dev, hip_option, case):
 def _lds_levels(m, n):
     import ctypes
     from nr3d_lib_amd import _hip as H
-    f = H.lib().nr3d_lotd_fwd_lds_levels
-    f.restype = ctypes.c_uint64
-    return int(f(ctypes.byref(m._cmeta()), ctypes.c_uint32(n)))
+    return H.lib().nr3d_lotd_fwd_lds_levels(ctypes.byref(m._cmeta()), n)
 
 
 def test_forward_nan_table_entry_lds_staged(oracle, inputs, dev, hip_option):

@@ -323,10 +323,9 @@ def test_sort(oracle, dev, P, dtype, wave, hip_option):
     v2 = T(x, dev).clone()
     payload = torch.from_numpy(rng.integers(-2 ** 40, 2 ** 40, S)).to(dev)
     from nr3d_lib_amd import _hip as H
-    import ctypes as Cc
     pit = T(pi, dev)
     p0 = payload.clone()
-    H.check(H.lib().nr3d_packed_sort(H.u32(pit.shape[0]), Cc.c_uint64(S), Cc.c_int(H.DTYPE_CODE[v2.dtype]), H.ptr(v2), H.ptr(payload),
+    H.check(H.lib().nr3d_packed_sort(pit.shape[0], S, H.DTYPE_CODE[v2.dtype], H.ptr(v2), H.ptr(payload),
                                      H.ptr(pit), H.stream_of(v2)))
     assert torch.equal(payload, p0[idx]) and torch.equal(v2, v)
     assert P.packed_sort_qsort(T(x, dev).clone(), T(pi, dev), False) is None

@@ -9,9 +9,7 @@ from util import LOTD_CASES
 @pytest.fixture
 def fold_bytes(hiplib):
     from nr3d_lib_amd import _hip as H
-    f = H.lib().nr3d_lotd_pair_fold_bytes
-    f.restype = C.c_uint64
-    return lambda m, n, ml: int(f(C.byref(m._cmeta()), H.u32(n), H.i32(ml)))
+    return lambda m, n, ml: H.lib().nr3d_lotd_pair_fold_bytes(C.byref(m._cmeta()), n, ml)
 
 
 def _meta(case):

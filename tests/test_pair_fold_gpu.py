@@ -35,9 +35,7 @@ def _inputs(m, n, seed, dev):
 
 def _fold_bytes(m, n, max_level):
     from nr3d_lib_amd import _hip as H
-    f = H.lib().nr3d_lotd_pair_fold_bytes
-    f.restype = C.c_uint64
-    return int(f(C.byref(m._cmeta()), H.u32(n), H.i32(max_level)))
+    return H.lib().nr3d_lotd_pair_fold_bytes(C.byref(m._cmeta()), n, max_level)
 
 
 def _bwd(m, x, p, dy, max_level=None):

@@ -20,21 +20,20 @@ for cap in (2, 4, 8):
     gs = []
     for width in (8, 4, 2):
         gm = _lotd._CMeta()
-        H.check(H.lib().nr3d_lotd_meta_regroup(C.byref(meta._c), C.c_uint32(width), C.c_uint32(cap), C.byref(gm)))
+        H.check(H.lib().nr3d_lotd_meta_regroup(C.byref(meta._c), width, cap, C.byref(gm)))
         if gm.n_pseudo_levels:
             gs.append((gm, torch.frombuffer(bytearray(bytes(gm)), dtype=torch.uint8).to(dev)))
     groups.append((cap, gs))
-H.lib().nr3d_lotd_dparam_workspace_bytes.restype = C.c_uint64
 ref = None
 for cap, gs in groups:
-    need = max(int(H.lib().nr3d_lotd_dparam_workspace_bytes(C.byref(gm), H.u32(N), H.u32(1))) for gm, _ in gs)
+    need = max(H.lib().nr3d_lotd_dparam_workspace_bytes(C.byref(gm), N, 1) for gm, _ in gs)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     def run():
         dp = torch.zeros(meta.n_params, device=dev)
         for gm, gd in gs:
-            H.check(H.lib().nr3d_lotd_bwd_dparam(C.byref(gm), H.ptr(gd), H.u32(N), C.c_int(H.F32), C.c_int(H.F32), H.ptr(gT), H.i64(1), H.i64(N),
-                                                 H.ptr(x), H.ptr(params), None, None, H.u32(0), H.u32(1), H.i32(meta.n_levels), H.ptr(dp), H.ptr(ws),
-                                                 C.c_uint64(need), H.stream_of(x)))
+            H.check(H.lib().nr3d_lotd_bwd_dparam(C.byref(gm), H.ptr(gd), N, H.F32, H.F32, H.ptr(gT), 1, N,
+                                                 H.ptr(x), H.ptr(params), None, None, 0, 1, meta.n_levels, H.ptr(dp), H.ptr(ws),
+                                                 need, H.stream_of(x)))
         return dp
     dp = run(); run(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
