@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <atomic>
+#include <initializer_list>
 
 #include "../../include/nr3d_hip.h"
 #include "options.h"
@@ -21,6 +23,35 @@ int fail(const char *fmt, ...);
 #define NR3D_LAUNCH_CHECK() NR3D_HIP_CHECK(hipGetLastError())
 
 static inline uint32_t div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+
+// Raising the dynamic-LDS limit of kernels (launches above 64 KiB need it).  Naming a kernel here instantiates it.
+// lds_limit_always: on every call (a launch lambda shared by kernels of one signature has no per-kernel static to remember in).
+template <typename... K>
+static inline int lds_limit_always(const char *file, int line, int bytes, K... kernels) {
+	for (const void *k : {(const void *)kernels...}) {
+		const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+		if (e != hipSuccess) return fail("raising the dynamic LDS limit to %d bytes failed: %s (%s:%d)", bytes, hipGetErrorString(e), file, line);
+	}
+	return 0;
+}
+// lds_limit: once per device and launch site.  The site keeps a `static LdsOnce`: one bit per device id, relaxed (two threads that race
+// set the attribute twice, which is harmless); an id the mask has no bit for sets the attribute on every call.  `dev`: the current
+// device id, -1 while nobody has asked for it (then asked for here and kept, so that the sites of one call ask once).
+struct LdsOnce { std::atomic<uint64_t> done{0}; };
+template <typename... K>
+static inline int lds_limit(const char *file, int line, LdsOnce &once, int &dev, int bytes, K... kernels) {
+	if (dev < 0) {
+		const hipError_t e = hipGetDevice(&dev);
+		if (e != hipSuccess) return fail("hipGetDevice failed: %s (%s:%d)", hipGetErrorString(e), file, line);
+	}
+	if (dev < 64 && ((once.done.load(std::memory_order_relaxed) >> dev) & 1ull)) return 0;
+	if (int rc = lds_limit_always(file, line, bytes, kernels...)) return rc;
+	if (dev < 64) once.done.fetch_or(1ull << dev, std::memory_order_relaxed);
+	return 0;
+}
+#define NR3D_LDS_LIMIT(once, dev, ...) ::nr3d::lds_limit(__FILE__, __LINE__, once, dev, __VA_ARGS__)
+#define NR3D_LDS_LIMIT_ALWAYS(...) ::nr3d::lds_limit_always(__FILE__, __LINE__, __VA_ARGS__)
+#define NR3D_TRY(expr) do { if (int _rc = (expr)) return _rc; } while (0)
 
 // Optional HIP-event timing of individual kernels (nr3d_prof_enable / nr3d_prof_read, include/nr3d_hip.h): a Scope records
 // an event pair on the launch stream around the launches in its lifetime when its id is enabled, and costs one load

@@ -1548,16 +1548,10 @@ static int fwd_fast_path(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *m
 	served = true;
 	uint64_t staged = 0;
 	if (lds_stage_enabled() && N >= kLdsMinPoints && meta->n_pseudo_levels <= 64) {
-		static bool attr_set_dev[64] = {};
-		int dev_id = 0;
-		NR3D_HIP_CHECK(hipGetDevice(&dev_id));
-		if (!attr_set_dev[dev_id & 63]) {
-			NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_fwd_lds<true, PT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsGroupBytes));
-			NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_fwd_lds<false, PT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsGroupBytes));
-			NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_fwd_lds<true, PT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsGroupBytes));
-			NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_fwd_lds<false, PT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsGroupBytes));
-			attr_set_dev[dev_id & 63] = true;
-		}
+		static LdsOnce once;
+		int dev = -1;
+		NR3D_TRY(NR3D_LDS_LIMIT(once, dev, (int)kLdsGroupBytes, k_fwd_lds<true, PT, 1>, k_fwd_lds<false, PT, 1>, k_fwd_lds<true, PT, 2>,
+		                        k_fwd_lds<false, PT, 2>));
 		LdsLevels grp;
 		uint32_t n_grp = 0, grp_bytes = 0;
 		auto flush = [&]() {
@@ -1736,47 +1730,33 @@ extern "C" uint64_t nr3d_lotd_pair_fold_bytes(const nr3d_lotd_meta_t *meta, uint
 	return meta ? pair_fold_layout(meta, N, max_level, gcols, n_zero, slot_off) : 0;
 }
 
-static int launch_bwd_dparam(bool second, const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N,
-                             const void *dL_ddLdx, const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x,
-                             const void *params, const int64_t *batch_inds, const int64_t *batch_offsets,
-                             uint32_t batch_data_size, uint32_t n_batches, int32_t max_level, void *dL_dparam,
-                             void *workspace, uint64_t workspace_bytes, void *stream, int32_t min_level = 0, bool p_half = false) {
-	// p_half: `params` are __half tables (read by the product-type levels only; dL_dparam stays float)
-	if (N == 0 || max_level <= -1 || min_level > max_level) return 0;
-	NR3D_CHECK(dL_dy && x && params && dL_dparam, "LoTD::bwd: NULL tensor pointer");
+static int launch_bwd_dparam(const DparamPass &p) {
+	const nr3d_lotd_meta_t *meta = p.meta;
+	if (p.N == 0 || p.max_level <= -1 || p.min_level > p.max_level) return 0;
+	NR3D_CHECK(p.dL_dy && p.x && p.params && p.dparam, "LoTD::bwd: NULL tensor pointer");
 	// atomic-free binned path: metas without NPlaneSum/CPfast levels, when the caller supplied the workspace (batched
 	// params need n_batches, the number of table sets behind `params`)
-	const bool batched = batch_inds || batch_offsets || batch_data_size;
-	if (workspace && (!batched || n_batches > 0)) {
+	const bool batched = p.batch.inds || p.batch.offsets || p.batch.data_size;
+	if (p.workspace && (!batched || p.n_batches > 0)) {
 		bool handled = false;
-		const Batch bb{batch_inds, batch_offsets, batch_data_size, meta->n_params};
-		if (int rc = dparam_binned(second, meta, meta_dev, N, (const float *)dL_ddLdx, (const float *)dL_dy, g_sn, g_se,
-		                           (const float *)x, (const float *)params, bb, batched ? n_batches : 1u, max_level,
-		                           (float *)dL_dparam, workspace, workspace_bytes, (hipStream_t)stream, handled, nullptr,
-		                           min_level, false, false, false, p_half))
-			return rc;
+		DparamPass q = p;
+		if (!batched) q.n_batches = 1u;
+		NR3D_TRY(dparam_binned(q, handled));
 		if (handled) return 0;
 	}
 	uint32_t n_blocks;
-	const Sched s = make_sched(N, meta, n_blocks);
-	const Batch ba{batch_inds, batch_offsets, batch_data_size, meta->n_params};
-	const auto md = (const nr3d_lotd_meta_t *)meta_dev;
+	const Sched s = make_sched(p.N, meta, n_blocks);
 	const bool dh = meta->c_hash_only != 0;
 	DISPATCH_DG(meta->n_dims_to_encode, meta->n_feat_per_pseudo_lvl, {
 		auto launch = [&](auto kern, auto *tab) {
-			hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(kBlock), 0, (hipStream_t)stream, s, md, N, min_level, max_level,
-			                   meta->interpolation_type, (const float *)dL_ddLdx, (const float *)dL_dy, g_sn, g_se,
-			                   (const float *)x, tab, ba, (float *)dL_dparam);
+			hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(kBlock), 0, p.st, s, p.meta_dev, p.N, p.min_level, p.max_level,
+			                   meta->interpolation_type, p.dL_ddLdx, p.dL_dy, p.g_sn, p.g_se, p.x, tab, p.batch, p.dparam);
 		};
-		const float *pf = (const float *)params;
-		const __half *ph = (const __half *)params;
-		// Dense / Hash levels read no table: the hash-only instantiations serve both storage types
-		if (dh || !p_half) {
-			if (second) { if (dh) launch(k_bwd_dparam<D, G, true, true>, pf); else launch(k_bwd_dparam<D, G, true, false>, pf); }
-			else        { if (dh) launch(k_bwd_dparam<D, G, false, true>, pf); else launch(k_bwd_dparam<D, G, false, false>, pf); }
-		} else {
-			if (second) launch(k_bwd_dparam<D, G, true, false, __half>, ph); else launch(k_bwd_dparam<D, G, false, false, __half>, ph);
-		}
+		const float *pf = (const float *)p.params;
+		// Dense / Hash levels read no table: the hash-only instantiations serve both storage types (no k_bwd_dparam<., ., ., true, __half>)
+		if (dh || !p.p_half)
+			with_bool(p.second, [&](auto S) { if (dh) launch(k_bwd_dparam<D, G, S(), true>, pf); else launch(k_bwd_dparam<D, G, S(), false>, pf); });
+		else with_bool(p.second, [&](auto S) { launch(k_bwd_dparam<D, G, S(), false, __half>, (const __half *)p.params); });
 	});
 	NR3D_LAUNCH_CHECK();
 	return 0;
@@ -1788,9 +1768,12 @@ extern "C" int nr3d_lotd_bwd_dparam(const nr3d_lotd_meta_t *meta, const void *me
                                     uint32_t batch_data_size, uint32_t n_batches, int32_t max_level, void *dL_dparam,
                                     void *workspace, uint64_t workspace_bytes, void *stream) {
 	if (int rc = check_common(meta, meta_dev, x_dtype, param_dtype, true)) return rc;
-	return launch_bwd_dparam(false, meta, meta_dev, N, nullptr, dL_dy, g_sn, g_se, x, params, batch_inds,
-	                         batch_offsets, batch_data_size, n_batches, max_level, dL_dparam, workspace, workspace_bytes,
-	                         stream, 0, param_dtype == NR3D_F16);
+	DparamPass p = plain_pass(meta, meta_dev, N, dL_dy, g_sn, g_se, x, dL_dparam);
+	p.params = params; p.p_half = param_dtype == NR3D_F16;
+	p.batch = Batch{batch_inds, batch_offsets, batch_data_size, meta->n_params}; p.n_batches = n_batches;
+	p.min_level = 0; p.max_level = max_level;
+	p.workspace = workspace; p.workspace_bytes = workspace_bytes; p.st = (hipStream_t)stream;
+	return launch_bwd_dparam(p);
 }
 
 extern "C" int nr3d_lotd_pair_path_ok(const nr3d_lotd_meta_t *meta) { return (meta && pair_applies(meta)) ? 1 : 0; }
@@ -1817,11 +1800,12 @@ extern "C" int nr3d_lotd_bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const vo
 	}
 	NR3D_CHECK(dL_dy && x && dL_dparam && workspace, "LoTD::bwd: NULL tensor pointer");
 	bool handled = false;
-	const Batch bb{nullptr, nullptr, 0u, meta->n_params};
-	if (int rc = dparam_binned(false, meta, meta_dev, N, nullptr, (const float *)dL_dy, g_sn, g_se, (const float *)x, nullptr, bb,
-	                           1u, max_level, (float *)dL_dparam, workspace, workspace_bytes, (hipStream_t)stream, handled, nullptr,
-	                           0, grad_dtype == NR3D_F16, out_dtype == NR3D_F16, assign != 0, false, (uint32_t *)fold))
-		return rc;
+	DparamPass p = plain_pass(meta, meta_dev, N, dL_dy, g_sn, g_se, x, dL_dparam);
+	p.g_half = grad_dtype == NR3D_F16; p.out_half = out_dtype == NR3D_F16; p.assign = assign != 0;
+	p.max_level = max_level;
+	p.workspace = workspace; p.workspace_bytes = workspace_bytes; p.st = (hipStream_t)stream;
+	p.fold = (uint32_t *)fold;
+	NR3D_TRY(dparam_binned(p, handled));
 	NR3D_CHECK(handled, "LoTD::bwd_dparam_typed: the pair-record path does not apply to this meta / workspace");
 	return 0;
 }
@@ -1834,9 +1818,12 @@ extern "C" int nr3d_lotd_bwd_dparam_levels(const nr3d_lotd_meta_t *meta, const v
                                            void *stream) {
 	if (int rc = check_common(meta, meta_dev, x_dtype, param_dtype, true)) return rc;
 	NR3D_CHECK(min_level >= 0, "LoTD::bwd: min_level must be >= 0");
-	return launch_bwd_dparam(false, meta, meta_dev, N, nullptr, dL_dy, g_sn, g_se, x, params, batch_inds,
-	                         batch_offsets, batch_data_size, n_batches, max_level, dL_dparam, workspace, workspace_bytes,
-	                         stream, min_level, param_dtype == NR3D_F16);
+	DparamPass p = plain_pass(meta, meta_dev, N, dL_dy, g_sn, g_se, x, dL_dparam);
+	p.params = params; p.p_half = param_dtype == NR3D_F16;
+	p.batch = Batch{batch_inds, batch_offsets, batch_data_size, meta->n_params}; p.n_batches = n_batches;
+	p.min_level = min_level; p.max_level = max_level;
+	p.workspace = workspace; p.workspace_bytes = workspace_bytes; p.st = (hipStream_t)stream;
+	return launch_bwd_dparam(p);
 }
 
 extern "C" void nr3d_lotd_set_dparam_chunk_log2(int log2_points) { set_dparam_chunk_log2(log2_points); }
@@ -1853,9 +1840,13 @@ extern "C" int nr3d_lotd_bwd_bwd_dparam(const nr3d_lotd_meta_t *meta, const void
                                         void *stream) {
 	if (int rc = check_common(meta, meta_dev, x_dtype, param_dtype, true)) return rc;
 	NR3D_CHECK(N == 0 || dL_ddLdx != nullptr, "LoTD::bwd_bwd_input: dL_ddLdx is NULL");
-	return launch_bwd_dparam(true, meta, meta_dev, N, dL_ddLdx, dL_dy, g_sn, g_se, x, params, batch_inds,
-	                         batch_offsets, batch_data_size, n_batches, max_level, dL_dparam, workspace, workspace_bytes,
-	                         stream, 0, param_dtype == NR3D_F16);
+	DparamPass p = plain_pass(meta, meta_dev, N, dL_dy, g_sn, g_se, x, dL_dparam);
+	p.second = true; p.dL_ddLdx = (const float *)dL_ddLdx;
+	p.params = params; p.p_half = param_dtype == NR3D_F16;
+	p.batch = Batch{batch_inds, batch_offsets, batch_data_size, meta->n_params}; p.n_batches = n_batches;
+	p.min_level = 0; p.max_level = max_level;
+	p.workspace = workspace; p.workspace_bytes = workspace_bytes; p.st = (hipStream_t)stream;
+	return launch_bwd_dparam(p);
 }
 
 extern "C" int nr3d_lotd_bwd_bwd_ddLdy(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int param_dtype,

@@ -1421,9 +1421,10 @@ static uint64_t vm_direct_plan(const nr3d_lotd_meta_t *m, uint32_t n, int32_t mi
 // (the sorted-points path of large VM levels: lotd_sorted.hip, its own translation unit)
 
 // plan for the pseudo levels of record class `cls` (0 levels => n_pseudo == 0)
-static bool make_plan(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t n_batches, uint32_t cls, BinPlan &plan,
-                      uint64_t &offs_words, int32_t min_level = 0, int32_t max_level = 0x7fffffff, bool forest = false,
-                      uint64_t skip = 0) {
+// a plan's pseudo levels: those of levels [min_level, max_level] without the ones in `skip` (bit q: served elsewhere); forest: its record counts
+struct PlanLevels { int32_t min_level, max_level; bool forest; uint64_t skip; };
+static bool make_plan(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t n_batches, uint32_t cls, const PlanLevels &lv, BinPlan &plan,
+                      uint64_t &offs_words) {
 	const uint32_t D = m->n_dims_to_encode, G = m->n_feat_per_pseudo_lvl;
 	const uint32_t kBinPts = bin_points(G, cls);
 	if (m->n_pseudo_levels > kMaxPlanLevels) return false;
@@ -1437,11 +1438,11 @@ static bool make_plan(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t n_ba
 	uint64_t base = 0;
 	for (uint32_t q = 0; q < m->n_pseudo_levels; ++q) {
 		const nr3d_lotd_level_t &L = m->levels[m->map_levels[q]];
-		if (rec_class(rec_count(L.type, D, forest)) != cls) continue;
-		if (q < 64u && ((skip >> q) & 1ull)) continue;          // served without records (k_cp_direct) or by another plan
+		if (rec_class(rec_count(L.type, D, lv.forest)) != cls) continue;
+		if (q < 64u && ((lv.skip >> q) & 1ull)) continue;          // served without records (k_cp_direct) or by another plan
 		// levels outside the requested range get no stage-A blocks, offsets or work items (max_level schedules, the
 		// level-bucket calls of the data-parallel path)
-		if ((int32_t)m->map_levels[q] < min_level || (int32_t)m->map_levels[q] > max_level) continue;
+		if ((int32_t)m->map_levels[q] < lv.min_level || (int32_t)m->map_levels[q] > lv.max_level) continue;
 		const uint64_t n_virtual = (uint64_t)plan.n_batches * L.size;
 		if (n_virtual > 0xFFFFFFFFull) return false;
 		const uint32_t nb = div_up(n_virtual, 1u << lg);
@@ -1478,7 +1479,7 @@ static bool layout(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t n_batch
 	for (uint32_t cls : kClasses) {
 		BinPlan plan;
 		uint64_t ow;
-		if (!make_plan(m, n_chunk, n_batches, cls, plan, ow, 0, 0x7fffffff, forest)) return false;
+		if (!make_plan(m, n_chunk, n_batches, cls, PlanLevels{0, 0x7fffffff, forest, 0}, plan, ow)) return false;
 		const uint64_t rb = (uint64_t)plan.n_pseudo * plan.n_blk * (1 + m->n_feat_per_pseudo_lvl) * plan.cap * 4;
 		const uint64_t ob = ((ow * 4 + 255) / 256) * 256;
 		l.rec_bytes = rb > l.rec_bytes ? rb : l.rec_bytes;
@@ -1491,7 +1492,7 @@ static bool layout(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t n_batch
 	}
 	if (!forest && n_batches <= 1 && pair_applies(m)) {       // lotd_pair.hip runs in the same regions
 		uint64_t rb, ob, pb, qb;
-		pair_layout(m, n_chunk, kWorkUnits, rb, ob, pb, qb);
+		pair_layout(m, n_chunk, rb, ob, pb, qb);
 		l.rec_bytes = rb > l.rec_bytes ? rb : l.rec_bytes;
 		l.offs_bytes = ob > l.offs_bytes ? ob : l.offs_bytes;
 		l.plan_bytes = pb > l.plan_bytes ? pb : l.plan_bytes;
@@ -1540,99 +1541,65 @@ uint64_t dparam_workspace_bytes(const nr3d_lotd_meta_t *m, uint32_t n_points, ui
 // NR3D_OPT_VM_SPLIT = 0: VM levels through the one-thread-per-point stage A (A/B, cross-check)
 static bool vm_split_enabled() { return opt::on(NR3D_OPT_VM_SPLIT); }
 
+// stage A, the replica plan and stage B of one record class
 template <int D, int G, int NR, bool DH>
-static int launch_class(bool second, const BinPlan &pl, const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_t n,
-                        int32_t max_level, const float *xc, const float *vc, const float *gc, int64_t sn, int64_t se,
-                        const void *params_, bool p_half, const Batch &ba, uint32_t *rec, uint32_t *offs, uint32_t *plan_buf,
-                        float *partial, float *dparam, hipStream_t st, const ForestDev *fo = nullptr) {
+static int launch_class(const DparamPass &p, DparamChunk &c, const BinPlan &pl) {
 	constexpr int BP = BinCfg<G, NR>::BP;
-	const float *params = (const float *)params_;        // half tables: only the !DH instantiations read them (k_bin<..., __half>)
+	const nr3d_lotd_meta_t *md = p.meta_dev;
+	const float *params = (const float *)p.params;       // half tables: only the !DH instantiations read them (k_bin<..., __half>)
+	const Batch &ba = c.ba;
+	uint32_t *rec = c.rec, *offs = c.offs;
+	float *partial = c.partial, *dparam = p.dparam;
+	hipStream_t st = p.st;
 	uint32_t nb_max = 0;
 	for (uint32_t q = 0; q < pl.n_pseudo; ++q) nb_max = nb_max > pl.nb[q] ? nb_max : pl.nb[q];
 	const uint32_t NB = pl.bucket_base[pl.n_pseudo];
-	uint32_t *tot = plan_buf, *rep = plan_buf + NB, *item_start = plan_buf + 2 * (size_t)NB;
+	uint32_t *tot = c.plan_buf, *rep = c.plan_buf + NB, *item_start = c.plan_buf + 2 * (size_t)NB;
 	const size_t bin_lds = ((size_t)(1 + G) * BinCfg<G, NR>::cap + nb_max + 1) * sizeof(uint32_t);
-	static bool attr_set_dev[64] = {};                 // per device: a process may drive several GPUs
-	int dev_id = 0;
-	NR3D_HIP_CHECK(hipGetDevice(&dev_id));
-	bool &attr_set = attr_set_dev[dev_id & 63];
-	if (!attr_set) {
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_accum<D, G>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsDoubles * 8));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin<D, G, true, NR, DH>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin<D, G, false, NR, DH>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-		if constexpr (!DH) {
-			NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin<D, G, true, NR, false, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-			NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin<D, G, false, NR, false, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-		}
-		attr_set = true;
+	static LdsOnce once_acc, once_bin;                  // per device: a process may drive several GPUs
+	NR3D_TRY(NR3D_LDS_LIMIT(once_acc, c.dev, kLdsDoubles * 8, k_accum<D, G>));
+	NR3D_TRY(NR3D_LDS_LIMIT(once_bin, c.dev, kBinLdsDyn, k_bin<D, G, true, NR, DH>, k_bin<D, G, false, NR, DH>));
+	if constexpr (!DH) {
+		static LdsOnce once_half;
+		NR3D_TRY(NR3D_LDS_LIMIT(once_half, c.dev, kBinLdsDyn, k_bin<D, G, true, NR, false, __half>, k_bin<D, G, false, NR, false, __half>));
 	}
+	// every stage-A kernel takes the same arguments up to the tables; `more`: what a forest kernel takes between the batch and the records
+	auto stage_a = [&](auto kern, int threads, auto *tab, auto... more) {
+		hipLaunchKernelGGL(kern, dim3(pl.n_blk, pl.n_pseudo), dim3(threads), bin_lds, st, pl, md, c.n, p.max_level, p.meta->interpolation_type,
+		                   c.xc, c.vc, c.gc, c.sn, c.se, tab, ba, more..., rec, offs);
+	};
 	prof::g_mask & (1u << NR3D_PROF_LOTD_BIN) ? prof::begin(NR3D_PROF_LOTD_BIN, st) : (void)0;
-	if (fo) {
+	if (p.forest) {
 		if constexpr (D == 3 && (NR == 8 || NR == 24 || NR == 48)) {
-			static bool fattr_dev[64] = {};
-			if (!fattr_dev[dev_id & 63]) {
-				NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_forest<G, true, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-				NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_forest<G, false, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-				fattr_dev[dev_id & 63] = true;
-			}
-			auto forest_launch = [&](auto kern, auto *tab) {
-				hipLaunchKernelGGL(kern, dim3(pl.n_blk, pl.n_pseudo), dim3(BP), bin_lds, st, pl, md, n, max_level,
-				                   meta->interpolation_type, xc, vc, gc, sn, se, tab, ba, *fo, rec, offs);
-			};
+			static LdsOnce once_forest;
+			NR3D_TRY(NR3D_LDS_LIMIT(once_forest, c.dev, kBinLdsDyn, k_bin_forest<G, true, NR>, k_bin_forest<G, false, NR>));
 			bool done = false;
 			if constexpr (NR != 8) {                       // product types read the owner block's tables; Dense / Hash read none
-				if (p_half) {
-					static bool hattr_dev[64] = {};
-					if (!hattr_dev[dev_id & 63]) {
-						NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_forest<G, true, NR, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-						NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_forest<G, false, NR, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-						hattr_dev[dev_id & 63] = true;
-					}
-					if (second) forest_launch(k_bin_forest<G, true, NR, __half>, (const __half *)params_);
-					else forest_launch(k_bin_forest<G, false, NR, __half>, (const __half *)params_);
+				if (p.p_half) {
+					static LdsOnce once_forest_half;
+					NR3D_TRY(NR3D_LDS_LIMIT(once_forest_half, c.dev, kBinLdsDyn, k_bin_forest<G, true, NR, __half>, k_bin_forest<G, false, NR, __half>));
+					with_bool(p.second, [&](auto S) { stage_a(k_bin_forest<G, S(), NR, __half>, BP, (const __half *)p.params, *p.forest); });
 					done = true;
 				}
 			}
-			if (!done) { if (second) forest_launch(k_bin_forest<G, true, NR>, params); else forest_launch(k_bin_forest<G, false, NR>, params); }
+			if (!done) with_bool(p.second, [&](auto S) { stage_a(k_bin_forest<G, S(), NR>, BP, params, *p.forest); });
 		} else {
 			return ::nr3d::fail("LoTD forest: the binned path handles 3-D metas only");
 		}
 	} else if (D == 3 && NR == 24 && !DH && vm_split_enabled()) {
 		// class 24 in 3-D is the VM levels: three threads per point (six records each) instead of one with 18
 		if constexpr (D == 3 && NR == 24 && !DH) {
-			static bool vattr_dev[64] = {};
-			if (!vattr_dev[dev_id & 63]) {
-				NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_vm3<G, true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-				NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_vm3<G, false, float>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-				NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_vm3<G, true, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-				NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_bin_vm3<G, false, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, kBinLdsDyn));
-				vattr_dev[dev_id & 63] = true;
-			}
-			auto vm_launch = [&](auto kern, auto *tab) {
-				hipLaunchKernelGGL(kern, dim3(pl.n_blk, pl.n_pseudo), dim3(BP * 3), bin_lds, st, pl, md, n, max_level,
-				                   meta->interpolation_type, xc, vc, gc, sn, se, tab, ba, rec, offs);
-			};
-			if (p_half) {
-				if (second) vm_launch(k_bin_vm3<G, true, __half>, (const __half *)params_); else vm_launch(k_bin_vm3<G, false, __half>, (const __half *)params_);
-			} else {
-				if (second) vm_launch(k_bin_vm3<G, true, float>, params); else vm_launch(k_bin_vm3<G, false, float>, params);
-			}
+			static LdsOnce once_vm3;
+			NR3D_TRY(NR3D_LDS_LIMIT(once_vm3, c.dev, kBinLdsDyn, k_bin_vm3<G, true, float>, k_bin_vm3<G, false, float>, k_bin_vm3<G, true, __half>,
+			                        k_bin_vm3<G, false, __half>));
+			with_bool(p.second, [&](auto S) { with_tables(p.params, p.p_half, [&](auto *tab) {
+				stage_a(k_bin_vm3<G, S(), pointee_t<decltype(tab)>>, BP * 3, tab);
+			}); });
 		}
-	} else if (!DH && p_half) {
-		if constexpr (!DH) {
-			if (second)
-				hipLaunchKernelGGL((k_bin<D, G, true, NR, false, __half>), dim3(pl.n_blk, pl.n_pseudo), dim3(BP), bin_lds, st, pl, md, n, max_level,
-				                   meta->interpolation_type, xc, vc, gc, sn, se, (const __half *)params_, ba, rec, offs);
-			else
-				hipLaunchKernelGGL((k_bin<D, G, false, NR, false, __half>), dim3(pl.n_blk, pl.n_pseudo), dim3(BP), bin_lds, st, pl, md, n, max_level,
-				                   meta->interpolation_type, xc, vc, gc, sn, se, (const __half *)params_, ba, rec, offs);
-		}
-	} else if (second)
-		hipLaunchKernelGGL((k_bin<D, G, true, NR, DH>), dim3(pl.n_blk, pl.n_pseudo), dim3(BP), bin_lds, st, pl, md, n, max_level,
-		                   meta->interpolation_type, xc, vc, gc, sn, se, params, ba, rec, offs);
-	else
-		hipLaunchKernelGGL((k_bin<D, G, false, NR, DH>), dim3(pl.n_blk, pl.n_pseudo), dim3(BP), bin_lds, st, pl, md, n, max_level,
-		                   meta->interpolation_type, xc, vc, gc, sn, se, params, ba, rec, offs);
+	} else if (!DH && p.p_half) {
+		if constexpr (!DH) with_bool(p.second, [&](auto S) { stage_a(k_bin<D, G, S(), NR, false, __half>, BP, (const __half *)p.params); });
+	} else
+		with_bool(p.second, [&](auto S) { stage_a(k_bin<D, G, S(), NR, DH>, BP, params); });
 	prof::end(NR3D_PROF_LOTD_BIN, st);
 	hipLaunchKernelGGL(k_bucket_totals, dim3(div_up(NB, 4)), dim3(256), 0, st, pl, offs, tot);
 	hipLaunchKernelGGL(k_plan_items, dim3(1), dim3(1024), 0, st, NB, pl.n_blk, kWorkUnits, tot, rep, item_start);
@@ -1678,198 +1645,188 @@ namespace lotd {
 // NR3D_OPT_PAIR_SECOND = 0: d(dL/dx)/dparam of pair-path metas through the 12-byte corner records (A/B, and the cross-check)
 static bool pair_second_enabled() { return opt::on(NR3D_OPT_PAIR_SECOND); }
 
-int dparam_binned(bool second, const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, const float *dL_ddLdx,
-                  const float *dL_dy, int64_t g_sn, int64_t g_se, const float *x, const float *params, const Batch &batch,
-                  uint32_t n_batches, int32_t max_level, float *dparam, void *workspace, uint64_t workspace_bytes,
-                  hipStream_t st, bool &handled, const ForestDev *forest, int32_t min_level, bool g_half, bool out_half, bool assign,
-                  bool p_half, uint32_t *fold) {
+// CP levels whose table fits LDS, straight from (x, dL_dy) into the partial-table region and from there into dparam: no records
+static int cp_direct_route(const DparamPass &p, DparamChunk &c, const CpPlan &cp, uint32_t max_acc) {
+	static LdsOnce once;
+	NR3D_TRY(NR3D_LDS_LIMIT(once, c.dev, (int)kCpLdsBytes, k_cp_direct<false, float>, k_cp_direct<true, float>, k_cp_direct<false, __half>,
+	                        k_cp_direct<true, __half>));
+	const size_t lds = (size_t)max_acc * 8;
+	with_bool(p.second, [&](auto S) { with_tables(p.params, p.p_half, [&](auto *tab) {
+		hipLaunchKernelGGL((k_cp_direct<S(), pointee_t<decltype(tab)>>), dim3(cp.R, cp.n_items), dim3(kCpThreads), lds, p.st, cp, p.meta_dev, c.n,
+		                   p.meta->interpolation_type, c.xc, c.vc, c.gc, c.sn, c.se, tab, c.partial, opt::on(NR3D_OPT_DIRECT_FIXED) ? 1u : 0u);
+	}); });
+	hipLaunchKernelGGL(k_cp_reduce, dim3(div_up(max_acc, 256u), cp.n_items), dim3(256), 0, p.st, cp, p.meta_dev, c.partial, p.dparam);
+	NR3D_LAUNCH_CHECK();
+	return 0;
+}
+
+// small VM levels, like the CP levels above
+static int vm_direct_route(const DparamPass &p, DparamChunk &c, const VmPlan &vp) {
+	static LdsOnce once;
+	constexpr int kVmLds = ((2 << kVmDirectLg) + 2 * (int)kVmDirectMaxLines) * 8;
+	NR3D_TRY(NR3D_LDS_LIMIT(once, c.dev, kVmLds, k_vm_direct<false, float>, k_vm_direct<true, float>, k_vm_direct<false, __half>,
+	                        k_vm_direct<true, __half>));
+	// (fp64 accumulators: fixed point pays in k_cp_direct, which is LDS bound -- 1.29 -> 0.98 ms on configs[3] -- but in
+	// k_vm_direct the bound scan and the conversions cost more than they save: slice-major 1.28 -> 1.48 ms, plane-major
+	// 5.13 -> 5.21 ms per pass)
+	{
+		prof::Scope ps(NR3D_PROF_LOTD_DIRECT, p.st);
+		with_bool(p.second, [&](auto S) { with_tables(p.params, p.p_half, [&](auto *tab) {
+			hipLaunchKernelGGL((k_vm_direct<S(), pointee_t<decltype(tab)>>), dim3(vp.R, vp.n_items), dim3(kVmDirectThreads), (size_t)vp.stride * 8, p.st, vp,
+			                   p.meta_dev, c.n, p.meta->interpolation_type, c.xc, c.vc, c.gc, c.sn, c.se, tab, c.partial);
+		}); });
+	}
+	hipLaunchKernelGGL(k_vm_direct_reduce, dim3(div_up(vp.stride, 256u), vp.n_items), dim3(256), 0, p.st, vp, p.meta_dev, c.partial, p.dparam);
+	NR3D_LAUNCH_CHECK();
+	return 0;
+}
+
+// the record classes of one chunk: only the (D, G, class) triples some level type can produce are instantiated
+static int class_route(const DparamPass &p, DparamChunk &c, const BinPlan &pl, uint32_t cls) {
+	const nr3d_lotd_meta_t *meta = p.meta;
+	const uint32_t D = meta->n_dims_to_encode, G = meta->n_feat_per_pseudo_lvl;
+	int rc = 0;
+	if (p.forest) {                                    // 3-D (binnable); one stage-A kernel per record class
+#define NR3D_FOREST_G(G_) do { if (cls == 8) rc = launch_class<3, G_, 8, true>(p, c, pl); else if (cls == 24) rc = launch_class<3, G_, 24, true>(p, c, pl); \
+	else if (cls == 48) rc = launch_class<3, G_, 48, true>(p, c, pl); } while (0)
+		if (G == 2) NR3D_FOREST_G(2); else if (G == 4) NR3D_FOREST_G(4);
+		else return ::nr3d::fail("LoTD forest bwd (binned): pseudo levels of 8 features run as their width-4 regrouping (stage_a_meta)");
+#undef NR3D_FOREST_G
+		return rc;
+	}
+	DISPATCH_DG_BIN(D, G, {
+		// hash-only metas (every level Dense or Hash) get kernels without the product-type code
+		if (meta->c_hash_only) {
+			if constexpr (D <= 3) rc = launch_class<D, G, 8, true>(p, c, pl);
+			else rc = launch_class<D, G, 16, true>(p, c, pl);
+		} else if (cls == 8) rc = launch_class<D, G, 8, false>(p, c, pl);
+		else if (cls == 16) {
+			if constexpr (D >= 3) rc = launch_class<D, G, 16, false>(p, c, pl);
+		} else if (cls == 24) {
+			if constexpr (D == 3) rc = launch_class<D, G, 24, false>(p, c, pl);
+		} else {
+			if constexpr (D == 4) rc = launch_class<D, G, 32, false>(p, c, pl);
+		}
+	});
+	return rc;
+}
+
+int dparam_binned(const DparamPass &pass, bool &handled) {
 	handled = false;
+	DparamPass p = pass;                               // + what this function settles: the stage-A meta, assign, fold
 	BinLayout lay;
-	const uint32_t nc = chunk_points(N);
+	const uint32_t N = p.N, nc = chunk_points(N);
+	const bool forest = p.forest != nullptr;
 	nr3d_lotd_meta_t narrow;
-	const bool narrowed = workspace && stage_a_meta(meta, forest != nullptr, narrow);
-	if (narrowed) meta = &narrow;
-	if (!workspace || !binnable(meta, forest != nullptr) || !layout(meta, nc, n_batches, lay, forest != nullptr)) return 0;
-	if (workspace_bytes < lay.total + (narrowed ? kStageAMetaBytes : 0)) return 0;
+	const bool narrowed = p.workspace && stage_a_meta(p.meta, forest, narrow);
+	if (narrowed) p.meta = &narrow;
+	const nr3d_lotd_meta_t *meta = p.meta;
+	if (!p.workspace || !binnable(meta, forest) || !layout(meta, nc, p.n_batches, lay, forest)) return 0;
+	if (p.workspace_bytes < lay.total + (narrowed ? kStageAMetaBytes : 0)) return 0;
 	handled = true;
+	char *ws = (char *)p.workspace;
 	if (narrowed) {
 		// the narrowed meta travels BY VALUE in a launch's kernel arguments (2.6 KB of the 4 KB a launch may carry) and one
 		// workgroup writes it to the end of the workspace: no host pointer outlives this call (round-5 advisor: an async copy
 		// from the stack-local `narrow` relied on the runtime staging pageable memory before returning, and a stream capture
 		// would have kept the dangling pointer)
-		k_store_meta<<<1, 256, 0, st>>>(narrow, (uint32_t *)((char *)workspace + lay.total));
+		k_store_meta<<<1, 256, 0, p.st>>>(narrow, (uint32_t *)(ws + lay.total));
 		NR3D_HIP_CHECK(hipGetLastError());
-		meta_dev = (char *)workspace + lay.total;
+		p.meta_dev = (const nr3d_lotd_meta_t *)(ws + lay.total);
 	}
-	const auto md = (const nr3d_lotd_meta_t *)meta_dev;
-	const uint32_t D = meta->n_dims_to_encode, G = meta->n_feat_per_pseudo_lvl, E = meta->n_encoded_dims;
-	uint32_t *rec = (uint32_t *)workspace;
-	uint32_t *offs = (uint32_t *)((char *)workspace + lay.rec_bytes);
-	uint32_t *plan_buf = (uint32_t *)((char *)workspace + lay.rec_bytes + lay.offs_bytes);
-	float *partial = (float *)((char *)workspace + lay.rec_bytes + lay.offs_bytes + lay.plan_bytes);
-	float *gt = (float *)((char *)workspace + lay.rec_bytes + lay.offs_bytes + lay.plan_bytes + lay.part_bytes);
-	const bool row_major = (g_se == 1 && g_sn == (int64_t)E && E > 1) || g_half;      // half gradients always go through gt
+	const uint32_t D = meta->n_dims_to_encode, E = meta->n_encoded_dims;
+	DparamChunk c;
+	c.rec = (uint32_t *)ws;
+	c.offs = (uint32_t *)(ws + lay.rec_bytes);
+	c.plan_buf = (uint32_t *)(ws + lay.rec_bytes + lay.offs_bytes);
+	c.partial = (float *)(ws + lay.rec_bytes + lay.offs_bytes + lay.plan_bytes);
+	c.gt = (float *)(ws + lay.rec_bytes + lay.offs_bytes + lay.plan_bytes + lay.part_bytes);
+	c.dev = -1;
+	const bool row_major = (p.g_se == 1 && p.g_sn == (int64_t)E && E > 1) || p.g_half;      // half gradients always go through gt
+	// one table set, every point in it: what the routes without records need
+	const bool plain = !forest && p.n_batches <= 1 && !p.batch.inds && !p.batch.offsets && !p.batch.data_size;
 	// an unbatched 3-D Dense/Hash meta with 2-feature pseudo levels: pair records (lotd_pair.hip), first and second order
-	const bool use_pair = !forest && n_batches <= 1 && !batch.inds && !batch.offsets && !batch.data_size && pair_applies(meta) &&
-	                      !(second && !pair_second_enabled());
-	if ((g_half || out_half) && !use_pair)
+	const bool use_pair = plain && pair_applies(meta) && !(p.second && !pair_second_enabled());
+	if ((p.g_half || p.out_half) && !use_pair)
 		return ::nr3d::fail("LoTD::bwd: half gradients are served natively on the pair-record path only (nr3d_lotd_half_params_ok)");
 	// uninitialised dparam: the pair path assigns when ONE pass covers every level; otherwise zero-fill and accumulate
-	const bool assign_now = assign && use_pair && N <= nc && min_level <= 0 && max_level >= (int32_t)meta->n_levels - 1;
-	if (assign && !assign_now)
-		NR3D_HIP_CHECK(hipMemsetAsync(dparam, 0, (size_t)(n_batches ? n_batches : 1u) * meta->n_params * (out_half ? 2 : 4), st));
+	p.assign = pass.assign && use_pair && N <= nc && p.min_level <= 0 && p.max_level >= (int32_t)meta->n_levels - 1;
+	if (pass.assign && !p.assign)
+		NR3D_HIP_CHECK(hipMemsetAsync(p.dparam, 0, (size_t)(p.n_batches ? p.n_batches : 1u) * meta->n_params * (p.out_half ? 2 : 4), p.st));
+	if (!(N <= nc && !p.second)) p.fold = nullptr;      // the folded route: one first-order pass
 
 	for (uint32_t p0 = 0; p0 < N; p0 += nc) {
-		const uint32_t n = (N - p0) < nc ? (N - p0) : nc;
-		const float *xc = x + (size_t)p0 * D;
-		const float *vc = dL_ddLdx ? dL_ddLdx + (size_t)p0 * D : nullptr;
-		const float *gc = g_half ? reinterpret_cast<const float *>(reinterpret_cast<const __half *>(dL_dy) + (int64_t)p0 * g_sn)
-		                         : dL_dy + (int64_t)p0 * g_sn;
-		int64_t sn = g_sn, se = g_se;
-		Batch ba = batch;                              // this chunk's view of the batch description
-		if (ba.inds) ba.inds += p0;
-		ba.first_point = p0;
-		// the feature-major copy of dL_dy, made when the first path that reads columns asks for it (round 6: a pass whose levels all go over
+		const uint32_t n = c.n = (N - p0) < nc ? (N - p0) : nc;
+		c.xc = p.x + (size_t)p0 * D;
+		c.vc = p.dL_ddLdx ? p.dL_ddLdx + (size_t)p0 * D : nullptr;
+		c.g_rows = p.g_half ? reinterpret_cast<const float *>(reinterpret_cast<const __half *>(p.dL_dy) + (int64_t)p0 * p.g_sn)
+		                    : p.dL_dy + (int64_t)p0 * p.g_sn;
+		c.gc = c.g_rows;
+		c.sn = p.g_sn; c.se = p.g_se;
+		c.ba = p.batch;
+		if (c.ba.inds) c.ba.inds += p0;
+		c.ba.first_point = p0;
+		// the feature-major copy of dL_dy, made when the first route that reads columns asks for it (round 6: a pass whose levels all go over
 		// sorted points -- the reference's forest workload -- never does: 0.13 ms)
 		bool gt_ready = !row_major;
 		auto need_gt = [&]() {
 			if (gt_ready) return;
-			if (g_half) launch_transpose<__half>(n, E, reinterpret_cast<const __half *>(gc), g_sn, g_se, gt, st);
-			else launch_transpose<float>(n, E, gc, g_sn, g_se, gt, st);
-			gc = gt; sn = 1; se = (int64_t)n;
+			if (p.g_half) launch_transpose<__half>(n, E, reinterpret_cast<const __half *>(c.g_rows), p.g_sn, p.g_se, c.gt, p.st);
+			else launch_transpose<float>(n, E, c.g_rows, p.g_sn, p.g_se, c.gt, p.st);
+			c.gc = c.gt; c.sn = 1; c.se = (int64_t)n;
 			gt_ready = true;
 		};
+		// the routes of a chunk, in this order; `served`: the pseudo levels the routes so far took
+		// 1. pair records: the whole chunk
 		if (use_pair) {
 			need_gt();
-			if (int rc = pair_chunk(meta, md, n, xc, gc, sn, se, min_level, max_level, kWorkUnits, dparam,
-			                        (out_half ? 1u : 0u) | (assign_now ? 2u : 0u), rec, offs, plan_buf, partial, st,
-			                        second ? vc : nullptr, (N <= nc && !second) ? fold : nullptr))
-				return rc;
+			NR3D_TRY(pair_chunk(p, c));
 			continue;
 		}
-		// CP levels whose table fits LDS skip the records (k_cp_direct): they run first, in the partial-table region the
-		// record classes use afterwards
-		uint64_t cp_mask = 0;
-		if (!forest && n_batches <= 1 && !batch.inds && !batch.offsets && !batch.data_size) {
+		uint64_t served = 0;
+		// 2. CP direct: they run first, in the partial-table region the record classes use afterwards
+		if (plain) {
 			CpPlan cp;
 			uint32_t max_acc = 0;
-			cp_mask = cp_plan(meta, n, min_level, max_level, lay.part_bytes / 4, cp, max_acc);
-			if (cp_mask) {
-				static bool cp_attr[64] = {};
-				int dev_id = 0;
-				NR3D_HIP_CHECK(hipGetDevice(&dev_id));
-				if (!cp_attr[dev_id & 63]) {
-					NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_cp_direct<false, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCpLdsBytes));
-					NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_cp_direct<true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCpLdsBytes));
-					NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_cp_direct<false, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCpLdsBytes));
-					NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_cp_direct<true, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCpLdsBytes));
-					cp_attr[dev_id & 63] = true;
-				}
+			if ((served = cp_plan(meta, n, p.min_level, p.max_level, lay.part_bytes / 4, cp, max_acc))) {
 				need_gt();
-				const size_t lds = (size_t)max_acc * 8;
-				auto cp_launch = [&](auto kern, auto *tab) {
-					hipLaunchKernelGGL(kern, dim3(cp.R, cp.n_items), dim3(kCpThreads), lds, st, cp, md, n, meta->interpolation_type, xc, vc,
-					                   gc, sn, se, tab, partial, opt::on(NR3D_OPT_DIRECT_FIXED) ? 1u : 0u);
-				};
-				if (p_half) {
-					if (second) cp_launch(k_cp_direct<true, __half>, (const __half *)params); else cp_launch(k_cp_direct<false, __half>, (const __half *)params);
-				} else {
-					if (second) cp_launch(k_cp_direct<true, float>, params); else cp_launch(k_cp_direct<false, float>, params);
-				}
-				hipLaunchKernelGGL(k_cp_reduce, dim3(div_up(max_acc, 256u), cp.n_items), dim3(256), 0, st, cp, md, partial, dparam);
-				NR3D_LAUNCH_CHECK();
+				NR3D_TRY(cp_direct_route(p, c, cp, max_acc));
 			}
 		}
-		// VM levels over sorted points (single tables, batches, forests): points sorted by (block, coordinate), bands accumulated in LDS, no
+		// 3. VM levels over sorted points (single tables, batches, forests): points sorted by (block, coordinate), bands accumulated in LDS, no
 		// records.  Asked BEFORE k_vm_direct since round 6: with unit records and fixed-point accumulators it beats k_vm_direct + records on
 		// configs[3] too (dL/dparam 4.90 -> 4.46 ms, d(dL/dx)/dparam 5.04 -> 4.71 at 2^22 points), so small tables take it from 2^21 points on
-		// (lotd_sorted.hip); its scratch is the record / offsets region, which the classes below use afterwards
-		if (!g_half) {
+		// (lotd_sorted.hip); its scratch is the record / offsets region, which the classes below use afterwards.  Reads the caller's rows: no gt
+		if (!p.g_half) {
 			VsPlan vsp;
-			const uint64_t smask = vm_sorted_plan(meta, n, n_batches, forest != nullptr, min_level, max_level, cp_mask, vsp);
+			const uint64_t smask = vm_sorted_plan(meta, n, p.n_batches, forest, p.min_level, p.max_level, served, vsp);
 			if (smask) {
 				VsScratch vss;
-				vm_sorted_scratch(vsp, n, E, second, forest != nullptr, vss);
+				vm_sorted_scratch(vsp, n, E, p.second, forest, vss);
 				if (vss.total <= lay.rec_bytes + lay.offs_bytes) {
-					if (int rc = vm_sorted_run(second, vsp, meta, md, n, xc, vc, dL_dy + (int64_t)p0 * g_sn, g_sn, g_se, params, p_half, ba, forest, dparam,
-					                           (char *)workspace, vss, st))
-						return rc;
-					cp_mask |= smask;
+					NR3D_TRY(vm_sorted_run(p, c, vsp, vss));
+					served |= smask;
 				}
 			}
 		}
-		// small VM levels skip the records altogether (k_vm_direct), like the CP levels above
-		if (!forest && n_batches <= 1 && !batch.inds && !batch.offsets && !batch.data_size) {
+		// 4. VM direct
+		if (plain) {
 			VmPlan vp;
-			const uint64_t vmask = vm_direct_plan(meta, n, min_level, max_level, lay.part_bytes / 4, vp, cp_mask);
+			const uint64_t vmask = vm_direct_plan(meta, n, p.min_level, p.max_level, lay.part_bytes / 4, vp, served);
 			if (vmask) {
-				static bool vattr[64] = {};
-				int dev_id = 0;
-				NR3D_HIP_CHECK(hipGetDevice(&dev_id));
-				constexpr int kVmLds = ((2 << kVmDirectLg) + 2 * (int)kVmDirectMaxLines) * 8;
-				if (!vattr[dev_id & 63]) {
-					NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_vm_direct<false, float>, hipFuncAttributeMaxDynamicSharedMemorySize, kVmLds));
-					NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_vm_direct<true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, kVmLds));
-					NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_vm_direct<false, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, kVmLds));
-					NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_vm_direct<true, __half>, hipFuncAttributeMaxDynamicSharedMemorySize, kVmLds));
-					vattr[dev_id & 63] = true;
-				}
 				need_gt();
-				auto vd_launch = [&](auto kern, auto *tab) {
-					hipLaunchKernelGGL(kern, dim3(vp.R, vp.n_items), dim3(kVmDirectThreads), (size_t)vp.stride * 8, st, vp, md, n, meta->interpolation_type, xc, vc,
-					                   gc, sn, se, tab, partial);
-				};
-				// (fp64 accumulators: fixed point pays in k_cp_direct, which is LDS bound -- 1.29 -> 0.98 ms on configs[3] -- but in
-				// k_vm_direct the bound scan and the conversions cost more than they save: slice-major 1.28 -> 1.48 ms, plane-major
-				// 5.13 -> 5.21 ms per pass)
-				{
-					prof::Scope ps(NR3D_PROF_LOTD_DIRECT, st);
-					if (p_half) {
-						if (second) vd_launch(k_vm_direct<true, __half>, (const __half *)params); else vd_launch(k_vm_direct<false, __half>, (const __half *)params);
-					} else {
-						if (second) vd_launch(k_vm_direct<true, float>, params); else vd_launch(k_vm_direct<false, float>, params);
-					}
-				}
-				hipLaunchKernelGGL(k_vm_direct_reduce, dim3(div_up(vp.stride, 256u), vp.n_items), dim3(256), 0, st, vp, md, partial, dparam);
-				NR3D_LAUNCH_CHECK();
-				cp_mask |= vmask;
+				NR3D_TRY(vm_direct_route(p, c, vp));
+				served |= vmask;
 			}
 		}
+		// 5. the record classes: whatever is left
 		for (uint32_t cls : kClasses) {
 			BinPlan pl;
 			uint64_t ow;
-			make_plan(meta, n, n_batches, cls, pl, ow, min_level, max_level, forest != nullptr, cp_mask);
+			make_plan(meta, n, p.n_batches, cls, PlanLevels{p.min_level, p.max_level, forest, served}, pl, ow);
 			if (pl.n_pseudo == 0) continue;
 			need_gt();
-			int rc = 0;
-			if (forest) {                                  // 3-D (binnable); one stage-A kernel per record class
-				const uint32_t G = meta->n_feat_per_pseudo_lvl;
-#define NR3D_FOREST_CLASS(G_, NR_) rc = launch_class<3, G_, NR_, true>(second, pl, meta, md, n, max_level, xc, vc, gc, sn, se, params, p_half, ba, rec, offs, plan_buf, partial, dparam, st, forest)
-#define NR3D_FOREST_G(G_) do { if (cls == 8) NR3D_FOREST_CLASS(G_, 8); else if (cls == 24) NR3D_FOREST_CLASS(G_, 24); \
-	else if (cls == 48) NR3D_FOREST_CLASS(G_, 48); } while (0)
-				if (G == 2) NR3D_FOREST_G(2); else if (G == 4) NR3D_FOREST_G(4);
-				else return ::nr3d::fail("LoTD forest bwd (binned): pseudo levels of 8 features run as their width-4 regrouping (stage_a_meta)");
-#undef NR3D_FOREST_G
-#undef NR3D_FOREST_CLASS
-				if (rc) return rc;
-				continue;
-			}
-			// only the (D, class) pairs some level type can produce are instantiated
-			DISPATCH_DG_BIN(D, G, {
-				// hash-only metas (every level Dense or Hash) get kernels without the product-type code
-				if (meta->c_hash_only) {
-					if constexpr (D <= 3) rc = launch_class<D, G, 8, true>(second, pl, meta, md, n, max_level, xc, vc, gc, sn, se, params, p_half, ba, rec, offs, plan_buf, partial, dparam, st, forest);
-					else rc = launch_class<D, G, 16, true>(second, pl, meta, md, n, max_level, xc, vc, gc, sn, se, params, p_half, ba, rec, offs, plan_buf, partial, dparam, st);
-				} else if (cls == 8) rc = launch_class<D, G, 8, false>(second, pl, meta, md, n, max_level, xc, vc, gc, sn, se, params, p_half, ba, rec, offs, plan_buf, partial, dparam, st);
-				else if (cls == 16) {
-					if constexpr (D >= 3) rc = launch_class<D, G, 16, false>(second, pl, meta, md, n, max_level, xc, vc, gc, sn, se, params, p_half, ba, rec, offs, plan_buf, partial, dparam, st);
-				} else if (cls == 24) {
-					if constexpr (D == 3) rc = launch_class<D, G, 24, false>(second, pl, meta, md, n, max_level, xc, vc, gc, sn, se, params, p_half, ba, rec, offs, plan_buf, partial, dparam, st);
-				} else {
-					if constexpr (D == 4) rc = launch_class<D, G, 32, false>(second, pl, meta, md, n, max_level, xc, vc, gc, sn, se, params, p_half, ba, rec, offs, plan_buf, partial, dparam, st);
-				}
-			});
-			if (rc) return rc;
+			NR3D_TRY(class_route(p, c, pl, cls));
 		}
 	}
 	return 0;

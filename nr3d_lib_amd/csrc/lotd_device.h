@@ -11,6 +11,7 @@
 // exactly like the reference's nvcc build.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 namespace nr3d {
 namespace lotd {
@@ -732,29 +733,79 @@ __device__ __forceinline__ void locate_forest(const float (&xp)[3], const Lvl &L
 // lotd_bin.hip: atomic-free parameter-gradient path (all level types but NPlaneSum/CPfast, no batching)
 uint64_t dparam_workspace_bytes(const nr3d_lotd_meta_t *m, uint32_t n_points, uint32_t n_batches, bool forest = false);
 void set_dparam_chunk_log2(int lg);
-// `forest` != NULL: the points live in the blocks of a forest (n_batches = n_trees); Dense/Hash 3-D metas only
-// levels below `min_level` are left out (their part of dparam is not touched)
-int dparam_binned(bool second, const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, const float *dL_ddLdx,
-                  const float *dL_dy, int64_t g_sn, int64_t g_se, const float *x, const float *params, const Batch &batch,
-                  uint32_t n_batches, int32_t max_level, float *dparam, void *workspace, uint64_t workspace_bytes,
-                  hipStream_t st, bool &handled, const ForestDev *forest = nullptr, int32_t min_level = 0, bool g_half = false,
-                  bool out_half = false, bool assign = false, bool p_half = false, uint32_t *fold = nullptr);
+// one dL/dparam pass: plain_pass() below, then by name what the call has beyond it (the struct itself has no defaults)
+struct DparamPass {
+	bool second;                        // d(dL/dx)/dparam for dL_ddLdx instead of dL/dparam
+	const nr3d_lotd_meta_t *meta, *meta_dev;
+	uint32_t N;
+	const float *dL_ddLdx;              // second order: [N, D]; NULL otherwise
+	const float *dL_dy;                 // [N, E] with strides (g_sn, g_se)
+	int64_t g_sn, g_se;
+	bool g_half;                        // dL_dy is __half (pair path only)
+	const float *x;
+	const void *params;
+	bool p_half;                        // `params` points to __half tables (the product-type levels read their other factors from them)
+	Batch batch;
+	uint32_t n_batches;
+	int32_t min_level, max_level;       // levels below `min_level` are left out (their part of dparam is not touched)
+	float *dparam;
+	bool out_half;                      // dparam is __half (pair path only)
+	bool assign;                        // dparam arrives UNINITIALISED -- the pair path writes every element when one pass covers all
+	                                    // levels, every other case zero-fills it first
+	void *workspace;
+	uint64_t workspace_bytes;
+	hipStream_t st;
+	const ForestDev *forest;            // != NULL: the points live in the blocks of a forest (n_batches = n_trees); 3-D metas only
+	uint32_t *fold;                     // hand-over buffer of the folded route (pair_fold_layout), filled by the dL/dx kernel; or NULL
+};
+// what dparam_binned derives for one chunk of the pass's points; the routes of a chunk run on it one after the other
+struct DparamChunk {
+	uint32_t n;
+	const float *xc, *vc;               // the chunk's rows of x and dL_ddLdx
+	const float *g_rows;                // the chunk's rows of the caller's dL_dy (strides p.g_sn, p.g_se; read as __half when p.g_half)
+	const float *gc;                    // dL_dy as the column readers take it, strides (sn, se): g_rows, or `gt` once a route asked for columns
+	int64_t sn, se;
+	Batch ba;                           // this chunk's view of the batch description
+	uint32_t *rec, *offs, *plan_buf;    // the workspace's regions (lotd_bin.hip: layout)
+	float *partial, *gt;
+	int dev;                            // the current device id once a route asked for it (lds_limit), -1 before
+};
+
+// run-time order / storage type -> the kernel instantiation: f(std::true_type or std::false_type), f(the tables as const float * or
+// const __half *); pointee_t names the storage type inside f.  Only where every combination is instantiated anyway.
+template <typename F> static inline void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <typename F> static inline void with_tables(const void *params, bool p_half, F &&f) {
+	if (p_half) f((const __half *)params); else f((const float *)params);
+}
+template <typename P> using pointee_t = std::remove_const_t<std::remove_pointer_t<P>>;
+
+// the pass of a float dL/dparam call on one table set: first order, every level, dparam accumulated into, no batch, no forest,
+// no hand-over buffer, no workspace, the null stream.  A caller then states by name what its call has beyond that.
+static inline DparamPass plain_pass(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, const void *dL_dy, int64_t g_sn,
+                                    int64_t g_se, const void *x, void *dparam) {
+	DparamPass p;
+	p.second = false; p.meta = meta; p.meta_dev = (const nr3d_lotd_meta_t *)meta_dev; p.N = N;
+	p.dL_ddLdx = nullptr; p.dL_dy = (const float *)dL_dy; p.g_sn = g_sn; p.g_se = g_se; p.g_half = false;
+	p.x = (const float *)x; p.params = nullptr; p.p_half = false;
+	p.batch = Batch{nullptr, nullptr, 0u, meta->n_params}; p.n_batches = 1u;
+	p.min_level = 0; p.max_level = 0x7fffffff;
+	p.dparam = (float *)dparam; p.out_half = false; p.assign = false;
+	p.workspace = nullptr; p.workspace_bytes = 0; p.st = nullptr;
+	p.forest = nullptr; p.fold = nullptr;
+	return p;
+}
+
+// `handled` false: the binned path does not apply (the caller's atomic kernels run)
+int dparam_binned(const DparamPass &pass, bool &handled);
 bool dparam_one_pass(uint32_t n_points);     // the pass covers all n_points (one chunk)
-// p_half: `params` points to __half tables (the product-type levels read their other factors from them)
-// g_half: dL_dy is __half; out_half: dparam is __half (pair path only); assign: dparam arrives UNINITIALISED -- the pair
-// path writes every element when one pass covers all levels, every other case zero-fills it first
 
 // lotd_pair.hip: pair-record form of the same path for unbatched 3-D Dense/Hash metas with 2-feature pseudo levels
 bool pair_applies(const nr3d_lotd_meta_t *m);
 uint32_t pair_direct_levels(const nr3d_lotd_meta_t *m, uint32_t n_points);   // pseudo levels k_pair_direct serves (no records)
-void pair_layout(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t units, uint64_t &rec_bytes, uint64_t &offs_bytes,
-                 uint64_t &plan_bytes, uint64_t &part_bytes);
-int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_t n, const float *x, const float *g,
-               int64_t g_sn, int64_t g_se, int32_t min_level, int32_t max_level, uint32_t units, float *dparam,
-               uint32_t out_flags /* bit 0: dparam is __half; bit 1: assign (dparam uninitialised, every element of the
-               plan's levels is written) */, void *rec, uint32_t *offs, uint32_t *plan_buf, float *partial, hipStream_t st,
-               const float *vin = nullptr /* second order: dL_ddLdx [n, 3] */,
-               uint32_t *fold = nullptr /* hand-over buffer of the folded route (pair_fold_layout), filled by the dL/dx kernel */);
+void pair_layout(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint64_t &rec_bytes, uint64_t &offs_bytes, uint64_t &plan_bytes,
+                 uint64_t &part_bytes);
+// one chunk over pair records; p.assign: as settled for this pass, p.fold: NULL unless the folded route may run
+int pair_chunk(const DparamPass &p, DparamChunk &c);
 uint64_t pair_fold_layout(const nr3d_lotd_meta_t *m, uint32_t n, int32_t max_level, uint32_t &gcols, uint32_t &zero_words,
                           uint32_t &slot_off);
 

@@ -309,8 +309,9 @@ extern "C" int nr3d_lotd_forest_fwd(const nr3d_lotd_meta_t *meta, const void *me
 			hipLaunchKernelGGL(kern, grid, dim3(kBlock), 0, (hipStream_t)stream, md, dev_of(forest), N, max_level,
 			                   meta->interpolation_type, x, tab, ba, pair_ok, y, y_sn, y_se, dy_dx, d_sn, d_se);
 		};
-		if (p_half) { if (dy_dx) launch(k_forest_fwd<G, true, __half>, (const __half *)params); else launch(k_forest_fwd<G, false, __half>, (const __half *)params); }
-		else        { if (dy_dx) launch(k_forest_fwd<G, true, float>, (const float *)params); else launch(k_forest_fwd<G, false, float>, (const float *)params); }
+		with_tables(params, p_half, [&](auto *tab) { with_bool(dy_dx != nullptr, [&](auto DY) {
+			launch(k_forest_fwd<G, DY(), pointee_t<decltype(tab)>>, tab);
+		}); });
 	});
 	NR3D_LAUNCH_CHECK();
 	return 0;
@@ -335,10 +336,14 @@ extern "C" int nr3d_lotd_forest_bwd_dparam(const nr3d_lotd_meta_t *meta, const v
 	if (workspace) {
 		const ForestDev fo = dev_of(forest);
 		bool handled = false;
-		const int64_t E = meta->n_encoded_dims;
-		if (int rc = dparam_binned(dL_ddLdx != nullptr, meta, meta_dev, N, dL_ddLdx, dL_dy, E, 1, x, (const float *)params, ba,
-		                           forest->n_trees, max_level, dL_dparam, workspace, workspace_bytes, (hipStream_t)stream, handled, &fo,
-		                           0, false, false, false, p_half)) return rc;
+		DparamPass p = plain_pass(meta, meta_dev, N, dL_dy, meta->n_encoded_dims, 1, x, dL_dparam);
+		p.second = dL_ddLdx != nullptr; p.dL_ddLdx = dL_ddLdx;
+		p.params = params; p.p_half = p_half;
+		p.batch = ba; p.n_batches = forest->n_trees;
+		p.max_level = max_level;
+		p.workspace = workspace; p.workspace_bytes = workspace_bytes; p.st = (hipStream_t)stream;
+		p.forest = &fo;
+		NR3D_TRY(dparam_binned(p, handled));
 		if (handled) return 0;
 	}
 	const dim3 grid(div_up(N, kBlock), meta->n_pseudo_levels);
@@ -347,8 +352,9 @@ extern "C" int nr3d_lotd_forest_bwd_dparam(const nr3d_lotd_meta_t *meta, const v
 			hipLaunchKernelGGL(kern, grid, dim3(kBlock), 0, (hipStream_t)stream, md, dev_of(forest), N, meta->n_encoded_dims, max_level,
 			                   meta->interpolation_type, dL_ddLdx, dL_dy, x, tab, ba, dL_dparam);
 		};
-		if (p_half) { if (dL_ddLdx) launch(k_forest_bwd_dparam<G, true, __half>, (const __half *)params); else launch(k_forest_bwd_dparam<G, false, __half>, (const __half *)params); }
-		else        { if (dL_ddLdx) launch(k_forest_bwd_dparam<G, true, float>, (const float *)params); else launch(k_forest_bwd_dparam<G, false, float>, (const float *)params); }
+		with_tables(params, p_half, [&](auto *tab) { with_bool(dL_ddLdx != nullptr, [&](auto S) {
+			launch(k_forest_bwd_dparam<G, S(), pointee_t<decltype(tab)>>, tab);
+		}); });
 	});
 	NR3D_LAUNCH_CHECK();
 	return 0;

@@ -1164,8 +1164,8 @@ uint32_t pair_direct_levels(const nr3d_lotd_meta_t *m, uint32_t n_points) {
 }
 
 // workspace needs of the pair path for a chunk of n_chunk points (regions as in lotd_bin.hip's layout)
-void pair_layout(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t units, uint64_t &rec_bytes, uint64_t &offs_bytes,
-                 uint64_t &plan_bytes, uint64_t &part_bytes) {
+void pair_layout(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint64_t &rec_bytes, uint64_t &offs_bytes, uint64_t &plan_bytes,
+                 uint64_t &part_bytes) {
 	PairPlan plan;
 	uint64_t ow;
 	pair_plan(m, n_chunk, 0, 0x7fffffff, plan, ow);
@@ -1173,7 +1173,7 @@ void pair_layout(const nr3d_lotd_meta_t *m, uint32_t n_chunk, uint32_t units, ui
 	rec_bytes = (uint64_t)plan.n_pseudo * plan.n_blk * plan.cap * 16;
 	offs_bytes = ((ow * 4 + 255) / 256) * 256;
 	plan_bytes = (((uint64_t)NB * 3 + 4) * 4 + 255) / 256 * 256;
-	part_bytes = (uint64_t)(kPairUnits + NB + kDirectMaxWg) * (2u << plan.lg) * 4;   // the pair path's own item count, not `units`; + k_pair_direct
+	part_bytes = (uint64_t)(kPairUnits + NB + kDirectMaxWg) * (2u << plan.lg) * 4;   // stage B's items + k_pair_direct
 }
 
 void launch_plan_items(uint32_t NB, uint32_t n_blk, uint32_t units, const uint32_t *tot, uint32_t *rep, uint32_t *item_start,
@@ -1205,10 +1205,18 @@ uint64_t pair_fold_layout(const nr3d_lotd_meta_t *m, uint32_t n, int32_t max_lev
 	return (uint64_t)(slot_off + div_up(n, (uint32_t)kBlock)) * 4u;
 }
 
-// one chunk of points: dL_dy given feature-major or with any strides (g_sn, g_se)
-int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_t n, const float *x, const float *g,
-               int64_t g_sn, int64_t g_se, int32_t min_level, int32_t max_level, uint32_t units, float *dparam, uint32_t out_flags,
-               void *rec, uint32_t *offs, uint32_t *plan_buf, float *partial, hipStream_t st, const float *vin, uint32_t *fold) {
+// one chunk of points: dL_dy given feature-major or with any strides (c.sn, c.se)
+int pair_chunk(const DparamPass &p, DparamChunk &c) {
+	const nr3d_lotd_meta_t *meta = p.meta, *md = p.meta_dev;
+	const uint32_t n = c.n, units = kPairUnits;
+	// what the kernels take: bit 0: dparam is __half; bit 1: assign (dparam uninitialised, every element of the plan's levels is written)
+	const uint32_t out_flags = (p.out_half ? 1u : 0u) | (p.assign ? 2u : 0u);
+	const int32_t min_level = p.min_level, max_level = p.max_level;
+	const float *x = c.xc, *g = c.gc, *vin = p.second ? c.vc : nullptr;
+	const int64_t g_sn = c.sn, g_se = c.se;
+	uint32_t *offs = c.offs, *plan_buf = c.plan_buf, *fold = p.fold;
+	float *dparam = p.dparam, *partial = c.partial;
+	hipStream_t st = p.st;
 	// vin != NULL: second order (d(dL/dx)/dparam for dL_ddLdx = vin, [n, 3]); fold != NULL: the folded route (pair_fold_layout)
 	uint32_t f_gcols = 0, f_zero = 0, f_slot = 0;
 	if (fold && (vin || min_level > 0 || pair_fold_layout(meta, n, max_level, f_gcols, f_zero, f_slot) == 0)) fold = nullptr;
@@ -1233,29 +1241,18 @@ int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_
 	// gmax | plan ticket: two spare words of the plan region, or the hand-over buffer's head (zeroed by the dL/dx kernel)
 	uint32_t *gmax = fold ? fold : plan_buf + 3 * (size_t)NB + 2;
 	uint32_t *bticket = fold ? fold + kFoldHead : nullptr;
-	units = kPairUnits;
 	const size_t bin_lds_max = (size_t)kPairBp * 4 * 16 + (size_t)(kPMaxNb + 2) * 8;
-	static bool attr_set_dev[64] = {};
-	int dev_id = 0;
-	NR3D_HIP_CHECK(hipGetDevice(&dev_id));
-	if (!attr_set_dev[dev_id & 63]) {
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_bin<kPairBp>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds_max));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_bin<kPairBp, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds_max));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_direct<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_direct<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_direct<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_direct<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_accum<kPairUnroll, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_pair_accum<kPairUnroll, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax * 8));
-		attr_set_dev[dev_id & 63] = true;
-	}
+	static LdsOnce once_bin, once_acc;
+	NR3D_TRY(NR3D_LDS_LIMIT(once_bin, c.dev, (int)bin_lds_max, k_pair_bin<kPairBp>, k_pair_bin<kPairBp, true>));
+	NR3D_TRY(NR3D_LDS_LIMIT(once_acc, c.dev, kPLdsMax * 8, k_pair_direct<true>, k_pair_direct<false>, k_pair_direct<true, true>,
+	                        k_pair_direct<false, true>, k_pair_accum<kPairUnroll, false>, k_pair_accum<kPairUnroll, true>));
 	if (!fold) NR3D_HIP_CHECK(hipMemsetAsync(gmax, 0, 2 * sizeof(uint32_t), st));      // gmax | ticket of k_pair_plan
 	const size_t bin_lds = (size_t)kPairBp * 4 * 16 + (size_t)(nb_max + 1) * 4;     // stage | hist
 	// first order: the Dense levels' records in quad form (NR3D_PAIR_QUAD=0: pair records only)
 	const uint32_t quad_on = (!vin && pair_quad_enabled()) ? 1u : 0u;
 #define NR3D_PAIR_BIN(BP) if (vin) NR3D_PAIR_BIN_(BP, true); else NR3D_PAIR_BIN_(BP, false)
 #define NR3D_PAIR_BIN_(BP, SEC) hipLaunchKernelGGL((k_pair_bin<BP, SEC>), dim3(pl.n_blk, pl.n_pseudo), dim3(BP), bin_lds, st, pl, md, n, max_level, \
-	meta->interpolation_type, x, g, g_sn, g_se, (u32x4 *)rec, offs, fold ? nullptr : gmax, dp, vin, quad_on)
+	meta->interpolation_type, x, g, g_sn, g_se, (u32x4 *)c.rec, offs, fold ? nullptr : gmax, dp, vin, quad_on)
 	{
 		prof::Scope ps(NR3D_PROF_LOTD_BIN, st);
 		NR3D_PAIR_BIN(kPairBp);
@@ -1293,7 +1290,7 @@ int pair_chunk(const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_
 	// folded: stage B also sums the direct buckets (n_dred rows of kPAccThreads accumulators, in front) and its split buckets
 	const uint32_t n_dred = fold ? nbk_direct * ((2u << pl.lg) / kPAccThreads) : 0u;
 #define NR3D_PAIR_ACC(U, F) hipLaunchKernelGGL((k_pair_accum<U, F>), dim3(n_dred + units + NB), dim3(kPAccThreads), (size_t)(16u << pl.lg), st, pl, md, \
-	(const u32x4 *)rec, offs, rep, item_start, gmax, partial, dparam, out_flags, bticket, n_dred, dp, dpart)
+	(const u32x4 *)c.rec, offs, rep, item_start, gmax, partial, dparam, out_flags, bticket, n_dred, dp, dpart)
 	{
 		prof::Scope ps(NR3D_PROF_LOTD_ACCUM, st);
 		if (pair_fixed()) NR3D_PAIR_ACC(kPairUnroll, true); else NR3D_PAIR_ACC(kPairUnroll, false);

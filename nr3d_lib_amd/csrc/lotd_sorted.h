@@ -28,9 +28,7 @@ struct VsScratch { uint64_t stats, multi_list, plan, key_in[2], key_out[2], keyb
 uint64_t vm_sorted_plan(const nr3d_lotd_meta_t *m, uint32_t n, uint32_t n_blocks, bool forest, int32_t min_level, int32_t max_level,
                         uint64_t skip, VsPlan &vp);
 void vm_sorted_scratch(const VsPlan &vp, uint32_t n, uint32_t E, bool second, bool forest, VsScratch &s);
-int vm_sorted_run(bool second, const VsPlan &vp, const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_t n, const float *x,
-                  const float *vin, const float *g, int64_t g_sn, int64_t g_se, const void *params, bool p_half, const Batch &ba,
-                  const ForestDev *forest, float *dparam, char *scratch, const VsScratch &s, hipStream_t st);
+int vm_sorted_run(const DparamPass &p, DparamChunk &c, const VsPlan &vp, const VsScratch &s);
 
 }  // namespace lotd
 }  // namespace nr3d

@@ -1121,11 +1121,15 @@ void vm_sorted_scratch(const VsPlan &vp, uint32_t n, uint32_t E, bool second, bo
 }
 
 // runs the plan on `st`; scratch = the record / offsets regions of the workspace (the record classes run afterwards)
-int vm_sorted_run(bool second, const VsPlan &vp, const nr3d_lotd_meta_t *meta, const nr3d_lotd_meta_t *md, uint32_t n, const float *x,
-                         const float *vin, const float *g, int64_t g_sn, int64_t g_se, const void *params, bool p_half, const Batch &ba,
-                         const ForestDev *forest, float *dparam, char *scratch, const VsScratch &s, hipStream_t st) {
-	const uint32_t E = meta->n_encoded_dims;
-	const bool FO = forest != nullptr;
+int vm_sorted_run(const DparamPass &p, DparamChunk &c, const VsPlan &vp, const VsScratch &s) {
+	const nr3d_lotd_meta_t *meta = p.meta, *md = p.meta_dev;
+	const uint32_t n = c.n, E = meta->n_encoded_dims;
+	const float *x = c.xc, *vin = c.vc, *g = c.g_rows;      // the caller's rows, never the feature-major copy
+	const int64_t g_sn = p.g_sn, g_se = p.g_se;
+	const bool second = p.second, FO = p.forest != nullptr;
+	const Batch &ba = c.ba;
+	char *scratch = (char *)c.rec;
+	hipStream_t st = p.st;
 	uint32_t *key_in[2] = {(uint32_t *)(scratch + s.key_in[0]), (uint32_t *)(scratch + s.key_in[1])};
 	uint32_t *key_out[2] = {(uint32_t *)(scratch + s.key_out[0]), (uint32_t *)(scratch + s.key_out[1])};
 	uint32_t *perm[2] = {(uint32_t *)(scratch + s.perm[0]), (uint32_t *)(scratch + s.perm[1])};
@@ -1165,7 +1169,7 @@ int vm_sorted_run(bool second, const VsPlan &vp, const nr3d_lotd_meta_t *meta, c
 	for (int o = 0; o < 2; ++o) {
 		dv.permb[o] = permb[o]; dv.xm[o] = (const float *)(scratch + s.xm[o]);
 		dv.cinfo[o] = (const VsCand *)(scratch + s.cinfo[o]);
-		if (FO) hipLaunchKernelGGL(k_vs_cands, dim3(div_up(n, 256)), dim3(256), 0, st, n_cand, permb[o], x, ba, *forest, (float *)(scratch + s.xm[o]),
+		if (FO) hipLaunchKernelGGL(k_vs_cands, dim3(div_up(n, 256)), dim3(256), 0, st, n_cand, permb[o], x, ba, *p.forest, (float *)(scratch + s.xm[o]),
 		                           (VsCand *)(scratch + s.cinfo[o]));
 	}
 	uint32_t *stats = (uint32_t *)(scratch + s.stats);
@@ -1188,42 +1192,30 @@ int vm_sorted_run(bool second, const VsPlan &vp, const nr3d_lotd_meta_t *meta, c
 	if (FO) hipLaunchKernelGGL(k_vs_plan<true>, dim3(div_up(plan_threads, 256)), dim3(256), 0, st, vpd, dv, md, n, ba);
 	else hipLaunchKernelGGL(k_vs_plan<false>, dim3(div_up(plan_threads, 256)), dim3(256), 0, st, vpd, dv, md, n, ba);
 	hipLaunchKernelGGL(k_vs_scan, dim3(1), dim3(1024), 0, st, vp.n_items, dv);
-	const ForestDev fo = forest ? *forest : ForestDev{};
+	const ForestDev fo = p.forest ? *p.forest : ForestDev{};
 	dv.units = (const VsUnit *)(scratch + s.units);
 	const uint32_t opt_fix = opt::get(NR3D_OPT_DIRECT_FIXED) != 0 ? 1u : 0u;      // (k_cp_direct's switch: 0 keeps fp64 accumulators everywhere)
 	uint32_t *item_tmax = opt_fix ? (uint32_t *)(scratch + s.item_tmax) : nullptr;
-	if (opt_fix) {
-		if (p_half) { if (FO) hipLaunchKernelGGL((k_vs_tmax<__half, true>), dim3(vp.n_items), dim3(256), 0, st, vpd, dv, md, (const __half *)params, ba, item_tmax);
-		              else hipLaunchKernelGGL((k_vs_tmax<__half, false>), dim3(vp.n_items), dim3(256), 0, st, vpd, dv, md, (const __half *)params, ba, item_tmax); }
-		else { if (FO) hipLaunchKernelGGL((k_vs_tmax<float, true>), dim3(vp.n_items), dim3(256), 0, st, vpd, dv, md, (const float *)params, ba, item_tmax);
-		       else hipLaunchKernelGGL((k_vs_tmax<float, false>), dim3(vp.n_items), dim3(256), 0, st, vpd, dv, md, (const float *)params, ba, item_tmax); }
-	}
+	if (opt_fix)
+		with_tables(p.params, p.p_half, [&](auto *tab) { with_bool(FO, [&](auto F) {
+			hipLaunchKernelGGL((k_vs_tmax<pointee_t<decltype(tab)>, F()>), dim3(vp.n_items), dim3(256), 0, st, vpd, dv, md, tab, ba, item_tmax);
+		}); });
 	if (FO) hipLaunchKernelGGL(k_vs_units<true>, dim3(div_up(vp.w_max, 256)), dim3(256), 0, st, vpd, dv, md, ba, fo, item_tmax, (VsUnit *)(scratch + s.units));
 	else hipLaunchKernelGGL(k_vs_units<false>, dim3(div_up(vp.w_max, 256)), dim3(256), 0, st, vpd, dv, md, ba, fo, item_tmax, (VsUnit *)(scratch + s.units));
 	NR3D_LAUNCH_CHECK();
-	static bool attr[64] = {};
-	int dev_id = 0;
-	NR3D_HIP_CHECK(hipGetDevice(&dev_id));
-	if (!attr[dev_id & 63]) {
-#define NR3D_VS_ATTR(S_, P_, F_) NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_vm_sorted<S_, P_, F_>, hipFuncAttributeMaxDynamicSharedMemorySize, kVsLds))
-		NR3D_VS_ATTR(false, float, false); NR3D_VS_ATTR(true, float, false); NR3D_VS_ATTR(false, __half, false); NR3D_VS_ATTR(true, __half, false);
-		NR3D_VS_ATTR(false, float, true); NR3D_VS_ATTR(true, float, true); NR3D_VS_ATTR(false, __half, true); NR3D_VS_ATTR(true, __half, true);
-#undef NR3D_VS_ATTR
-		attr[dev_id & 63] = true;
-	}
-	auto launch = [&](auto kern, auto *tab) {
-		hipLaunchKernelGGL(kern, dim3(vp.w_max), dim3(kVsThreads), (size_t)kVsLds, st, vpd, vp.rb_max, vp.rd_max, dv, n, meta->interpolation_type, x, vin, g, g_sn, g_se,
-		                   tab, ba, fo, dparam, opt_fix);
-	};
+	static LdsOnce once;
+#define NR3D_VS_ALL(F_) k_vm_sorted<false, float, F_>, k_vm_sorted<true, float, F_>, k_vm_sorted<false, __half, F_>, k_vm_sorted<true, __half, F_>
+	NR3D_TRY(NR3D_LDS_LIMIT(once, c.dev, kVsLds, NR3D_VS_ALL(false), NR3D_VS_ALL(true)));
+#undef NR3D_VS_ALL
 	{
 		prof::Scope ps(NR3D_PROF_LOTD_DIRECT, st);
-#define NR3D_VS_GO(F_) do { if (p_half) { if (second) launch(k_vm_sorted<true, __half, F_>, (const __half *)params); else launch(k_vm_sorted<false, __half, F_>, (const __half *)params); } \
-	else { if (second) launch(k_vm_sorted<true, float, F_>, (const float *)params); else launch(k_vm_sorted<false, float, F_>, (const float *)params); } } while (0)
-		if (FO) NR3D_VS_GO(true); else NR3D_VS_GO(false);
-#undef NR3D_VS_GO
+		with_bool(FO, [&](auto F) { with_bool(second, [&](auto S) { with_tables(p.params, p.p_half, [&](auto *tab) {
+			hipLaunchKernelGGL((k_vm_sorted<S(), pointee_t<decltype(tab)>, F()>), dim3(vp.w_max), dim3(kVsThreads), (size_t)kVsLds, st, vpd, vp.rb_max, vp.rd_max,
+			                   dv, n, meta->interpolation_type, x, vin, g, g_sn, g_se, tab, ba, fo, p.dparam, opt_fix);
+		}); }); });
 	}
-	hipLaunchKernelGGL(k_vs_reduce_items, dim3(vp.n_items + (vp.m_slots / 2u) * kVsRedChunks), dim3(256), 0, st, vpd, dv, md, ba, dparam);
-	hipLaunchKernelGGL(k_vs_reduce_lines, dim3(vp.n_groups * div_up(2u * vp.rd_max, 64u)), dim3(1024), 0, st, vpd, dv, md, ba, dparam);
+	hipLaunchKernelGGL(k_vs_reduce_items, dim3(vp.n_items + (vp.m_slots / 2u) * kVsRedChunks), dim3(256), 0, st, vpd, dv, md, ba, p.dparam);
+	hipLaunchKernelGGL(k_vs_reduce_lines, dim3(vp.n_groups * div_up(2u * vp.rd_max, 64u)), dim3(1024), 0, st, vpd, dv, md, ba, p.dparam);
 	NR3D_LAUNCH_CHECK();
 	return 0;
 }

@@ -882,27 +882,13 @@ extern "C" int nr3d_mlp_forward(const nr3d_mlp_desc_t *desc, uint64_t n, const f
 	const uint32_t grid = (uint32_t)(n_tiles / 4 + 1 < 1024 ? n_tiles / 4 + 1 : 1024);
 	int rc = 0;
 	MLP_DISPATCH(s, {
-		static bool attr[64] = {};
-		int dev = 0;
-		if (hipGetDevice(&dev) != hipSuccess) { rc = ::nr3d::fail("mlp_forward: hipGetDevice failed"); return; }
-		if (!attr[dev & 63]) {
-			if (hipFuncSetAttribute((const void *)k_mlp_fwd<IN_T, W_T, OUT_T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess ||
-			    hipFuncSetAttribute((const void *)k_mlp_fwd<IN_T, W_T, OUT_T, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess ||
-			    hipFuncSetAttribute((const void *)k_mlp_fwd<IN_T, W_T, OUT_T, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess) {
-				rc = ::nr3d::fail("mlp_forward: cannot raise the dynamic LDS limit"); return;
-			}
-			attr[dev & 63] = true;
-		}
+		static LdsOnce once;
+		int dev = -1;
+		if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlp_fwd<IN_T, W_T, OUT_T, 0>, k_mlp_fwd<IN_T, W_T, OUT_T, 1>, k_mlp_fwd<IN_T, W_T, OUT_T, 2>))) return;
 		if (x3) {
-			static bool attr3[64] = {};
-			if (!attr3[dev & 63]) {
-				if (hipFuncSetAttribute((const void *)k_mlp_fwd<IN_T, W_T, OUT_T, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess ||
-				    hipFuncSetAttribute((const void *)k_mlp_fwd<IN_T, W_T, OUT_T, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess ||
-				    hipFuncSetAttribute((const void *)k_mlp_fwd<IN_T, W_T, OUT_T, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess) {
-					rc = ::nr3d::fail("mlp_forward: cannot raise the dynamic LDS limit"); return;
-				}
-				attr3[dev & 63] = true;
-			}
+			static LdsOnce once3;
+			if ((rc = NR3D_LDS_LIMIT(once3, dev, kMaxLds, k_mlp_fwd<IN_T, W_T, OUT_T, 0, true>, k_mlp_fwd<IN_T, W_T, OUT_T, 1, true>,
+			                         k_mlp_fwd<IN_T, W_T, OUT_T, 2, true>))) return;
 			if (x_fm)
 				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 2, true>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 			else if (a.x_vec && a.in_dim % 4 == 0)
@@ -961,7 +947,7 @@ extern "C" int nr3d_mlp_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const 
 	const bool gy_fast = a.gy_vec && desc->dims[desc->n_layers] % 4 == 0;
 	const int fast = !gy_fast ? 0 : x_fm ? 2 : (a.x_vec && desc->dims[0] % 4 == 0) ? 1 : 0;
 	auto launch = [&](auto kern) -> int {
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBwd));
+		NR3D_TRY(NR3D_LDS_LIMIT_ALWAYS(kMaxLdsBwd, kern));
 		hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, (hipStream_t)stream, a);
 		return 0;
 	};
@@ -1024,7 +1010,7 @@ extern "C" int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t 
 	const uint32_t grid = (uint32_t)(n_tiles / nw + 1 < 256 ? n_tiles / nw + 1 : 256);     // one workgroup per CU: dW lives in registers
 	const uint32_t nh = desc->n_layers - 1;
 	auto launch = [&](auto kern) -> int {
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBwd));
+		NR3D_TRY(NR3D_LDS_LIMIT_ALWAYS(kMaxLdsBwd, kern));
 		hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, (hipStream_t)stream, a);
 		return 0;
 	};

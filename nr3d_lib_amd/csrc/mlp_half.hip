@@ -999,17 +999,9 @@ extern "C" int nr3d_mlp_half_forward(const nr3d_mlp_desc_t *desc, uint64_t n, co
 	const uint32_t grid = (uint32_t)(n_tiles / 4 + 1 < 2048 ? n_tiles / 4 + 1 : 2048);
 	int rc = 0;
 	MLPH_DISPATCH(s, {
-		static bool attr[64] = {};
-		int dev = 0;
-		if (hipGetDevice(&dev) != hipSuccess) { rc = ::nr3d::fail("mlp_half_forward: hipGetDevice failed"); return; }
-		if (!attr[dev & 63]) {
-			if (hipFuncSetAttribute((const void *)k_mlph_fwd<IN_T, W_T, OUT_T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess ||
-			    hipFuncSetAttribute((const void *)k_mlph_fwd<IN_T, W_T, OUT_T, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess ||
-			    hipFuncSetAttribute((const void *)k_mlph_fwd<IN_T, W_T, OUT_T, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess) {
-				rc = ::nr3d::fail("mlp_half_forward: cannot raise the dynamic LDS limit"); return;
-			}
-			attr[dev & 63] = true;
-		}
+		static LdsOnce once;
+		int dev = -1;
+		if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlph_fwd<IN_T, W_T, OUT_T, 0>, k_mlph_fwd<IN_T, W_T, OUT_T, 1>, k_mlph_fwd<IN_T, W_T, OUT_T, 2>))) return;
 		if (x_fm)
 			hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 2>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 		else if (a.x_vec && a.in_dim % 4 == 0)
@@ -1064,7 +1056,7 @@ extern "C" int nr3d_mlp_half_backward(const nr3d_mlp_desc_t *desc, uint64_t n, c
 		const size_t lds = (size_t)a.total_bytes + (size_t)(tbytes > reduce ? tbytes : reduce);
 		const uint32_t grid = (uint32_t)(n_tiles / nw + 1 < 256 ? n_tiles / nw + 1 : 256);
 		auto launch = [&](auto kern) -> int {
-			NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBwd));
+			NR3D_TRY(NR3D_LDS_LIMIT_ALWAYS(kMaxLdsBwd, kern));
 			hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, (hipStream_t)stream, a);
 			return 0;
 		};
@@ -1086,7 +1078,7 @@ extern "C" int nr3d_mlp_half_backward(const nr3d_mlp_desc_t *desc, uint64_t n, c
 	const size_t lds = (size_t)a.total_bytes + (size_t)(tbytes > reduce ? tbytes : reduce);
 	const uint32_t grid = (uint32_t)(n_tiles / nw + 1 < 256 ? n_tiles / nw + 1 : 256);     // one workgroup per CU: dW lives in registers
 	auto launch = [&](auto kern) -> int {
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBwd));
+		NR3D_TRY(NR3D_LDS_LIMIT_ALWAYS(kMaxLdsBwd, kern));
 		hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, (hipStream_t)stream, a);
 		return 0;
 	};

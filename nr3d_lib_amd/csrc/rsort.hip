@@ -202,14 +202,10 @@ int sort_pairs(void *tmp, int batch, const uint32_t *const *kin, const uint32_t 
 	a.totals = (uint32_t *)p; p += align256((size_t)batch * 512u * 4u);
 	uint32_t *tk[2], *tv[2];
 	for (int b = 0; b < batch; ++b) { tk[b] = (uint32_t *)p; p += align256(4ull * n_max); tv[b] = (uint32_t *)p; p += align256(4ull * n_max); }
-	static bool attr[64] = {};
-	int dev_id = 0;
-	NR3D_HIP_CHECK(hipGetDevice(&dev_id));
-	if (!attr[dev_id & 63]) {
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_scatter<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_lds<8>()));
-		NR3D_HIP_CHECK(hipFuncSetAttribute((const void *)k_scatter<9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_lds<9>()));
-		attr[dev_id & 63] = true;
-	}
+	static LdsOnce once8, once9;
+	int dev = -1;
+	NR3D_TRY(NR3D_LDS_LIMIT(once8, dev, (int)scatter_lds<8>(), k_scatter<8>));
+	NR3D_TRY(NR3D_LDS_LIMIT(once9, dev, (int)scatter_lds<9>(), k_scatter<9>));
 	for (int ps = 0; ps < passes; ++ps) {
 		const bool to_out = ((passes - 1 - ps) & 1) == 0;          // the last pass lands in kout / vout
 		for (int b = 0; b < batch; ++b) {

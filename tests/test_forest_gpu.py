@@ -96,13 +96,15 @@ def test_half_tables_read_natively(oracle, dev, case, binned, monkeypatch):
     for native in (True, False):
         monkeypatch.setattr(_lotd, "NATIVE_HALF", native)
         y, j = _lotd.lod_fwd(metas, xt, ph, bit, need_input_grad=True)
+        y0, j0 = _lotd.lod_fwd(metas, xt, ph, bit, need_input_grad=False)          # the forward kernel without the Jacobian
+        assert j0 is None
         dx, dp = _lotd.lod_bwd(metas, gh, xt, ph, j, bit, need_input_grad=True, need_param_grad=True)
         ddy, dp2, dx2 = _lotd.lod_bwd_bwd_input(metas, vt, gh, xt, ph, j, bit, need_dLdinput_ddLdoutput=True,
                                                 need_dLdinput_dparams=True, need_dLdinput_dinput=True)
-        outs.append((y, j, dx, ddy, dx2, dp, dp2))
+        outs.append((y, j, dx, ddy, dx2, dp, dp2, y0))
     for k, (a, b) in enumerate(zip(*outs)):
         assert a.dtype == b.dtype
-        if k >= 5 and not binned:
+        if k in (5, 6) and not binned:
             assert_close(a.float(), b.float().cpu().numpy(), rel=1e-3, name=f"output {k} (atomics)", levels=m_ref)
         else:
             assert torch.equal(a, b), f"output {k}: half tables vs their fp32 copy"
@@ -354,8 +356,11 @@ def test_vm_levels_over_sorted_points(oracle, dev, forest, continuity, case, hip
     halves = []
     for native in (True, False):
         monkeypatch.setattr(_lotd, "NATIVE_HALF", native)
-        halves.append(_lotd.lod_bwd(metas, gh, xt, ph, None, bit, need_input_grad=False, need_param_grad=True)[1])
-    assert halves[0].dtype == halves[1].dtype and torch.equal(halves[0], halves[1])
+        halves.append((_lotd.lod_bwd(metas, gh, xt, ph, None, bit, need_input_grad=False, need_param_grad=True)[1],
+                       _lotd.lod_bwd_bwd_input(metas, vt, gh, xt, ph, None, bit, need_dLdinput_ddLdoutput=False, need_dLdinput_dparams=True,
+                                               need_dLdinput_dinput=False)[1]))
+    for a, b in zip(*halves):           # first and second order
+        assert a.dtype == b.dtype and torch.equal(a, b)
 
 
 @pytest.mark.parametrize("case", ["mixed", "vm_cuboid"])

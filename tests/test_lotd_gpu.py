@@ -878,7 +878,7 @@ def test_points_on_cell_faces(oracle, dev, case):
 
 @pytest.mark.parametrize("case", ["mixed", "mixed_cuboid", "mixed_smooth"])
 @pytest.mark.parametrize("points", ["uniform", "slab", "batched"])
-def test_vm_levels_over_sorted_points(oracle, dev, case, points, hip_option):
+def test_vm_levels_over_sorted_points(oracle, dev, case, points, hip_option, monkeypatch):
     """VM levels over SORTED points (lotd_sorted.hip; option vm_sorted = 2 takes it whatever the table size, vm_direct = 0 hands it
     every VM level): a band's points are one range of the order of x_a; "slab" puts 40 000 points into two cell rows (one band
     with replicas, added in a fixed order), "batched" three table copies with permuted placement and skipped points.  Against the
@@ -916,6 +916,17 @@ def test_vm_levels_over_sorted_points(oracle, dev, case, points, hip_option):
             assert torch.equal(dp, outs[mode][0]) and torch.equal(dp2, outs[mode][1]), "two runs over sorted points differ"
         outs[mode] = (dp, dp2)
     assert_close(outs[2][0], outs[0][0].cpu().numpy(), rel=1e-5, name="sorted vs records", levels=m_ref)
+    # half tables read natively: the same bits as the run on their fp32 copy, first and second order
+    ph, gh = pt.half(), gt.half()
+    hip_option("vm_sorted", 2)
+    halves = []
+    for native in (True, False):
+        monkeypatch.setattr(_lotd, "NATIVE_HALF", native)
+        halves.append((_lotd.lod_bwd(m, gh, xt, ph, None, need_input_grad=False, need_param_grad=True, **kw)[1],
+                       _lotd.lod_bwd_bwd_input(m, vt, gh, xt, ph, None, need_dLdinput_ddLdoutput=False, need_dLdinput_dparams=True,
+                                               need_dLdinput_dinput=False, **kw)[1]))
+    for a, b in zip(*halves):
+        assert a.dtype == b.dtype and torch.equal(a, b)
 
 
 @pytest.mark.parametrize("case", ["mixed", "mixed_cuboid", "mixed_smooth", "cp_2d", "cp_only_2d4d"])
