@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 16
+#define NR3D_ABI_VERSION 17
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -900,6 +900,34 @@ int nr3d_freq_encode_bwd(uint64_t B, uint32_t D, uint32_t n_freq, uint32_t C, co
  * d_x [B, D]    = dL/dx:     -v[d] sum_f 4^f (g[f,0,d] y[f,0,d] + g[f,1,d] y[f,1,d])      (needs grad). */
 int nr3d_freq_encode_bwd_bwd(uint64_t B, uint32_t D, uint32_t n_freq, uint32_t C, const float *v, const float *grad, const float *y,
                              int64_t y_stride, float *d_grad, float *d_x, void *stream);
+
+/* =================================================================================================
+ * NeuS coarse ray query: one up-sampling stage on fixed-length rows in one launch
+ *   reference         the torch op chain of nr3d_lib/graphics/neus/neus_ray_query.py:258-270 (neus_ray_sdf_to_alpha |
+ *                     neus_ray_sdf_to_upsample_alpha, ray_alpha_to_vw, batch_sample_pdf, cat, sort); no native twin there
+ * One 64-lane wave per ray, the row staged in LDS; no workspace, no atomics, no host wait; the same bits run after run.
+ * ============================================================================================== */
+
+/* Rows of n + m elements up to this cap are served (the default four stages of 64 + 65 end at 325). */
+#define NR3D_NEUS_UPSAMPLE_MAX_ROW 1024
+int nr3d_neus_upsample_max_row(void);
+
+/* For each of R rays: depth, sdf [R, n] float32 (n >= 2; depth non-decreasing per row) are the interval boundaries and the SDF there.
+ * Interval opacity alpha_i, i < n - 1:
+ *   use_estimate == 0: c = sigmoid(sdf inv_s), alpha_i = max(0, (c_i - c_{i+1}) / (c_i + 1e-5));
+ *   use_estimate != 0: delta_i = depth_{i+1} - depth_i, mid_i = (sdf_i + sdf_{i+1}) / 2, slope_i = (sdf_{i+1} - sdf_i) / (delta_i + 1e-5),
+ *     s_i = clamp(min(slope_{i-1}, slope_i), -10, 0) with slope_{-1} = 0, c_prev|c_next = sigmoid((mid_i -|+ s_i delta_i / 2) inv_s),
+ *     alpha_i = max(0, (c_prev - c_next) / (c_prev + 1e-5)).
+ * Weights w_i = alpha_i prod_{j<i} (1 - alpha_j); cdf_0 = 0, cdf_{i+1} = cdf_i + w_i / max(sum w, 1e-5).
+ * u: the CDF positions to invert, m >= 1 per row, non-decreasing; row r starts at u + r * u_stride, u_stride 0 (one shared row) or m.
+ * For every u_j: k = the first index with cdf_k >= u_j (n if none), lo = max(k - 1, 0), hi = min(k, n - 1), den = cdf_hi - cdf_lo (1 where
+ * below 1e-5), fine_j = depth_lo + (u_j - cdf_lo) / den * (depth_hi - depth_lo), then raised to the running maximum of the row (a no-op
+ * wherever that expression is monotone, which it is up to its last rounding).
+ * Outputs, fully written: fine [R, m]; merged [R, n + m] = the sorted union of the row's depth and fine; order int32 [R, n + m] = the
+ * position in cat(depth, fine) every merged element came from, depth elements first among equal values.
+ * n + m <= NR3D_NEUS_UPSAMPLE_MAX_ROW, otherwise an error before any launch.  R == 0 is a no-op. */
+int nr3d_neus_upsample_stage(uint32_t R, uint32_t n, uint32_t m, const float *depth, const float *sdf, const float *u, int64_t u_stride,
+                             float inv_s, int use_estimate, float *fine, float *merged, int32_t *order, void *stream);
 
 #ifdef __cplusplus
 }

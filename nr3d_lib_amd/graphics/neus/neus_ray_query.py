@@ -8,25 +8,34 @@ The up-sampling loop is where the secondary pack ops run end to end on the devic
 opacity -> ``packed_alpha_to_vw`` -> exclusive ``packed_cumsum`` normalised with ``packed_div`` -> ``packed_sample_cdf``
 (``packed_invert_cdf``) -> ``merge_two_packs_sorted_aligned`` of the new depths into the packed buffer, once per
 ``upsample_inv_s_factors`` entry; ``merge_two_batch_a_includes_b`` joins coarse and fine samples.
-(The reference reads ``marched.ridx_hitx`` at :470, an attribute its records do not have; ``ridx_hit`` is used here.)"""
+(The reference reads ``marched.ridx_hitx`` at :470, an attribute its records do not have; ``ridx_hit`` is used here.)
+
+``neus_ray_query_coarse_multi_upsample`` (:132-356) is the vanilla NeuS query that needs no occupancy grid: coarse boundaries on
+every ray between ``near`` and ``far``, the up-sampling on fixed-length rows, one query at the mid-points.  Its stage runs in one
+launch (``bindings._neus_upsample.upsample_stage``) while ``FUSED_UPSAMPLE`` is set."""
 from types import SimpleNamespace
 from typing import Dict, List, Tuple
 
 import torch
 import torch.nn.functional as F
 
-from nr3d_lib_amd.graphics.nerf.nerf_utils import packed_alpha_to_vw
+from nr3d_lib_amd.bindings import _neus_upsample
+from nr3d_lib_amd.graphics.nerf.nerf_utils import packed_alpha_to_vw, ray_alpha_to_vw
 from nr3d_lib_amd.graphics.neus.neus_utils import (neus_packed_sdf_to_alpha, neus_packed_sdf_to_upsample_alpha,
-                                                   neus_ray_sdf_to_alpha)
+                                                   neus_ray_sdf_to_alpha, neus_ray_sdf_to_upsample_alpha)
 from nr3d_lib_amd.graphics.pack_ops import (get_pack_infos_from_batch, merge_two_batch_a_includes_b,
                                             merge_two_packs_sorted_aligned, packed_cumsum, packed_diff, packed_div,
                                             packed_volume_render_compression)
-from nr3d_lib_amd.graphics.raysample import (batch_sample_step_linear, batch_sample_step_wrt_depth,
-                                             batch_sample_step_wrt_sqrt_depth, packed_sample_cdf)
+from nr3d_lib_amd.graphics.raysample import (batch_sample_pdf, batch_sample_step_linear, batch_sample_step_wrt_depth,
+                                             batch_sample_step_wrt_sqrt_depth, cdf_positions, packed_sample_cdf)
 from nr3d_lib_amd.profile import profile
 
-__all__ = ['neus_ray_query_sphere_trace', 'neus_ray_query_march_occ_multi_upsample', 'neus_ray_query_march_occ_multi_upsample_compressed',
-           'neus_ray_query_march_occ_multi_upsample_compressed_strategy']
+__all__ = ['neus_ray_query_sphere_trace', 'neus_ray_query_coarse_multi_upsample', 'neus_ray_query_march_occ_multi_upsample',
+           'neus_ray_query_march_occ_multi_upsample_compressed', 'neus_ray_query_march_occ_multi_upsample_compressed_strategy']
+
+# The stage of neus_ray_query_coarse_multi_upsample between two SDF queries: True = one launch of the HIP kernel for rows that are
+# float32, on the GPU and within _neus_upsample.MAX_ROW; False (and every other row) = the reference's torch op chain.  Same semantics.
+FUSED_UPSAMPLE = True
 
 _RAY_ATTRS = (('ts', 'rays_ts'), ('fidx', 'rays_fidx'), ('bidx', 'rays_bidx'), ('pix', 'rays_pix'),
               ('h_appear', 'rays_h_appear'))
@@ -56,10 +65,10 @@ def _march(model, ray_tested, rays_o, rays_d, near, far, perturb, march_cfg):
     return accel.ray_march(rays_o, rays_d, near=near, far=far, perturb=perturb, **march_cfg)
 
 
-def _check_model(model):
+def _check_model(model, need_accel=True):
     for need in ('forward', 'forward_sdf', 'forward_inv_s'):
         assert hasattr(model, need), f"model.{need}() is requried"
-    assert getattr(model, 'accel', None) is not None, "model.accel is required"
+    assert not need_accel or getattr(model, 'accel', None) is not None, "model.accel is required"
 
 
 class _Query(SimpleNamespace):
@@ -172,6 +181,102 @@ def _upsample(q, marched, upsample_inv_s_factors, upsample_use_estimate_alpha, p
                                            torch.tensor(q.num_fine, device=device))
         return order.values, stage_of[order.indices]
     return stage_depths[0], torch.ones_like(stage_depths[0], dtype=torch.long)
+
+
+def _row_stage(depth, sdf, num_fine, inv_s, use_estimate_alpha, perturb):
+    """one up-sampling stage on rows depth, sdf [num_rays, n] -> (the num_fine new depths, the sorted union [num_rays, n + num_fine],
+    the position in cat([depth, fine], -1) of every element of the union)"""
+    if FUSED_UPSAMPLE and depth.is_cuda and depth.dtype == torch.float32 and sdf.dtype == torch.float32 \
+            and depth.shape[-1] + num_fine <= _neus_upsample.MAX_ROW:
+        u = cdf_positions(depth, depth.shape[:-1], num_fine, perturb)
+        return _neus_upsample.upsample_stage(depth.contiguous(), sdf.contiguous(), u, inv_s, use_estimate_alpha)
+    alpha = neus_ray_sdf_to_upsample_alpha(sdf, depth, inv_s) if use_estimate_alpha else neus_ray_sdf_to_alpha(sdf, inv_s)
+    fine = batch_sample_pdf(depth, ray_alpha_to_vw(alpha), num_fine, perturb=perturb)
+    merged, order = torch.sort(torch.cat([depth, fine], dim=-1), dim=-1)
+    return fine, merged, order
+
+
+def neus_ray_query_coarse_multi_upsample(
+        model, ray_tested: Dict[str, torch.Tensor],
+        with_rgb: bool = True, with_normal: bool = True, perturb: bool = False, nablas_has_grad: bool = False,
+        forward_inv_s: float = None,
+        compression=True, num_coarse: int = 64, coarse_step_cfg=dict(step_mode='linear'),
+        upsample_mode: str = 'multistep_estimate', num_fine: int = 64,
+        upsample_inv_s: float = 64., upsample_s_divisor: float = 1.0,
+        upsample_inv_s_factors: List[int] = [1, 2, 4, 8], upsample_use_estimate_alpha=False,
+        num_nograd: int = 1024, chunksize_query: int = 2 ** 24) -> Tuple[dict, dict]:
+    """Vanilla NeuS ray query (nr3d_lib/graphics/neus/neus_ray_query.py:132-356): ``num_coarse + 1`` boundaries per ray, up-sampled
+    without gradient, then ``model.forward_sdf`` at all boundaries for the opacities and ``model.forward`` at the interval mid-points.
+    ``upsample_mode``: 'multistep_estimate' -- one stage of ``num_fine // 2 * 2 + 1`` new depths per entry of
+    ``upsample_inv_s_factors``, the SDF queried at the new depths between stages; 'direct_use' -- one stage of ``num_fine`` on the
+    coarse boundaries; 'direct_more' -- one stage of ``num_fine`` on ``num_nograd`` uniform boundaries (queried in chunks).
+    Result: the empty buffer; ``type='batched'`` over all tested rays (``compression=False``); or ``type='packed'`` over the rays
+    that keep a sample after ``packed_volume_render_compression`` -- only those samples reach ``model.forward``.
+    Two reference defects, neither mode runs there: 'direct_use' and 'direct_more' call ``.sort(d_all, dim=-1)`` on a name that is
+    not bound yet (:220, :239) -- a sort along the last axis is meant; 'direct_more' lerps ``near`` [num_rays] against
+    [num_nograd] steps without unsqueezing (:222) -- ``near`` / ``far`` are taken as columns."""
+    _check_model(model, need_accel=False)
+    empty = dict(type='empty', rays_inds_hit=[])
+    if ray_tested['num_rays'] == 0:
+        return empty, {}
+    q = _setup(model, ray_tested, with_rgb, with_normal, nablas_has_grad, forward_inv_s, num_fine, upsample_inv_s,
+               upsample_s_divisor, upsample_inv_s_factors)
+    rays_o, rays_d, rays_inds, device, dtype = q.rays_o, q.rays_d, q.rays_inds, q.device, q.dtype
+    depths_coarse_1, _ = _coarse_boundaries(q, num_coarse, coarse_step_cfg, perturb)
+    pts = lambda d: torch.addcmul(rays_o[..., None, :], rays_d[..., None, :], d[..., None])
+    sdf_extra = lambda d: q.sdf_attrs(q.spread(None, d.shape[-1]))
+
+    @torch.no_grad()
+    def upsample():
+        if upsample_mode == 'multistep_estimate':
+            d_all = depths_coarse_1
+            sdf_all = q.query_sdf(pts(d_all), sdf_extra(d_all))
+            for i, factor in enumerate(upsample_inv_s_factors):
+                fine, d_all, order = _row_stage(d_all, sdf_all, q.num_fine[i], q.upsample_inv_s * factor,
+                                                upsample_use_estimate_alpha, perturb)
+                if i < q.n_stages - 1:
+                    sdf_all = torch.cat([sdf_all, q.query_sdf(pts(fine), sdf_extra(fine))], dim=-1).gather(-1, order.long())
+            return d_all
+        if upsample_mode == 'direct_use':
+            d = depths_coarse_1
+            sdf = q.query_sdf(pts(d), sdf_extra(d))
+        elif upsample_mode == 'direct_more':
+            steps = torch.linspace(0, 1, num_nograd, device=device, dtype=torch.float)
+            d = torch.lerp(q.near.unsqueeze(-1), q.far.unsqueeze(-1), steps)
+            sdf = _chunked(lambda x, **kw: q.query_sdf(x, kw), dict(x=pts(d), **sdf_extra(d)), chunksize_query)
+        else:
+            raise RuntimeError(f"Invalid upsample_mode={upsample_mode}")
+        return _row_stage(d, sdf, num_fine, q.upsample_inv_s, upsample_use_estimate_alpha, perturb)[1]
+
+    with profile("Upsampling"):
+        d_all = upsample()
+    with profile("Acquire volume buffer"):
+        d_mid = 0.5 * (d_all[..., 1:] + d_all[..., :-1])
+        alpha = neus_ray_sdf_to_alpha(q.query_sdf(pts(d_all), sdf_extra(d_all)), q.forward_inv_s)
+        if not compression:
+            vb = dict(type='batched', rays_inds_hit=rays_inds, num_per_hit=d_mid.size(-1), t=d_mid.to(dtype),
+                      opacity_alpha=alpha.to(dtype))
+            if q.full_uses['bidx']:
+                vb['rays_bidx_hit'] = ray_tested['rays_bidx']
+            if with_rgb or with_normal:
+                vb.update(q.full_query(pts(d_mid), q.full_attrs(q.spread(None, d_mid.shape[-1]))))
+            return vb, {'render.num_per_ray': d_mid.size(-1)}
+
+        # `pack_infos` is over all tested rays
+        pack_infos = get_pack_infos_from_batch(alpha.shape[0], alpha.shape[1], device=device)
+        nidx_useful, pack_infos_useful, pidx_useful = packed_volume_render_compression(alpha.flatten(), pack_infos)
+        if nidx_useful.numel() == 0:
+            return empty, {}
+        depths_packed = d_mid.flatten()[pidx_useful]
+        vb = dict(type='packed', rays_inds_hit=rays_inds[nidx_useful], pack_infos_hit=pack_infos_useful, t=depths_packed.to(dtype),
+                  opacity_alpha=alpha.flatten()[pidx_useful].to(dtype))
+        if q.full_uses['bidx']:
+            vb['rays_bidx_hit'] = ray_tested['rays_bidx'][nidx_useful]
+        if with_rgb or with_normal:
+            ridx = torch.arange(alpha.shape[0], device=device).unsqueeze(-1).expand_as(alpha).flatten()[pidx_useful]
+            vb.update(q.full_query(torch.addcmul(rays_o[ridx], rays_d[ridx], depths_packed.unsqueeze(-1)),
+                                   q.full_attrs(lambda t: t[ridx])))
+        return vb, {'render.num_per_ray0': d_mid.size(-1), 'render.num_per_ray': pack_infos_useful[:, 1]}
 
 
 def neus_ray_query_march_occ_multi_upsample(

@@ -1,12 +1,24 @@
-"""NeuS opacity from SDF samples -- counterpart of nr3d_lib/graphics/neus/neus_utils.py:52-111,164-189 (the functions the
-upsampling driver uses).  Alpha of the interval between two consecutive samples = relative drop of the logistic CDF
-``sigmoid(sdf * inv_s)``; packed variants take the difference inside each pack (last sample: appended value or 0)."""
+"""NeuS opacity from SDF samples -- counterpart of nr3d_lib/graphics/neus/neus_utils.py:48-217 (same names, arguments and return
+conventions).  Alpha of the interval between two consecutive samples = relative drop of the logistic CDF
+``sigmoid(sdf * inv_s)``; packed variants take the difference inside each pack (last sample: appended value or 0).
+(The reference's ``neus_packed_sdf_to_vw`` calls ``packed_alpha_to_vw`` without its ``pack_infos`` (:115) and its
+``neus_packed_sdf_to_tau`` tests a tensor for truth (:103); here the pack_infos are passed and the test is ``is not None``.)"""
+from typing import Union
+
 import torch
+import torch.nn.functional as F
 
-from nr3d_lib_amd.graphics.pack_ops import packed_diff
+from nr3d_lib_amd.graphics.nerf.nerf_utils import ray_alpha_to_vw
+from nr3d_lib_amd.graphics.pack_ops import packed_alpha_to_vw, packed_diff
 
-__all__ = ['neus_cdf', 'neus_ray_cdf_to_alpha', 'neus_ray_sdf_to_alpha', 'neus_packed_cdf_to_alpha',
-           'neus_packed_sdf_to_alpha', 'neus_packed_sdf_to_upsample_alpha']
+__all__ = ['neus_pdf', 'neus_cdf', 'neus_ray_cdf_to_alpha', 'neus_ray_sdf_to_tau', 'neus_ray_sdf_to_alpha', 'neus_ray_sdf_to_vw',
+           'neus_packed_cdf_to_alpha', 'neus_packed_sdf_to_tau', 'neus_packed_sdf_to_alpha', 'neus_packed_sdf_to_vw',
+           'neus_estimate_sdf_nablas_to_alpha', 'neus_packed_sdf_to_upsample_alpha', 'neus_ray_sdf_to_upsample_alpha']
+
+
+def neus_pdf(x: torch.Tensor, inv_s):
+    """logistic density with scale 1 / inv_s, the cosh clamped to [-20, 20] (maths/common.py:109-120)"""
+    return 0.25 * inv_s / (torch.cosh(inv_s * x / 2.).clamp(-20, 20) ** 2)
 
 
 def neus_cdf(x, inv_s):
@@ -26,6 +38,17 @@ def neus_ray_sdf_to_alpha(sdf: torch.Tensor, inv_s, append_cdf_1=False):
     return neus_ray_cdf_to_alpha(neus_cdf(sdf, inv_s), append_cdf_1=append_cdf_1)
 
 
+def neus_ray_sdf_to_tau(sdf: torch.Tensor, inv_s, append_cdf_1=False):
+    """optical depth of every interval: drop of log sigmoid(sdf * inv_s), clamped at 0 (neus_utils.py:67-73)"""
+    logcdf = F.logsigmoid(sdf * inv_s)
+    append = sdf.new_zeros((*sdf.shape[:-1], 1)) if append_cdf_1 else None      # log(cdf = 1) = 0
+    return (-torch.diff(logcdf, append=append)).clamp_min(0)
+
+
+def neus_ray_sdf_to_vw(sdf: torch.Tensor, inv_s, append_cdf_1=False):
+    return ray_alpha_to_vw(neus_ray_sdf_to_alpha(sdf, inv_s, append_cdf_1=append_cdf_1))
+
+
 def neus_packed_cdf_to_alpha(cdf: torch.Tensor, pack_infos: torch.Tensor, append_cdf_1=False,
                              pack_cdf_appends: torch.Tensor = None):
     if append_cdf_1:
@@ -38,6 +61,40 @@ def neus_packed_sdf_to_alpha(sdf: torch.Tensor, inv_s, pack_infos: torch.Tensor,
                              pack_sdf_appends: torch.Tensor = None):
     appends = None if pack_sdf_appends is None else neus_cdf(pack_sdf_appends, inv_s)
     return neus_packed_cdf_to_alpha(neus_cdf(sdf, inv_s), pack_infos, append_cdf_1=append_cdf_1, pack_cdf_appends=appends)
+
+
+def neus_packed_sdf_to_tau(sdf: torch.Tensor, inv_s, pack_infos: torch.Tensor, append_cdf_1=False,
+                           pack_sdf_appends: torch.Tensor = None):
+    logcdf = F.logsigmoid(sdf * inv_s)
+    if append_cdf_1:
+        appends = sdf.new_zeros(pack_infos.shape[0])
+    else:
+        appends = None if pack_sdf_appends is None else F.logsigmoid(pack_sdf_appends * inv_s)
+    return (-packed_diff(logcdf, pack_infos, pack_appends=appends)).clamp_min(0)
+
+
+def neus_packed_sdf_to_vw(sdf: torch.Tensor, inv_s, pack_infos: torch.Tensor, append_cdf_1=False,
+                          pack_sdf_appends: torch.Tensor = None):
+    return packed_alpha_to_vw(neus_packed_sdf_to_alpha(sdf, inv_s, pack_infos, append_cdf_1=append_cdf_1,
+                                                       pack_sdf_appends=pack_sdf_appends), pack_infos)
+
+
+def neus_estimate_sdf_nablas_to_alpha(sdf: torch.Tensor, deltas: torch.Tensor, nablas: torch.Tensor, dirs: torch.Tensor,
+                                      inv_s: Union[float, torch.Tensor], dir_scales: torch.Tensor = 1, ratio: float = 1,
+                                      delta_max: float = 1e+10) -> torch.Tensor:
+    """the original NeuS opacity: sdf [...] at the interval's sample moved half an interval (``deltas * dir_scales``, at most
+    ``delta_max``) back and forth along the slope ``dirs . nablas`` (dirs normalised; only its negative part counts, annealed by
+    ``ratio``) -> alpha [...] (neus_utils.py:121-158)"""
+    true_cos = (dirs * nablas).sum(-1, keepdim=True)
+    if ratio == 1:
+        iter_cos = -F.relu(-true_cos)
+    elif ratio == 0:
+        iter_cos = -F.relu(-true_cos * 0.5 + 0.5)
+    else:
+        iter_cos = -(F.relu(-true_cos * 0.5 + 0.5) * (1.0 - ratio) + F.relu(-true_cos) * ratio)
+    half = deltas.new_tensor([-0.5, 0.5]) * (deltas * dir_scales).unsqueeze(-1).clamp_max(delta_max)
+    cdf = torch.sigmoid(torch.addcmul(sdf.unsqueeze(-1), iter_cos, half) * inv_s)
+    return ((cdf[..., 0] - cdf[..., 1]) / (cdf[..., 0] + 1e-5)).clamp_min(0)
 
 
 @torch.no_grad()
@@ -53,3 +110,15 @@ def neus_packed_sdf_to_upsample_alpha(sdf: torch.Tensor, depth_samples: torch.Te
     half = slope * deltas * 0.5
     cdf_prev, cdf_next = torch.sigmoid((mid - half) * inv_s), torch.sigmoid((mid + half) * inv_s)
     return ((cdf_prev - cdf_next) / (cdf_prev + 1e-5)).clamp_min_(0)
+
+
+@torch.no_grad()
+def neus_ray_sdf_to_upsample_alpha(sdf: torch.Tensor, depth_samples: torch.Tensor, inv_s) -> torch.Tensor:
+    """batched form of the above: sdf, depth_samples [..., n] at the interval boundaries -> alpha [..., n-1] (neus_utils.py:190-217)"""
+    deltas = depth_samples.diff(dim=-1)
+    mid = (sdf[..., :-1] + sdf[..., 1:]) * 0.5
+    slope = sdf.diff(dim=-1) / (deltas + 1e-5)
+    prev = torch.cat([slope.new_zeros((*slope.shape[:-1], 1)), slope[..., :-1]], -1)
+    slope = torch.minimum(prev, slope).clamp_(-10.0, 0.0)
+    cdf = torch.sigmoid(torch.addcmul(mid.unsqueeze(-1), slope.unsqueeze(-1), deltas.unsqueeze(-1) * deltas.new_tensor([-0.5, 0.5])) * inv_s)
+    return ((cdf[..., 0] - cdf[..., 1]) / (cdf[..., 0] + 1e-5)).clamp_min_(0)

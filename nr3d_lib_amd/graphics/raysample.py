@@ -1,14 +1,15 @@
 """Depth samplers on rays -- counterpart of the parts of nr3d_lib/graphics/raysample.py the hot-path drivers use:
-``packed_sample_cdf`` (:38-62, on the HIP ``packed_invert_cdf``) and the three ``batch_sample_step_*`` ladders
-(:285-383).  Same names, arguments and return conventions."""
+``packed_sample_cdf`` / ``packed_sample_pdf`` (:38-84, on the HIP ``packed_invert_cdf``), the batched inverse-CDF samplers
+``batch_sample_cdf`` / ``batch_sample_pdf`` (:221-282, plain torch) and the three ``batch_sample_step_*`` ladders (:285-383).
+Same names, arguments and return conventions."""
 from typing import Tuple
 
 import torch
 
-from nr3d_lib_amd.graphics.pack_ops import packed_invert_cdf
+from nr3d_lib_amd.graphics.pack_ops import packed_cumsum, packed_div, packed_invert_cdf
 
-__all__ = ['packed_sample_cdf', 'batch_sample_step_linear', 'batch_sample_step_wrt_depth',
-           'batch_sample_step_wrt_sqrt_depth']
+__all__ = ['packed_sample_cdf', 'packed_sample_pdf', 'batch_sample_cdf', 'batch_sample_pdf', 'batch_sample_step_linear',
+           'batch_sample_step_wrt_depth', 'batch_sample_step_wrt_sqrt_depth']
 
 
 def _per_ray(near, far, prefix_shape):
@@ -83,3 +84,42 @@ def packed_sample_cdf(bins: torch.Tensor, cdfs: torch.Tensor, pack_infos: torch.
     else:
         u = torch.linspace(0., 1., num_to_sample + 2, device=bins.device, dtype=bins.dtype)[1:-1].expand(n_packs, num_to_sample)
     return packed_invert_cdf(bins, cdfs.to(bins.dtype), u.contiguous(), pack_infos)
+
+
+@torch.no_grad()
+def packed_sample_pdf(bins: torch.Tensor, weights: torch.Tensor, pack_infos: torch.Tensor, num_to_sample: int,
+                      perturb=False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``packed_sample_cdf`` on the normalised exclusive cumsum of the interval weights (packed [num_pts], trailing zero in every
+    pack) (raysample.py:64-84)"""
+    cdfs = packed_cumsum(weights, pack_infos, exclusive=True)
+    last = cdfs[pack_infos[..., 0] + pack_infos[..., 1] - 1]
+    return packed_sample_cdf(bins, packed_div(cdfs, last.clamp_min(1e-5), pack_infos), pack_infos, num_to_sample, perturb=perturb)
+
+
+def cdf_positions(like: torch.Tensor, prefix, num_to_sample: int, perturb: bool) -> torch.Tensor:
+    """the positions in (0, 1) the batched samplers invert the CDF at: one shared row [num_to_sample] of interior linspace
+    points, or with ``perturb`` one stratified (hence sorted) row per ray [*prefix, num_to_sample]"""
+    if perturb:
+        return batch_sample_step_linear(like.new_zeros(prefix), like.new_ones(prefix), num_to_sample, perturb=True).contiguous()
+    return torch.linspace(0., 1., num_to_sample + 2, device=like.device, dtype=like.dtype)[1:-1].contiguous()
+
+
+@torch.no_grad()
+def batch_sample_cdf(bins: torch.Tensor, cdf: torch.Tensor, num_to_sample: int, perturb=False, eps: float = 1e-5) -> torch.Tensor:
+    """inverse-CDF sampling per ray: bins, cdf [..., n] (cdf with a leading zero) -> t [..., num_to_sample] (raysample.py:221-259)"""
+    u = cdf_positions(bins, bins.shape[:-1], num_to_sample, perturb).expand((*bins.shape[:-1], num_to_sample)).contiguous()
+    inds = torch.searchsorted(cdf.detach(), u, right=False)
+    below, above = (inds - 1).clamp_min(0), inds.clamp_max(cdf.shape[-1] - 1)
+    cdf_lo, cdf_hi = cdf.gather(-1, below), cdf.gather(-1, above)
+    bins_lo, bins_hi = bins.gather(-1, below), bins.gather(-1, above)
+    denom = cdf_hi - cdf_lo
+    denom[denom < eps] = 1
+    return bins_lo + (u - cdf_lo) / denom * (bins_hi - bins_lo)
+
+
+@torch.no_grad()
+def batch_sample_pdf(bins: torch.Tensor, weights: torch.Tensor, num_to_sample: int, perturb=False, eps=1e-5) -> torch.Tensor:
+    """bins [..., n], interval weights [..., n-1] -> t [..., num_to_sample] (raysample.py:262-282)"""
+    pdf = weights / torch.sum(weights, -1, keepdim=True).clamp_min(eps)
+    cdf = torch.cat([pdf.new_zeros((*pdf.shape[:-1], 1)), torch.cumsum(pdf, -1)], -1)
+    return batch_sample_cdf(bins, cdf, num_to_sample, perturb, eps)
