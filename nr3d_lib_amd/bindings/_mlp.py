@@ -66,24 +66,32 @@ def _ptr_array(tensors):
     return arr
 
 
-def pack(desc: MLPDesc, weights, biases, with_backward=False) -> torch.Tensor:
-    """weights[l] [dims[l+1], dims[l]], biases[l] [dims[l+1]] | None (fp32, contiguous, on one GPU) -> packed buffer"""
-    if not desc.fusable:
-        raise RuntimeError("mlp.pack: network outside the fused kernels' range")
+def _pack(desc: MLPDesc, weights, biases, with_backward, half):
+    name, dtype = ("mlp.pack_half", torch.float16) if half else ("mlp.pack", torch.float32)
+    if not (desc.half_fusable if half else desc.fusable):
+        raise RuntimeError(f"{name}: network outside the fused kernels' range")
     dev = weights[0].device
     H.require_gpu(*weights)
-    ws = [w.detach().float().contiguous() for w in weights]
-    bs = [None if b is None else b.detach().float().contiguous() for b in biases]
+    ws = [w.detach().to(dtype).contiguous() for w in weights]
+    bs = [None if b is None else b.detach().to(dtype).contiguous() for b in biases]
     for l, w in enumerate(ws):
         if tuple(w.shape) != (desc.dims[l + 1], desc.dims[l]):
-            raise RuntimeError(f"mlp.pack: weights[{l}] has shape {list(w.shape)}, expected {[desc.dims[l + 1], desc.dims[l]]}")
-    if with_backward and not desc.backward_fusable:
-        raise RuntimeError("mlp.pack: the fused backward does not apply to this network")
-    packed = H.empty(desc.packed_floats + (desc.backward_floats if with_backward else 0), dtype=torch.float32, device=dev)
+            raise RuntimeError(f"{name}: weights[{l}] has shape {list(w.shape)}, expected {[desc.dims[l + 1], desc.dims[l]]}")
+    if with_backward and not (desc.half_backward_fusable if half else desc.backward_fusable):
+        raise RuntimeError(f"{name}: the fused backward does not apply to this network")
+    if half:
+        packed = H.empty(desc.half_packed_bytes + (desc.half_backward_bytes if with_backward else 0), dtype=torch.uint8, device=dev)
+    else:
+        packed = H.empty(desc.packed_floats + (desc.backward_floats if with_backward else 0), dtype=torch.float32, device=dev)
+    entry = H.lib().nr3d_mlp_half_pack if half else H.lib().nr3d_mlp_pack
     with H.on_device(dev):
-        H.check(H.lib().nr3d_mlp_pack(C.byref(desc._c), _ptr_array(ws), _ptr_array(bs), H.ptr(packed), int(with_backward),
-                                      H.stream_of(packed)))
+        H.check(entry(C.byref(desc._c), _ptr_array(ws), _ptr_array(bs), H.ptr(packed), int(with_backward), H.stream_of(packed)))
     return packed
+
+
+def pack(desc: MLPDesc, weights, biases, with_backward=False) -> torch.Tensor:
+    """weights[l] [dims[l+1], dims[l]], biases[l] [dims[l+1]] | None (fp32, contiguous, on one GPU) -> packed buffer"""
+    return _pack(desc, weights, biases, with_backward, half=False)
 
 
 def _layout(t2: torch.Tensor):
@@ -97,51 +105,69 @@ def _layout(t2: torch.Tensor):
     return t2.contiguous(), w, 1
 
 
-def forward(desc: MLPDesc, x: torch.Tensor, packed: torch.Tensor) -> torch.Tensor:
-    """x [..., in] fp32 (row-major with any row stride, or feature-major) -> y [..., out]"""
+def _rows(g2: torch.Tensor):
+    """[n, w] dL_dy -> (tensor, row stride): rows with any row stride are read in place, anything else is copied"""
+    g2 = g2 if (g2.stride(-1) == 1 or g2.shape[1] == 1) else g2.contiguous()
+    return g2, (g2.stride(0) if g2.shape[0] > 1 else g2.shape[1])
+
+
+def _grad_pool(desc: MLPDesc, has_bias, dev):
+    """([dL_dW_l], [dL_db_l | None]) the kernels ADD their workgroups' partial sums into (one atomic per element and workgroup):
+    views of ONE zero-filled fp32 buffer -- one fill launch instead of 2 per layer"""
+    n_layers = len(desc.dims) - 1
+    sizes = [desc.dims[l + 1] * desc.dims[l] for l in range(n_layers)] + [desc.dims[l + 1] if has_bias[l] else 0 for l in range(n_layers)]
+    parts = torch.zeros(sum(sizes), dtype=torch.float32, device=dev).split(sizes)
+    dWs = [parts[l].view(desc.dims[l + 1], desc.dims[l]) for l in range(n_layers)]
+    return dWs, [parts[n_layers + l] if has_bias[l] else None for l in range(n_layers)]
+
+
+def _forward(desc: MLPDesc, x, packed, half):
+    name, dtype, what = ("mlp.forward_half", torch.float16, "half") if half else ("mlp.forward", torch.float32, "fp32")
     H.require_gpu(x, packed)
-    if x.dtype != torch.float32 or x.shape[-1] != desc.dims[0]:
-        raise RuntimeError(f"mlp.forward: expected fp32 input with {desc.dims[0]} features, got {x.dtype} {list(x.shape)}")
+    if x.dtype != dtype or x.shape[-1] != desc.dims[0]:
+        raise RuntimeError(f"{name}: expected {what} input with {desc.dims[0]} features, got {x.dtype} {list(x.shape)}")
     x2, xs, xf = _layout(x.reshape(-1, x.shape[-1]))
     n = x2.shape[0]
-    y = H.empty((n, desc.dims[-1]), dtype=torch.float32, device=x.device)
+    y = H.empty((n, desc.dims[-1]), dtype=dtype, device=x.device)
+    entry = H.lib().nr3d_mlp_half_forward if half else H.lib().nr3d_mlp_forward
     with H.on_device(x.device):
-        H.check(H.lib().nr3d_mlp_forward(C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(packed), H.ptr(y), y.shape[1],
-                                         H.stream_of(x)))
+        H.check(entry(C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(packed), H.ptr(y), y.shape[1], H.stream_of(x)))
     return y.view(*x.shape[:-1], desc.dims[-1])
+
+
+def forward(desc: MLPDesc, x: torch.Tensor, packed: torch.Tensor) -> torch.Tensor:
+    """x [..., in] fp32 (row-major with any row stride, or feature-major) -> y [..., out]"""
+    return _forward(desc, x, packed, half=False)
+
+
+def _backward(desc: MLPDesc, x, dL_dy, packed, need_dx, has_bias, half):
+    name, dtype, what = ("mlp.backward_half", torch.float16, "half") if half else ("mlp.backward", torch.float32, "fp32")
+    H.require_gpu(x, dL_dy, packed)
+    x2 = x.reshape(-1, desc.dims[0])
+    g2 = dL_dy.reshape(-1, desc.dims[-1])
+    if x2.dtype != dtype or g2.dtype != dtype or x2.shape[0] != g2.shape[0]:
+        raise RuntimeError(f"{name}: expected {what} x [n, in] and dL_dy [n, out]")
+    x2, xs, xf = _layout(x2)
+    g2, gs = _rows(g2)
+    n, dev = x2.shape[0], x.device
+    dWs, dbs = _grad_pool(desc, [True] * (len(desc.dims) - 1) if has_bias is None else list(has_bias), dev)
+    dx, gxs, gxf = None, desc.dims[0], 1
+    if need_dx and xf != 1:
+        dx, gxs, gxf = H.empty((desc.dims[0], n), dtype=dtype, device=dev).t(), 1, n
+    elif need_dx:
+        dx = H.empty((n, desc.dims[0]), dtype=dtype, device=dev)
+    entry = H.lib().nr3d_mlp_half_backward if half else H.lib().nr3d_mlp_backward
+    with H.on_device(dev):
+        H.check(entry(C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(g2), gs, H.ptr(packed), H.ptr(dx), gxs, gxf, _ptr_array(dWs),
+                      _ptr_array(dbs), H.stream_of(x)))
+    return (None if dx is None else dx.reshape(x.shape)), dWs, dbs
 
 
 def backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, packed: torch.Tensor, need_dx=True, has_bias=None):
     """-> (dL_dx | None, [dL_dW_l], [dL_db_l | None]); `packed` from pack(..., with_backward=True).  dL_dx has the layout
     of x: for a feature-major x (the LoTD features) it is feature-major too, which is what the LoTD parameter-gradient
     pass reads without a transposition."""
-    H.require_gpu(x, dL_dy, packed)
-    n_layers = len(desc.dims) - 1
-    x2 = x.reshape(-1, desc.dims[0])
-    g2 = dL_dy.reshape(-1, desc.dims[-1])
-    if x2.dtype != torch.float32 or g2.dtype != torch.float32 or x2.shape[0] != g2.shape[0]:
-        raise RuntimeError("mlp.backward: expected fp32 x [n, in] and dL_dy [n, out]")
-    x2, xs, xf = _layout(x2)
-    g2 = g2 if (g2.stride(-1) == 1 or g2.shape[1] == 1) else g2.contiguous()
-    n, dev = x2.shape[0], x.device
-    has_bias = [True] * n_layers if has_bias is None else list(has_bias)
-    # the kernel ADDS its workgroups' partial sums into dW / db (one atomic per element and workgroup): all of them are views
-    # of ONE zero-filled buffer -- one fill launch instead of 2 per layer
-    sizes = [desc.dims[l + 1] * desc.dims[l] for l in range(n_layers)] + [desc.dims[l + 1] if has_bias[l] else 0 for l in range(n_layers)]
-    pool = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
-    parts = pool.split(sizes)
-    dWs = [parts[l].view(desc.dims[l + 1], desc.dims[l]) for l in range(n_layers)]
-    dbs = [parts[n_layers + l] if has_bias[l] else None for l in range(n_layers)]
-    dx, gxs, gxf = None, desc.dims[0], 1
-    if need_dx and xf != 1:
-        dx, gxs, gxf = H.empty((desc.dims[0], n), dtype=torch.float32, device=dev).t(), 1, n
-    elif need_dx:
-        dx = H.empty((n, desc.dims[0]), dtype=torch.float32, device=dev)
-    with H.on_device(dev):
-        H.check(H.lib().nr3d_mlp_backward(
-            C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(g2), g2.stride(0) if n > 1 else desc.dims[-1], H.ptr(packed), H.ptr(dx),
-            gxs, gxf, _ptr_array(dWs), _ptr_array(dbs), H.stream_of(x)))
-    return (None if dx is None else dx.reshape(x.shape)), dWs, dbs
+    return _backward(desc, x, dL_dy, packed, need_dx, has_bias, half=False)
 
 
 def backward_backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, ddL_dx: torch.Tensor, packed: torch.Tensor, need_dgy=True,
@@ -154,7 +180,6 @@ def backward_backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, ddL_d
     H.require_gpu(x, dL_dy, ddL_dx, packed)
     if not desc.second_order_fusable:
         raise RuntimeError("mlp.backward_backward: the fused double backward does not apply to this network")
-    n_layers = len(desc.dims) - 1
     x2 = x.reshape(-1, desc.dims[0])
     v2 = ddL_dx.reshape(-1, desc.dims[0])
     g2 = dL_dy.reshape(-1, desc.dims[-1])
@@ -163,18 +188,13 @@ def backward_backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, ddL_d
         raise RuntimeError("mlp.backward_backward: expected fp32 x [n, in], dL_dy [n, out] and ddL_dx [n, in]")
     x2, xs, xf = _layout(x2)
     v2, vs, vf = _layout(v2)
-    g2 = g2 if (g2.stride(-1) == 1 or g2.shape[1] == 1) else g2.contiguous()
+    g2, gs = _rows(g2)
     n, dev = x2.shape[0], x.device
-    # accumulated into by the kernel (atomics): views of one zero-filled buffer, as in backward()
-    has_bias = [False] * n_layers if has_bias is None else list(has_bias)
-    sizes = [desc.dims[l + 1] * desc.dims[l] for l in range(n_layers)] + [desc.dims[l + 1] if has_bias[l] else 0 for l in range(n_layers)]
-    parts = torch.zeros(sum(sizes), dtype=torch.float32, device=dev).split(sizes)
-    dWs = [parts[l].view(desc.dims[l + 1], desc.dims[l]) for l in range(n_layers)]
-    dbs = [parts[n_layers + l] if has_bias[l] else None for l in range(n_layers)]
+    dWs, dbs = _grad_pool(desc, [False] * (len(desc.dims) - 1) if has_bias is None else list(has_bias), dev)
     dgy = H.empty((n, desc.dims[-1]), dtype=torch.float32, device=dev) if need_dgy else None
     with H.on_device(dev):
         H.check(H.lib().nr3d_mlp_backward_backward(
-            C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(g2), g2.stride(0) if n > 1 else desc.dims[-1], H.ptr(v2), vs, vf,
+            C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(g2), gs, H.ptr(v2), vs, vf,
             H.ptr(packed), H.ptr(dgy), desc.dims[-1], _ptr_array(dWs), H.stream_of(x)))
     return (None if dgy is None else dgy.view(dL_dy.shape)), dWs, dbs
 
@@ -185,63 +205,15 @@ def backward_backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, ddL_d
 # ------------------------------------------------------------------------------------------------
 def pack_half(desc: MLPDesc, weights, biases, with_backward=False) -> torch.Tensor:
     """weights[l] [dims[l+1], dims[l]], biases[l] [dims[l+1]] | None (half, on one GPU) -> packed byte buffer"""
-    if not desc.half_fusable:
-        raise RuntimeError("mlp.pack_half: network outside the fused kernels' range")
-    dev = weights[0].device
-    H.require_gpu(*weights)
-    ws = [w.detach().half().contiguous() for w in weights]
-    bs = [None if b is None else b.detach().half().contiguous() for b in biases]
-    for l, w in enumerate(ws):
-        if tuple(w.shape) != (desc.dims[l + 1], desc.dims[l]):
-            raise RuntimeError(f"mlp.pack_half: weights[{l}] has shape {list(w.shape)}, expected {[desc.dims[l + 1], desc.dims[l]]}")
-    if with_backward and not desc.half_backward_fusable:
-        raise RuntimeError("mlp.pack_half: the fused backward does not apply to this network")
-    packed = H.empty(desc.half_packed_bytes + (desc.half_backward_bytes if with_backward else 0), dtype=torch.uint8, device=dev)
-    with H.on_device(dev):
-        H.check(H.lib().nr3d_mlp_half_pack(C.byref(desc._c), _ptr_array(ws), _ptr_array(bs), H.ptr(packed), int(with_backward),
-                                           H.stream_of(packed)))
-    return packed
+    return _pack(desc, weights, biases, with_backward, half=True)
 
 
 def forward_half(desc: MLPDesc, x: torch.Tensor, packed: torch.Tensor) -> torch.Tensor:
     """x [..., in] half (row-major with any row stride, or feature-major) -> y [..., out] half"""
-    H.require_gpu(x, packed)
-    if x.dtype != torch.float16 or x.shape[-1] != desc.dims[0]:
-        raise RuntimeError(f"mlp.forward_half: expected half input with {desc.dims[0]} features, got {x.dtype} {list(x.shape)}")
-    x2, xs, xf = _layout(x.reshape(-1, x.shape[-1]))
-    n = x2.shape[0]
-    y = H.empty((n, desc.dims[-1]), dtype=torch.float16, device=x.device)
-    with H.on_device(x.device):
-        H.check(H.lib().nr3d_mlp_half_forward(C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(packed), H.ptr(y), y.shape[1],
-                                              H.stream_of(x)))
-    return y.view(*x.shape[:-1], desc.dims[-1])
+    return _forward(desc, x, packed, half=True)
 
 
 def backward_half(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, packed: torch.Tensor, need_dx=True, has_bias=None):
     """-> (dL_dx half | None, [dL_dW_l fp32], [dL_db_l fp32 | None]); `packed` from pack_half(..., with_backward=True).  The
     parameter gradients are the fp32 sums the kernel accumulated (the caller rounds them to the parameters' dtype)."""
-    H.require_gpu(x, dL_dy, packed)
-    n_layers = len(desc.dims) - 1
-    x2 = x.reshape(-1, desc.dims[0])
-    g2 = dL_dy.reshape(-1, desc.dims[-1])
-    if x2.dtype != torch.float16 or g2.dtype != torch.float16 or x2.shape[0] != g2.shape[0]:
-        raise RuntimeError("mlp.backward_half: expected half x [n, in] and dL_dy [n, out]")
-    x2, xs, xf = _layout(x2)
-    g2 = g2 if (g2.stride(-1) == 1 or g2.shape[1] == 1) else g2.contiguous()
-    n, dev = x2.shape[0], x.device
-    has_bias = [True] * n_layers if has_bias is None else list(has_bias)
-    sizes = [desc.dims[l + 1] * desc.dims[l] for l in range(n_layers)] + [desc.dims[l + 1] if has_bias[l] else 0 for l in range(n_layers)]
-    pool = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
-    parts = pool.split(sizes)
-    dWs = [parts[l].view(desc.dims[l + 1], desc.dims[l]) for l in range(n_layers)]
-    dbs = [parts[n_layers + l] if has_bias[l] else None for l in range(n_layers)]
-    dx, gxs, gxf = None, desc.dims[0], 1
-    if need_dx and xf != 1:
-        dx, gxs, gxf = H.empty((desc.dims[0], n), dtype=torch.float16, device=dev).t(), 1, n
-    elif need_dx:
-        dx = H.empty((n, desc.dims[0]), dtype=torch.float16, device=dev)
-    with H.on_device(dev):
-        H.check(H.lib().nr3d_mlp_half_backward(
-            C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(g2), g2.stride(0) if n > 1 else desc.dims[-1], H.ptr(packed), H.ptr(dx),
-            gxs, gxf, _ptr_array(dWs), _ptr_array(dbs), H.stream_of(x)))
-    return (None if dx is None else dx.reshape(x.shape)), dWs, dbs
+    return _backward(desc, x, dL_dy, packed, need_dx, has_bias, half=True)

@@ -20,29 +20,16 @@
 // dH^T = W^T . dY^T on the same register map, and accumulates dW = dH^T . H_prev over the wave's samples: that
 // product contracts over SAMPLES, which the register map has in the lane index, so both operands go through a
 // per-wave LDS transposition tile ([feature][sample] -> one sample pair per MFMA step).
+//
+// Host side: what does not depend on the precision -- tile classes, eligibility, the backward's wave count / LDS bytes / grid, layout
+// flags, the pack launches' layer table -- is csrc/mlp_plan.h, shared with csrc/mlp_half.hip; this file adds the fp32 sizes and tables.
 #include "common.h"
 #include "mlp_device.h"      // register map, dense layers (f32 MFMA / bf16 MFMA x3), loads and stores
+#include "mlp_plan.h"        // the host-side plan shared with mlp_half.hip: shape, dispatch, backward launch plan, layouts
 #include <type_traits>
 
 namespace nr3d {
 namespace mlp {
-
-struct Shape {
-	uint32_t n_layers;                         // linear layers (hidden + output)
-	uint32_t in_t, w_t, out_t;                 // 32-wide tiles of the input, the (widest) hidden layer, the output
-};
-
-static bool shape_of(const nr3d_mlp_desc_t *d, Shape &s) {
-	if (!d || d->n_layers < 2 || d->n_layers > NR3D_MLP_MAX_LAYERS) return false;
-	uint32_t w = 0;
-	for (uint32_t l = 1; l < d->n_layers; ++l) w = d->dims[l] > w ? d->dims[l] : w;
-	for (uint32_t l = 0; l <= d->n_layers; ++l) if (d->dims[l] == 0 || d->dims[l] > 128) return false;
-	s.n_layers = d->n_layers;
-	// 3-tile widths run on the 4-tile instantiation (one all-zero tile)
-	auto round = [](uint32_t t) { return t == 3 ? 4u : t; };
-	s.in_t = round(tiles(d->dims[0])); s.w_t = round(tiles(w)); s.out_t = round(tiles(d->dims[d->n_layers]));
-	return true;
-}
 
 static uint64_t packed_floats(const Shape &s) {
 	return (uint64_t)layer_floats(s.in_t, s.w_t) + (uint64_t)(s.n_layers - 2) * layer_floats(s.w_t, s.w_t) + layer_floats(s.w_t, s.out_t);
@@ -349,8 +336,7 @@ __device__ __forceinline__ void zero_tiles(f16v (&r)[NT]) {
 // feature-major x + row-major dL/dy
 // Networks of 32-wide layers with <= 2 hidden layers leave room for EIGHT waves per workgroup, two per SIMD (round 4, as csrc/mlp_half.hip):
 // the kernel is a chain of LDS round trips and dependent MFMAs per tile, a second wave per SIMD hides part of it.
-template <int IN_T, int W_T, int OUT_T, int NH> struct BwdCfg { static constexpr int kMaxWaves = (IN_T == 1 && W_T == 1 && OUT_T == 1 && NH <= 2) ? 8 : 4; };
-constexpr int kMaxLdsBwd = 160 * 1024;
+template <int IN_T, int W_T, int OUT_T, int NH> struct BwdCfg { static constexpr int kMaxWaves = bwd_max_waves_f32(IN_T, W_T, OUT_T, NH); };
 // X3 (round 6): the forward recomputation, the dH = W^T dPre chain and the sample contraction dW = dPre^T H all run on the bf16 MFMA with
 // three-piece splits (dense_x3 / dense_x3_t / bwd_layer<..., true>); a.packed then points at the x3 planes of the forward layers.
 // The ReLU masks come from the SAME forward arithmetic as nr3d_mlp_forward's x3 route.
@@ -745,31 +731,6 @@ extern "C" uint64_t nr3d_mlp_packed_floats(const nr3d_mlp_desc_t *desc) {
 	return n * 4 <= (uint64_t)kMaxLds ? forward_floats(s) : 0;      // 0: the fused kernels do not apply to this network
 }
 
-static int fill_pack(const nr3d_mlp_desc_t *d, const Shape &s, const float *const *weights, const float *const *biases, PackArgs &p) {
-	p.n_layers = d->n_layers;
-	uint32_t off = 0;
-	for (uint32_t l = 0; l < d->n_layers; ++l) {
-		NR3D_CHECK(weights[l] != nullptr, "mlp_pack: weights[%u] is NULL", l);
-		p.w[l] = weights[l];
-		p.b[l] = biases ? biases[l] : nullptr;
-		p.in_dim[l] = d->dims[l]; p.out_dim[l] = d->dims[l + 1];
-		p.ni[l] = l == 0 ? s.in_t : s.w_t;
-		p.no[l] = l + 1 == d->n_layers ? s.out_t : s.w_t;
-		p.offset[l] = off;
-		off += layer_floats(p.ni[l], p.no[l]);
-	}
-	p.offset[d->n_layers] = off;
-	return 0;
-}
-
-// the fused backward keeps every layer's dW in accumulator registers: hidden width <= 64, at most 2 hidden layers of
-// width > 32 (3 of width <= 32), input / output no wider (in tiles) than the hidden layers
-static bool backward_ok(const Shape &s) {
-	if (s.w_t > 2 || s.in_t > s.w_t || s.out_t > s.w_t) return false;
-	const uint32_t nh = s.n_layers - 1;
-	return s.w_t == 1 ? nh <= 3 : nh <= 2;
-}
-
 // the f32 backward's LDS copy of the forward layers (mlp_device.h kGS / kHS)
 static uint64_t padded_floats(const Shape &s) {
 	return (uint64_t)layer_floats_pad(s.in_t, s.w_t) + (uint64_t)(s.n_layers - 2) * layer_floats_pad(s.w_t, s.w_t) + layer_floats_pad(s.w_t, s.out_t);
@@ -785,17 +746,12 @@ static uint32_t bwd_tile_floats(const Shape &s) { return (32u * (s.in_t > s.out_
 // weights the backward keeps in LDS: one padded copy of the forward layers, f32 or (x3) their bf16 planes
 static uint64_t bwd_weight_floats(const Shape &s, bool x3) { return x3 ? padded_x3_floats(s) : padded_floats(s); }
 
-static uint32_t bwd_waves(const Shape &s, bool x3 = false) {
-	if (x3 && x3_floats(s) == 0) return 0;
-	const uint64_t wbytes = bwd_weight_floats(s, x3) * 4;
-	const uint64_t reduce = ((uint64_t)s.w_t * s.w_t * 1024 + (uint64_t)s.w_t * 64) * 4;     // one layer at a time
-	const uint32_t max_waves = (s.in_t == 1 && s.w_t == 1 && s.out_t == 1 && s.n_layers - 1 <= 2) ? 8u : 4u;      // = BwdCfg<...>::kMaxWaves
-	for (uint32_t nw = max_waves; nw >= 1; --nw) {
-		const uint64_t t = (uint64_t)nw * bwd_tile_floats(s) * 4;
-		// the whole 160 KB (the kernel has no static LDS)
-		if (wbytes + (t > reduce ? t : reduce) <= (uint64_t)kMaxLdsBwd) return nw;
-	}
-	return 0;
+// the launch of k_mlp_bwd / k_mlp_bwd2 on a network backward_ok() admits: as many waves as fit next to the weights (nw == 0: none, or
+// x3 asked for a network without x3 planes)
+static BwdPlan bwd_plan_of(const Shape &s, bool x3, uint64_t n = 0) {
+	if (x3 && x3_floats(s) == 0) return {0, 0, 0};
+	return bwd_plan(bwd_weight_floats(s, x3) * 4, (uint64_t)bwd_tile_floats(s) * 4, s.w_t,
+	                bwd_max_waves_f32(s.in_t, s.w_t, s.out_t, s.n_layers - 1), 1, 0, n);
 }
 
 // Does the x3 option put the backward on the bf16 MFMA?  The kernel is not bound by its MFMAs -- counters of 32 -> 64 -> 64 -> 16
@@ -806,11 +762,8 @@ static uint32_t bwd_waves(const Shape &s, bool x3 = false) {
 // against four: 5.49 / 3.96 -> f32 (so do 64->64->64 and 32->64->64->64).  Until the transposing read (dense_x3_t) the small shapes
 // kept a second, transposed set of planes in LDS (every weight read 16 bytes): equal within 2 % now, and gone.
 static bool backward_x3(const Shape &s) {
-	const uint32_t w0 = bwd_waves(s, false), w3 = bwd_waves(s, true);
-	// no x3 kernel is built (BWD_CASE) for the 64-wide shapes it does not win on: two hidden layers with a 64-wide input or output
-	// (w3 < w0), and 64 -> 64 -> 64 (same waves, backward equal within 3 %: the splits of its 64-wide tiles eat what the cheaper
-	// products bring, and the f32 kernel spills less)
-	if (s.w_t == 2 && ((s.n_layers == 3 && s.in_t + s.out_t >= 3) || s.in_t + s.out_t >= 4)) return false;
+	if (!bwd_has_x3(s.in_t, s.w_t, s.out_t, s.n_layers - 1)) return false;          // no x3 kernel is built for these (mlp_plan.h)
+	const uint32_t w0 = bwd_plan_of(s, false).nw, w3 = bwd_plan_of(s, true).nw;
 	return w3 != 0 && w3 >= w0;
 }
 
@@ -818,7 +771,7 @@ static bool backward_x3(const Shape &s) {
 constexpr uint32_t kBwdHeader = 4;
 extern "C" uint64_t nr3d_mlp_backward_packed_floats(const nr3d_mlp_desc_t *desc) {
 	Shape s;
-	if (!shape_of(desc, s) || nr3d_mlp_packed_floats(desc) == 0 || !backward_ok(s) || bwd_waves(s) == 0) return 0;
+	if (!shape_of(desc, s) || nr3d_mlp_packed_floats(desc) == 0 || !backward_ok(s) || bwd_plan_of(s, false).nw == 0) return 0;
 	return kBwdHeader;
 }
 
@@ -830,35 +783,21 @@ extern "C" int nr3d_mlp_pack(const nr3d_mlp_desc_t *desc, const float *const *we
 	NR3D_CHECK(weights && packed, "mlp_pack: NULL pointer");
 	NR3D_CHECK(!with_backward || nr3d_mlp_backward_packed_floats(desc) != 0, "mlp_pack: the fused backward does not apply to this network");
 	PackArgs p;
-	if (int rc = fill_pack(desc, s, weights, biases, p)) return rc;
+	fill_layers(desc, s, false, layer_floats, p);
+	for (uint32_t l = 0; l < desc->n_layers; ++l) {
+		NR3D_CHECK(weights[l] != nullptr, "mlp_pack: weights[%u] is NULL", l);
+		p.w[l] = weights[l];
+		p.b[l] = biases ? biases[l] : nullptr;
+	}
 	hipLaunchKernelGGL(k_mlp_pack, dim3(16, desc->n_layers), dim3(256), 0, (hipStream_t)stream, p, packed);
 	if (x3_floats(s)) {
 		PackArgs x = p;
-		uint32_t off = 0;
-		for (uint32_t l = 0; l < desc->n_layers; ++l) { x.offset[l] = off; off += layer_x3_floats(p.ni[l], p.no[l]); }
-		x.offset[desc->n_layers] = off;
+		fill_layers(desc, s, false, layer_x3_floats, x);
 		hipLaunchKernelGGL(k_mlp_pack_x3, dim3(16, desc->n_layers), dim3(256), 0, (hipStream_t)stream, x, packed + packed_floats(s));
 	}
 	NR3D_LAUNCH_CHECK();
 	return 0;
 }
-
-#define MLP_DISPATCH(S, ...)                                                                                   \
-	do {                                                                                                       \
-		const uint32_t _i = (S).in_t, _w = (S).w_t, _o = (S).out_t;                                            \
-		auto _go = [&](auto I, auto W, auto O) { constexpr int IN_T = decltype(I)::value, W_T = decltype(W)::value, OUT_T = decltype(O)::value; __VA_ARGS__; }; \
-		auto _ow = [&](auto I, auto W) {                                                                       \
-			if (_o == 1) _go(I, W, std::integral_constant<int, 1>{});                                          \
-			else if (_o == 2) _go(I, W, std::integral_constant<int, 2>{});                                     \
-			else _go(I, W, std::integral_constant<int, 4>{}); };                                               \
-		auto _iw = [&](auto I) {                                                                               \
-			if (_w == 1) _ow(I, std::integral_constant<int, 1>{});                                             \
-			else if (_w == 2) _ow(I, std::integral_constant<int, 2>{});                                        \
-			else _ow(I, std::integral_constant<int, 4>{}); };                                                  \
-		if (_i == 1) _iw(std::integral_constant<int, 1>{});                                                    \
-		else if (_i == 2) _iw(std::integral_constant<int, 2>{});                                               \
-		else _iw(std::integral_constant<int, 4>{});                                                            \
-	} while (0)
 
 extern "C" int nr3d_mlp_forward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, int64_t x_stride, int64_t x_feature_stride,
                                 const float *packed, float *y, int64_t y_stride, void *stream) {
@@ -867,21 +806,23 @@ extern "C" int nr3d_mlp_forward(const nr3d_mlp_desc_t *desc, uint64_t n, const f
 	if (n == 0) return 0;
 	NR3D_CHECK(x && packed && y, "mlp_forward: NULL pointer");
 	FwdArgs a;
-	const bool x_fm = x_feature_stride != 1;
-	NR3D_CHECK(!x_fm || x_stride == 1, "mlp_forward: x must be row-major (feature stride 1) or feature-major (row stride 1)");
-	a.n = n; a.x = x; a.xs = x_fm ? x_feature_stride : x_stride; a.y = y; a.ys = y_stride; a.packed = packed;
+	Layout lx, ly;
+	NR3D_TRY(layout_of("mlp_forward", "x", x, x_stride, x_feature_stride, desc->dims[0], 16, lx));
+	NR3D_TRY(layout_of("mlp_forward", "y", y, y_stride, 1, desc->dims[desc->n_layers], 16, ly));
+	a.n = n; a.x = x; a.xs = lx.stride; a.y = y; a.ys = ly.stride; a.packed = packed;
 	a.packed_floats = (uint32_t)packed_floats(s);
 	const bool x3 = x3_enabled() && x3_floats(s) != 0;
 	if (x3) { a.packed = packed + packed_floats(s); a.packed_floats = (uint32_t)x3_floats(s); }
 	a.n_layers = desc->n_layers; a.in_dim = desc->dims[0]; a.out_dim = desc->dims[desc->n_layers];
 	a.hidden_act = (int)desc->hidden_activation; a.out_act = (int)desc->output_activation;
-	a.x_vec = ((uintptr_t)x % 16 == 0 && x_stride % 4 == 0) ? 1u : 0u;
-	a.y_vec = ((uintptr_t)y % 16 == 0 && y_stride % 4 == 0) ? 1u : 0u;
+	a.x_vec = lx.vec; a.y_vec = ly.vec;
 	const size_t lds = (size_t)a.packed_floats * 4;
 	const uint64_t n_tiles = (n + 31) / 32;
 	const uint32_t grid = (uint32_t)(n_tiles / 4 + 1 < 1024 ? n_tiles / 4 + 1 : 1024);
+	const int xf = fast_of(lx);
 	int rc = 0;
-	MLP_DISPATCH(s, {
+	dispatch_tiles(s, [&](auto I, auto W, auto O) {
+		constexpr int IN_T = decltype(I)::value, W_T = decltype(W)::value, OUT_T = decltype(O)::value;
 		static LdsOnce once;
 		int dev = -1;
 		if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlp_fwd<IN_T, W_T, OUT_T, 0>, k_mlp_fwd<IN_T, W_T, OUT_T, 1>, k_mlp_fwd<IN_T, W_T, OUT_T, 2>))) return;
@@ -889,15 +830,15 @@ extern "C" int nr3d_mlp_forward(const nr3d_mlp_desc_t *desc, uint64_t n, const f
 			static LdsOnce once3;
 			if ((rc = NR3D_LDS_LIMIT(once3, dev, kMaxLds, k_mlp_fwd<IN_T, W_T, OUT_T, 0, true>, k_mlp_fwd<IN_T, W_T, OUT_T, 1, true>,
 			                         k_mlp_fwd<IN_T, W_T, OUT_T, 2, true>))) return;
-			if (x_fm)
+			if (xf == 2)
 				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 2, true>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
-			else if (a.x_vec && a.in_dim % 4 == 0)
+			else if (xf == 1)
 				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 1, true>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 			else
 				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 0, true>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
-		} else if (x_fm)
+		} else if (xf == 2)
 			hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 2>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
-		else if (a.x_vec && a.in_dim % 4 == 0)
+		else if (xf == 1)
 			hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 1>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 		else
 			hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 0>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
@@ -915,12 +856,13 @@ extern "C" int nr3d_mlp_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const 
 	if (n == 0) return 0;
 	NR3D_CHECK(x && dL_dy && packed && dL_dW, "mlp_backward: NULL pointer");
 	BwdArgs a;
-	const bool x_fm = x_feature_stride != 1, gx_fm = dL_dx && gx_feature_stride != 1;
-	NR3D_CHECK(!x_fm || x_stride == 1, "mlp_backward: x must be row-major (feature stride 1) or feature-major (row stride 1)");
-	NR3D_CHECK(!gx_fm || gx_stride == 1, "mlp_backward: dL_dx must be row-major (feature stride 1) or feature-major (row stride 1)");
-	a.n = n; a.x = x; a.xs = x_fm ? x_feature_stride : x_stride; a.gy = dL_dy; a.gys = gy_stride; a.packed = packed;
-	a.gx = dL_dx; a.gxs = gx_fm ? gx_feature_stride : gx_stride;
-	a.x_fm = x_fm ? 1u : 0u; a.gx_fm = gx_fm ? 1u : 0u;
+	Layout lx, lgy, lgx;
+	NR3D_TRY(layout_of("mlp_backward", "x", x, x_stride, x_feature_stride, desc->dims[0], 16, lx));
+	NR3D_TRY(layout_of("mlp_backward", "dL_dx", dL_dx, gx_stride, gx_feature_stride, desc->dims[0], 16, lgx));
+	NR3D_TRY(layout_of("mlp_backward", "dL_dy", dL_dy, gy_stride, 1, desc->dims[desc->n_layers], 16, lgy));
+	a.n = n; a.x = x; a.xs = lx.stride; a.gy = dL_dy; a.gys = lgy.stride; a.packed = packed;
+	a.gx = dL_dx; a.gxs = lgx.stride;
+	a.x_fm = lx.fm; a.gx_fm = lgx.fm;
 	// round 6: on the bf16 MFMA with three-piece splits (forward recomputation, dH chain, dW) when the option is on and the planes fit
 	const bool x3 = x3_enabled() && backward_x3(s);
 	a.total_floats = (uint32_t)bwd_weight_floats(s, x3);                 // of the LDS copy (the kernel pads the packed layers itself)
@@ -933,33 +875,23 @@ extern "C" int nr3d_mlp_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const 
 	for (uint32_t l = 0; l <= desc->n_layers; ++l) a.dims[l] = desc->dims[l];
 	a.n_layers = desc->n_layers;
 	a.hidden_act = (int)desc->hidden_activation; a.out_act = (int)desc->output_activation;
-	a.x_vec = ((uintptr_t)x % 16 == 0 && x_stride % 4 == 0) ? 1u : 0u;
-	a.gy_vec = ((uintptr_t)dL_dy % 16 == 0 && gy_stride % 4 == 0) ? 1u : 0u;
-	a.gx_vec = (dL_dx && (uintptr_t)dL_dx % 16 == 0 && gx_stride % 4 == 0) ? 1u : 0u;
+	a.x_vec = lx.vec; a.gy_vec = lgy.vec; a.gx_vec = lgx.vec;
 	a.tile_floats = bwd_tile_floats(s);
-	const uint32_t nw = bwd_waves(s, x3);
-	const uint64_t reduce = ((uint64_t)s.w_t * s.w_t * 1024 + (uint64_t)s.w_t * 64) * 4;
-	const uint64_t tbytes = (uint64_t)nw * a.tile_floats * 4;
-	const size_t lds = (size_t)a.total_floats * 4 + (size_t)(tbytes > reduce ? tbytes : reduce);
-	const uint64_t n_tiles = (n + 31) / 32;
-	const uint32_t grid = (uint32_t)(n_tiles / nw + 1 < 256 ? n_tiles / nw + 1 : 256);     // one workgroup per CU: dW lives in registers
+	const BwdPlan plan = bwd_plan_of(s, x3, n);
 	const uint32_t nh = desc->n_layers - 1;
-	const bool gy_fast = a.gy_vec && desc->dims[desc->n_layers] % 4 == 0;
-	const int fast = !gy_fast ? 0 : x_fm ? 2 : (a.x_vec && desc->dims[0] % 4 == 0) ? 1 : 0;
+	const int fast = fast_of(lx, lgy);
 	auto launch = [&](auto kern) -> int {
 		NR3D_TRY(NR3D_LDS_LIMIT_ALWAYS(kMaxLdsBwd, kern));
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, (hipStream_t)stream, a);
+		hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(64 * plan.nw), plan.lds_bytes, (hipStream_t)stream, a);
 		return 0;
 	};
 	int rc = 0;
 #define BWD_CASE(I, W, O, H) if (s.in_t == I && s.w_t == W && s.out_t == O && nh == H) { \
-		if (x3) { if constexpr (!(W == 2 && ((H == 2 && I + O >= 3) || I + O >= 4))) /* (= backward_x3()) */ \
+		if (x3) { if constexpr (bwd_has_x3(I, W, O, H)) \
 		              rc = fast == 2 ? launch(k_mlp_bwd<I, W, O, H, 2, true>) : fast == 1 ? launch(k_mlp_bwd<I, W, O, H, 1, true>) : launch(k_mlp_bwd<I, W, O, H, 0, true>); \
 		          else rc = ::nr3d::fail("mlp_backward: no bf16 MFMA backward for this shape"); } \
 		else rc = fast == 2 ? launch(k_mlp_bwd<I, W, O, H, 2>) : fast == 1 ? launch(k_mlp_bwd<I, W, O, H, 1>) : launch(k_mlp_bwd<I, W, O, H, 0>); } else
-	BWD_CASE(1, 1, 1, 1) BWD_CASE(1, 1, 1, 2) BWD_CASE(1, 1, 1, 3)
-	BWD_CASE(1, 2, 1, 1) BWD_CASE(1, 2, 1, 2) BWD_CASE(1, 2, 2, 1) BWD_CASE(1, 2, 2, 2)
-	BWD_CASE(2, 2, 1, 1) BWD_CASE(2, 2, 1, 2) BWD_CASE(2, 2, 2, 1) BWD_CASE(2, 2, 2, 2)
+	NR3D_MLP_BWD_SHAPES(BWD_CASE)
 	rc = ::nr3d::fail("mlp_backward: no kernel for this shape");
 #undef BWD_CASE
 	if (rc) return rc;
@@ -979,12 +911,14 @@ extern "C" int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t 
 	if (n == 0) return 0;
 	NR3D_CHECK(x && dL_dy && ddL_dx && packed && dL_dW, "mlp_backward_backward: NULL pointer");
 	Bwd2Args a;
-	const bool x_fm = x_feature_stride != 1, v_fm = v_feature_stride != 1;
-	NR3D_CHECK(!x_fm || x_stride == 1, "mlp_backward_backward: x must be row-major (feature stride 1) or feature-major (row stride 1)");
-	NR3D_CHECK(!v_fm || v_stride == 1, "mlp_backward_backward: ddL_dx must be row-major (feature stride 1) or feature-major (row stride 1)");
-	a.n = n; a.x = x; a.xs = x_fm ? x_feature_stride : x_stride; a.gy = dL_dy; a.gys = gy_stride;
-	a.v = ddL_dx; a.vs = v_fm ? v_feature_stride : v_stride; a.ggy = dL_ddLdy; a.ggys = ggy_stride;
-	a.x_fm = x_fm ? 1u : 0u; a.v_fm = v_fm ? 1u : 0u;
+	Layout lx, lv, lgy, lggy;
+	NR3D_TRY(layout_of("mlp_backward_backward", "x", x, x_stride, x_feature_stride, desc->dims[0], 16, lx));
+	NR3D_TRY(layout_of("mlp_backward_backward", "ddL_dx", ddL_dx, v_stride, v_feature_stride, desc->dims[0], 16, lv));
+	NR3D_TRY(layout_of("mlp_backward_backward", "dL_dy", dL_dy, gy_stride, 1, desc->dims[desc->n_layers], 16, lgy));
+	NR3D_TRY(layout_of("mlp_backward_backward", "dL_ddLdy", dL_ddLdy, ggy_stride, 1, desc->dims[desc->n_layers], 16, lggy));
+	a.n = n; a.x = x; a.xs = lx.stride; a.gy = dL_dy; a.gys = lgy.stride;
+	a.v = ddL_dx; a.vs = lv.stride; a.ggy = dL_ddLdy; a.ggys = lggy.stride;
+	a.x_fm = lx.fm; a.v_fm = lv.fm;
 	// the route of nr3d_mlp_backward under the same option state: the masks of the forward recomputation are bit for bit its masks
 	const bool x3 = x3_enabled() && backward_x3(s);
 	a.packed = x3 ? packed + packed_floats(s) : packed;
@@ -996,33 +930,22 @@ extern "C" int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t 
 	for (uint32_t l = 0; l <= desc->n_layers; ++l) a.dims[l] = desc->dims[l];
 	a.n_layers = desc->n_layers;
 	a.hidden_act = (int)desc->hidden_activation; a.out_act = (int)desc->output_activation;
-	a.x_vec = ((uintptr_t)x % 16 == 0 && x_stride % 4 == 0) ? 1u : 0u;
-	a.v_vec = ((uintptr_t)ddL_dx % 16 == 0 && v_stride % 4 == 0) ? 1u : 0u;
-	a.gy_vec = ((uintptr_t)dL_dy % 16 == 0 && gy_stride % 4 == 0) ? 1u : 0u;
-	a.ggy_vec = (dL_ddLdy && (uintptr_t)dL_ddLdy % 16 == 0 && ggy_stride % 4 == 0) ? 1u : 0u;
+	a.x_vec = lx.vec; a.v_vec = lv.vec; a.gy_vec = lgy.vec; a.ggy_vec = lggy.vec;
 	a.tile_floats = bwd_tile_floats(s);
-	const uint32_t nw = bwd_waves(s, x3);
-	NR3D_CHECK(nw != 0, "mlp_backward_backward: no wave fits LDS");
-	const uint64_t reduce = ((uint64_t)s.w_t * s.w_t * 1024 + (uint64_t)s.w_t * 64) * 4;
-	const uint64_t tbytes = (uint64_t)nw * a.tile_floats * 4;
-	const size_t lds = (size_t)a.total_floats * 4 + (size_t)(tbytes > reduce ? tbytes : reduce);
-	const uint64_t n_tiles = (n + 31) / 32;
-	const uint32_t grid = (uint32_t)(n_tiles / nw + 1 < 256 ? n_tiles / nw + 1 : 256);     // one workgroup per CU: dW lives in registers
+	const BwdPlan plan = bwd_plan_of(s, x3, n);
+	NR3D_CHECK(plan.nw != 0, "mlp_backward_backward: no wave fits LDS");
 	const uint32_t nh = desc->n_layers - 1;
 	auto launch = [&](auto kern) -> int {
 		NR3D_TRY(NR3D_LDS_LIMIT_ALWAYS(kMaxLdsBwd, kern));
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, (hipStream_t)stream, a);
+		hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(64 * plan.nw), plan.lds_bytes, (hipStream_t)stream, a);
 		return 0;
 	};
 	int rc = 0;
 #define BWD2_CASE(I, W, O, H) if (s.in_t == I && s.w_t == W && s.out_t == O && nh == H) { \
-		if (x3) { if constexpr (!(W == 2 && ((H == 2 && I + O >= 3) || I + O >= 4))) /* (= backward_x3()) */ \
-		              rc = launch(k_mlp_bwd2<I, W, O, H, true>); \
+		if (x3) { if constexpr (bwd_has_x3(I, W, O, H)) rc = launch(k_mlp_bwd2<I, W, O, H, true>); \
 		          else rc = ::nr3d::fail("mlp_backward_backward: no bf16 MFMA kernel for this shape"); } \
 		else rc = launch(k_mlp_bwd2<I, W, O, H>); } else
-	BWD2_CASE(1, 1, 1, 1) BWD2_CASE(1, 1, 1, 2) BWD2_CASE(1, 1, 1, 3)
-	BWD2_CASE(1, 2, 1, 1) BWD2_CASE(1, 2, 1, 2) BWD2_CASE(1, 2, 2, 1) BWD2_CASE(1, 2, 2, 2)
-	BWD2_CASE(2, 2, 1, 1) BWD2_CASE(2, 2, 1, 2) BWD2_CASE(2, 2, 2, 1) BWD2_CASE(2, 2, 2, 2)
+	NR3D_MLP_BWD_SHAPES(BWD2_CASE)
 	rc = ::nr3d::fail("mlp_backward_backward: no kernel for this shape");
 #undef BWD2_CASE
 	if (rc) return rc;

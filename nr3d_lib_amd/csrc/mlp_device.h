@@ -1,26 +1,18 @@
 // nr3d_lib_amd/csrc/mlp_device.h -- device side of the fused fp32 decoder (round 6): the register map, the dense layers on the f32
 // MFMA and on the bf16 MFMA with three-piece splits, row / column loads and stores.  mlp.hip holds the kernels and the host side of
-// the decoder.  See mlp.hip's header comment for the layout.
+// the decoder (mlp_plan.h: the part of the host side it shares with mlp_half.hip).  See mlp.hip's header comment for the layout.
 #pragma once
 #include "common.h"
+#include "mlp_plan.h"        // kThreads, kMaxLds, tiles()
 #include <type_traits>
-
-// 1: streaming (non-temporal) row loads / stores as in rounds 3-4; 0: plain (see mlp_half.hip: the 16-byte pieces of a row arrive over
-// four instructions, L1 / L2 serve the re-touches of a line only for plain accesses)
-#ifndef NR3D_MLP_NT
-#define NR3D_MLP_NT 0
-#endif
 
 namespace nr3d {
 namespace mlp {
+using namespace mlp_plan;
 
 typedef float f16v __attribute__((ext_vector_type(16)));
 typedef float f4v __attribute__((ext_vector_type(4)));
 
-constexpr int kThreads = 256;                  // 4 waves per workgroup, one 32-sample tile per wave at a time
-constexpr int kMaxLds = 144 * 1024;            // of the CU's 160 KB
-
-__host__ __device__ constexpr uint32_t tiles(uint32_t d) { return (d + 31u) / 32u; }
 // floats of one packed layer: weights [NO][NI][4][64][4] + bias [NO * 32]
 __host__ __device__ constexpr uint32_t layer_floats(uint32_t ni, uint32_t no) { return no * ni * 1024u + no * 32u; }
 
@@ -337,6 +329,8 @@ __device__ __forceinline__ void dense_x3_t(const float *__restrict__ wp, const f
 }
 
 // rows of a [n, dim] matrix on the register map: lane (s = lane & 31, h = lane >> 5) owns features 32t + 8q + 4h + b
+// Row loads / stores are plain accesses, not streaming (non-temporal) ones as in rounds 3-4: the 16-byte pieces of a row arrive over
+// four instructions, and L1 / L2 serve the re-touches of a line only for plain accesses (see mlp_half.hip)
 template <int NT>
 __device__ __forceinline__ void load_rows(const float *__restrict__ p, int64_t stride, uint32_t dim, uint64_t row, bool valid,
                                           bool vec, int lane, f16v (&r)[NT]) {
@@ -349,7 +343,7 @@ __device__ __forceinline__ void load_rows(const float *__restrict__ p, int64_t s
 			f4v v = {0.0f, 0.0f, 0.0f, 0.0f};
 			if (valid && f < dim) {
 				const float *src = p + (int64_t)row * stride + f;
-				if (vec && f + 3 < dim) v = NR3D_MLP_NT ? __builtin_nontemporal_load(reinterpret_cast<const f4v *>(src)) : *reinterpret_cast<const f4v *>(src);
+				if (vec && f + 3 < dim) v = *reinterpret_cast<const f4v *>(src);
 				else {
 #pragma unroll
 					for (int b = 0; b < 4; ++b) if (f + b < dim) v[b] = src[b];
@@ -375,7 +369,7 @@ __device__ __forceinline__ void load_rows_fast(const float *__restrict__ p, int6
 #pragma unroll
 		for (int q = 0; q < 4; ++q) {
 			const uint32_t f = 32u * t + 8u * q + 4u * h;
-			const f4v v = NR3D_MLP_NT ? __builtin_nontemporal_load(reinterpret_cast<const f4v *>(base + (f < dim ? f : 0u))) : *reinterpret_cast<const f4v *>(base + (f < dim ? f : 0u));
+			const f4v v = *reinterpret_cast<const f4v *>(base + (f < dim ? f : 0u));
 #pragma unroll
 			for (int b = 0; b < 4; ++b) r[t][4 * q + b] = v[b];
 		}
@@ -427,8 +421,8 @@ __device__ __forceinline__ void store_rows(float *__restrict__ p, int64_t stride
 			float *dst = p + (int64_t)row * stride + f;
 			if (vec && f + 3 < dim) {
 				const f4v v = {r[t][4 * q], r[t][4 * q + 1], r[t][4 * q + 2], r[t][4 * q + 3]};
-				// (rows wider than one tile: plain stores, L2 merges the row's 16-byte pieces into whole lines -- mlp_half.hip, store_rows)
-				if (NT > 1 || !NR3D_MLP_NT) *reinterpret_cast<f4v *>(dst) = v; else __builtin_nontemporal_store(v, reinterpret_cast<f4v *>(dst));
+				// (plain stores: L2 merges the row's 16-byte pieces into whole lines -- mlp_half.hip, store_rows)
+				*reinterpret_cast<f4v *>(dst) = v;
 			} else {
 #pragma unroll
 				for (int b = 0; b < 4; ++b) if (f + b < dim) dst[b] = r[t][4 * q + b];

@@ -21,22 +21,19 @@
 // writes, one 16-byte read per MFMA operand); dW / db accumulate in fp32 registers over all of a wave's tiles, are summed over
 // the workgroup in LDS and added to fp32 global buffers with one atomic per element and workgroup (the binding rounds them to
 // the parameters' dtype afterwards).
+// Host side: the plan shared with csrc/mlp.hip is csrc/mlp_plan.h; this file adds the half sizes and the two backward tables.
 #include "common.h"
+#include "mlp_plan.h"        // the host-side plan shared with mlp.hip: shape, dispatch, backward launch plan, layouts
 #include <type_traits>
 
-// x / dL_dy rows are fetched as 8-byte pieces, four instructions per 64-byte row, and dL/dx / y leave the same way: as streaming
-// (non-temporal) accesses every piece went to L2 / HBM on its own; as plain accesses the L1 serves the three re-touches of a line and L2
-// merges the pieces of a row (round 5, measured at 2^22 samples: 32 -> 64 -> 64 -> 16 fwd + bwd 0.739 -> 0.632 ms, 32 -> 32 -> 32 -> 16
-// 0.489 -> 0.317, 64 -> 64 -> 64 -> 64 1.53 -> 1.22; loads alone 0.645, stores alone 0.685)
-#ifndef NR3D_MLPH_NT_LOAD
-#define NR3D_MLPH_NT_LOAD 0
-#endif
-#ifndef NR3D_MLPH_NT_STORE
-#define NR3D_MLPH_NT_STORE 0
-#endif
+// x / dL_dy rows are fetched as 8-byte pieces, four instructions per 64-byte row, and dL/dx / y leave the same way, all as PLAIN
+// accesses: as streaming (non-temporal) accesses every piece went to L2 / HBM on its own; as plain accesses the L1 serves the three
+// re-touches of a line and L2 merges the pieces of a row (round 5, measured at 2^22 samples: 32 -> 64 -> 64 -> 16 fwd + bwd
+// 0.739 -> 0.632 ms, 32 -> 32 -> 32 -> 16 0.489 -> 0.317, 64 -> 64 -> 64 -> 64 1.53 -> 1.22; loads alone 0.645, stores alone 0.685)
 
 namespace nr3d {
 namespace mlph {
+using namespace mlp_plan;
 
 typedef float f16v __attribute__((ext_vector_type(16)));
 typedef float f4v __attribute__((ext_vector_type(4)));
@@ -45,25 +42,9 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-constexpr int kThreads = 256;
-constexpr int kMaxLds = 144 * 1024;
-
-__host__ __device__ constexpr uint32_t tiles(uint32_t d) { return (d + 31u) / 32u; }
 // bytes of one packed layer: weights [NO][NI][2 steps][64 lanes][8 halfs] + bias fp32 [NO * 32]
 __host__ __device__ constexpr uint32_t layer_bytes(uint32_t ni, uint32_t no) { return no * ni * 2048u + no * 128u; }
 
-struct Shape { uint32_t n_layers, in_t, w_t, out_t; };
-
-static bool shape_of(const nr3d_mlp_desc_t *d, Shape &s) {
-	if (!d || d->n_layers < 2 || d->n_layers > NR3D_MLP_MAX_LAYERS) return false;
-	uint32_t w = 0;
-	for (uint32_t l = 1; l < d->n_layers; ++l) w = d->dims[l] > w ? d->dims[l] : w;
-	for (uint32_t l = 0; l <= d->n_layers; ++l) if (d->dims[l] == 0 || d->dims[l] > 128) return false;
-	s.n_layers = d->n_layers;
-	auto round = [](uint32_t t) { return t == 3 ? 4u : t; };      // 3-tile widths run on the 4-tile instantiation
-	s.in_t = round(tiles(d->dims[0])); s.w_t = round(tiles(w)); s.out_t = round(tiles(d->dims[d->n_layers]));
-	return true;
-}
 static uint64_t packed_bytes(const Shape &s) {
 	return (uint64_t)layer_bytes(s.in_t, s.w_t) + (uint64_t)(s.n_layers - 2) * layer_bytes(s.w_t, s.w_t) + layer_bytes(s.w_t, s.out_t);
 }
@@ -238,7 +219,7 @@ __device__ __forceinline__ void load_rows_fast(const __half *__restrict__ p, int
 #pragma unroll
 		for (int q = 0; q < 4; ++q) {
 			const uint32_t f = 32u * t + 8u * q + 4u * h;
-			const h4 v = NR3D_MLPH_NT_LOAD ? __builtin_nontemporal_load(reinterpret_cast<const h4 *>(base + (f < dim ? f : 0u))) : *reinterpret_cast<const h4 *>(base + (f < dim ? f : 0u));
+			const h4 v = *reinterpret_cast<const h4 *>(base + (f < dim ? f : 0u));
 #pragma unroll
 			for (int b = 0; b < 4; ++b) r[t][q >> 1][(q & 1) * 4 + b] = v[b];
 		}
@@ -276,7 +257,7 @@ __device__ __forceinline__ void store_rows(__half *__restrict__ p, int64_t strid
 			// rows wider than one tile (NT > 1): a lane's 8-byte pieces of a 128-byte row arrive over eight instructions -- as streaming
 			// (non-temporal) stores each piece went to HBM as a partial sector write (32 -> 64 -> 64 -> 64 forward: 1.15 ms for 0.54 GB of
 			// output); as plain stores L2 merges them into whole lines first
-			if (vec && f + 3 < dim) { if (NT > 1 || !NR3D_MLPH_NT_STORE) *reinterpret_cast<h4 *>(dst) = v; else __builtin_nontemporal_store(v, reinterpret_cast<h4 *>(dst)); }
+			if (vec && f + 3 < dim) *reinterpret_cast<h4 *>(dst) = v;
 			else {
 #pragma unroll
 				for (int b = 0; b < 4; ++b) if (f + b < dim) dst[b] = v[b];
@@ -516,8 +497,7 @@ __device__ __forceinline__ void zero_tiles(f16v (&r)[NT]) {
 // Networks of 32-wide layers leave room for EIGHT waves per workgroup, two per SIMD: the kernel is a chain of LDS round trips and
 // dependent MFMAs per tile, a second wave per SIMD hides half of it (dW of such a network is <= 64 registers; the cap is then 256 per
 // lane).  64-wide hidden layers keep four waves and the whole register file (at 256 registers 32 -> 64 -> 64 -> 16 spills 300-400 dwords).
-template <int IN_T, int W_T, int OUT_T> struct BwdCfg { static constexpr int kMaxWaves = (IN_T == 1 && W_T == 1 && OUT_T == 1) ? 8 : 4; };
-constexpr int kMaxLdsBwd = 160 * 1024;
+template <int IN_T, int W_T, int OUT_T> struct BwdCfg { static constexpr int kMaxWaves = bwd_max_waves_half(IN_T, W_T, OUT_T); };
 template <int IN_T, int W_T, int OUT_T, int NH, int FAST>
 __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T>::kMaxWaves * 64)) void k_mlph_bwd(BwdArgs a) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -881,44 +861,21 @@ extern "C" uint64_t nr3d_mlp_half_packed_bytes(const nr3d_mlp_desc_t *desc) {
 	return n <= (uint64_t)kMaxLds ? n : 0;
 }
 
-static bool backward_ok(const Shape &s) {        // dW of every layer lives in accumulator registers (as csrc/mlp.hip)
-	if (s.w_t > 2 || s.in_t > s.w_t || s.out_t > s.w_t) return false;
-	const uint32_t nh = s.n_layers - 1;
-	return s.w_t == 1 ? nh <= 3 : nh <= 2;
-}
 // per-wave [feature][sample] tiles: X, H_1 .. H_NH, G_out
 static uint32_t bwd_tile_halfs(const Shape &s) { return (32u * s.in_t + (s.n_layers - 1) * 32u * s.w_t + 32u * s.out_t) * (uint32_t)kTSH; }
-static uint32_t bwd_waves(const Shape &s) {
-	const uint64_t wbytes = packed_bytes(s) + transposed_bytes(s);
-	const uint64_t reduce = ((uint64_t)s.w_t * s.w_t * 1024 + (uint64_t)s.w_t * 64) * 4;
-	const uint32_t max_waves = (s.in_t == 1 && s.w_t == 1 && s.out_t == 1) ? 8u : 4u;      // = BwdCfg<IN_T, W_T, OUT_T>::kMaxWaves
-	for (uint32_t nw = max_waves; nw >= 1; --nw) {
-		const uint64_t t = (uint64_t)nw * bwd_tile_halfs(s) * 2;
-		if (wbytes + (t > reduce ? t : reduce) <= (uint64_t)(nw > 4 ? kMaxLdsBwd : kMaxLds)) return nw;
-	}
-	return 0;
-}
 
-// k_mlph_bwd_split: eight waves when LDS holds the weights (forward + transposed) and eight waves' tiles, else four
-static uint32_t split_waves(const Shape &s) {
-	const uint64_t wbytes = packed_bytes(s) + transposed_bytes(s);
-	const uint64_t reduce = ((uint64_t)s.w_t * s.w_t * 1024 + (uint64_t)s.w_t * 64) * 4;
-	// (eight waves = 256 registers per lane: only the narrow-input, narrow-output shapes stay clear of scratch there)
-#ifdef NR3D_MLPH_FORCE_NW4
-	const uint32_t nw_first = 4;
-#else
-	const uint32_t nw_first = (s.in_t == 1 && s.out_t == 1) ? 8 : 4;
-#endif
-	for (uint32_t nw = nw_first; nw >= 4; nw -= 4) {
-		const uint64_t t = (uint64_t)nw * bwd_tile_halfs(s) * 2;
-		if (wbytes + (t > reduce ? t : reduce) <= (uint64_t)kMaxLdsBwd) return nw;
-	}
-	return 0;
+// The backward launch of a network backward_ok() admits (nw == 0: no wave fits LDS next to the forward + transposed weights).
+// 32-wide hidden layers: k_mlph_bwd with as many waves as fit, more than four only where the whole 160 KB hold them; 64-wide hidden
+// layers: dW split over the waves of the workgroup (k_mlph_bwd_split), eight waves where LDS holds their tiles, else four
+static BwdPlan bwd_plan_of(const Shape &s, uint64_t n = 0) {
+	const uint64_t wbytes = packed_bytes(s) + transposed_bytes(s), tbytes = (uint64_t)bwd_tile_halfs(s) * 2;
+	if (s.w_t == 2) return bwd_plan(wbytes, tbytes, s.w_t, split_max_waves(s.in_t, s.out_t), 4, 0, n);
+	return bwd_plan(wbytes, tbytes, s.w_t, bwd_max_waves_half(s.in_t, s.w_t, s.out_t), 1, 4, n);
 }
 
 extern "C" uint64_t nr3d_mlp_half_backward_packed_bytes(const nr3d_mlp_desc_t *desc) {
 	Shape s;
-	if (!shape_of(desc, s) || nr3d_mlp_half_packed_bytes(desc) == 0 || !backward_ok(s) || (s.w_t == 2 ? split_waves(s) : bwd_waves(s)) == 0) return 0;
+	if (!shape_of(desc, s) || nr3d_mlp_half_packed_bytes(desc) == 0 || !backward_ok(s) || bwd_plan_of(s).nw == 0) return 0;
 	return transposed_bytes(s);
 }
 
@@ -930,52 +887,23 @@ extern "C" int nr3d_mlp_half_pack(const nr3d_mlp_desc_t *desc, const void *const
 	NR3D_CHECK(weights && packed, "mlp_half_pack: NULL pointer");
 	NR3D_CHECK(!with_backward || nr3d_mlp_half_backward_packed_bytes(desc) != 0, "mlp_half_pack: the fused backward does not apply to this network");
 	PackArgs p;
-	p.n_layers = desc->n_layers; p.transposed = 0;
-	uint32_t off = 0;
+	p.transposed = 0;
+	fill_layers(desc, s, false, layer_bytes, p);
 	for (uint32_t l = 0; l < desc->n_layers; ++l) {
 		NR3D_CHECK(weights[l] != nullptr, "mlp_half_pack: weights[%u] is NULL", l);
 		p.w[l] = (const __half *)weights[l];
 		p.b[l] = biases ? (const __half *)biases[l] : nullptr;
-		p.in_dim[l] = desc->dims[l]; p.out_dim[l] = desc->dims[l + 1];
-		p.ni[l] = l == 0 ? s.in_t : s.w_t;
-		p.no[l] = l + 1 == desc->n_layers ? s.out_t : s.w_t;
-		p.offset[l] = off;
-		off += layer_bytes(p.ni[l], p.no[l]);
 	}
-	p.offset[desc->n_layers] = off;
 	hipLaunchKernelGGL(k_mlph_pack, dim3(16, desc->n_layers), dim3(256), 0, (hipStream_t)stream, p, (unsigned char *)packed);
 	if (with_backward) {
 		PackArgs t = p;
 		t.transposed = 1;
-		uint32_t toff = 0;
-		for (uint32_t l = 0; l < desc->n_layers; ++l) {
-			t.ni[l] = p.no[l]; t.no[l] = p.ni[l];
-			t.offset[l] = toff;
-			toff += layer_bytes(t.ni[l], t.no[l]);
-		}
-		t.offset[desc->n_layers] = toff;
+		fill_layers(desc, s, true, layer_bytes, t);
 		hipLaunchKernelGGL(k_mlph_pack, dim3(16, desc->n_layers), dim3(256), 0, (hipStream_t)stream, t, (unsigned char *)packed + packed_bytes(s));
 	}
 	NR3D_LAUNCH_CHECK();
 	return 0;
 }
-
-#define MLPH_DISPATCH(S, ...)                                                                                  \
-	do {                                                                                                       \
-		const uint32_t _i = (S).in_t, _w = (S).w_t, _o = (S).out_t;                                            \
-		auto _go = [&](auto I, auto W, auto O) { constexpr int IN_T = decltype(I)::value, W_T = decltype(W)::value, OUT_T = decltype(O)::value; __VA_ARGS__; }; \
-		auto _ow = [&](auto I, auto W) {                                                                       \
-			if (_o == 1) _go(I, W, std::integral_constant<int, 1>{});                                          \
-			else if (_o == 2) _go(I, W, std::integral_constant<int, 2>{});                                     \
-			else _go(I, W, std::integral_constant<int, 4>{}); };                                               \
-		auto _iw = [&](auto I) {                                                                               \
-			if (_w == 1) _ow(I, std::integral_constant<int, 1>{});                                             \
-			else if (_w == 2) _ow(I, std::integral_constant<int, 2>{});                                        \
-			else _ow(I, std::integral_constant<int, 4>{}); };                                                  \
-		if (_i == 1) _iw(std::integral_constant<int, 1>{});                                                    \
-		else if (_i == 2) _iw(std::integral_constant<int, 2>{});                                               \
-		else _iw(std::integral_constant<int, 4>{});                                                            \
-	} while (0)
 
 extern "C" int nr3d_mlp_half_forward(const nr3d_mlp_desc_t *desc, uint64_t n, const void *x, int64_t x_stride, int64_t x_feature_stride,
                                      const void *packed, void *y, int64_t y_stride, void *stream) {
@@ -984,27 +912,29 @@ extern "C" int nr3d_mlp_half_forward(const nr3d_mlp_desc_t *desc, uint64_t n, co
 	if (n == 0) return 0;
 	NR3D_CHECK(x && packed && y, "mlp_half_forward: NULL pointer");
 	FwdArgs a;
-	const bool x_fm = x_feature_stride != 1;
-	NR3D_CHECK(!x_fm || x_stride == 1, "mlp_half_forward: x must be row-major (feature stride 1) or feature-major (row stride 1)");
-	a.n = n; a.x = (const __half *)x; a.xs = x_fm ? x_feature_stride : x_stride; a.y = (__half *)y; a.ys = y_stride;
+	Layout lx, ly;
+	NR3D_TRY(layout_of("mlp_half_forward", "x", x, x_stride, x_feature_stride, desc->dims[0], 8, lx));
+	NR3D_TRY(layout_of("mlp_half_forward", "y", y, y_stride, 1, desc->dims[desc->n_layers], 8, ly));
+	a.n = n; a.x = (const __half *)x; a.xs = lx.stride; a.y = (__half *)y; a.ys = ly.stride;
 	a.packed = (const unsigned char *)packed;
 	a.packed_bytes = (uint32_t)packed_bytes(s);
 	a.n_layers = desc->n_layers; a.in_dim = desc->dims[0]; a.out_dim = desc->dims[desc->n_layers];
 	a.hidden_act = (int)desc->hidden_activation; a.out_act = (int)desc->output_activation;
-	a.x_vec = ((uintptr_t)x % 8 == 0 && x_stride % 4 == 0) ? 1u : 0u;
-	a.y_vec = ((uintptr_t)y % 8 == 0 && y_stride % 4 == 0) ? 1u : 0u;
+	a.x_vec = lx.vec; a.y_vec = ly.vec;
 	const size_t lds = (size_t)a.packed_bytes;
 	const uint64_t n_tiles = (n + 31) / 32;
 	// 17 KB of weights per workgroup: several workgroups share a CU (the kernel streams x / y; waves hide each other's latency)
 	const uint32_t grid = (uint32_t)(n_tiles / 4 + 1 < 2048 ? n_tiles / 4 + 1 : 2048);
+	const int xf = fast_of(lx);
 	int rc = 0;
-	MLPH_DISPATCH(s, {
+	dispatch_tiles(s, [&](auto I, auto W, auto O) {
+		constexpr int IN_T = decltype(I)::value, W_T = decltype(W)::value, OUT_T = decltype(O)::value;
 		static LdsOnce once;
 		int dev = -1;
 		if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlph_fwd<IN_T, W_T, OUT_T, 0>, k_mlph_fwd<IN_T, W_T, OUT_T, 1>, k_mlph_fwd<IN_T, W_T, OUT_T, 2>))) return;
-		if (x_fm)
+		if (xf == 2)
 			hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 2>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
-		else if (a.x_vec && a.in_dim % 4 == 0)
+		else if (xf == 1)
 			hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 1>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 		else
 			hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 0>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
@@ -1022,13 +952,14 @@ extern "C" int nr3d_mlp_half_backward(const nr3d_mlp_desc_t *desc, uint64_t n, c
 	if (n == 0) return 0;
 	NR3D_CHECK(x && dL_dy && packed && dL_dW, "mlp_half_backward: NULL pointer");
 	BwdArgs a;
-	const bool x_fm = x_feature_stride != 1, gx_fm = dL_dx && gx_feature_stride != 1;
-	NR3D_CHECK(!x_fm || x_stride == 1, "mlp_half_backward: x must be row-major (feature stride 1) or feature-major (row stride 1)");
-	NR3D_CHECK(!gx_fm || gx_stride == 1, "mlp_half_backward: dL_dx must be row-major (feature stride 1) or feature-major (row stride 1)");
-	a.n = n; a.x = (const __half *)x; a.xs = x_fm ? x_feature_stride : x_stride; a.gy = (const __half *)dL_dy; a.gys = gy_stride;
+	Layout lx, lgy, lgx;
+	NR3D_TRY(layout_of("mlp_half_backward", "x", x, x_stride, x_feature_stride, desc->dims[0], 8, lx));
+	NR3D_TRY(layout_of("mlp_half_backward", "dL_dx", dL_dx, gx_stride, gx_feature_stride, desc->dims[0], 8, lgx));
+	NR3D_TRY(layout_of("mlp_half_backward", "dL_dy", dL_dy, gy_stride, 1, desc->dims[desc->n_layers], 8, lgy));
+	a.n = n; a.x = (const __half *)x; a.xs = lx.stride; a.gy = (const __half *)dL_dy; a.gys = lgy.stride;
 	a.packed = (const unsigned char *)packed;
-	a.gx = (__half *)dL_dx; a.gxs = gx_fm ? gx_feature_stride : gx_stride;
-	a.x_fm = x_fm ? 1u : 0u; a.gx_fm = gx_fm ? 1u : 0u;
+	a.gx = (__half *)dL_dx; a.gxs = lgx.stride;
+	a.x_fm = lx.fm; a.gx_fm = lgx.fm;
 	a.fwd_bytes = (uint32_t)packed_bytes(s);
 	a.total_bytes = a.fwd_bytes + (uint32_t)transposed_bytes(s);
 	for (uint32_t l = 0; l < desc->n_layers; ++l) {
@@ -1039,54 +970,34 @@ extern "C" int nr3d_mlp_half_backward(const nr3d_mlp_desc_t *desc, uint64_t n, c
 	for (uint32_t l = 0; l <= desc->n_layers; ++l) a.dims[l] = desc->dims[l];
 	a.n_layers = desc->n_layers;
 	a.hidden_act = (int)desc->hidden_activation; a.out_act = (int)desc->output_activation;
-	a.x_vec = ((uintptr_t)x % 8 == 0 && x_stride % 4 == 0) ? 1u : 0u;
-	a.gy_vec = ((uintptr_t)dL_dy % 8 == 0 && gy_stride % 4 == 0) ? 1u : 0u;
-	a.gx_vec = (dL_dx && (uintptr_t)dL_dx % 8 == 0 && gx_stride % 4 == 0) ? 1u : 0u;
+	a.x_vec = lx.vec; a.gy_vec = lgy.vec; a.gx_vec = lgx.vec;
 	a.tile_halfs = bwd_tile_halfs(s);
 	const uint32_t nh = desc->n_layers - 1;
-	const bool gy_fast = a.gy_vec && desc->dims[desc->n_layers] % 4 == 0;
-	const int fast = !gy_fast ? 0 : x_fm ? 2 : (a.x_vec && desc->dims[0] % 4 == 0) ? 1 : 0;
-	const uint64_t n_tiles = (n + 31) / 32;
-	const uint64_t reduce = ((uint64_t)s.w_t * s.w_t * 1024 + (uint64_t)s.w_t * 64) * 4;
+	const int fast = fast_of(lx, lgy);
+	const BwdPlan plan = bwd_plan_of(s, n);
+	auto launch = [&](auto kern) -> int {
+		NR3D_TRY(NR3D_LDS_LIMIT_ALWAYS(kMaxLdsBwd, kern));
+		hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(64 * plan.nw), plan.lds_bytes, (hipStream_t)stream, a);
+		return 0;
+	};
 	int rc = 0;
 	if (s.w_t == 2) {
-		// 64-wide hidden layers: dW split over the waves of the workgroup (k_mlph_bwd_split), eight waves where LDS holds their tiles
-		const uint32_t nw = split_waves(s);
-		const uint64_t tbytes = (uint64_t)nw * a.tile_halfs * 2;
-		const size_t lds = (size_t)a.total_bytes + (size_t)(tbytes > reduce ? tbytes : reduce);
-		const uint32_t grid = (uint32_t)(n_tiles / nw + 1 < 256 ? n_tiles / nw + 1 : 256);
-		auto launch = [&](auto kern) -> int {
-			NR3D_TRY(NR3D_LDS_LIMIT_ALWAYS(kMaxLdsBwd, kern));
-			hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, (hipStream_t)stream, a);
-			return 0;
-		};
 #define SPLIT_LAUNCH(I, O, H, NW_) (fast == 2 ? launch(k_mlph_bwd_split<I, 2, O, H, 2, NW_>) : fast == 1 ? launch(k_mlph_bwd_split<I, 2, O, H, 1, NW_>) : launch(k_mlph_bwd_split<I, 2, O, H, 0, NW_>))
-#define SPLIT_CASE(I, O, H) if (s.in_t == I && s.out_t == O && nh == H) rc = SPLIT_LAUNCH(I, O, H, 4); else
-		if (s.in_t == 1 && s.out_t == 1 && nh == 1) rc = nw == 8 ? SPLIT_LAUNCH(1, 1, 1, 8) : SPLIT_LAUNCH(1, 1, 1, 4);
-		else if (s.in_t == 1 && s.out_t == 1 && nh == 2) rc = nw == 8 ? SPLIT_LAUNCH(1, 1, 2, 8) : SPLIT_LAUNCH(1, 1, 2, 4);
-		else
+#define SPLIT_CASE(I, O, H) if (s.in_t == I && s.out_t == O && nh == H) { \
+		if constexpr (split_max_waves(I, O) == 8) rc = plan.nw == 8 ? SPLIT_LAUNCH(I, O, H, 8) : SPLIT_LAUNCH(I, O, H, 4); \
+		else rc = SPLIT_LAUNCH(I, O, H, 4); } else
+		SPLIT_CASE(1, 1, 1) SPLIT_CASE(1, 1, 2)
 		SPLIT_CASE(1, 2, 1) SPLIT_CASE(1, 2, 2) SPLIT_CASE(2, 1, 1) SPLIT_CASE(2, 1, 2) SPLIT_CASE(2, 2, 1) SPLIT_CASE(2, 2, 2)
 		rc = ::nr3d::fail("mlp_half_backward: no kernel for this shape");
 #undef SPLIT_LAUNCH
 #undef SPLIT_CASE
-		if (rc) return rc;
-		NR3D_LAUNCH_CHECK();
-		return 0;
-	}
-	const uint32_t nw = bwd_waves(s);
-	const uint64_t tbytes = (uint64_t)nw * a.tile_halfs * 2;
-	const size_t lds = (size_t)a.total_bytes + (size_t)(tbytes > reduce ? tbytes : reduce);
-	const uint32_t grid = (uint32_t)(n_tiles / nw + 1 < 256 ? n_tiles / nw + 1 : 256);     // one workgroup per CU: dW lives in registers
-	auto launch = [&](auto kern) -> int {
-		NR3D_TRY(NR3D_LDS_LIMIT_ALWAYS(kMaxLdsBwd, kern));
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, (hipStream_t)stream, a);
-		return 0;
-	};
+	} else {
 #define BWD_CASE(I, W, O, H) if (s.in_t == I && s.w_t == W && s.out_t == O && nh == H) \
 		rc = fast == 2 ? launch(k_mlph_bwd<I, W, O, H, 2>) : fast == 1 ? launch(k_mlph_bwd<I, W, O, H, 1>) : launch(k_mlph_bwd<I, W, O, H, 0>); else
-	BWD_CASE(1, 1, 1, 1) BWD_CASE(1, 1, 1, 2) BWD_CASE(1, 1, 1, 3)
-	rc = ::nr3d::fail("mlp_half_backward: no kernel for this shape");
+		BWD_CASE(1, 1, 1, 1) BWD_CASE(1, 1, 1, 2) BWD_CASE(1, 1, 1, 3)
+		rc = ::nr3d::fail("mlp_half_backward: no kernel for this shape");
 #undef BWD_CASE
+	}
 	if (rc) return rc;
 	NR3D_LAUNCH_CHECK();
 	return 0;

@@ -55,3 +55,30 @@ def test_packed_sizes_of_the_fused_decoder():
     for dims in ((32, 128, 128, 16), (32, 64, 64, 64, 16), (32, 32, 64)):
         d = _mlp.MLPDesc(list(dims), 1, 0)
         assert d.packed_floats > 0 and d.backward_floats == 0 and not d.backward_fusable, dims
+
+
+def test_size_queries_match_the_recorded_plan():
+    """the four size queries of the fused decoder (host arithmetic of csrc/mlp_plan.h, mlp.hip and mlp_half.hip: tile classes, LDS
+    limits, whether the fused backward applies) against tests/golden/mlp_plan_sizes.npz, which tests/golden/make_golden_mlp_sizes.py
+    recorded from the library BEFORE the plan became one shared header: 2..8 linear layers x input, uniform hidden and output widths
+    from {1, 32, 33, 64, 65, 96, 97, 128}, nets with mixed hidden widths, the invalid widths 0 and 129 -- exact equality"""
+    import ctypes as C
+    import os
+
+    import numpy as np
+    from nr3d_lib_amd import _hip as H
+    from nr3d_lib_amd.bindings import _mlp
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mlp_plan_sizes.npz"))
+    nets, sizes, queries = gold["nets"], gold["sizes"], [str(q) for q in gold["queries"]]
+    assert queries == ["nr3d_mlp_packed_floats", "nr3d_mlp_backward_packed_floats", "nr3d_mlp_half_packed_bytes",
+                       "nr3d_mlp_half_backward_packed_bytes"]
+    assert len(nets) == 7 * 8 ** 3 + 9 + 8 and sizes.shape == (len(nets), 4)
+    lib = H.lib()
+    for row, want in zip(nets, sizes):
+        c = _mlp._CDesc()
+        c.n_layers = int(row[0])
+        for i in range(c.n_layers + 1):
+            c.dims[i] = int(row[1 + i])
+        c.hidden_activation, c.output_activation = _mlp.ACT_RELU, _mlp.ACT_NONE
+        got = [int(getattr(lib, q)(C.byref(c))) for q in queries]
+        assert got == [int(v) for v in want], (row[1:2 + c.n_layers].tolist(), got, want.tolist())

@@ -541,3 +541,96 @@ def test_fp32_backward_on_the_bf16_mfma_is_fp32_grade(dev, hip_option, dims):
     assert max(err[0]) < 2e-5 and max(err[1]) < 2e-5, err
     for e0, e1 in zip(err[0], err[1]):
         assert e1 <= 3.0 * e0 + 1e-6, f"three-piece bf16 backward {e1:.2e} against the f32 MFMA's {e0:.2e}"
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# every entry of the backward dispatch tables, launched once: csrc/mlp.hip BWD_CASE over NR3D_MLP_BWD_SHAPES (mlp_plan.h) x FAST x the
+# bf16 route, csrc/mlp_half.hip BWD_CASE / SPLIT_CASE x FAST.  Dims from the tile classes (32 or 64 per tile); n = 257: eight waves
+# with a tile each + one partial tile + a second workgroup, the smallest size at which a wrong wave count, LDS size or grid of the
+# launch plan shows; n = 1: one partial tile
+# ------------------------------------------------------------------------------------------------------------------------
+BWD_SHAPES = [(1, 1, 1, 1), (1, 1, 1, 2), (1, 1, 1, 3), (1, 2, 1, 1), (1, 2, 1, 2), (1, 2, 2, 1), (1, 2, 2, 2),
+              (2, 2, 1, 1), (2, 2, 1, 2), (2, 2, 2, 1), (2, 2, 2, 2)]             # (in, width, out) tiles, hidden layers
+HALF_BWD_SHAPES = [(1, 1, 1, 1), (1, 1, 1, 2), (1, 1, 1, 3)] + [(i, 2, o, h) for i in (1, 2) for o in (1, 2) for h in (1, 2)]
+TABLE_NS = (257, 1)
+
+
+def _table_dims(shape, fast):
+    """fast 0: ragged widths (dL/dy rows of 3 / 33 elements have no aligned pieces); 1, 2: whole tiles"""
+    i, w, o, h = shape
+    return [32 * i - 14 if fast == 0 else 32 * i] + [32 * w] * h + [32 * o - 29 if fast == 0 else 32 * o]
+
+
+def _table_inputs(dims, n, fast, dev, dtype=torch.float32):
+    """x row-major (fast 0, 1) or feature-major (fast 2; for n = 1 the two coincide), dL/dy row-major"""
+    g = torch.Generator(device="cpu").manual_seed(100 + n)
+    x = torch.randn(n, dims[0], generator=g).to(dev).to(dtype)
+    gy = torch.randn(n, dims[-1], generator=g).to(dev).to(dtype)
+    return (x.t().contiguous().t() if fast == 2 else x), gy
+
+
+_table_refs = {}
+
+
+def _table_reference(key, m, x, gy):
+    """fp64 and fp32 torch evaluations of one (shape, fast, n): computed once, shared by the two mlp_x3 cases"""
+    if key not in _table_refs:
+        _table_refs[key] = (_reference(m, x, gy, torch.float64), _reference(m, x, gy, torch.float32))
+    return _table_refs[key]
+
+
+@pytest.mark.parametrize("x3", [0, 1])
+@pytest.mark.parametrize("fast", [0, 1, 2])
+@pytest.mark.parametrize("shape", BWD_SHAPES)
+def test_every_fp32_backward_table_entry(dev, hip_option, shape, fast, x3):
+    """k_mlp_bwd<I, W, O, H, FAST, X3> for every shape of the table, FAST 0 / 1 / 2 and both MFMA routes (shapes without a bf16
+    backward run the f32 kernel under mlp_x3 = 1), and the forward's XF / X3 selection with the same inputs -- against fp64 with
+    torch's own fp32 error as the yardstick"""
+    from nr3d_lib_amd.bindings import _mlp
+    hip_option("mlp_x3", x3)
+    dims = _table_dims(shape, fast)
+    m = _net(dims, "relu", None, True, dev, seed=21)
+    desc = m.fused_desc()
+    assert desc is not None and desc.backward_fusable
+    packed = _mlp.pack(desc, [l.weight for l in m.layers], [l.bias for l in m.layers], with_backward=True)
+    for n in TABLE_NS:
+        x, gy = _table_inputs(dims, n, fast, dev)
+        (y64, dx64, dW64, db64), (y32, dx32, dW32, db32) = _table_reference((shape, fast, n), m, x, gy)
+        _check(f"n={n} y", _mlp.forward(desc, x, packed), y64, y32)
+        dx, dWs, dbs = _mlp.backward(desc, x, gy, packed, need_dx=True)
+        assert n == 1 or fast != 2 or dx.stride() == (1, n)
+        _check(f"n={n} dL_dx", dx, dx64, dx32)
+        for l in range(len(dims) - 1):
+            _check(f"n={n} dL_dW{l}", dWs[l], dW64[l], dW32[l])
+            _check(f"n={n} dL_db{l}", dbs[l], db64[l], db32[l])
+
+
+@pytest.mark.parametrize("fast", [0, 1, 2])
+@pytest.mark.parametrize("shape", HALF_BWD_SHAPES)
+def test_every_half_backward_table_entry(dev, shape, fast):
+    """k_mlph_bwd<1, 1, 1, H, FAST> and k_mlph_bwd_split<I, 2, O, H, FAST, NW> for every shape of the two tables and FAST 0 / 1 / 2
+    (and k_mlph_fwd's XF with the same inputs): the yardsticks of test_half_fused_forward_backward"""
+    from nr3d_lib_amd.bindings import _mlp
+    from nr3d_lib_amd.models.blocks import MLP
+    dims = _table_dims(shape, fast)
+    torch.manual_seed(23)
+    m = MLP(dims[0], dims[-1], D=len(dims) - 2, W=dims[1:-1], activation="relu", bias=True, dtype=torch.half, device=dev)
+    with torch.no_grad():
+        for p in m.parameters():
+            p.copy_(torch.randn_like(p) * (0.4 if p.dim() > 1 else 0.2))
+    desc = m.fused_desc()
+    assert desc is not None and desc.half_backward_fusable
+    packed = _mlp.pack_half(desc, [l.weight for l in m.layers], [l.bias for l in m.layers], with_backward=True)
+    tol = 2.0 ** -7
+    for n in TABLE_NS:
+        x, gy = _table_inputs(dims, n, fast, dev, torch.half)
+        y64, dx64, dW64, db64 = _half_reference(m, x, gy)
+        _check_half(f"n={n} y", _mlp.forward_half(desc, x, packed), y64, 2.0 ** -9)
+        dx, dWs, dbs = _mlp.backward_half(desc, x, gy, packed, need_dx=True)
+        assert dx.dtype == torch.float16 and dx.shape == dx64.shape and (n == 1 or fast != 2 or dx.stride() == (1, n))
+        bad = ((dx.double() - dx64).abs().amax(1) > tol * float(dx64.abs().max()))
+        assert torch.isfinite(dx).all() and float(bad.float().mean()) <= 0.02, f"n={n} dL_dx: {int(bad.sum())} of {n} rows off"
+        for l in range(len(dims) - 1):
+            assert dWs[l].dtype == torch.float32
+            _check_half(f"n={n} dL_dW{l}", dWs[l], dW64[l], 4 * tol if n < 100 else tol)
+            _check_half(f"n={n} dL_db{l}", dbs[l], db64[l], 4 * tol if n < 100 else tol)

@@ -289,3 +289,40 @@ def test_sdf_chain_end_to_end(dev):
         scale = float(b.abs().max()) or 1.0
         err = float((a - b).abs().max()) / scale
         assert err < 1e-4, f"gradient {i}: rel err {err:.2e}"
+
+
+# (in, width, out) tiles and hidden layers of csrc/mlp.hip's BWD2_CASE table (NR3D_MLP_BWD_SHAPES, mlp_plan.h)
+BWD_SHAPES = [(1, 1, 1, 1), (1, 1, 1, 2), (1, 1, 1, 3), (1, 2, 1, 1), (1, 2, 1, 2), (1, 2, 2, 1), (1, 2, 2, 2),
+              (2, 2, 1, 1), (2, 2, 1, 2), (2, 2, 2, 1), (2, 2, 2, 2)]
+_table_refs = {}
+
+
+@pytest.mark.parametrize("x3", [0, 1])
+@pytest.mark.parametrize("shape", BWD_SHAPES)
+def test_every_double_backward_table_entry(dev, hip_option, shape, x3):
+    """k_mlp_bwd2<I, W, O, H, X3> for every shape of the table and both MFMA routes (shapes without a bf16 kernel run the f32 one
+    under mlp_x3 = 1), launched once each: ragged widths (18 / 50 in, 3 / 33 out), x feature-major and ddL_dx row-major, n = 257
+    (eight waves with a tile each + one partial tile + a second workgroup: the smallest size at which a wrong wave count, LDS size
+    or grid of the launch plan shows) and n = 1"""
+    from nr3d_lib_amd.bindings import _mlp
+    hip_option("mlp_x3", x3)
+    i, w, o, h = shape
+    dims = [32 * i - 14] + [32 * w] * h + [32 * o - 29]
+    m = _net(dims, "relu", None, True, dev, seed=21)
+    d = _desc(m)
+    assert d.second_order_fusable
+    ws, bs = _params(m)
+    packed = _mlp.pack(d, ws, bs, with_backward=True)
+    for n in (257, 1):
+        g = torch.Generator(device="cpu").manual_seed(100 + n)
+        x = torch.randn(n, dims[0], generator=g).to(dev)
+        gy = torch.randn(n, dims[-1], generator=g).to(dev)
+        v = torch.randn(n, dims[0], generator=g).to(dev)
+        if (shape, n) not in _table_refs:                  # computed once, shared by the two mlp_x3 cases
+            _table_refs[(shape, n)] = (_double_reference(m, x, gy, v, torch.float64), _double_reference(m, x, gy, v, torch.float32))
+        (ref64, ggy64), (ref32, ggy32) = _table_refs[(shape, n)]
+        dgy, dWs, _ = _mlp.backward_backward(d, _layouts(x, "feature_major"), gy, v, packed, need_dgy=True)
+        assert torch.isfinite(dgy).all()
+        _check(f"n={n} dL/d(dL_dy)", dgy, ggy64, ggy32)
+        for l, (a, r64, r32) in enumerate(zip(dWs, ref64, ref32)):
+            _check(f"n={n} dW[{l}]", a, r64, r32)
