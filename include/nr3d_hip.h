@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 17
+#define NR3D_ABI_VERSION 18
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -928,6 +928,52 @@ int nr3d_neus_upsample_max_row(void);
  * n + m <= NR3D_NEUS_UPSAMPLE_MAX_ROW, otherwise an error before any launch.  R == 0 is a no-op. */
 int nr3d_neus_upsample_stage(uint32_t R, uint32_t n, uint32_t m, const float *depth, const float *sdf, const float *u, int64_t u_stride,
                              float inv_s, int use_estimate, float *fine, float *merged, int32_t *order, void *stream);
+
+/* -------------------------------------------------------------------------------------------------
+ * The same stage on the packs of a marcher: the up-sampling of neus_ray_query_march_occ_multi_upsample[_compressed] in one launch
+ *   reference         the packed op chain of nr3d_lib/graphics/neus/neus_ray_query.py (neus_packed_sdf_to_alpha |
+ *                     neus_packed_sdf_to_upsample_alpha, packed_alpha_to_vw, packed_cumsum, packed_div, packed_sample_cdf,
+ *                     merge_two_packs_sorted_aligned and the index-puts of the driver); no native twin there
+ * One 64-lane wave per pack, four packs per workgroup, no workgroup barrier; no atomics, no host wait; every output element is written
+ * once by a fixed lane, so the result is the same bits run after run.
+ * ------------------------------------------------------------------------------------------------- */
+
+/* Packs with len + m up to this are staged in LDS (4 * 3 * this many floats per workgroup); longer ones run the same code on global
+ * memory with the CDF in the caller's workspace.  A compile-time choice (-DNR3D_NEUS_UPSAMPLE_PACKED_LDS_ROW=256|512|1024). */
+#ifndef NR3D_NEUS_UPSAMPLE_PACKED_LDS_ROW
+#define NR3D_NEUS_UPSAMPLE_PACKED_LDS_ROW 512
+#endif
+int nr3d_neus_upsample_packed_lds_row(void);
+
+/* depth, sdf float32 [N], packed: pack p holds the len_p elements from first_p on, pack_infos int64 [P, 2] = (first_p, len_p); depth is
+ * non-decreasing inside a pack.
+ * PRECONDITION: the packs tile [0, N) in order -- first_0 = 0, first_{p+1} = first_p + len_p, len_p >= 1 -- which is what every marcher
+ * of this library returns for its hit rays.  The layout of the outputs relies on it; a pack_infos that breaks it makes packs overlap
+ * in the outputs, but no access leaves the buffers (a pack is clipped to [0, N), and one without elements gets fine = 0).
+ * Per pack, with n = len_p (the last element of a pack closes no interval: alpha_{n-1} = 0):
+ *   opacity, use_estimate == 0 (neus_packed_sdf_to_alpha): c = sigmoid(sdf inv_s), alpha_i = max(0, (c_i - c_{i+1}) / (c_i + 1e-5));
+ *   use_estimate != 0 (neus_packed_sdf_to_upsample_alpha): dsdf_i = sdf_{i+1} - sdf_i, delta_i = depth_{i+1} - depth_i,
+ *     slope_i = dsdf_i / (delta_i + 1e-5), s_i = clamp(min(slope_{i-1}, slope_i), -10, 0) with slope_{-1} = 0, mid_i = sdf_i + dsdf_i / 2,
+ *     half_i = s_i delta_i / 2, c_prev|c_next = sigmoid((mid_i -|+ half_i) inv_s), alpha_i = max(0, (c_prev - c_next) / (c_prev + 1e-5));
+ *   weights (packed_alpha_to_vw, early_stop_eps 1e-4, alpha_thre 0): T_i = prod_{j<i, alpha_j > 0} (1 - alpha_j); w_i = alpha_i T_i while
+ *     T_i >= 1e-4, w_i = 0 from the first T_i < 1e-4 on (the product associates as a scan tree);
+ *   cdf_i = (sum_{j<i} w_j) / max(sum_{j<n-1} w_j, 1e-5): summed first, divided afterwards;
+ *   inversion (packed_invert_cdf) at u_j: pos = min(first k with cdf_k >= u_j, n - 1); pos == 0 -> depth_0; else pmf = cdf_pos - cdf_{pos-1},
+ *     pmf < 1e-5 -> depth_{pos-1}, otherwise fmaf((u_j - cdf_{pos-1}) / pmf, depth_pos - depth_{pos-1}, depth_{pos-1}); then raised to the
+ *     running maximum over j (a no-op wherever the expression is monotone in u).  A pack of one element therefore gives depth_0 and
+ *     one without mass depth_{n-2}, for every u.
+ * u: m >= 1 CDF positions per pack, non-decreasing; pack p reads u + p * u_stride, u_stride 0 (one shared row) or m.
+ * Outputs, fully written: fine [P, m].  With merge != 0 also merged [N + P m]: pack p starts at first_p + p m and is the sorted union of
+ * its depths and its new depths, a new depth BEFORE an old one of equal value and equal new depths in their order
+ * (merge_two_packs_sorted_aligned); pack_infos_out int64 [P, 2] = (first_p + p m, len_p + m); pidx_fine int64 [P, m] = the index in
+ * merged of every new depth.  With need_sdf != 0 (needs merge) sdf_merged [N + P m] holds every old SDF value at its depth's index in
+ * merged; the elements at pidx_fine are NOT written, the caller fills them with the SDF at the new depths.
+ * cdf_workspace: float32 [N], contents undefined on return; always required (packs longer than the LDS row keep their CDF there).
+ * Unused outputs may be NULL.  m >= 1, u_stride in {0, m}, N + P m < 2^31, otherwise an error before any launch.  P == 0 is a no-op. */
+int nr3d_neus_upsample_stage_packed(uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf, const int64_t *pack_infos,
+                                    const float *u, int64_t u_stride, float inv_s, int use_estimate, int merge, int need_sdf,
+                                    float *cdf_workspace, float *fine, float *merged, float *sdf_merged, int64_t *pidx_fine,
+                                    int64_t *pack_infos_out, void *stream);
 
 #ifdef __cplusplus
 }

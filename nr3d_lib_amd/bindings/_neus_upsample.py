@@ -1,30 +1,33 @@
-"""nr3d_lib_amd.bindings._neus_upsample -- one up-sampling stage of the vanilla NeuS coarse ray query in one launch
-(csrc/neus_upsample.hip through include/nr3d_hip.h).
+"""nr3d_lib_amd.bindings._neus_upsample -- one up-sampling stage of the NeuS ray queries in one launch (csrc/neus_upsample.hip
+through include/nr3d_hip.h): ``upsample_stage`` on the fixed-length rows of the vanilla coarse query, ``upsample_stage_packed`` on
+the packs of the occupancy-march queries.
 
 Like ``_mlp`` this module has NO reference twin: the reference runs a stage as a chain of torch ops between two SDF queries
 (nr3d_lib/graphics/neus/neus_ray_query.py:258-270).  ``graphics.neus.neus_ray_query.neus_ray_query_coarse_multi_upsample`` is its
-caller.  A CPU tensor raises RuntimeError; there is no fallback here."""
+caller of the row form, ``_upsample`` of the same module (``neus_ray_query_march_occ_multi_upsample[_compressed]``) of the packed one.
+A CPU tensor raises RuntimeError; there is no fallback here."""
 import torch
 
 from .. import _hip as H
 
-__all__ = ["MAX_ROW", "upsample_stage"]
+__all__ = ["MAX_ROW", "PACKED_LDS_ROW", "upsample_stage", "upsample_stage_packed"]
 
 
 def __getattr__(name):
     """``MAX_ROW``: the library's cap on n + m (NR3D_NEUS_UPSAMPLE_MAX_ROW), asked of the library so that it is stated once"""
     if name == "MAX_ROW":
         return int(H.lib().nr3d_neus_upsample_max_row())
+    if name == "PACKED_LDS_ROW":        # packs with len + m up to this are staged in LDS by upsample_stage_packed, longer ones are not
+        return int(H.lib().nr3d_neus_upsample_packed_lds_row())
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-def _chk(name, t, shape):
-    fn = "upsample_stage"
+def _chk(name, t, shape, fn="upsample_stage", dtype=torch.float32):
     if not isinstance(t, torch.Tensor):
         raise RuntimeError(f"{fn}: `{name}` must be a tensor, got {type(t).__name__}")
     H.require_gpu(t)
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{fn}: `{name}` must be float32, got {t.dtype}")
+    if t.dtype != dtype:
+        raise RuntimeError(f"{fn}: `{name}` must be {str(dtype).split('.')[-1]}, got {t.dtype}")
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise RuntimeError(f"{fn}: `{name}` must be {list(shape)}, got {list(t.shape)}")
     if not t.is_contiguous():
@@ -69,3 +72,59 @@ def upsample_stage(depth, sdf, u, inv_s, use_estimate):
                                                      1 if use_estimate else 0, H.ptr(fine), H.ptr(merged), H.ptr(order),
                                                      H.stream_of(depth)))
     return fine, merged, order
+
+
+def upsample_stage_packed(depth, sdf, pack_infos, u, inv_s, use_estimate, merge=True, need_sdf=True):
+    """The stage on packs.  depth, sdf float32 [N], packed (depth non-decreasing inside a pack); pack_infos int64 [P, 2] = (first, len);
+    u float32 [m] (one row of CDF positions for every pack) or [P, m] (per pack), non-decreasing, m >= 1.
+    PRECONDITION: the packs tile [0, N) in order -- first_0 = 0, first_{p+1} = first_p + len_p, len_p >= 1 -- as the ``pack_infos`` of
+    the hit rays of every marcher of this library do.  The layout of the outputs relies on it; it is not checked (that would be a
+    host wait), and breaking it makes packs overlap in the outputs without any access leaving the buffers.
+    -> (fine [P, m]: ``packed_sample_cdf`` of the pack's up-sampling CDF at u -- the opacity of ``neus_packed_sdf_to_alpha``, or of
+    ``neus_packed_sdf_to_upsample_alpha`` with ``use_estimate``, through ``packed_alpha_to_vw`` and the normalised exclusive
+    ``packed_cumsum``;
+    merged [N + P m]: per pack the sorted union of depth and fine, pack p starting at first_p + p m, a new depth before an equal old one
+    (``merge_two_packs_sorted_aligned``);
+    sdf_merged [N + P m]: sdf at the old depths' places in merged; the places ``pidx_fine`` are left for the caller to fill;
+    pidx_fine int64 [P, m]: the index in merged of every new depth;
+    pack_infos_out int64 [P, 2] = (first_p + p m, len_p + m)).
+    ``merge=False`` returns None for the last four (and needs no ``need_sdf``), ``need_sdf=False`` None for sdf_merged.
+    Packs of any length are served: those with len + m <= PACKED_LDS_ROW in LDS, longer ones on global memory."""
+    fn = "upsample_stage_packed"
+    _chk("depth", depth, None, fn)
+    if depth.dim() != 1:
+        raise RuntimeError(f"{fn}: `depth` must be [N], got {list(depth.shape)}")
+    N = depth.shape[0]
+    _chk("sdf", sdf, (N,), fn)
+    _chk("pack_infos", pack_infos, None, fn, torch.int64)
+    if pack_infos.dim() != 2 or pack_infos.shape[1] != 2:
+        raise RuntimeError(f"{fn}: `pack_infos` must be [P, 2], got {list(pack_infos.shape)}")
+    P = pack_infos.shape[0]
+    _chk("u", u, None, fn)
+    if u.dim() == 1 and u.shape[0] >= 1:
+        m, u_stride = u.shape[0], 0
+    elif u.dim() == 2 and u.shape[0] == P and u.shape[1] >= 1:
+        m, u_stride = u.shape[1], u.shape[1]
+    else:
+        raise RuntimeError(f"{fn}: `u` must be [m] or [{P}, m] with m >= 1, got {list(u.shape)}")
+    dev = depth.device
+    for name, t in (("sdf", sdf), ("pack_infos", pack_infos), ("u", u)):
+        if t.device != dev:
+            raise RuntimeError(f"{fn}: `{name}` is on {t.device}, depth on {dev}")
+    if N + P * m >= 2 ** 31:
+        raise RuntimeError(f"{fn}: N + P m = {N + P * m}, the merged buffer holds at most 2^31 - 1 elements (split the batch)")
+    need_sdf = bool(merge and need_sdf)
+    fine = H.empty((P, m), dtype=torch.float32, device=dev)
+    merged = H.empty((N + P * m,), dtype=torch.float32, device=dev) if merge else None
+    sdf_merged = H.empty((N + P * m,), dtype=torch.float32, device=dev) if need_sdf else None
+    pidx_fine = H.empty((P, m), dtype=torch.int64, device=dev) if merge else None
+    pack_infos_out = H.empty((P, 2), dtype=torch.int64, device=dev) if merge else None
+    if P:
+        workspace = H.empty((max(N, 1),), dtype=torch.float32, device=dev)       # the CDF of the packs that do not fit the LDS row
+        with H.on_device(dev):
+            H.check(H.lib().nr3d_neus_upsample_stage_packed(P, N, m, H.ptr(depth), H.ptr(sdf), H.ptr(pack_infos), H.ptr(u), u_stride,
+                                                            float(inv_s), 1 if use_estimate else 0, 1 if merge else 0,
+                                                            1 if need_sdf else 0, H.ptr(workspace), H.ptr(fine), H.ptr(merged),
+                                                            H.ptr(sdf_merged), H.ptr(pidx_fine), H.ptr(pack_infos_out),
+                                                            H.stream_of(depth)))
+    return fine, merged, sdf_merged, pidx_fine, pack_infos_out

@@ -1,4 +1,5 @@
-// nr3d_lib_amd/csrc/neus_upsample.hip -- one up-sampling stage of the vanilla NeuS coarse ray query on fixed-length rows, in one launch.
+// nr3d_lib_amd/csrc/neus_upsample.hip -- one up-sampling stage of the NeuS ray queries in one launch: on the fixed-length rows of the
+// vanilla coarse query (k_stage) and on the packs of the occupancy-march queries (k_stage_packed, further down).
 //
 // The reference runs a stage between two SDF queries as a chain of small torch ops (nr3d_lib/graphics/neus/neus_ray_query.py:258-270:
 // neus_ray_sdf_to_alpha | neus_ray_sdf_to_upsample_alpha -> ray_alpha_to_vw -> batch_sample_pdf -> cat -> sort).  Rows hold tens to a
@@ -158,6 +159,162 @@ __global__ __launch_bounds__(kWaves * 64) void k_stage(uint32_t R, int n, int m,
 	}
 }
 
+// ---- the packed stage: the same scheme on the packs of a marcher (nr3d_neus_upsample_stage_packed) ----------------------------------
+// One wave per pack, its length from pack_infos.  The arithmetic restates the packed op chain of the march-occ drivers
+// (neus_packed_sdf_to_alpha | neus_packed_sdf_to_upsample_alpha -> packed_alpha_to_vw -> exclusive packed_cumsum -> packed_div ->
+// packed_invert_cdf -> merge_two_packs_sorted_aligned), which is not the row chain above: the estimate's mid-point and half step are
+// formed differently, the weights stop at a transmittance below 1e-4, the CDF is summed first and divided afterwards, the inversion
+// returns the bin's lower depth for a pmf below 1e-5 and lerps with one fmaf, and the merge puts a new depth BEFORE an equal old one.
+constexpr int kPackedLdsRow = NR3D_NEUS_UPSAMPLE_PACKED_LDS_ROW;   // packs with len + m up to this are staged: kWaves * 3 L floats of LDS
+
+// The body over the pack's four arrays: D, S = depths and SDF [n], C = the CDF [n], F = the new depths [m].  Called once with LDS
+// pointers and once with global ones; inlined, each call resolves to DS or global instructions.  Only this wave touches these rows, in
+// both address spaces: what its lanes store is read back by other lanes of the same wave after wave_sync().  That is enough for the
+// global arrays too: a wave's vector memory instructions reach its compute unit's L1 in program order, the L1 is write-through and
+// shared by nothing that writes these rows, so a load issued after a store of the same wave returns the stored value; the
+// wavefront-scope fence keeps the compiler from moving the accesses across it, and no wider scope is needed because no other wave,
+// workgroup or atomic is involved.
+template <bool ESTIMATE, bool STAGED>
+__device__ __forceinline__ void packed_body(int n, int m, int lane, const float *D, const float *S, float *C, float *F,
+                                            const float *__restrict__ u_row, float inv_s, float *__restrict__ fine_row, bool merge,
+                                            int64_t out_begin, float *__restrict__ m_row, float *__restrict__ s_row,
+                                            int64_t *__restrict__ pidx_row) {
+	// ---- weights of the n - 1 intervals (w_{n-1} = 0) and, at the same index, their exclusive sum into C ----
+	float carry_T = 1.0f, carry_c = 0.0f;
+	bool stopped = false;
+	for (int b = 0; b < n; b += 64) {
+		const int i = b + lane;
+		float alpha = 0.0f;
+		if (i < n - 1) {
+			const float s0 = S[i], s1 = S[i + 1];
+			float c_prev, c_next;
+			if (ESTIMATE) {
+				const float d0 = D[i], delta = D[i + 1] - d0, d_sdf = s1 - s0;
+				const float slope = d_sdf / (delta + 1e-5f);
+				const float before = i > 0 ? (s0 - S[i - 1]) / ((d0 - D[i - 1]) + 1e-5f) : 0.0f;
+				const float sl = fminf(fmaxf(fminf(before, slope), -10.0f), 0.0f);
+				const float mid = s0 + d_sdf * 0.5f, half = sl * delta * 0.5f;
+				c_prev = sigmoidf((mid - half) * inv_s);
+				c_next = sigmoidf((mid + half) * inv_s);
+			} else {
+				c_prev = sigmoidf(s0 * inv_s);
+				c_next = sigmoidf(s1 * inv_s);
+			}
+			alpha = fmaxf((c_prev - c_next) / (c_prev + 1e-5f), 0.0f);
+		}
+		// packed_alpha_to_vw(early_stop_eps = 1e-4, alpha_thre = 0): an alpha <= 0 leaves T as it is; w = alpha T while T >= 1e-4 and
+		// 0 from the first T below on (decided on the scanned T: the product associates as a tree)
+		const float incl = wave_incl_mul(alpha <= 0.0f ? 1.0f : 1.0f - alpha, lane);
+		float excl = __shfl_up(incl, 1, 64);
+		if (lane == 0) excl = 1.0f;
+		const float T = carry_T * excl;
+		const unsigned long long below = __ballot(T < 1e-4f);
+		const int first = below ? __ffsll((long long)below) - 1 : 64;
+		const float w = (stopped || lane >= first) ? 0.0f : alpha * T;
+		stopped = stopped || below != 0ull;
+		carry_T *= __shfl(incl, 63, 64);
+		const float incl_w = carry_c + wave_incl_add(w, lane);
+		const float before_w = __shfl_up(incl_w, 1, 64);
+		if (i < n) C[i] = lane == 0 ? carry_c : before_w;
+		carry_c = __shfl(incl_w, 63, 64);
+	}
+	wave_sync();
+
+	// ---- cdf_i / max(cdf_{n-1}, 1e-5) ----
+	const float norm = n > 0 ? fmaxf(C[n - 1], 1e-5f) : 1.0f;
+	wave_sync();                                              // every lane holds cdf_{n-1} before its owner divides it
+	for (int i = lane; i < n; i += 64) C[i] = C[i] / norm;
+	wave_sync();
+
+	// ---- inverse CDF at every u_j (k_invert_cdf, pack_ops.hip) ----
+	float carry_f = -INFINITY;
+	for (int b = 0; b < m; b += 64) {
+		const int j = b + lane;
+		float f = -INFINITY;
+		if (j < m) {
+			f = 0.0f;                                         // a pack without elements (outside the contract) has nothing to read
+			if (n > 0) {
+				const float uj = u_row[j];
+				int lo = 0, hi = n;                           // first k with C[k] >= uj, n when there is none
+				while (lo < hi) {
+					const int mid = (lo + hi) >> 1;
+					if (C[mid] < uj) lo = mid + 1; else hi = mid;
+				}
+				const int pos = min(lo, n - 1);
+				if (pos == 0) f = D[0];
+				else {
+					const float c0 = C[pos - 1], pmf = C[pos] - c0, d0 = D[pos - 1];
+					f = pmf < 1e-5f ? d0 : fmaf((uj - c0) / pmf, D[pos] - d0, d0);
+				}
+			}
+		}
+		// as in k_stage: the running maximum keeps the new depths non-decreasing, which the merge relies on; it changes nothing
+		// wherever the expression is monotone in u already
+		f = fmaxf(wave_incl_max(f, lane), carry_f);
+		carry_f = __shfl(f, 63, 64);
+		if (j < m) {
+			F[j] = f;
+			if (STAGED) fine_row[j] = f;
+		}
+	}
+	if (!merge) return;
+	wave_sync();
+
+	// ---- merge path, a new depth before an equal old one (k_merge: the lower bound of the new value among the old ones): output slot
+	// q takes D[i] or F[q - i], i = the number of old depths among the first q outputs; every index is in range by construction ----
+	const int nm = n + m;
+	for (int q = lane; q < nm; q += 64) {
+		int lo = max(0, q - m), hi = min(q, n);
+		while (lo < hi) {
+			const int mid = (lo + hi) >> 1;                    // lo <= mid < hi: mid < n, 1 <= q - mid <= m
+			if (D[mid] < F[q - mid - 1]) lo = mid + 1; else hi = mid;
+		}
+		const int i = lo, j = q - lo;
+		const bool old = i < n && (j >= m || D[i] < F[j]);
+		m_row[q] = old ? D[i] : F[j];
+		if (!old) pidx_row[j] = out_begin + q;
+		else if (s_row) s_row[q] = S[i];
+	}
+}
+
+template <bool ESTIMATE>
+__global__ __launch_bounds__(kWaves * 64) void k_stage_packed(uint32_t P, int64_t N, int m, const float *__restrict__ depth,
+                                                               const float *__restrict__ sdf, const int64_t *__restrict__ pack_infos,
+                                                               const float *__restrict__ u, int64_t u_stride, float inv_s,
+                                                               float *__restrict__ cdf_ws, float *__restrict__ fine,
+                                                               float *__restrict__ merged, float *__restrict__ sdf_merged,
+                                                               int64_t *__restrict__ pidx_fine, int64_t *__restrict__ pack_infos_out) {
+	__shared__ __attribute__((aligned(16))) float lds[kWaves * 3 * kPackedLdsRow];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const uint32_t p = blockIdx.x * kWaves + wave;
+	if (p >= P) return;                                   // wave-uniform; nothing below synchronises across waves
+	// the pack, clipped to [0, N): whatever pack_infos holds, every access below stays inside the buffers
+	const int64_t b64 = pack_infos[2 * (size_t)p], n64 = pack_infos[2 * (size_t)p + 1];
+	const int64_t first = b64 < 0 ? 0 : (b64 > N ? N : b64);
+	const int n = (int)(n64 < 0 ? 0 : (n64 > N - first ? N - first : n64));
+	const int64_t out_begin = first + (int64_t)p * m;
+	const float *d_row = depth + first, *s_row = sdf + first, *u_row = u + (int64_t)p * u_stride;
+	float *f_row = fine + (size_t)p * m;
+	const bool merge = merged != nullptr;
+	float *mo = merge ? merged + out_begin : nullptr, *so = sdf_merged ? sdf_merged + out_begin : nullptr;
+	int64_t *po = merge ? pidx_fine + (size_t)p * m : nullptr;
+	if (merge && lane == 0) {
+		pack_infos_out[2 * (size_t)p] = out_begin;
+		pack_infos_out[2 * (size_t)p + 1] = (int64_t)n + m;
+	}
+	if (n + m <= kPackedLdsRow) {                         // wave-uniform
+		float *D = lds + (size_t)wave * (3 * kPackedLdsRow), *S = D + n, *C = S + n, *F = C + n;
+		for (int i = lane; i < n; i += 64) {
+			D[i] = d_row[i];
+			S[i] = s_row[i];
+		}
+		wave_sync();
+		packed_body<ESTIMATE, true>(n, m, lane, D, S, C, F, u_row, inv_s, f_row, merge, out_begin, mo, so, po);
+	} else {
+		packed_body<ESTIMATE, false>(n, m, lane, d_row, s_row, cdf_ws + first, f_row, u_row, inv_s, nullptr, merge, out_begin, mo, so, po);
+	}
+}
+
 }  // namespace neus_upsample
 }  // namespace nr3d
 
@@ -186,6 +343,36 @@ extern "C" int nr3d_neus_upsample_stage(uint32_t R, uint32_t n, uint32_t m, cons
 	else
 		hipLaunchKernelGGL(neus_upsample::k_stage<false>, grid, block, lds, st, R, (int)n, (int)m, depth, sdf, u, u_stride, inv_s, fine,
 		                   merged, order);
+	NR3D_LAUNCH_CHECK();
+	return 0;
+}
+
+extern "C" int nr3d_neus_upsample_packed_lds_row(void) { return neus_upsample::kPackedLdsRow; }
+
+extern "C" int nr3d_neus_upsample_stage_packed(uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf,
+                                               const int64_t *pack_infos, const float *u, int64_t u_stride, float inv_s, int use_estimate,
+                                               int merge, int need_sdf, float *cdf_workspace, float *fine, float *merged,
+                                               float *sdf_merged, int64_t *pidx_fine, int64_t *pack_infos_out, void *stream) {
+	NR3D_CHECK(m >= 1, "neus_upsample_stage_packed: m = %u, at least 1 new depth per pack", m);
+	NR3D_CHECK(u_stride == 0 || u_stride == (int64_t)m, "neus_upsample_stage_packed: u_stride = %lld, must be 0 (one shared row) or m = %u",
+	           (long long)u_stride, m);
+	NR3D_CHECK(N < (1ull << 31) && N + (uint64_t)P * m < (1ull << 31),
+	           "neus_upsample_stage_packed: N + P m = %llu + %u * %u, the merged buffer holds at most 2^31 - 1 elements",
+	           (unsigned long long)N, P, m);
+	NR3D_CHECK(!need_sdf || merge, "neus_upsample_stage_packed: need_sdf without merge");
+	if (P == 0) return 0;
+	NR3D_CHECK(depth && sdf && pack_infos && u && cdf_workspace && fine, "neus_upsample_stage_packed: NULL tensor pointer");
+	NR3D_CHECK(!merge || (merged && pidx_fine && pack_infos_out), "neus_upsample_stage_packed: merge without merged, pidx_fine or pack_infos_out");
+	NR3D_CHECK(!need_sdf || sdf_merged, "neus_upsample_stage_packed: need_sdf without sdf_merged");
+	const dim3 grid(div_up(P, neus_upsample::kWaves)), block(neus_upsample::kWaves * 64);
+	hipStream_t st = (hipStream_t)stream;
+	float *mg = merge ? merged : nullptr, *sm = need_sdf ? sdf_merged : nullptr;
+	if (use_estimate)
+		hipLaunchKernelGGL(neus_upsample::k_stage_packed<true>, grid, block, 0, st, P, (int64_t)N, (int)m, depth, sdf, pack_infos, u, u_stride,
+		                   inv_s, cdf_workspace, fine, mg, sm, pidx_fine, pack_infos_out);
+	else
+		hipLaunchKernelGGL(neus_upsample::k_stage_packed<false>, grid, block, 0, st, P, (int64_t)N, (int)m, depth, sdf, pack_infos, u, u_stride,
+		                   inv_s, cdf_workspace, fine, mg, sm, pidx_fine, pack_infos_out);
 	NR3D_LAUNCH_CHECK();
 	return 0;
 }

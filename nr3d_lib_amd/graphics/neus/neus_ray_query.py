@@ -12,7 +12,8 @@ opacity -> ``packed_alpha_to_vw`` -> exclusive ``packed_cumsum`` normalised with
 
 ``neus_ray_query_coarse_multi_upsample`` (:132-356) is the vanilla NeuS query that needs no occupancy grid: coarse boundaries on
 every ray between ``near`` and ``far``, the up-sampling on fixed-length rows, one query at the mid-points.  Its stage runs in one
-launch (``bindings._neus_upsample.upsample_stage``) while ``FUSED_UPSAMPLE`` is set."""
+launch (``bindings._neus_upsample.upsample_stage``) while ``FUSED_UPSAMPLE`` is set.  The stage of the march-occ drivers runs in
+one launch on the packs (``upsample_stage_packed``) while ``FUSED_UPSAMPLE_PACKED`` is set, in place of the pack-op chain above."""
 from types import SimpleNamespace
 from typing import Dict, List, Tuple
 
@@ -36,6 +37,9 @@ __all__ = ['neus_ray_query_sphere_trace', 'neus_ray_query_coarse_multi_upsample'
 # The stage of neus_ray_query_coarse_multi_upsample between two SDF queries: True = one launch of the HIP kernel for rows that are
 # float32, on the GPU and within _neus_upsample.MAX_ROW; False (and every other row) = the reference's torch op chain.  Same semantics.
 FUSED_UPSAMPLE = True
+# The stage of the march-occ drivers (_upsample): True = one launch of the packed HIP kernel per stage for float32 samples on the GPU,
+# no merge on the last stage; False (and every other input) = the reference's pack-op chain.  Same semantics.
+FUSED_UPSAMPLE_PACKED = True
 
 _RAY_ATTRS = (('ts', 'rays_ts'), ('fidx', 'rays_fidx'), ('bidx', 'rays_bidx'), ('pix', 'rays_pix'),
               ('h_appear', 'rays_h_appear'))
@@ -152,8 +156,21 @@ def _upsample(q, marched, upsample_inv_s_factors, upsample_use_estimate_alpha, p
     sdf = _chunked(lambda x, **kw: q.query_sdf(x, kw),
                    dict(x=marched.samples, **q.sdf_attrs(lambda t: t[marched.ridx])), chunksize_query)
     stage_depths = []
+    fused = FUSED_UPSAMPLE_PACKED and depth_samples.is_cuda and depth_samples.dtype == torch.float32 and sdf.dtype == torch.float32
     for i, factor in enumerate(upsample_inv_s_factors):
         inv_s = q.upsample_inv_s * factor
+        if fused:
+            more = i < q.n_stages - 1                      # the last stage's union is read by nobody
+            u = cdf_positions(depth_samples, (n_hit,), q.num_fine[i], perturb)
+            fine, merged, sdf_m, pidx1, pinfo = _neus_upsample.upsample_stage_packed(
+                depth_samples.contiguous(), sdf.contiguous(), pack_infos, u, inv_s, upsample_use_estimate_alpha, merge=more, need_sdf=more)
+            stage_depths.append(fine)
+            if more:
+                x_fine = torch.addcmul(o_hit, d_hit, fine.unsqueeze(-1)).flatten(0, -2)
+                extra = {k: v.flatten(0, 1) for k, v in q.sdf_attrs(q.spread(hit, q.num_fine[i])).items()}
+                sdf_m[pidx1.flatten()] = q.query_sdf(x_fine, extra).to(sdf_m.dtype)
+                depth_samples, sdf, pack_infos = merged, sdf_m, pinfo
+            continue
         alpha = (neus_packed_sdf_to_upsample_alpha(sdf, depth_samples, inv_s, pack_infos) if upsample_use_estimate_alpha
                  else neus_packed_sdf_to_alpha(sdf, inv_s, pack_infos))
         cdf = packed_cumsum(packed_alpha_to_vw(alpha, pack_infos), pack_infos, exclusive=True)
