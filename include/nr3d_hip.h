@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 18
+#define NR3D_ABI_VERSION 19
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -448,13 +448,21 @@ int nr3d_occ_apply_max(uint64_t n_voxels, float ema_decay, const float *vmax, fl
  *   pass).
  * ============================================================================================== */
 #define NR3D_MLP_MAX_LAYERS 8
-enum { NR3D_MLP_ACT_NONE = 0, NR3D_MLP_ACT_RELU = 1 };
+/* NR3D_MLP_ACT_SOFTPLUS (ABI 19): torch.nn.Softplus(beta = softplus_beta, threshold = 20) -- h = z where beta z > 20, else
+ * log1p(exp(beta z)) / beta, evaluated on the fp32 accumulator -- the activation of the reference's SDF decoders
+ * (nr3d_lib/models/fields/sdf/mlp_sdf.py:30: {'type': 'softplus', 'beta': 100.}).  A HIDDEN activation only, on the forward and the
+ * first backward of both precisions: as output_activation, or with a softplus_beta that is not finite or not > 0, every size query
+ * below returns 0 (the caller keeps its unfused path).  A valid softplus network has the sizes of the same dims with ReLU.  The
+ * fused double backward does not take it (nr3d_mlp_backward_backward_ok returns 0). */
+enum { NR3D_MLP_ACT_NONE = 0, NR3D_MLP_ACT_RELU = 1, NR3D_MLP_ACT_SOFTPLUS = 2 };
 
 typedef struct nr3d_mlp_desc {
 	uint32_t n_layers;                          /* linear layers: hidden layers + 1 */
 	uint32_t dims[NR3D_MLP_MAX_LAYERS + 1];
 	uint32_t hidden_activation;                 /* NR3D_MLP_ACT_* after every hidden layer */
-	uint32_t output_activation;
+	uint32_t output_activation;                 /* NR3D_MLP_ACT_NONE or NR3D_MLP_ACT_RELU */
+	float softplus_beta;                        /* read only when hidden_activation == NR3D_MLP_ACT_SOFTPLUS (ABI 19; at the end: a
+	                                             * zero-initialised desc with ReLU / no activations means what it meant before) */
 } nr3d_mlp_desc_t;
 
 uint64_t nr3d_mlp_packed_floats(const nr3d_mlp_desc_t *desc);
@@ -482,7 +490,9 @@ int nr3d_mlp_forward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, in
  *   dL/db_l and dL/dx are zero (the network is piecewise linear) and are not produced.
  * packed comes from nr3d_mlp_pack(..., with_backward = 1); the forward is recomputed with nr3d_mlp_backward's route under the same
  * options (NR3D_OPT_MLP_X3), so the masks are bit for bit the ones its dL/dx used.  nr3d_mlp_backward_backward_ok: 1 when the
- * fused double backward applies (the shapes of nr3d_mlp_backward), else 0: the caller differentiates its unfused path. */
+ * fused double backward applies (the shapes of nr3d_mlp_backward with ReLU / no hidden activation), else 0: the caller differentiates
+ * its unfused path.  Softplus hidden layers are outside it (the network is not piecewise linear: dL/db_l and dL/dx are not zero);
+ * nr3d_mlp_backward_backward then fails with a message. */
 int nr3d_mlp_backward_backward_ok(const nr3d_mlp_desc_t *desc);
 int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, int64_t x_stride, int64_t x_feature_stride,
                                const float *dL_dy, int64_t gy_stride, const float *ddL_dx, int64_t v_stride, int64_t v_feature_stride,

@@ -8,26 +8,29 @@ import torch
 from .. import _hip as H
 
 MAX_LAYERS = 8
-ACT_NONE, ACT_RELU = 0, 1
+ACT_NONE, ACT_RELU, ACT_SOFTPLUS = 0, 1, 2
 
 
 class _CDesc(C.Structure):
     _fields_ = [("n_layers", C.c_uint32), ("dims", C.c_uint32 * (MAX_LAYERS + 1)), ("hidden_activation", C.c_uint32),
-                ("output_activation", C.c_uint32)]
+                ("output_activation", C.c_uint32), ("softplus_beta", C.c_float)]
 
 
 class MLPDesc:
-    """dims = [in_features, hidden..., out_features]"""
+    """dims = [in_features, hidden..., out_features]; beta: of ``hidden_activation=ACT_SOFTPLUS`` (torch.nn.Softplus(beta,
+    threshold=20) after every hidden layer; forward and first backward of both precisions, no fused double backward), not read otherwise"""
 
-    def __init__(self, dims, hidden_activation=ACT_RELU, output_activation=ACT_NONE):
+    def __init__(self, dims, hidden_activation=ACT_RELU, output_activation=ACT_NONE, beta=1.0):
         self.dims = [int(d) for d in dims]
         self.hidden_activation, self.output_activation = int(hidden_activation), int(output_activation)
+        self.beta = float(beta)
         c = _CDesc()
         n_layers = len(self.dims) - 1
         c.n_layers = n_layers if 1 <= n_layers <= MAX_LAYERS else 0
         for i, d in enumerate(self.dims[:MAX_LAYERS + 1]):
             c.dims[i] = d
         c.hidden_activation, c.output_activation = self.hidden_activation, self.output_activation
+        c.softplus_beta = self.beta if self.hidden_activation == ACT_SOFTPLUS else 0.0
         self._c = c
         l = H.lib()
         self.packed_floats = l.nr3d_mlp_packed_floats(C.byref(c)) if c.n_layers else 0
@@ -173,7 +176,8 @@ def backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, packed: torch.
 def backward_backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, ddL_dx: torch.Tensor, packed: torch.Tensor, need_dgy=True,
                       has_bias=None):
     """The double backward: gradients of <dL/dx, ddL_dx> (dL/dx = backward()'s, a function of the parameters and dL_dy) ->
-    (dL/d(dL_dy) | None, [dL/dW_l], [dL/db_l | None]).  dL/dx and dL/db_l are zero (the network is piecewise linear): dL/dx is not
+    (dL/d(dL_dy) | None, [dL/dW_l], [dL/db_l | None]).  ReLU / linear networks only (softplus hidden layers: desc.second_order_fusable is
+    False and the caller differentiates its torch route).  dL/dx and dL/db_l are zero (the network is piecewise linear): dL/dx is not
     produced, dL/db_l are zero views of the dW pool for the layers has_bias marks (default: none).  x and ddL_dx row-major with any
     row stride or feature-major, dL_dy rows with any row stride (0 included: an expanded ones); `packed` from
     pack(..., with_backward=True).  dL/d(dL_dy) has dL_dy's shape."""

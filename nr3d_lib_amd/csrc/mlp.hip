@@ -120,11 +120,13 @@ struct FwdArgs {
 	uint32_t n_layers, in_dim, out_dim;
 	int hidden_act, out_act;
 	uint32_t x_vec, y_vec;
+	float beta;                                // of a softplus hidden activation (the SP instantiations)
 };
 
 // (X3, one input and one output tile, hidden layers up to 64 wide: two workgroups per CU = two waves per SIMD -- the piece splitting is VALU work, the products MFMA work, and
 // only ANOTHER wave's instructions overlap them; at 260 registers the first version ran one wave per SIMD and the two added up)
-template <int IN_T, int W_T, int OUT_T, int XF, bool X3 = false>
+// SP: the hidden activation is softplus (mlp_device.h hidden_layer); a.hidden_act is not read
+template <int IN_T, int W_T, int OUT_T, int XF, bool X3 = false, bool SP = false>
 __global__ __launch_bounds__(kThreads, (X3 && IN_T == 1 && W_T <= 2 && OUT_T == 1) ? 2 : 1) void k_mlp_fwd(FwdArgs a) {
 	extern __shared__ __attribute__((aligned(16))) float lds[];
 	stage_weights(a.packed, a.packed_floats, lds);          // (X3: a.packed points at the x3 region, a.packed_floats is its size)
@@ -152,13 +154,11 @@ __global__ __launch_bounds__(kThreads, (X3 && IN_T == 1 && W_T <= 2 && OUT_T == 
 		uint32_t opaque = 0;
 		if constexpr (IN_T >= 4 || W_T >= 4 || OUT_T >= 4) asm volatile("s_mov_b32 %0, 0" : "=s"(opaque));
 		const float *wl = lds + opaque;
-		if constexpr (X3) dense_x3<IN_T, W_T, true>(wl, xin, hcur, a.hidden_act, lane);
-		else dense<IN_T, W_T, true>(wl, xin, hcur, a.hidden_act, lane);
+		hidden_layer<IN_T, W_T, X3, false, SP>(wl, xin, hcur, a.hidden_act, a.beta, lane);
 #pragma unroll 1
 		for (uint32_t l = 1; l + 1 < a.n_layers; ++l) {
 			f16v hn[W_T];
-			if constexpr (X3) dense_x3<W_T, W_T, true>(wl + off_hidden + (l - 1) * sz_hidden, hcur, hn, a.hidden_act, lane);
-			else dense<W_T, W_T, true>(wl + off_hidden + (l - 1) * sz_hidden, hcur, hn, a.hidden_act, lane);
+			hidden_layer<W_T, W_T, X3, false, SP>(wl + off_hidden + (l - 1) * sz_hidden, hcur, hn, a.hidden_act, a.beta, lane);
 #pragma unroll
 			for (int t = 0; t < W_T; ++t) hcur[t] = hn[t];
 		}
@@ -204,6 +204,8 @@ struct BwdArgs {
 	uint32_t x_fm, gx_fm;                      // x is read / dL/dx is stored feature-major (xs / gxs = feature stride)
 	const float *packed;                       // the forward layers: f32, or their x3 planes
 	uint32_t total_floats;                     // of their padded LDS copy
+	float beta;                                // of a softplus hidden activation (the SP instantiations); in the 4 bytes of padding in
+	                                           // front of the pointers: the struct, hence the ReLU kernels' argument block, is unchanged
 	float *dW[NR3D_MLP_MAX_LAYERS];            // accumulated into (atomics): zero them for plain gradients
 	float *db[NR3D_MLP_MAX_LAYERS];            // may be NULL
 	uint32_t dims[NR3D_MLP_MAX_LAYERS + 1];
@@ -216,7 +218,8 @@ struct BwdArgs {
 // One layer of the backward sweep.  g = dL/d(pre-activation of this layer's output) on the register map (NO tiles);
 // TG: LDS tile that receives g as [feature][sample]; TB: the layer's INPUT activations as [feature][sample] (NI tiles);
 // wT: the padded LDS copy of THIS layer (read transposed).  Accumulates dW (NO x NI tiles) and the per-lane bias partial sums; when PREV, leaves
-// dL/d(input of the layer) in gp, masked with the ReLU derivative of the input activations when MASK.
+// dL/d(input of the layer) in gp, times the derivative of the input activations: MASK 1 = ReLU (H > 0), 2 = softplus with `beta`, which the
+// same tile gives as -expm1(-beta H) (mlp_act.h), 0 = none.
 // eight consecutive samples of a [feature][sample] tile row as the three bf16 pieces of an MFMA operand (mlp_device.h split3)
 __device__ __forceinline__ void split3_row8(const float *__restrict__ src, bf8 (&p)[3], float &sum) {
 	const f4v lo = *reinterpret_cast<const f4v *>(src), hi = *reinterpret_cast<const f4v *>(src + 4);
@@ -228,10 +231,10 @@ __device__ __forceinline__ void split3_row8(const float *__restrict__ src, bf8 (
 	}
 }
 
-template <int NO, int NI, bool PREV, bool MASK, bool X3 = false>
+template <int NO, int NI, bool PREV, int MASK, bool X3 = false>
 __device__ __forceinline__ void bwd_layer(const f16v (&g)[NO], float *__restrict__ TG, const float *__restrict__ TB,
                                           const float *__restrict__ wT, f16v (&dW)[NO][NI], float (&db)[NO], f16v (&gp)[NI],
-                                          int lane) {
+                                          int lane, float beta = 0.0f) {
 	const int r = lane & 31, h = lane >> 5;
 	write_tile<NO>(TG, NO, g, lane);
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -277,7 +280,13 @@ __device__ __forceinline__ void bwd_layer(const f16v (&g)[NO], float *__restrict
 	if (PREV) {
 		if constexpr (X3) dense_x3_t<NO, NI>(wT, g, gp, lane);          // wT: the padded copy of the FORWARD layer's x3 planes
 		else dense_t<NO, NI>(wT, g, gp, lane);                          //     ... of the forward layer
-		if (MASK) {
+		if constexpr (MASK == 2) {
+#pragma unroll
+			for (int t = 0; t < NI; ++t)
+#pragma unroll
+				for (int j = 0; j < 16; ++j)
+					gp[t][j] *= mlp_act::softplus_grad(TB[(32 * t + 8 * (j >> 2) + 4 * h + (j & 3)) * kTS + r], beta);
+		} else if (MASK) {
 #pragma unroll
 			for (int t = 0; t < NI; ++t)
 #pragma unroll
@@ -340,7 +349,10 @@ template <int IN_T, int W_T, int OUT_T, int NH> struct BwdCfg { static constexpr
 // X3 (round 6): the forward recomputation, the dH = W^T dPre chain and the sample contraction dW = dPre^T H all run on the bf16 MFMA with
 // three-piece splits (dense_x3 / dense_x3_t / bwd_layer<..., true>); a.packed then points at the x3 planes of the forward layers.
 // The ReLU masks come from the SAME forward arithmetic as nr3d_mlp_forward's x3 route.
-template <int IN_T, int W_T, int OUT_T, int NH, int FAST, bool X3 = false>
+// SP: softplus hidden layers (hidden_layer / bwd_layer<..., MASK = 2>): the H_l tiles kept for dW also give the derivative.
+// (the ReLU / linear instantiations call dense / dense_x3 directly, not through hidden_layer: the extra inlining level alone moved the
+// register allocation of four of them by 1 - 8 VGPRs and 7 spilled dwords)
+template <int IN_T, int W_T, int OUT_T, int NH, int FAST, bool X3 = false, bool SP = false>
 __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T, NH>::kMaxWaves * 64)) void k_mlp_bwd(BwdArgs a) {
 	extern __shared__ __attribute__((aligned(16))) float lds[];
 	// FAST: the next tile's rows are requested before a tile's LAST step, not at its top: their 32 - 64 registers then overlap one
@@ -412,13 +424,15 @@ __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T, NH>::kMaxWaves * 64)) voi
 			load_rows<OUT_T>(a.gy, a.gys, a.dims[NH + 1], row, valid, a.gy_vec != 0, lane, g_out);
 		}
 		// ---- forward, activations kept as [feature][sample] tiles ----
-		if constexpr (X3) dense_x3<IN_T, W_T, true, true>(wf, xin, hcur, a.hidden_act, lane);
+		if constexpr (SP) hidden_layer<IN_T, W_T, X3, true, true>(wf, xin, hcur, a.hidden_act, a.beta, lane);
+		else if constexpr (X3) dense_x3<IN_T, W_T, true, true>(wf, xin, hcur, a.hidden_act, lane);
 		else dense<IN_T, W_T, true, true>(wf, xin, hcur, a.hidden_act, lane);
 		write_tile<W_T>(TH1, W_T, hcur, lane);
 #pragma unroll
 		for (int l = 1; l < NH; ++l) {
 			f16v hn[W_T];
-			if constexpr (X3) dense_x3<W_T, W_T, true, true>(wf + f0 + (l - 1) * fh, hcur, hn, a.hidden_act, lane);
+			if constexpr (SP) hidden_layer<W_T, W_T, X3, true, true>(wf + f0 + (l - 1) * fh, hcur, hn, a.hidden_act, a.beta, lane);
+			else if constexpr (X3) dense_x3<W_T, W_T, true, true>(wf + f0 + (l - 1) * fh, hcur, hn, a.hidden_act, lane);
 			else dense<W_T, W_T, true, true>(wf + f0 + (l - 1) * fh, hcur, hn, a.hidden_act, lane);
 #pragma unroll
 			for (int t = 0; t < W_T; ++t) hcur[t] = hn[t];
@@ -437,7 +451,8 @@ __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T, NH>::kMaxWaves * 64)) voi
 		// ---- backward sweep ----
 		const bool relu = a.hidden_act == NR3D_MLP_ACT_RELU;
 		f16v g[W_T];
-		if (relu) bwd_layer<OUT_T, W_T, true, true, X3>(g_out, TGO, TH1 + (NH - 1) * 32 * W_T * kTS, wt + t0 + (NH - 1) * th, dWo, dbo, g, lane);
+		if constexpr (SP) bwd_layer<OUT_T, W_T, true, 2, X3>(g_out, TGO, TH1 + (NH - 1) * 32 * W_T * kTS, wt + t0 + (NH - 1) * th, dWo, dbo, g, lane, a.beta);
+		else if (relu) bwd_layer<OUT_T, W_T, true, true, X3>(g_out, TGO, TH1 + (NH - 1) * 32 * W_T * kTS, wt + t0 + (NH - 1) * th, dWo, dbo, g, lane);
 		else bwd_layer<OUT_T, W_T, true, false, X3>(g_out, TGO, TH1 + (NH - 1) * 32 * W_T * kTS, wt + t0 + (NH - 1) * th, dWo, dbo, g, lane);
 		write_tile<IN_T>(TX, IN_T, xin, lane);                           // into G_out's rows: their reader, the step above, is done; x leaves the registers here
 #pragma unroll
@@ -445,7 +460,8 @@ __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T, NH>::kMaxWaves * 64)) voi
 			f16v gp[W_T];
 			float *TG = TH1 + l * 32 * W_T * kTS;                       // H_{l+1} is dead once its mask has been applied
 			const float *TB = TH1 + (l - 1) * 32 * W_T * kTS;
-			if (relu) bwd_layer<W_T, W_T, true, true, X3>(g, TG, TB, wt + t0 + (l - 1) * th, dWh[l - 1], dbh[l - 1], gp, lane);
+			if constexpr (SP) bwd_layer<W_T, W_T, true, 2, X3>(g, TG, TB, wt + t0 + (l - 1) * th, dWh[l - 1], dbh[l - 1], gp, lane, a.beta);
+			else if (relu) bwd_layer<W_T, W_T, true, true, X3>(g, TG, TB, wt + t0 + (l - 1) * th, dWh[l - 1], dbh[l - 1], gp, lane);
 			else bwd_layer<W_T, W_T, true, false, X3>(g, TG, TB, wt + t0 + (l - 1) * th, dWh[l - 1], dbh[l - 1], gp, lane);
 #pragma unroll
 			for (int t = 0; t < W_T; ++t) g[t] = gp[t];
@@ -821,27 +837,26 @@ extern "C" int nr3d_mlp_forward(const nr3d_mlp_desc_t *desc, uint64_t n, const f
 	const uint32_t grid = (uint32_t)(n_tiles / 4 + 1 < 1024 ? n_tiles / 4 + 1 : 1024);
 	const int xf = fast_of(lx);
 	int rc = 0;
+	const bool sp = mlp_act::softplus_hidden(desc);
+	a.beta = desc->softplus_beta;
 	dispatch_tiles(s, [&](auto I, auto W, auto O) {
 		constexpr int IN_T = decltype(I)::value, W_T = decltype(W)::value, OUT_T = decltype(O)::value;
-		static LdsOnce once;
-		int dev = -1;
-		if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlp_fwd<IN_T, W_T, OUT_T, 0>, k_mlp_fwd<IN_T, W_T, OUT_T, 1>, k_mlp_fwd<IN_T, W_T, OUT_T, 2>))) return;
-		if (x3) {
-			static LdsOnce once3;
-			if ((rc = NR3D_LDS_LIMIT(once3, dev, kMaxLds, k_mlp_fwd<IN_T, W_T, OUT_T, 0, true>, k_mlp_fwd<IN_T, W_T, OUT_T, 1, true>,
-			                         k_mlp_fwd<IN_T, W_T, OUT_T, 2, true>))) return;
+		// the (bf16 route, softplus) variant of the tile class: the LDS limit of its three XF kernels once per device, then the launch
+		auto go = [&](auto X3c, auto SPc) {
+			constexpr bool X3 = decltype(X3c)::value, SP = decltype(SPc)::value;
+			static LdsOnce once;
+			int dev = -1;
+			if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlp_fwd<IN_T, W_T, OUT_T, 0, X3, SP>, k_mlp_fwd<IN_T, W_T, OUT_T, 1, X3, SP>,
+			                         k_mlp_fwd<IN_T, W_T, OUT_T, 2, X3, SP>))) return;
 			if (xf == 2)
-				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 2, true>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 2, X3, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 			else if (xf == 1)
-				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 1, true>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 1, X3, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 			else
-				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 0, true>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
-		} else if (xf == 2)
-			hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 2>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
-		else if (xf == 1)
-			hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 1>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
-		else
-			hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 0>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 0, X3, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+		};
+		if (x3) { if (sp) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{}); }
+		else { if (sp) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
 	});
 	if (rc) return rc;
 	NR3D_LAUNCH_CHECK();
@@ -877,6 +892,8 @@ extern "C" int nr3d_mlp_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const 
 	a.hidden_act = (int)desc->hidden_activation; a.out_act = (int)desc->output_activation;
 	a.x_vec = lx.vec; a.gy_vec = lgy.vec; a.gx_vec = lgx.vec;
 	a.tile_floats = bwd_tile_floats(s);
+	a.beta = desc->softplus_beta;
+	const bool sp = mlp_act::softplus_hidden(desc);
 	const BwdPlan plan = bwd_plan_of(s, x3, n);
 	const uint32_t nh = desc->n_layers - 1;
 	const int fast = fast_of(lx, lgy);
@@ -886,27 +903,33 @@ extern "C" int nr3d_mlp_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const 
 		return 0;
 	};
 	int rc = 0;
+#define BWD_FAST(I, W, O, H, X, S) (fast == 2 ? launch(k_mlp_bwd<I, W, O, H, 2, X, S>) : fast == 1 ? launch(k_mlp_bwd<I, W, O, H, 1, X, S>) : launch(k_mlp_bwd<I, W, O, H, 0, X, S>))
 #define BWD_CASE(I, W, O, H) if (s.in_t == I && s.w_t == W && s.out_t == O && nh == H) { \
-		if (x3) { if constexpr (bwd_has_x3(I, W, O, H)) \
-		              rc = fast == 2 ? launch(k_mlp_bwd<I, W, O, H, 2, true>) : fast == 1 ? launch(k_mlp_bwd<I, W, O, H, 1, true>) : launch(k_mlp_bwd<I, W, O, H, 0, true>); \
+		if (x3) { if constexpr (bwd_has_x3(I, W, O, H)) rc = sp ? BWD_FAST(I, W, O, H, true, true) : BWD_FAST(I, W, O, H, true, false); \
 		          else rc = ::nr3d::fail("mlp_backward: no bf16 MFMA backward for this shape"); } \
-		else rc = fast == 2 ? launch(k_mlp_bwd<I, W, O, H, 2>) : fast == 1 ? launch(k_mlp_bwd<I, W, O, H, 1>) : launch(k_mlp_bwd<I, W, O, H, 0>); } else
+		else rc = sp ? BWD_FAST(I, W, O, H, false, true) : BWD_FAST(I, W, O, H, false, false); } else
 	NR3D_MLP_BWD_SHAPES(BWD_CASE)
 	rc = ::nr3d::fail("mlp_backward: no kernel for this shape");
 #undef BWD_CASE
+#undef BWD_FAST
 	if (rc) return rc;
 	NR3D_LAUNCH_CHECK();
 	return 0;
 }
 
-// the double backward runs on every shape the fused backward runs on (same LDS plan, same waves)
-extern "C" int nr3d_mlp_backward_backward_ok(const nr3d_mlp_desc_t *desc) { return nr3d_mlp_backward_packed_floats(desc) != 0 ? 1 : 0; }
+// the double backward runs on every shape the fused backward runs on (same LDS plan, same waves) -- with ReLU / no hidden activation: a
+// softplus network is not piecewise linear (its double backward has bias and x terms and a third chain; not built)
+extern "C" int nr3d_mlp_backward_backward_ok(const nr3d_mlp_desc_t *desc) {
+	return desc && !mlp_act::softplus_hidden(desc) && nr3d_mlp_backward_packed_floats(desc) != 0 ? 1 : 0;
+}
 
 extern "C" int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, int64_t x_stride, int64_t x_feature_stride,
                                           const float *dL_dy, int64_t gy_stride, const float *ddL_dx, int64_t v_stride,
                                           int64_t v_feature_stride, const float *packed, float *dL_ddLdy, int64_t ggy_stride,
                                           float *const *dL_dW, void *stream) {
 	Shape s;
+	NR3D_CHECK(!(desc && mlp_act::softplus_hidden(desc)), "mlp_backward_backward: the fused double backward does not take softplus hidden layers "
+	           "(differentiate the unfused path)");
 	NR3D_CHECK(shape_of(desc, s) && nr3d_mlp_backward_backward_ok(desc), "mlp_backward_backward: the fused double backward does not apply to this network");
 	if (n == 0) return 0;
 	NR3D_CHECK(x && dL_dy && ddL_dx && packed && dL_dW, "mlp_backward_backward: NULL pointer");

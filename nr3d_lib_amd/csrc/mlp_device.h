@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "mlp_plan.h"        // kThreads, kMaxLds, tiles()
+#include "mlp_act.h"         // softplus
 #include <type_traits>
 
 namespace nr3d {
@@ -269,6 +270,17 @@ __device__ __forceinline__ void dense_x3(const float *__restrict__ wp, const f16
 #pragma unroll
 			for (int j = 0; j < 16; ++j) out[ot][j] = relu(out[ot][j]);
 	}
+}
+
+// one HIDDEN layer with its activation on either MFMA route.  SP: softplus (mlp_act.h) on the fp32 accumulators of the same dense
+// layer -- in instantiations of their own (k_mlp_fwd / k_mlp_bwd <..., SP = true>); the ReLU / linear ones keep their activation as the
+// run-time `act` inside dense / dense_x3, and their code, registers and scratch (k_mlp_bwd calls dense / dense_x3 directly for them:
+// this wrapper's extra inlining level alone moved the register allocation of four of its instantiations)
+template <int NI, int NO, bool X3, bool PAD, bool SP>
+__device__ __forceinline__ void hidden_layer(const float *__restrict__ wp, const f16v (&in)[NI], f16v (&out)[NO], int act, float beta, int lane) {
+	if constexpr (X3) dense_x3<NI, NO, true, PAD>(wp, in, out, SP ? (int)NR3D_MLP_ACT_NONE : act, lane);
+	else dense<NI, NO, true, PAD>(wp, in, out, SP ? (int)NR3D_MLP_ACT_NONE : act, lane);
+	if constexpr (SP) mlp_act::softplus_tiles<NO>(out, beta);
 }
 
 // out = W^T in on the bf16 MFMA from the PADDED x3 planes of the forward layer W (dense_t's counterpart: NI tiles of W's outputs come in,

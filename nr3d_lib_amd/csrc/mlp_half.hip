@@ -286,6 +286,7 @@ struct FwdArgs {
 	uint32_t n_layers, in_dim, out_dim;
 	int hidden_act, out_act;
 	uint32_t x_vec, y_vec;
+	float beta;                                // of a softplus hidden activation (the SP instantiations)
 };
 
 __device__ __forceinline__ void stage_weights(const unsigned char *__restrict__ packed, uint32_t n_bytes, unsigned char *lds) {
@@ -304,7 +305,9 @@ __device__ __forceinline__ void prefetch_x(const __half *__restrict__ p, int64_t
 	else load_rows_fast<NT>(p, stride, dim, row_clamped, lane, r);
 }
 
-template <int IN_T, int W_T, int OUT_T, int XF>
+// SP: softplus hidden layers (mlp_act.h), evaluated on the fp32 accumulators before they are rounded to half -- instantiations of their
+// own, so that the ReLU / linear kernels keep their code; a.hidden_act is not read
+template <int IN_T, int W_T, int OUT_T, int XF, bool SP = false>
 __global__ __launch_bounds__(kThreads) void k_mlph_fwd(FwdArgs a) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 	stage_weights(a.packed, a.packed_bytes, lds);
@@ -331,11 +334,13 @@ __global__ __launch_bounds__(kThreads) void k_mlph_fwd(FwdArgs a) {
 		} else {
 			load_rows<IN_T>(a.x, a.xs, a.in_dim, row, valid, a.x_vec != 0, lane, xin);
 		}
-		dense<IN_T, W_T, true>(wl, xin, hacc, a.hidden_act, lane);
+		dense<IN_T, W_T, true>(wl, xin, hacc, SP ? (int)NR3D_MLP_ACT_NONE : a.hidden_act, lane);
+		if constexpr (SP) mlp_act::softplus_tiles<W_T>(hacc, a.beta);
 		to_operand<W_T>(hacc, hop);
 #pragma unroll 1
 		for (uint32_t l = 1; l + 1 < a.n_layers; ++l) {
-			dense<W_T, W_T, true>(wl + off_hidden + (l - 1) * sz_hidden, hop, hacc, a.hidden_act, lane);
+			dense<W_T, W_T, true>(wl + off_hidden + (l - 1) * sz_hidden, hop, hacc, SP ? (int)NR3D_MLP_ACT_NONE : a.hidden_act, lane);
+			if constexpr (SP) mlp_act::softplus_tiles<W_T>(hacc, a.beta);
 			to_operand<W_T>(hacc, hop);
 		}
 		dense<W_T, OUT_T, true>(wl + off_hidden + (a.n_layers - 2) * sz_hidden, hop, yo, a.out_act, lane);
@@ -404,6 +409,7 @@ struct BwdArgs {
 	int hidden_act, out_act;
 	uint32_t x_vec, gy_vec, gx_vec;
 	uint32_t tile_halfs;                       // per wave
+	float beta;                                // of a softplus hidden activation (the SP instantiations)
 };
 
 // One layer of the backward sweep.  g = dL/d(pre-activation of this layer's output) in operand form (NO tiles); TG: LDS tile that
@@ -413,10 +419,12 @@ struct BwdArgs {
 // per-lane bias partial sums; when PREV, leaves dL/d(input of the layer) in gp (fp32, C/D map), masked when MASK.
 // BITS: the mask comes as hmask (the shapes whose backward spills: one register per layer instead of 8-16 live across the sweep);
 // otherwise from hin, the activations in operand form (the shapes that fit: 32 -> 64 -> 64 -> 16 is 6-10 % faster without the bit work)
-template <int NO, int NI, bool PREV, bool MASK, bool BITS>
+// MASK: 0 = none, 1 = ReLU, 2 = softplus with `beta`: dL/d(input) times -expm1(-beta h) of the (half) activations in hin (mlp_act.h; never BITS)
+template <int NO, int NI, bool PREV, int MASK, bool BITS>
 __device__ __forceinline__ void bwd_layer(const h8 (&g)[NO][2], _Float16 *__restrict__ TG, const _Float16 *__restrict__ TB,
                                           const unsigned char *__restrict__ wT, f16v (&dW)[NO][NI], float (&db)[NO], f16v (&gp)[NI],
-                                          const h8 (&hin)[NI][2], uint32_t hmask, int lane) {
+                                          const h8 (&hin)[NI][2], uint32_t hmask, int lane, float beta = 0.0f) {
+	static_assert(MASK != 2 || !BITS, "the softplus derivative needs the activations");
 	const int r = lane & 31, h = lane >> 5;
 	write_tile<NO>(TG, g, lane);
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -436,7 +444,12 @@ __device__ __forceinline__ void bwd_layer(const h8 (&g)[NO][2], _Float16 *__rest
 		}
 	if (PREV) {
 		dense<NO, NI, false>(wT, g, gp, NR3D_MLP_ACT_NONE, lane);
-		if (MASK) {
+		if constexpr (MASK == 2) {
+#pragma unroll
+			for (int t = 0; t < NI; ++t)
+#pragma unroll
+				for (int j = 0; j < 16; ++j) gp[t][j] *= mlp_act::softplus_grad((float)hin[t][j >> 3][j & 7], beta);
+		} else if (MASK) {
 #pragma unroll
 			for (int t = 0; t < NI; ++t)
 #pragma unroll
@@ -498,7 +511,8 @@ __device__ __forceinline__ void zero_tiles(f16v (&r)[NT]) {
 // dependent MFMAs per tile, a second wave per SIMD hides half of it (dW of such a network is <= 64 registers; the cap is then 256 per
 // lane).  64-wide hidden layers keep four waves and the whole register file (at 256 registers 32 -> 64 -> 64 -> 16 spills 300-400 dwords).
 template <int IN_T, int W_T, int OUT_T> struct BwdCfg { static constexpr int kMaxWaves = bwd_max_waves_half(IN_T, W_T, OUT_T); };
-template <int IN_T, int W_T, int OUT_T, int NH, int FAST>
+// SP: softplus hidden layers; the derivative comes from the activations in operand form (never the bit masks)
+template <int IN_T, int W_T, int OUT_T, int NH, int FAST, bool SP = false>
 __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T>::kMaxWaves * 64)) void k_mlph_bwd(BwdArgs a) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 	stage_weights(a.packed, a.total_bytes, lds);
@@ -558,12 +572,14 @@ __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T>::kMaxWaves * 64)) void k_
 		}
 		// ---- forward, activations kept in operand form (registers) and as [feature][sample] tiles (LDS) ----
 		write_tile<IN_T>(TX, xin, lane);
-		dense<IN_T, W_T, true>(wf, xin, hacc, a.hidden_act, lane);
+		dense<IN_T, W_T, true>(wf, xin, hacc, SP ? (int)NR3D_MLP_ACT_NONE : a.hidden_act, lane);
+		if constexpr (SP) mlp_act::softplus_tiles<W_T>(hacc, a.beta);
 		to_operand<W_T>(hacc, hop[0]);
 		write_tile<W_T>(TH1, hop[0], lane);
 #pragma unroll
 		for (int l = 1; l < NH; ++l) {
-			dense<W_T, W_T, true>(wf + f0 + (l - 1) * fh, hop[l - 1], hacc, a.hidden_act, lane);
+			dense<W_T, W_T, true>(wf + f0 + (l - 1) * fh, hop[l - 1], hacc, SP ? (int)NR3D_MLP_ACT_NONE : a.hidden_act, lane);
+			if constexpr (SP) mlp_act::softplus_tiles<W_T>(hacc, a.beta);
 			to_operand<W_T>(hacc, hop[l]);
 			write_tile<W_T>(TH1 + l * 32 * W_T * kTSH, hop[l], lane);
 			}
@@ -578,7 +594,7 @@ __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T>::kMaxWaves * 64)) void k_
 		// ---- backward sweep ----
 		const bool relu = a.hidden_act == NR3D_MLP_ACT_RELU;
 		static_assert(W_T <= 2, "one 32-bit ReLU mask per hidden layer");
-		constexpr bool BITS = (IN_T + OUT_T > 2) || (W_T == 1 && NH >= 3);      // the instantiations that spill with the activations live
+		constexpr bool BITS = !SP && ((IN_T + OUT_T > 2) || (W_T == 1 && NH >= 3));      // the instantiations that spill with the activations live
 		uint32_t hmask[NH];
 #pragma unroll
 		for (int l = 0; l < NH; ++l) {
@@ -592,7 +608,8 @@ __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T>::kMaxWaves * 64)) void k_
 			hmask[l] = m;
 		}
 		f16v g[W_T];
-		if (relu) bwd_layer<OUT_T, W_T, true, true, BITS>(g_out, TGO, TH1 + (NH - 1) * 32 * W_T * kTSH, wt + t0 + (NH - 1) * th, dWo, dbo, g, hop[NH - 1], hmask[NH - 1], lane);
+		if constexpr (SP) bwd_layer<OUT_T, W_T, true, 2, BITS>(g_out, TGO, TH1 + (NH - 1) * 32 * W_T * kTSH, wt + t0 + (NH - 1) * th, dWo, dbo, g, hop[NH - 1], 0u, lane, a.beta);
+		else if (relu) bwd_layer<OUT_T, W_T, true, true, BITS>(g_out, TGO, TH1 + (NH - 1) * 32 * W_T * kTSH, wt + t0 + (NH - 1) * th, dWo, dbo, g, hop[NH - 1], hmask[NH - 1], lane);
 		else bwd_layer<OUT_T, W_T, true, false, BITS>(g_out, TGO, TH1 + (NH - 1) * 32 * W_T * kTSH, wt + t0 + (NH - 1) * th, dWo, dbo, g, hop[NH - 1], 0u, lane);
 		h8 gop[W_T][2];
 #pragma unroll
@@ -601,7 +618,8 @@ __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T>::kMaxWaves * 64)) void k_
 			to_operand<W_T>(g, gop);
 			_Float16 *TG = TH1 + l * 32 * W_T * kTSH;                    // H_{l+1}'s tile is dead: the layer above has consumed it
 			const _Float16 *TB = TH1 + (l - 1) * 32 * W_T * kTSH;
-			if (relu) bwd_layer<W_T, W_T, true, true, BITS>(gop, TG, TB, wt + t0 + (l - 1) * th, dWh[l - 1], dbh[l - 1], gp, hop[l - 1], hmask[l - 1], lane);
+			if constexpr (SP) bwd_layer<W_T, W_T, true, 2, BITS>(gop, TG, TB, wt + t0 + (l - 1) * th, dWh[l - 1], dbh[l - 1], gp, hop[l - 1], 0u, lane, a.beta);
+			else if (relu) bwd_layer<W_T, W_T, true, true, BITS>(gop, TG, TB, wt + t0 + (l - 1) * th, dWh[l - 1], dbh[l - 1], gp, hop[l - 1], hmask[l - 1], lane);
 			else bwd_layer<W_T, W_T, true, false, BITS>(gop, TG, TB, wt + t0 + (l - 1) * th, dWh[l - 1], dbh[l - 1], gp, hop[l - 1], 0u, lane);
 #pragma unroll
 			for (int t = 0; t < W_T; ++t) g[t] = gp[t];
@@ -707,11 +725,21 @@ __device__ __forceinline__ void reduce_split(const f16v &dW, float db, float *__
 }
 
 // dL/d(pre-activation of the layer below) in operand form = half(W^T . dPre), masked by the ReLU mask of that layer's output
-template <int NO, int NI>
+// SP: `mask` holds that layer's (half) activations themselves, and the fp32 product is scaled by the softplus derivative they give
+// (mlp_act.h) before it is rounded
+template <int NO, int NI, bool SP = false>
 __device__ __forceinline__ void dx_layer(const h8 (&g)[NO][2], const unsigned char *__restrict__ wT, h8 (&gop)[NI][2], const us8 (&mask)[NI][2],
-                                         bool relu, int lane) {
+                                         bool relu, int lane, float beta = 0.0f) {
 	f16v gp[NI];
 	dense<NO, NI, false>(wT, g, gp, NR3D_MLP_ACT_NONE, lane);
+	if constexpr (SP) {
+#pragma unroll
+		for (int t = 0; t < NI; ++t)
+#pragma unroll
+			for (int j = 0; j < 16; ++j) gp[t][j] *= mlp_act::softplus_grad((float)__builtin_bit_cast(h8, mask[t][j >> 3])[j & 7], beta);
+		to_operand<NI>(gp, gop);
+		return;
+	}
 	to_operand<NI>(gp, gop);
 	if (relu) {
 #pragma unroll
@@ -719,7 +747,7 @@ __device__ __forceinline__ void dx_layer(const h8 (&g)[NO][2], const unsigned ch
 	}
 }
 
-template <int IN_T, int W_T, int OUT_T, int NH, int FAST, int NW>
+template <int IN_T, int W_T, int OUT_T, int NH, int FAST, int NW, bool SP = false>
 __global__ __launch_bounds__(NW * 64) void k_mlph_bwd_split(BwdArgs a) {
 	static_assert(W_T == 2 && NH >= 1 && NH <= 2, "the shapes whose dW does not fit one wave: 64-wide hidden layers");
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -783,19 +811,24 @@ __global__ __launch_bounds__(NW * 64) void k_mlph_bwd_split(BwdArgs a) {
 		}
 		// ---- forward on the wave's own tile: activations to LDS as [feature][sample], their signs as one word per layer ----
 		write_tile<IN_T>(mine + oX, xin, lane);
-		dense<IN_T, W_T, true>(wf, xin, hacc, a.hidden_act, lane);
+		dense<IN_T, W_T, true>(wf, xin, hacc, SP ? (int)NR3D_MLP_ACT_NONE : a.hidden_act, lane);
+		if constexpr (SP) mlp_act::softplus_tiles<W_T>(hacc, a.beta);
 		to_operand<W_T>(hacc, hop);
 		write_tile<W_T>(mine + oH1, hop, lane);
-		auto signs = [&](us8 (&m)[W_T][2]) {
+		auto signs = [&](us8 (&m)[W_T][2]) {                 // (SP: the activations themselves, dx_layer)
 #pragma unroll
-			for (int t = 0; t < W_T; ++t) { m[t][0] = relu_mask(hop[t][0]); m[t][1] = relu_mask(hop[t][1]); }
+			for (int t = 0; t < W_T; ++t) {
+				if constexpr (SP) { m[t][0] = __builtin_bit_cast(us8, hop[t][0]); m[t][1] = __builtin_bit_cast(us8, hop[t][1]); }
+				else { m[t][0] = relu_mask(hop[t][0]); m[t][1] = relu_mask(hop[t][1]); }
+			}
 		};
 		signs(hmask[0]);
 		if constexpr (NH == 2) {
 			h8 hin[W_T][2];
 #pragma unroll
 			for (int t = 0; t < W_T; ++t) { hin[t][0] = hop[t][0]; hin[t][1] = hop[t][1]; }
-			dense<W_T, W_T, true>(wf + f0, hin, hacc, a.hidden_act, lane);
+			dense<W_T, W_T, true>(wf + f0, hin, hacc, SP ? (int)NR3D_MLP_ACT_NONE : a.hidden_act, lane);
+			if constexpr (SP) mlp_act::softplus_tiles<W_T>(hacc, a.beta);
 			to_operand<W_T>(hacc, hop);
 			write_tile<W_T>(mine + oH1 + szH, hop, lane);
 			signs(hmask[1]);
@@ -813,7 +846,7 @@ __global__ __launch_bounds__(NW * 64) void k_mlph_bwd_split(BwdArgs a) {
 		__syncthreads();                                   // every wave's G_out, H and X tiles are in LDS
 		dw_round<OUT_T, W_T, NW>(tiles0, a.tile_halfs, oGO, oH1 + (NH - 1) * szH, dWo, dbo, wave, lane);
 		h8 gop[W_T][2];
-		dx_layer<OUT_T, W_T>(g_out, wt + t0 + (NH - 1) * th, gop, hmask[NH - 1], relu, lane);
+		dx_layer<OUT_T, W_T, SP>(g_out, wt + t0 + (NH - 1) * th, gop, hmask[NH - 1], relu, lane, a.beta);
 		__syncthreads();                                   // H_NH has been read by everyone: its rows take dPre of the layer below
 		if constexpr (NH == 2) {
 			write_tile<W_T>(mine + oH1 + szH, gop, lane);
@@ -822,7 +855,7 @@ __global__ __launch_bounds__(NW * 64) void k_mlph_bwd_split(BwdArgs a) {
 			h8 gin[W_T][2];
 #pragma unroll
 			for (int t = 0; t < W_T; ++t) { gin[t][0] = gop[t][0]; gin[t][1] = gop[t][1]; }
-			dx_layer<W_T, W_T>(gin, wt + t0, gop, hmask[0], relu, lane);
+			dx_layer<W_T, W_T, SP>(gin, wt + t0, gop, hmask[0], relu, lane, a.beta);
 			__syncthreads();
 		}
 		// ---- first layer ----
@@ -921,6 +954,7 @@ extern "C" int nr3d_mlp_half_forward(const nr3d_mlp_desc_t *desc, uint64_t n, co
 	a.n_layers = desc->n_layers; a.in_dim = desc->dims[0]; a.out_dim = desc->dims[desc->n_layers];
 	a.hidden_act = (int)desc->hidden_activation; a.out_act = (int)desc->output_activation;
 	a.x_vec = lx.vec; a.y_vec = ly.vec;
+	a.beta = desc->softplus_beta;
 	const size_t lds = (size_t)a.packed_bytes;
 	const uint64_t n_tiles = (n + 31) / 32;
 	// 17 KB of weights per workgroup: several workgroups share a CU (the kernel streams x / y; waves hide each other's latency)
@@ -929,15 +963,20 @@ extern "C" int nr3d_mlp_half_forward(const nr3d_mlp_desc_t *desc, uint64_t n, co
 	int rc = 0;
 	dispatch_tiles(s, [&](auto I, auto W, auto O) {
 		constexpr int IN_T = decltype(I)::value, W_T = decltype(W)::value, OUT_T = decltype(O)::value;
-		static LdsOnce once;
-		int dev = -1;
-		if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlph_fwd<IN_T, W_T, OUT_T, 0>, k_mlph_fwd<IN_T, W_T, OUT_T, 1>, k_mlph_fwd<IN_T, W_T, OUT_T, 2>))) return;
-		if (xf == 2)
-			hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 2>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
-		else if (xf == 1)
-			hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 1>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
-		else
-			hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 0>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+		auto go = [&](auto SPc) {
+			constexpr bool SP = decltype(SPc)::value;
+			static LdsOnce once;
+			int dev = -1;
+			if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlph_fwd<IN_T, W_T, OUT_T, 0, SP>, k_mlph_fwd<IN_T, W_T, OUT_T, 1, SP>,
+			                         k_mlph_fwd<IN_T, W_T, OUT_T, 2, SP>))) return;
+			if (xf == 2)
+				hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 2, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+			else if (xf == 1)
+				hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 1, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+			else
+				hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 0, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+		};
+		if (mlp_act::softplus_hidden(desc)) go(std::true_type{}); else go(std::false_type{});
 	});
 	if (rc) return rc;
 	NR3D_LAUNCH_CHECK();
@@ -972,6 +1011,8 @@ extern "C" int nr3d_mlp_half_backward(const nr3d_mlp_desc_t *desc, uint64_t n, c
 	a.hidden_act = (int)desc->hidden_activation; a.out_act = (int)desc->output_activation;
 	a.x_vec = lx.vec; a.gy_vec = lgy.vec; a.gx_vec = lgx.vec;
 	a.tile_halfs = bwd_tile_halfs(s);
+	a.beta = desc->softplus_beta;
+	const bool sp = mlp_act::softplus_hidden(desc);
 	const uint32_t nh = desc->n_layers - 1;
 	const int fast = fast_of(lx, lgy);
 	const BwdPlan plan = bwd_plan_of(s, n);
@@ -982,7 +1023,8 @@ extern "C" int nr3d_mlp_half_backward(const nr3d_mlp_desc_t *desc, uint64_t n, c
 	};
 	int rc = 0;
 	if (s.w_t == 2) {
-#define SPLIT_LAUNCH(I, O, H, NW_) (fast == 2 ? launch(k_mlph_bwd_split<I, 2, O, H, 2, NW_>) : fast == 1 ? launch(k_mlph_bwd_split<I, 2, O, H, 1, NW_>) : launch(k_mlph_bwd_split<I, 2, O, H, 0, NW_>))
+#define SPLIT_FAST(I, O, H, NW_, S) (fast == 2 ? launch(k_mlph_bwd_split<I, 2, O, H, 2, NW_, S>) : fast == 1 ? launch(k_mlph_bwd_split<I, 2, O, H, 1, NW_, S>) : launch(k_mlph_bwd_split<I, 2, O, H, 0, NW_, S>))
+#define SPLIT_LAUNCH(I, O, H, NW_) (sp ? SPLIT_FAST(I, O, H, NW_, true) : SPLIT_FAST(I, O, H, NW_, false))
 #define SPLIT_CASE(I, O, H) if (s.in_t == I && s.out_t == O && nh == H) { \
 		if constexpr (split_max_waves(I, O) == 8) rc = plan.nw == 8 ? SPLIT_LAUNCH(I, O, H, 8) : SPLIT_LAUNCH(I, O, H, 4); \
 		else rc = SPLIT_LAUNCH(I, O, H, 4); } else
@@ -990,13 +1032,16 @@ extern "C" int nr3d_mlp_half_backward(const nr3d_mlp_desc_t *desc, uint64_t n, c
 		SPLIT_CASE(1, 2, 1) SPLIT_CASE(1, 2, 2) SPLIT_CASE(2, 1, 1) SPLIT_CASE(2, 1, 2) SPLIT_CASE(2, 2, 1) SPLIT_CASE(2, 2, 2)
 		rc = ::nr3d::fail("mlp_half_backward: no kernel for this shape");
 #undef SPLIT_LAUNCH
+#undef SPLIT_FAST
 #undef SPLIT_CASE
 	} else {
+#define BWD_FAST(I, W, O, H, S) (fast == 2 ? launch(k_mlph_bwd<I, W, O, H, 2, S>) : fast == 1 ? launch(k_mlph_bwd<I, W, O, H, 1, S>) : launch(k_mlph_bwd<I, W, O, H, 0, S>))
 #define BWD_CASE(I, W, O, H) if (s.in_t == I && s.w_t == W && s.out_t == O && nh == H) \
-		rc = fast == 2 ? launch(k_mlph_bwd<I, W, O, H, 2>) : fast == 1 ? launch(k_mlph_bwd<I, W, O, H, 1>) : launch(k_mlph_bwd<I, W, O, H, 0>); else
+		rc = sp ? BWD_FAST(I, W, O, H, true) : BWD_FAST(I, W, O, H, false); else
 		BWD_CASE(1, 1, 1, 1) BWD_CASE(1, 1, 1, 2) BWD_CASE(1, 1, 1, 3)
 		rc = ::nr3d::fail("mlp_half_backward: no kernel for this shape");
 #undef BWD_CASE
+#undef BWD_FAST
 	}
 	if (rc) return rc;
 	NR3D_LAUNCH_CHECK();

@@ -4,6 +4,7 @@
 // (MFMA instruction, operand maps, LDS tiles); these facts do not, and each is stated here once.
 #pragma once
 #include "common.h"
+#include "mlp_act.h"      // which activations the kernels take
 #include <type_traits>
 
 namespace nr3d {
@@ -21,7 +22,7 @@ struct Shape {
 };
 
 static bool shape_of(const nr3d_mlp_desc_t *d, Shape &s) {
-	if (!d || d->n_layers < 2 || d->n_layers > NR3D_MLP_MAX_LAYERS) return false;
+	if (!d || d->n_layers < 2 || d->n_layers > NR3D_MLP_MAX_LAYERS || !mlp_act::activations_ok(d)) return false;
 	uint32_t w = 0;
 	for (uint32_t l = 1; l < d->n_layers; ++l) w = d->dims[l] > w ? d->dims[l] : w;
 	for (uint32_t l = 0; l <= d->n_layers; ++l) if (d->dims[l] == 0 || d->dims[l] > 128) return false;

@@ -5,7 +5,8 @@ width(s) W and an output layer, optional skip connections.  Same constructor, pa
 Where the reference runs one GEMM + one activation kernel per layer (or hands the network to tiny-cuda-nn), this module
 runs the whole network in ONE kernel on the fp32 MFMA (csrc/mlp.hip) -- or, for ``dtype=torch.half`` (the reference's autocast
 layers / its tcnn FullyFusedMLP), on the f16 MFMA (csrc/mlp_half.hip) -- whenever it can: on a GPU, ReLU / no
-activations, no skips / weight norm / equal_lr, every width <= 128.  Forward: activations stay in registers.  Backward
+activations or softplus hidden layers with beta >= ``FUSED_SOFTPLUS_MIN_BETA`` (the reference's SDF decoders:
+``{'type': 'softplus', 'beta': 100.}``), no skips / weight norm / equal_lr, every width <= 128.  Forward: activations stay in registers.  Backward
 (hidden width <= 64): the forward is recomputed from x inside the backward kernel, so autograd keeps x and nothing else.
 Everything else takes the layer-by-layer torch path below, with identical semantics.
 
@@ -13,7 +14,9 @@ Second order (``create_graph=True``: nablas = d sdf / dx and an eikonal loss on 
 backward is the same fused kernel, wrapped as ``FusedMLPBackwardFunction``, and the loss's backward through the nablas runs the fused
 double backward (csrc/mlp.hip k_mlp_bwd2, ``FUSED_SECOND_ORDER``) for both the fp32 and the half block (the half block's second order
 is evaluated in fp32 from the fp32 parameters, as its torch route does).  The double backward gives x no gradient (ReLU / linear
-networks: it is zero), so ``x.grad`` stays None when the eikonal term is x's only consumer."""
+networks: it is zero), so ``x.grad`` stays None when the eikonal term is x's only consumer.  A softplus network is not piecewise
+linear -- the eikonal term does give x and the biases a gradient -- and has no fused double backward (``desc.second_order_fusable`` is
+False): its create_graph backward differentiates the layer-by-layer torch evaluation of the same network."""
 from typing import List, Union
 
 import torch
@@ -29,6 +32,10 @@ USE_FUSED = True                       # False: always the layer-by-layer path (
 # False: a create_graph backward of a fused block differentiates the layer-by-layer torch evaluation (the route before the fused double
 # backward; A/B measurements, tests)
 FUSED_SECOND_ORDER = True
+# nn.Softplus hidden layers run on the fused kernels from this beta up (threshold 20, one beta for all hidden layers); below it they
+# keep the layer-by-layer path.  The line is the one at which get_nonlinearity (models/layers.py; the reference's layers.py:212) already
+# treats softplus as ReLU-like; every softplus of the reference has beta = 100, and the default nn.Softplus (beta = 1) stays on torch.
+FUSED_SOFTPLUS_MIN_BETA = 5.0
 # Reuse of the MFMA-ordered weight copy between calls.  OFF by default: packing is one ~3 us kernel, and the only cheap
 # change detector -- the parameters' (data_ptr, _version) -- does not see in-place edits made through `.data`
 # (EMA swaps `p.data.copy_(shadow)`, weight clipping, `.data.normal_()` re-initialisation), after which a cached copy
@@ -37,14 +44,25 @@ FUSED_SECOND_ORDER = True
 CACHE_PACKED = False
 
 
+def _torch_activation(h, desc, hidden):
+    """the activation behind a hidden / the output layer of ``desc`` in torch (the differentiable re-evaluations below)"""
+    from nr3d_lib_amd.bindings import _mlp
+    act = desc.hidden_activation if hidden else desc.output_activation
+    if act == _mlp.ACT_RELU:
+        return torch.relu(h)
+    if act == _mlp.ACT_SOFTPLUS:
+        return torch.nn.functional.softplus(h, desc.beta, 20.0)
+    return h
+
+
 class FusedMLPFunction(torch.autograd.Function):
     """y = MLP(x) through nr3d_mlp_forward; backward through nr3d_mlp_backward (recomputes the forward).
     args: desc, need (bool: a gradient may be asked for -> also pack the transposed layers), x, W_0, b_0 | None, W_1, ...
 
     Higher order (``create_graph=True``, e.g. the eikonal term on nablas = d sdf / dx): backward() then runs with grad
     mode on and returns the outputs of ``FusedMLPBackwardFunction`` -- the same fused kernel, whose own backward is the fused
-    double backward (or, with ``FUSED_SECOND_ORDER = False`` / outside its range, the gradients of a layer-by-layer PyTorch
-    evaluation of the same network on the saved inputs, which autograd can differentiate again).  First-order training never
+    double backward (or, with ``FUSED_SECOND_ORDER = False`` / outside its range -- softplus hidden layers among it --, the gradients
+    of a layer-by-layer PyTorch evaluation of the same network on the saved inputs, which autograd can differentiate again).  First-order training never
     takes that branch."""
 
     @staticmethod
@@ -99,9 +117,7 @@ class FusedMLPFunction(torch.autograd.Function):
             x_in = h
             for l, (W, b) in enumerate(zip(ws, bs)):
                 h = torch.nn.functional.linear(h, W, b)
-                act = ctx.desc.hidden_activation if l + 1 < len(ws) else ctx.desc.output_activation
-                if act == _mlp.ACT_RELU:
-                    h = torch.relu(h)
+                h = _torch_activation(h, ctx.desc, l + 1 < len(ws))
             wanted, slots = [], []
             if ctx.needs_input_grad[2]:
                 wanted.append(x_in); slots.append(0)
@@ -175,7 +191,8 @@ class FusedMLPBackwardFunction(torch.autograd.Function):
     third order is asked for (grad mode off) and desc.second_order_fusable -- dL/dW_l from the kernel, dL/db_l zeros (views of the
     same pool, as the torch route's), dL/d(dL/dy) when asked for, and None for x: its gradient is zero (piecewise linear network), and
     an [n, in] tensor of zeros would cost a full write for nothing -- so x.grad stays None when the eikonal term is x's only
-    consumer.  Every other case differentiates the layer-by-layer torch evaluation of the network, as the route before this one."""
+    consumer.  Every other case differentiates the layer-by-layer torch evaluation of the network, as the route before this one;
+    softplus hidden layers always do (not piecewise linear: there x and the biases DO get a gradient from the eikonal term)."""
 
     @staticmethod
     def _params(has_bias, flat):
@@ -226,8 +243,8 @@ class FusedMLPBackwardFunction(torch.autograd.Function):
         backward.  x and dL_dy enter as detached leaves: both are downstream of the parameters (dL_dy of a loss on y), and a gradient
         taken through the originals would run into their graph -- counting the parameters' path through them a second time (the
         engine propagates the dL_dy gradient returned here itself) and freeing that graph.  Third order (grad mode on): the result is
-        differentiable w.r.t. the parameters; terms through x vanish for these piecewise linear networks, terms through dL_dy are
-        not propagated."""
+        differentiable w.r.t. the parameters; terms through x vanish for the piecewise linear (ReLU / linear) networks -- for
+        softplus hidden layers they do not, and x gets its gradient below like any other input --, terms through dL_dy are not propagated."""
         from nr3d_lib_amd.bindings import _mlp
         create = torch.is_grad_enabled()
         need_x, need_gy = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
@@ -238,9 +255,7 @@ class FusedMLPBackwardFunction(torch.autograd.Function):
             h = xi
             for l, (W, b) in enumerate(zip(ws, bs)):
                 h = torch.nn.functional.linear(h, W, b)
-                act = ctx.desc.hidden_activation if l + 1 < len(ws) else ctx.desc.output_activation
-                if act == _mlp.ACT_RELU:
-                    h = torch.relu(h)
+                h = _torch_activation(h, ctx.desc, l + 1 < len(ws))
             slots = [xi]
             for W, b in zip(ws, bs):
                 slots += [W, b]
@@ -319,9 +334,14 @@ class MLP(nn.Module):
     @staticmethod
     def _act_code(layer):
         from nr3d_lib_amd.bindings import _mlp
+        """ACT_* of the layer's activation, or None when the fused kernels do not take it.  nn.Softplus fuses with threshold 20 and
+        beta >= FUSED_SOFTPLUS_MIN_BETA (5.0): the line at which get_nonlinearity already treats softplus as ReLU-like, far below the
+        beta = 100 of every softplus in the reference; the default beta = 1 deliberately stays on the torch path."""
         a = layer.activation
         if a is None:
             return _mlp.ACT_NONE
+        if isinstance(a, nn.Softplus):
+            return _mlp.ACT_SOFTPLUS if (a.threshold == 20 and a.beta >= FUSED_SOFTPLUS_MIN_BETA) else None
         return _mlp.ACT_RELU if isinstance(a, nn.ReLU) else None
 
     def fused_desc(self):
@@ -331,8 +351,11 @@ class MLP(nn.Module):
             ok = self._plain and self.D >= 1 and self.dtype in (None, torch.float32, torch.float16)
             hid = {self._act_code(l) for l in self.layers[:-1]}
             out = self._act_code(self.layers[-1])
+            # softplus: hidden layers only, and all of them with one beta
+            betas = {float(l.activation.beta) for l in self.layers[:-1] if isinstance(l.activation, nn.Softplus)}
+            ok = ok and out != _mlp.ACT_SOFTPLUS and len(betas) <= 1
             if ok and len(hid) == 1 and None not in hid and out is not None and len(self.layers) <= _mlp.MAX_LAYERS:
-                d = _mlp.MLPDesc([self.in_features, *self.Ws, self.out_features], hid.pop(), out)
+                d = _mlp.MLPDesc([self.in_features, *self.Ws, self.out_features], hid.pop(), out, beta=betas.pop() if betas else 1.0)
                 self._desc = d if (d.half_fusable if self.dtype == torch.float16 else d.fusable) else False
             else:
                 self._desc = False
@@ -369,7 +392,7 @@ class MLP(nn.Module):
         n_keep = n_cols
         if self.dtype == torch.float16:
             n_cols = min(self.out_features, (n_cols + 3) // 4 * 4)
-        sub = _mlp.MLPDesc([self.in_features, *self.Ws, n_cols], desc.hidden_activation, desc.output_activation)
+        sub = _mlp.MLPDesc([self.in_features, *self.Ws, n_cols], desc.hidden_activation, desc.output_activation, beta=desc.beta)
         params = []
         for layer in self.layers[:-1]:
             params += [layer.weight, layer.bias]
