@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 19
+#define NR3D_ABI_VERSION 20
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -165,8 +165,8 @@ int nr3d_lotd_meta_regroup(const nr3d_lotd_meta_t *meta, uint32_t width, uint32_
  * param_dtype: NR3D_F32, or NR3D_F16 -- `params` are __half tables, read as half and used as float (the reference's
  * (float, half, float) dispatch, lotd_encoding.h:1501-1504) by every kernel that reads table entries: every meta, batched
  * tables and (ABI 3) the forest entry points included; a half table gives bit for bit what its fp32 copy gives.  With NR3D_F16 nr3d_lotd_fwd writes y as __half
- * (the fp32 result rounded once); dy_dx, dL_dx and -- except through nr3d_lotd_bwd_dparam_typed -- dL_dparam stay float, and
- * so does dL_dy (the caller widens a half dL_dy; the pair-record path below reads it as it is).
+ * (the fp32 result rounded once); dy_dx and dL_dx stay float, and so do dL_dy and dL_dparam
+ * except where nr3d_lotd_half_params_ok says that nr3d_lotd_bwd_dparam takes them as __half (grad_dtype / out_dtype).
  */
 
 /* lod_fwd (lotd_torch_api.cu:232-395): y[i*y_sn + e*y_se] (params dtype);
@@ -186,60 +186,33 @@ int nr3d_lotd_bwd_dx(const nr3d_lotd_meta_t *meta, uint32_t n_points, int x_dtyp
                                       dL_dy; pass it to nr3d_lotd_bwd_dparam as dL_dy with strides (1, n_points) and
                                       the scatter skips its own transposition */,
                      int32_t max_level, void *fold /* optional out, the hand-over buffer of the folded pair path (see
-                                      nr3d_lotd_pair_fold_bytes below); NULL: max_level is not used */,
+                                      nr3d_lotd_bwd_dparam below); NULL: max_level is not used */,
                      void *stream);
 
-/* lod_bwd, parameter-gradient half (kernel_lod[_hashonly]_backward_grid, lotd_encoding.h:467-711,
- * lotd_hash_only.h:380-470).  dL_dparam: params dtype, same numel as params, ZERO-INIT by caller.
- * workspace: optional device scratch of >= nr3d_lotd_dparam_workspace_bytes() bytes; when given (and the meta has
- * no 4-D NPlaneMul / NPlaneSum level) the scatter runs atomic-free (binned records + fp64 LDS accumulation); otherwise
- * (NULL / too small / those levels) hardware f32 atomics are used.
- * n_batches: number of table sets behind `params` when batch_inds / batch_offsets / batch_data_size are used (the
- * reference derives it from params.numel(); 0 = unknown -> batched calls take the atomic path); 0 or 1 otherwise. */
+/* Scratch of nr3d_lotd_bwd_dparam's atomic-free routes for n_points points and n_batches table sets; 0: they do not serve this
+ * meta (4-D NPlaneMul / NPlaneSum levels). */
 uint64_t nr3d_lotd_dparam_workspace_bytes(const nr3d_lotd_meta_t *meta, uint32_t n_points, uint32_t n_batches);
 /* Tuning knob: points per pass of the atomic-free scatter = 2^log2_points (10..24; 0 restores the default 2^22 or
  * NR3D_LOTD_BIN_CHUNK_LOG2).  The workspace size follows; query it again after changing this. */
 void nr3d_lotd_set_dparam_chunk_log2(int log2_points);
-int nr3d_lotd_bwd_dparam(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t n_points,
-                         int x_dtype, int param_dtype, const void *dL_dy, int64_t dldy_sn, int64_t dldy_se,
-                         const void *x, const void *params, const int64_t *batch_inds,
-                         const int64_t *batch_offsets, uint32_t batch_data_size, uint32_t n_batches, int32_t max_level,
-                         void *dL_dparam, void *workspace, uint64_t workspace_bytes, void *stream);
-/* Same, restricted to levels min_level..max_level (the entries of the other levels in dL_dparam are not touched).  No
- * reference counterpart (it only has max_level): a data-parallel caller computes the gradient in level buckets and
- * starts the all-reduce of a finished bucket -- a contiguous slice of dL_dparam, levels are stored one after another
- * -- while the next bucket is being accumulated (bench.py, nr3d_lib_amd/distributed.py).  Per level the arithmetic is
- * that of nr3d_lotd_bwd_dparam; how a hot table slice is split over workgroups follows the records of the call, so the
- * buckets together equal the one-call result to fp32 rounding of the partial sums (each is an fp64 sum), not bitwise. */
-int nr3d_lotd_bwd_dparam_levels(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t n_points,
-                                int x_dtype, int param_dtype, const void *dL_dy, int64_t dldy_sn, int64_t dldy_se,
-                                const void *x, const void *params, const int64_t *batch_inds,
-                                const int64_t *batch_offsets, uint32_t batch_data_size, uint32_t n_batches,
-                                int32_t min_level, int32_t max_level, void *dL_dparam, void *workspace,
-                                uint64_t workspace_bytes, void *stream);
 
 /* dL_dy [N, E] (element (i, e) at i * g_sn + e * g_se; grad_dtype NR3D_F32 | NR3D_F16) -> out float [E][N], feature-major:
- * the layout the level-major kernels read.  The dL/dparam entry points make this copy themselves when handed a row-major
- * dL_dy; a caller that runs several of them on one dL_dy (d(dL/dx)/dparam and d(dL/dx)/dx of one second-order step) makes it
- * once and passes it with strides (1, N) to nr3d_lotd_bwd_bwd_dparam and nr3d_lotd_bwd_bwd_dx. */
+ * the layout the level-major kernels read.  nr3d_lotd_bwd_dparam makes this copy itself when handed a row-major dL_dy; a caller
+ * that runs several entries on one dL_dy (d(dL/dx)/dparam and d(dL/dx)/dx of one second-order step) makes it once and passes it
+ * with strides (1, N) to nr3d_lotd_bwd_dparam and nr3d_lotd_bwd_bwd_dx. */
 int nr3d_lotd_dLdy_feature_major(uint32_t n_points, uint32_t n_encoded_dims, int grad_dtype, const void *dL_dy,
                                  int64_t g_sn, int64_t g_se, float *out, void *stream);
 
 /* Native half-parameter storage, the reference's (float, half, float) type combination (<input, param, compute>,
  * csrc/lotd/include/lotd/lotd_encoding.h:1501-1504; PARAM_T accumulators lotd_encoding.h:72): x and dy_dx float, params /
- * y / dL_dy / dL_dparam __half, arithmetic in fp32.  nr3d_lotd_half_params_ok: 1 when nr3d_lotd_fwd (param_dtype
- * NR3D_F16: y is __half too), nr3d_lotd_bwd_dx (param_dtype NR3D_F16: dL_dy is __half, contiguous [N, E]) and
- * nr3d_lotd_bwd_dparam_typed serve this meta with half GRADIENTS as well (dL_dy read and dL_dparam written as __half) --
- * unbatched 3-D Dense/Hash metas with 2-feature pseudo levels; for every other meta the half TABLES are still read as they
- * are (param_dtype above) and only dL_dy / dL_dparam pass through float.  Unlike the reference's __half2 atomics the
- * parameter gradient is accumulated exactly and rounded to half once. */
+ * y / dL_dy / dL_dparam __half, arithmetic in fp32.  1 when nr3d_lotd_fwd (param_dtype NR3D_F16: y is __half too),
+ * nr3d_lotd_bwd_dx (param_dtype NR3D_F16: dL_dy is __half, contiguous [N, E]) and nr3d_lotd_bwd_dparam (grad_dtype / out_dtype
+ * NR3D_F16) serve this meta with half GRADIENTS as well -- unbatched 3-D Dense/Hash metas with 2-feature pseudo levels; for every
+ * other meta the half TABLES are still read as they are (param_dtype above) and only dL_dy / dL_dparam pass through float.
+ * Unlike the reference's __half2 atomics the parameter gradient is accumulated exactly and rounded to half once. */
 int nr3d_lotd_half_params_ok(const nr3d_lotd_meta_t *meta, int batched);
-/* first-order dL/dparam of the pair-record path (nr3d_lotd_pair_path_ok) with explicit dtypes: grad_dtype of dL_dy (any
- * strides; F32 for the feature-major copy that nr3d_lotd_bwd_dx leaves), out_dtype of dL_dparam.  assign == 0:
- * dL_dparam is ZERO-INIT by the caller and accumulated into, like nr3d_lotd_bwd_dparam; assign != 0: dL_dparam arrives
- * UNINITIALISED and is fully defined on return (the flush writes instead of read-modify-writing when one pass covers
- * all levels; the library zero-fills it itself otherwise).  workspace as nr3d_lotd_bwd_dparam; fold: NULL, or see
- * nr3d_lotd_pair_fold_bytes below. */
+/* 1 when an unbatched nr3d_lotd_bwd_dparam call with a workspace takes the pair-record path for this meta (3-D Dense/Hash
+ * levels, 2-feature pseudo levels): the path that honours `assign` without a fill and takes `fold`. */
 int nr3d_lotd_pair_path_ok(const nr3d_lotd_meta_t *meta);
 /* pseudo levels of a pair-path meta whose dL/dparam is accumulated straight from (x, dL_dy) in LDS instead of through
  * records (levels with <= 4 buckets; 0 when the pair path does not apply or NR3D_OPT_PAIR_DIRECT is 0).  Informational: which
@@ -248,32 +221,61 @@ int nr3d_lotd_pair_direct_levels(const nr3d_lotd_meta_t *meta, uint32_t n_points
 /* which pseudo levels (bit q) nr3d_lotd_fwd serves from LDS for a batch of n_points: Dense levels whose whole table fits; 0 when the
  * two-lane forward does not apply.  bench.py prices the forward kernels on the levels each serves. */
 uint64_t nr3d_lotd_fwd_lds_levels(const nr3d_lotd_meta_t *meta, uint32_t n_points);
-int nr3d_lotd_bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t n_points, int grad_dtype,
-                               const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
-                               int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
-                               void *fold, void *stream);
-/* (ABI 12) One backward call with both gradients on the pair path, in fewer launches (NR3D_OPT_PAIR_FOLD): the dL/dx kernel
- * hands the dL/dparam launches that follow it on the same stream what they used to make in launches of their own -- the
- * max |dL/dy| of the levels up to max_level (the fixed-point scale, bit for bit) and zeroed tickets.
- * nr3d_lotd_pair_fold_bytes: size of that device buffer for n_points and max_level; 0 when the folded route does not apply (option
- * off, not a pair-path meta, more points than one dL/dparam pass, levels up to max_level not the leading pseudo levels).
- * nr3d_lotd_bwd_dx (row-major dL_dy) fills `fold` (uninitialised, >= that many bytes; NULL or a size of 0: the route is not
- * taken).  nr3d_lotd_bwd_dparam_typed takes the same n_points, max_level and `fold`, enqueued after it on the same stream,
- * before any other call that uses `fold`; results are bit for bit those of the calls with fold == NULL. */
+/* size of the `fold` buffer of nr3d_lotd_bwd_dx / nr3d_lotd_bwd_dparam for n_points and max_level; 0 when the folded route does
+ * not apply (NR3D_OPT_PAIR_FOLD off, not a pair-path meta, more points than one dL/dparam pass, levels up to max_level not the
+ * leading pseudo levels). */
 uint64_t nr3d_lotd_pair_fold_bytes(const nr3d_lotd_meta_t *meta, uint32_t n_points, int32_t max_level);
+
+/* lod_bwd, parameter-gradient half (kernel_lod[_hashonly]_backward_grid, lotd_encoding.h:467-711, lotd_hash_only.h:380-470), and
+ * (ii) of lod_bwd_bwd_input below, d(dL/dx)/dparam (lotd_encoding.h:764-1041, lotd_hash_only.h:472-574): the one parameter-gradient
+ * entry of a single block.
+ *   dL_dy, grad_dtype   [N, E] with strides (dldy_sn, dldy_se), float or __half; the feature-major float copy that nr3d_lotd_bwd_dx
+ *                       (dL_dy_T) or nr3d_lotd_dLdy_feature_major leaves is passed with strides (1, n_points) and saves the
+ *                       transposition here.
+ *   dL_ddLdx            NULL: dL/dparam.  float [N, D]: d(dL/dx)/dparam for it (as nr3d_lotd_forest_bwd_dparam).
+ *   x                   float [N, D].
+ *   params, param_dtype the tables, always passed (the Dense / Hash levels' record routes do not read them).
+ *   batch_*, n_batches  as above; n_batches: number of table sets behind `params` when a batch argument is used (the reference
+ *                       derives it from params.numel(); 0 = unknown: such a call takes the atomic kernels), 0 or 1 otherwise.
+ *   min_level..max_level  the levels computed; the entries of other levels in dL_dparam are not touched.  min_level > 0 has no
+ *                       reference counterpart (it only has max_level): a data-parallel caller computes the gradient in level
+ *                       buckets and starts the all-reduce of a finished bucket -- a contiguous slice of dL_dparam, levels are stored
+ *                       one after another -- while the next bucket is accumulated (bench.py, nr3d_lib_amd/distributed.py).  Per
+ *                       level the arithmetic is that of the one-call gradient; how a hot table slice is split over workgroups
+ *                       follows the records of the call, so the buckets together equal the one-call result to fp32 rounding of the
+ *                       partial sums (each is an fp64 sum), not bitwise.
+ *   dL_dparam, out_dtype  float or __half, the numel of params.
+ *   assign              0: dL_dparam is ZERO-INIT by the caller and accumulated into.  != 0: dL_dparam arrives UNINITIALISED and is
+ *                       fully defined on return: the pair-record path writes instead of read-modify-writing when one first-order
+ *                       pass covers every level; in every other case (several passes, a level range, another meta, no or too
+ *                       small a workspace, second order, nothing to do: n_points == 0, max_level <= -1, min_level > max_level) the
+ *                       library zero-fills (n_batches ? n_batches : 1) * n_params elements first and accumulates.
+ *   workspace           optional device scratch of >= nr3d_lotd_dparam_workspace_bytes() bytes: with it (and no 4-D NPlaneMul /
+ *                       NPlaneSum level) the gradient is computed atomic-free (binned records + fp64 LDS accumulation); NULL / too
+ *                       small / those levels: hardware f32 atomics.
+ *   fold                NULL, or (ABI 12, NR3D_OPT_PAIR_FOLD) both gradients of one backward on the pair path in fewer launches:
+ *                       nr3d_lotd_bwd_dx (row-major dL_dy) fills `fold` (uninitialised, >= nr3d_lotd_pair_fold_bytes() bytes; a
+ *                       size of 0: pass NULL) with what the dL/dparam launches used to make in launches of their own -- the max
+ *                       |dL/dy| of the levels up to max_level (the fixed-point scale, bit for bit) and zeroed tickets.  This call
+ *                       takes the same n_points, max_level and `fold`, enqueued after it on the same stream, before any other call
+ *                       that uses `fold`; results are bit for bit those of the calls with fold == NULL.
+ * Half grad_dtype / out_dtype are served where nr3d_lotd_half_params_ok says so, and are an error where the pair-record path does
+ * not take the call (no workspace included); a float call falls back to the atomic kernels.  Refused: min_level < 0; dtype codes
+ * other than NR3D_F32 / NR3D_F16; second order with min_level > 0, half grad_dtype / out_dtype or fold; half grad_dtype /
+ * out_dtype with min_level > 0 or any batch argument; fold with min_level > 0. */
+int nr3d_lotd_bwd_dparam(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t n_points,
+                         int grad_dtype, const void *dL_dy, int64_t dldy_sn, int64_t dldy_se,
+                         const void *dL_ddLdx, const void *x, int param_dtype, const void *params,
+                         const int64_t *batch_inds, const int64_t *batch_offsets, uint32_t batch_data_size, uint32_t n_batches,
+                         int32_t min_level, int32_t max_level, int out_dtype, int assign, void *dL_dparam,
+                         void *workspace, uint64_t workspace_bytes, void *fold, void *stream);
 
 /* lod_bwd_bwd_input (lotd_torch_api.cu:575-729), three independent outputs:
  * (i)  dL_ddLdy[i, e] = sum_d dL_ddLdx[i, d] * dy_dx[i, e, d]      (lotd_encoding.h:1703-1727) */
 int nr3d_lotd_bwd_bwd_ddLdy(const nr3d_lotd_meta_t *meta, uint32_t n_points, int x_dtype, int param_dtype,
                             const void *dL_ddLdx, const void *dy_dx, int64_t dydx_sn, int64_t dydx_se,
                             void *dL_ddLdy, int64_t out_sn, int64_t out_se, void *stream);
-/* (ii) d(dL/dx)/dparam (lotd_encoding.h:764-1041, lotd_hash_only.h:472-574); ZERO-INIT output. */
-int nr3d_lotd_bwd_bwd_dparam(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t n_points,
-                             int x_dtype, int param_dtype, const void *dL_ddLdx,
-                             const void *dL_dy, int64_t dldy_sn, int64_t dldy_se, const void *x,
-                             const void *params, const int64_t *batch_inds, const int64_t *batch_offsets,
-                             uint32_t batch_data_size, uint32_t n_batches, int32_t max_level, void *dL_dparam,
-                             void *workspace, uint64_t workspace_bytes, void *stream);
+/* (ii) d(dL/dx)/dparam: nr3d_lotd_bwd_dparam with dL_ddLdx. */
 /* (iii) d(dL/dx)/dx (lotd_encoding.h:1157-1298, lotd_hash_only.h:576-695); dL_dx [N, D] fully written.
  * workspace: optional device scratch of nr3d_lotd_bwd_bwd_dx_workspace_bytes(meta, n_points) bytes (0: not served -- Dense /
  * Hash metas only).  With it the pseudo levels of a point are worked on side by side (one lane per (point, pseudo level), the

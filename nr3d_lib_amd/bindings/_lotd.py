@@ -401,7 +401,7 @@ def lod_bwd(lod_meta, dL_dy, input, params, dy_dx=None, batch_inds=None, batch_o
     """``level_buckets`` / ``on_bucket`` (no reference counterpart, non-batched params only): compute dL/dparam in the
     given order of inclusive level ranges ``[(lo, hi), ...]`` and call ``on_bucket(k, grad_slice)`` as soon as bucket k is
     enqueued -- ``grad_slice`` is the contiguous part of dL_dparam that holds those levels, e.g. to start its
-    all-reduce while the next bucket is accumulated (nr3d_lotd_bwd_dparam_levels)."""
+    all-reduce while the next bucket is accumulated (nr3d_lotd_bwd_dparam with min_level)."""
     if isinstance(lod_meta, tuple):
         from . import _forest
         return _forest.lod_bwd(lod_meta, dL_dy, input, params, dy_dx, batch_inds, batch_offsets, batch_data_size, max_level,
@@ -431,7 +431,7 @@ def lod_bwd(lod_meta, dL_dy, input, params, dy_dx=None, batch_inds=None, batch_o
         native = (_native_half(m, params, batched) and level_buckets is None and USE_BINNED_DPARAM and input.dtype == torch.float32
                   and dL_dy.is_contiguous() and E % 4 == 0 and dL_dy.data_ptr() % 8 == 0 and not nothing
                   and params.shape[0] == m.n_params)
-        # the pair-record path defines every element of dL_dparam itself (nr3d_lotd_bwd_dparam_typed, assign): no
+        # the pair-record path defines every element of dL_dparam itself (nr3d_lotd_bwd_dparam, assign): no
         # zero-fill and no read-modify-write of the 46 MiB gradient
         typed = (not nothing and not batched and level_buckets is None and USE_BINNED_DPARAM
                  and (native or params.dtype == torch.float32) and params.shape[0] == m.n_params
@@ -469,39 +469,32 @@ def lod_bwd(lod_meta, dL_dy, input, params, dy_dx=None, batch_inds=None, batch_o
                 H.check(H.lib().nr3d_lotd_bwd_dx(
                     C.byref(m._cmeta()), N, H.F32, gcode, H.ptr(g32), gsn, gse, H.ptr(j), jsn, jse, H.ptr(dL_dx), H.ptr(gT),
                     max_level, H.ptr(fold), st))
-            if need_param_grad and N > 0 and typed:
-                ws, wsb = _dparam_workspace(m, N, dev, 1)
-                if gT is not None:
-                    g32, gsn, gse, gcode = gT, 1, N, H.F32
-                H.check(H.lib().nr3d_lotd_bwd_dparam_typed(
-                    C.byref(m._cmeta()), H.ptr(m._dev(dev)), N, gcode, H.ptr(g32), gsn, gse, H.ptr(_f32c(input.detach())),
-                    max_level, H.F16 if native else H.F32, 1, H.ptr(dL_dparam), H.ptr(ws), wsb, H.ptr(fold), st))
-            elif need_param_grad and N > 0:
+            if need_param_grad and N > 0:
                 x32, (p32, pcode) = _f32c(input.detach()), _ptab(params)
                 nbat = _n_batches(m, p32, batch_offsets, batched)
                 ws, wsb = _dparam_workspace(m, N, dev, nbat)
                 if gT is not None:
-                    g32, gsn, gse = gT, 1, N
-                if level_buckets is None:
-                    H.check(H.lib().nr3d_lotd_bwd_dparam(
-                        C.byref(m._cmeta()), H.ptr(m._dev(dev)), N, H.F32, pcode, H.ptr(g32), gsn, gse, H.ptr(x32), H.ptr(p32),
-                        H.ptr(batch_inds), H.ptr(batch_offsets), bds, nbat, max_level, H.ptr(dL_dparam), H.ptr(ws), wsb, st))
-                else:
+                    g32, gsn, gse, gcode = gT, 1, N, H.F32
+                ranges = [(0, max_level)]
+                if level_buckets is not None:
                     if batched:
                         raise RuntimeError("bwd: level_buckets need non-batched params")
                     if params.dtype != torch.float32:
                         raise RuntimeError("bwd: level_buckets need float params (the slices handed out are the result)")
-                    seen = set()
-                    for k, (lo, hi) in enumerate(level_buckets):
+                    ranges, seen = [], set()
+                    for lo, hi in level_buckets:
                         lo, hi = int(lo), min(int(hi), m.n_levels - 1)
                         if lo < 0 or lo > hi or seen & set(range(lo, hi + 1)):
                             raise RuntimeError(f"bwd: bad or overlapping level bucket {(lo, hi)}")
                         seen |= set(range(lo, hi + 1))
-                        H.check(H.lib().nr3d_lotd_bwd_dparam_levels(
-                            C.byref(m._cmeta()), H.ptr(m._dev(dev)), N, H.F32, H.F32, H.ptr(g32), gsn, gse, H.ptr(x32), H.ptr(p32),
-                            None, None, 0, nbat, lo, min(hi, max_level), H.ptr(dL_dparam), H.ptr(ws), wsb, st))
-                        if on_bucket is not None:
-                            on_bucket(k, dL_dparam[m.level_offsets[lo]:m.level_offsets[hi + 1]])
+                        ranges.append((lo, hi))
+                for k, (lo, hi) in enumerate(ranges):
+                    H.check(H.lib().nr3d_lotd_bwd_dparam(
+                        C.byref(m._cmeta()), H.ptr(m._dev(dev)), N, gcode, H.ptr(g32), gsn, gse, None, H.ptr(x32), pcode, H.ptr(p32),
+                        H.ptr(batch_inds), H.ptr(batch_offsets), bds, nbat, lo, min(hi, max_level),
+                        H.F16 if native else H.F32, int(typed), H.ptr(dL_dparam), H.ptr(ws), wsb, H.ptr(fold), st))
+                    if level_buckets is not None and on_bucket is not None:
+                        on_bucket(k, dL_dparam[m.level_offsets[lo]:m.level_offsets[hi + 1]])
     return _cast(dL_dx, input.dtype), _cast(dL_dparam, params.dtype)
 
 
@@ -586,9 +579,9 @@ def lod_bwd_bwd_input(lod_meta, dL_ddLdx, dL_dy, input, params, dy_dx=None, batc
             if need_dp:
                 nbat = _n_batches(m, p32, batch_offsets, batched)
                 ws, wsb = _dparam_workspace(m, N, dev, nbat)
-                H.check(H.lib().nr3d_lotd_bwd_bwd_dparam(
-                    cm, md, N, H.F32, pcode, H.ptr(v32), H.ptr(g32), gsn, gse, H.ptr(x32), H.ptr(p32), H.ptr(batch_inds),
-                    H.ptr(batch_offsets), bds, nbat, max_level, H.ptr(dL_dparams), H.ptr(ws), wsb, st))
+                H.check(H.lib().nr3d_lotd_bwd_dparam(
+                    cm, md, N, H.F32, H.ptr(g32), gsn, gse, H.ptr(v32), H.ptr(x32), pcode, H.ptr(p32), H.ptr(batch_inds),
+                    H.ptr(batch_offsets), bds, nbat, 0, max_level, H.F32, 0, H.ptr(dL_dparams), H.ptr(ws), wsb, None, st))
     return _cast(dL_ddLdy, dL_dy.dtype), _cast(dL_dparams, params.dtype), _cast(dL_dx, input.dtype)
 
 

@@ -1730,50 +1730,72 @@ extern "C" uint64_t nr3d_lotd_pair_fold_bytes(const nr3d_lotd_meta_t *meta, uint
 	return meta ? pair_fold_layout(meta, N, max_level, gcols, n_zero, slot_off) : 0;
 }
 
-static int launch_bwd_dparam(const DparamPass &p) {
-	const nr3d_lotd_meta_t *meta = p.meta;
-	if (p.N == 0 || p.max_level <= -1 || p.min_level > p.max_level) return 0;
-	NR3D_CHECK(p.dL_dy && p.x && p.params && p.dparam, "LoTD::bwd: NULL tensor pointer");
+// The dL/dparam entry of a single block (include/nr3d_hip.h has the contract): the refusals, the pass record, the assign rule, then
+// the record routes where the workspace serves the call and the atomic kernels where it does not.
+extern "C" int nr3d_lotd_bwd_dparam(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int grad_dtype,
+                                    const void *dL_dy, int64_t g_sn, int64_t g_se, const void *dL_ddLdx, const void *x,
+                                    int param_dtype, const void *params, const int64_t *batch_inds, const int64_t *batch_offsets,
+                                    uint32_t batch_data_size, uint32_t n_batches, int32_t min_level, int32_t max_level,
+                                    int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
+                                    void *fold, void *stream) {
+	const auto f32_f16 = [](int t) { return t == NR3D_F32 || t == NR3D_F16; };
+	const bool second = dL_ddLdx != nullptr, half = grad_dtype == NR3D_F16 || out_dtype == NR3D_F16;
+	const bool batched = batch_inds || batch_offsets || batch_data_size;
+	NR3D_CHECK(f32_f16(grad_dtype), "LoTD::bwd_dparam: grad_dtype must be NR3D_F32 or NR3D_F16 (got %d)", grad_dtype);
+	NR3D_CHECK(f32_f16(param_dtype), "LoTD::bwd_dparam: param_dtype must be NR3D_F32 or NR3D_F16 (got %d)", param_dtype);
+	NR3D_CHECK(f32_f16(out_dtype), "LoTD::bwd_dparam: out_dtype must be NR3D_F32 or NR3D_F16 (got %d)", out_dtype);
+	NR3D_CHECK(min_level >= 0, "LoTD::bwd_dparam: min_level must be >= 0 (got %d)", min_level);
+	NR3D_CHECK(!(second && min_level > 0), "LoTD::bwd_dparam: a level range (min_level > 0) is first order only, dL_ddLdx must be NULL");
+	NR3D_CHECK(!(second && half), "LoTD::bwd_dparam: half grad_dtype / out_dtype are first order only, dL_ddLdx must be NULL");
+	NR3D_CHECK(!(second && fold), "LoTD::bwd_dparam: fold is first order only, dL_ddLdx must be NULL");
+	NR3D_CHECK(!(half && min_level > 0), "LoTD::bwd_dparam: half grad_dtype / out_dtype take no level range, min_level must be 0");
+	NR3D_CHECK(!(half && (batched || n_batches > 1u)),
+	           "LoTD::bwd_dparam: half grad_dtype / out_dtype take no batch (batch_inds, batch_offsets, batch_data_size, n_batches)");
+	NR3D_CHECK(!(fold && min_level > 0), "LoTD::bwd_dparam: fold takes no level range, min_level must be 0");
+	if (int rc = check_common(meta, meta_dev, NR3D_F32, param_dtype, true)) return rc;
+	DparamPass p = plain_pass(meta, meta_dev, N, dL_dy, g_sn, g_se, x, dL_dparam);
+	p.second = second; p.dL_ddLdx = (const float *)dL_ddLdx;
+	p.g_half = grad_dtype == NR3D_F16; p.out_half = out_dtype == NR3D_F16;
+	p.params = params; p.p_half = param_dtype == NR3D_F16;
+	p.batch = Batch{batch_inds, batch_offsets, batch_data_size, meta->n_params}; p.n_batches = batched ? n_batches : 1u;
+	p.min_level = min_level; p.max_level = max_level;
+	p.workspace = workspace; p.workspace_bytes = workspace_bytes; p.st = (hipStream_t)stream;
+	p.fold = (uint32_t *)fold;
+	const bool empty = N == 0 || max_level <= -1 || min_level > max_level;
+	NR3D_CHECK(empty || (dL_dy && x && params && dL_dparam), "LoTD::bwd: NULL tensor pointer");
+	// uninitialised dparam: the pair path assigns when ONE first-order pass covers every level; every other case zero-fills and accumulates
+	const auto zero_fill = [&]() {
+		return hipMemsetAsync(dL_dparam, 0, (size_t)(p.n_batches ? p.n_batches : 1u) * meta->n_params * (p.out_half ? 2 : 4), p.st);
+	};
+	p.assign = assign && !empty && !second && !batched && workspace && pair_applies(meta) && dparam_one_pass(N) && min_level == 0 &&
+	           max_level >= (int32_t)meta->n_levels - 1;
+	if (assign && !p.assign && dL_dparam) NR3D_HIP_CHECK(zero_fill());
+	if (empty) return 0;
 	// atomic-free binned path: metas without NPlaneSum/CPfast levels, when the caller supplied the workspace (batched
 	// params need n_batches, the number of table sets behind `params`)
-	const bool batched = p.batch.inds || p.batch.offsets || p.batch.data_size;
-	if (p.workspace && (!batched || p.n_batches > 0)) {
+	if (workspace && (!batched || n_batches > 0)) {
 		bool handled = false;
-		DparamPass q = p;
-		if (!batched) q.n_batches = 1u;
-		NR3D_TRY(dparam_binned(q, handled));
+		NR3D_TRY(dparam_binned(p, handled));
 		if (handled) return 0;
 	}
+	NR3D_CHECK(!half, "LoTD::bwd_dparam: half grad_dtype / out_dtype need the pair-record path (nr3d_lotd_half_params_ok) and its workspace");
+	if (p.assign) NR3D_HIP_CHECK(zero_fill());          // the workspace is too small for the pair path after all
 	uint32_t n_blocks;
-	const Sched s = make_sched(p.N, meta, n_blocks);
+	const Sched s = make_sched(N, meta, n_blocks);
 	const bool dh = meta->c_hash_only != 0;
 	DISPATCH_DG(meta->n_dims_to_encode, meta->n_feat_per_pseudo_lvl, {
 		auto launch = [&](auto kern, auto *tab) {
-			hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(kBlock), 0, p.st, s, p.meta_dev, p.N, p.min_level, p.max_level,
-			                   meta->interpolation_type, p.dL_ddLdx, p.dL_dy, p.g_sn, p.g_se, p.x, tab, p.batch, p.dparam);
+			hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(kBlock), 0, p.st, s, p.meta_dev, N, min_level, max_level,
+			                   meta->interpolation_type, p.dL_ddLdx, p.dL_dy, g_sn, g_se, p.x, tab, p.batch, p.dparam);
 		};
-		const float *pf = (const float *)p.params;
+		const float *pf = (const float *)params;
 		// Dense / Hash levels read no table: the hash-only instantiations serve both storage types (no k_bwd_dparam<., ., ., true, __half>)
 		if (dh || !p.p_half)
-			with_bool(p.second, [&](auto S) { if (dh) launch(k_bwd_dparam<D, G, S(), true>, pf); else launch(k_bwd_dparam<D, G, S(), false>, pf); });
-		else with_bool(p.second, [&](auto S) { launch(k_bwd_dparam<D, G, S(), false, __half>, (const __half *)p.params); });
+			with_bool(second, [&](auto S) { if (dh) launch(k_bwd_dparam<D, G, S(), true>, pf); else launch(k_bwd_dparam<D, G, S(), false>, pf); });
+		else with_bool(second, [&](auto S) { launch(k_bwd_dparam<D, G, S(), false, __half>, (const __half *)params); });
 	});
 	NR3D_LAUNCH_CHECK();
 	return 0;
-}
-
-extern "C" int nr3d_lotd_bwd_dparam(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int x_dtype,
-                                    int param_dtype, const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x,
-                                    const void *params, const int64_t *batch_inds, const int64_t *batch_offsets,
-                                    uint32_t batch_data_size, uint32_t n_batches, int32_t max_level, void *dL_dparam,
-                                    void *workspace, uint64_t workspace_bytes, void *stream) {
-	if (int rc = check_common(meta, meta_dev, x_dtype, param_dtype, true)) return rc;
-	DparamPass p = plain_pass(meta, meta_dev, N, dL_dy, g_sn, g_se, x, dL_dparam);
-	p.params = params; p.p_half = param_dtype == NR3D_F16;
-	p.batch = Batch{batch_inds, batch_offsets, batch_data_size, meta->n_params}; p.n_batches = n_batches;
-	p.min_level = 0; p.max_level = max_level;
-	p.workspace = workspace; p.workspace_bytes = workspace_bytes; p.st = (hipStream_t)stream;
-	return launch_bwd_dparam(p);
 }
 
 extern "C" int nr3d_lotd_pair_path_ok(const nr3d_lotd_meta_t *meta) { return (meta && pair_applies(meta)) ? 1 : 0; }
@@ -1786,67 +1808,10 @@ extern "C" int nr3d_lotd_pair_direct_levels(const nr3d_lotd_meta_t *meta, uint32
 	return (meta && pair_applies(meta)) ? (int)pair_direct_levels(meta, n_points) : 0;
 }
 
-extern "C" int nr3d_lotd_bwd_dparam_typed(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int grad_dtype,
-                                          const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x, int32_t max_level,
-                                          int out_dtype, int assign, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
-                                          void *fold, void *stream) {
-	if (int rc = check_common(meta, meta_dev, NR3D_F32, NR3D_F32)) return rc;
-	NR3D_CHECK((grad_dtype == NR3D_F32 || grad_dtype == NR3D_F16) && (out_dtype == NR3D_F32 || out_dtype == NR3D_F16),
-	           "LoTD::bwd_dparam_typed: f32 / f16 only");
-	if (N == 0 || max_level <= -1) {
-		if (assign && dL_dparam)
-			NR3D_HIP_CHECK(hipMemsetAsync(dL_dparam, 0, (size_t)meta->n_params * (out_dtype == NR3D_F16 ? 2 : 4), (hipStream_t)stream));
-		return 0;
-	}
-	NR3D_CHECK(dL_dy && x && dL_dparam && workspace, "LoTD::bwd: NULL tensor pointer");
-	bool handled = false;
-	DparamPass p = plain_pass(meta, meta_dev, N, dL_dy, g_sn, g_se, x, dL_dparam);
-	p.g_half = grad_dtype == NR3D_F16; p.out_half = out_dtype == NR3D_F16; p.assign = assign != 0;
-	p.max_level = max_level;
-	p.workspace = workspace; p.workspace_bytes = workspace_bytes; p.st = (hipStream_t)stream;
-	p.fold = (uint32_t *)fold;
-	NR3D_TRY(dparam_binned(p, handled));
-	NR3D_CHECK(handled, "LoTD::bwd_dparam_typed: the pair-record path does not apply to this meta / workspace");
-	return 0;
-}
-
-extern "C" int nr3d_lotd_bwd_dparam_levels(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int x_dtype,
-                                           int param_dtype, const void *dL_dy, int64_t g_sn, int64_t g_se, const void *x,
-                                           const void *params, const int64_t *batch_inds, const int64_t *batch_offsets,
-                                           uint32_t batch_data_size, uint32_t n_batches, int32_t min_level,
-                                           int32_t max_level, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
-                                           void *stream) {
-	if (int rc = check_common(meta, meta_dev, x_dtype, param_dtype, true)) return rc;
-	NR3D_CHECK(min_level >= 0, "LoTD::bwd: min_level must be >= 0");
-	DparamPass p = plain_pass(meta, meta_dev, N, dL_dy, g_sn, g_se, x, dL_dparam);
-	p.params = params; p.p_half = param_dtype == NR3D_F16;
-	p.batch = Batch{batch_inds, batch_offsets, batch_data_size, meta->n_params}; p.n_batches = n_batches;
-	p.min_level = min_level; p.max_level = max_level;
-	p.workspace = workspace; p.workspace_bytes = workspace_bytes; p.st = (hipStream_t)stream;
-	return launch_bwd_dparam(p);
-}
-
 extern "C" void nr3d_lotd_set_dparam_chunk_log2(int log2_points) { set_dparam_chunk_log2(log2_points); }
 
 extern "C" uint64_t nr3d_lotd_dparam_workspace_bytes(const nr3d_lotd_meta_t *meta, uint32_t n_points, uint32_t n_batches) {
 	return dparam_workspace_bytes(meta, n_points, n_batches);
-}
-
-extern "C" int nr3d_lotd_bwd_bwd_dparam(const nr3d_lotd_meta_t *meta, const void *meta_dev, uint32_t N, int x_dtype,
-                                        int param_dtype, const void *dL_ddLdx, const void *dL_dy, int64_t g_sn,
-                                        int64_t g_se, const void *x, const void *params, const int64_t *batch_inds,
-                                        const int64_t *batch_offsets, uint32_t batch_data_size, uint32_t n_batches,
-                                        int32_t max_level, void *dL_dparam, void *workspace, uint64_t workspace_bytes,
-                                        void *stream) {
-	if (int rc = check_common(meta, meta_dev, x_dtype, param_dtype, true)) return rc;
-	NR3D_CHECK(N == 0 || dL_ddLdx != nullptr, "LoTD::bwd_bwd_input: dL_ddLdx is NULL");
-	DparamPass p = plain_pass(meta, meta_dev, N, dL_dy, g_sn, g_se, x, dL_dparam);
-	p.second = true; p.dL_ddLdx = (const float *)dL_ddLdx;
-	p.params = params; p.p_half = param_dtype == NR3D_F16;
-	p.batch = Batch{batch_inds, batch_offsets, batch_data_size, meta->n_params}; p.n_batches = n_batches;
-	p.min_level = 0; p.max_level = max_level;
-	p.workspace = workspace; p.workspace_bytes = workspace_bytes; p.st = (hipStream_t)stream;
-	return launch_bwd_dparam(p);
 }
 
 extern "C" int nr3d_lotd_bwd_bwd_ddLdy(const nr3d_lotd_meta_t *meta, uint32_t N, int x_dtype, int param_dtype,

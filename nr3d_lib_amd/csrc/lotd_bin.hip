@@ -1713,7 +1713,7 @@ static int class_route(const DparamPass &p, DparamChunk &c, const BinPlan &pl, u
 
 int dparam_binned(const DparamPass &pass, bool &handled) {
 	handled = false;
-	DparamPass p = pass;                               // + what this function settles: the stage-A meta, assign, fold
+	DparamPass p = pass;                               // + what this function settles: the stage-A meta, fold
 	BinLayout lay;
 	const uint32_t N = p.N, nc = chunk_points(N);
 	const bool forest = p.forest != nullptr;
@@ -1749,10 +1749,8 @@ int dparam_binned(const DparamPass &pass, bool &handled) {
 	const bool use_pair = plain && pair_applies(meta) && !(p.second && !pair_second_enabled());
 	if ((p.g_half || p.out_half) && !use_pair)
 		return ::nr3d::fail("LoTD::bwd: half gradients are served natively on the pair-record path only (nr3d_lotd_half_params_ok)");
-	// uninitialised dparam: the pair path assigns when ONE pass covers every level; otherwise zero-fill and accumulate
-	p.assign = pass.assign && use_pair && N <= nc && p.min_level <= 0 && p.max_level >= (int32_t)meta->n_levels - 1;
-	if (pass.assign && !p.assign)
-		NR3D_HIP_CHECK(hipMemsetAsync(p.dparam, 0, (size_t)(p.n_batches ? p.n_batches : 1u) * meta->n_params * (p.out_half ? 2 : 4), p.st));
+	// p.assign (uninitialised dparam) comes settled: nr3d_lotd_bwd_dparam sets it only for ONE first-order pair pass over every level
+	if (p.assign && !(use_pair && N <= nc)) return ::nr3d::fail("LoTD::bwd (binned): assign without a single pair pass");
 	if (!(N <= nc && !p.second)) p.fold = nullptr;      // the folded route: one first-order pass
 
 	for (uint32_t p0 = 0; p0 < N; p0 += nc) {

@@ -750,8 +750,8 @@ struct DparamPass {
 	int32_t min_level, max_level;       // levels below `min_level` are left out (their part of dparam is not touched)
 	float *dparam;
 	bool out_half;                      // dparam is __half (pair path only)
-	bool assign;                        // dparam arrives UNINITIALISED -- the pair path writes every element when one pass covers all
-	                                    // levels, every other case zero-fills it first
+	bool assign;                        // dparam is UNINITIALISED and this pass writes every element: one first-order pair pass over all
+	                                    // levels (nr3d_lotd_bwd_dparam decides, and zero-fills in every other case)
 	void *workspace;
 	uint64_t workspace_bytes;
 	hipStream_t st;

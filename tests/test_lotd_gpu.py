@@ -288,7 +288,7 @@ def test_dparam_atomic_and_binned_paths_agree(oracle, dev, case):
 
 @pytest.mark.parametrize("case", ["ngp_small", "mixed", "dense_2d", "nplane"])
 def test_dparam_level_buckets(oracle, dev, case, bin_mode):
-    """dL/dparam computed in level buckets (nr3d_lotd_bwd_dparam_levels; the data-parallel path reduces a finished
+    """dL/dparam computed in level buckets (nr3d_lotd_bwd_dparam with min_level; the data-parallel path reduces a finished
     bucket while the next one is accumulated): the buckets together are the one-call gradient (to fp32 rounding of the
     fp64 partial sums: how a hot table slice is split over workgroups follows the call's records), every bucket callback
     sees exactly its levels' slice, and levels outside the buckets stay zero"""

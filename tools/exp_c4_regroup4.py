@@ -31,9 +31,9 @@ for cap, gs in groups:
     def run():
         dp = torch.zeros(meta.n_params, device=dev)
         for gm, gd in gs:
-            H.check(H.lib().nr3d_lotd_bwd_dparam(C.byref(gm), H.ptr(gd), N, H.F32, H.F32, H.ptr(gT), 1, N,
-                                                 H.ptr(x), H.ptr(params), None, None, 0, 1, meta.n_levels, H.ptr(dp), H.ptr(ws),
-                                                 need, H.stream_of(x)))
+            H.check(H.lib().nr3d_lotd_bwd_dparam(C.byref(gm), H.ptr(gd), N, H.F32, H.ptr(gT), 1, N, None,
+                                                 H.ptr(x), H.F32, H.ptr(params), None, None, 0, 1, 0, meta.n_levels, H.F32, 0,
+                                                 H.ptr(dp), H.ptr(ws), need, None, H.stream_of(x)))
         return dp
     dp = run(); run(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
