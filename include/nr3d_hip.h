@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 20
+#define NR3D_ABI_VERSION 21
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -454,8 +454,9 @@ int nr3d_occ_apply_max(uint64_t n_voxels, float ema_decay, const float *vmax, fl
  * log1p(exp(beta z)) / beta, evaluated on the fp32 accumulator -- the activation of the reference's SDF decoders
  * (nr3d_lib/models/fields/sdf/mlp_sdf.py:30: {'type': 'softplus', 'beta': 100.}).  A HIDDEN activation only, on the forward and the
  * first backward of both precisions: as output_activation, or with a softplus_beta that is not finite or not > 0, every size query
- * below returns 0 (the caller keeps its unfused path).  A valid softplus network has the sizes of the same dims with ReLU.  The
- * fused double backward does not take it (nr3d_mlp_backward_backward_ok returns 0). */
+ * below returns 0 (the caller keeps its unfused path).  A valid softplus network has the sizes of the same dims with ReLU.
+ * nr3d_mlp_backward_backward does not take it (nr3d_mlp_backward_backward_ok returns 0: the network is not piecewise linear); its
+ * double backward is nr3d_mlp_softplus_backward_backward (ABI 21), which also produces dL/db and dL/dx. */
 enum { NR3D_MLP_ACT_NONE = 0, NR3D_MLP_ACT_RELU = 1, NR3D_MLP_ACT_SOFTPLUS = 2 };
 
 typedef struct nr3d_mlp_desc {
@@ -499,6 +500,23 @@ int nr3d_mlp_backward_backward_ok(const nr3d_mlp_desc_t *desc);
 int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, int64_t x_stride, int64_t x_feature_stride,
                                const float *dL_dy, int64_t gy_stride, const float *ddL_dx, int64_t v_stride, int64_t v_feature_stride,
                                const float *packed, float *dL_ddLdy, int64_t ggy_stride, float *const *dL_dW, void *stream);
+/* Double backward with softplus hidden layers (ABI 21; the eikonal term of the reference's SDF decoders).  sigma'' = beta s e is not
+ * zero (s_l = sigmoid(beta z_l), e_l = 1 - s_l; above the threshold s = 1 and e = 0 exactly, as torch), so with u = dL_dy, v = ddL_dx,
+ * r_l / g_l the first backward's chain (r_L = m_L u, g_l = W_{l+1}^T r_{l+1}, r_l = s_l g_l) and t_l = s_l W_l t_{l-1} (t_0 = v):
+ *   q_l = beta e_l g_l t_l,   p_NH = q_NH,   p_l = q_l + s_l W_{l+1}^T p_{l+1}                 (hidden layers)
+ *   dL_dW[l] += sum over samples of r_l t_{l-1}^T + p_l h_{l-1}^T                               (output layer: the first term only)
+ *   dL_db[l] += sum over samples of p_l     (hidden layers; dL_db or entries may be NULL; the output layer's entry is not touched)
+ *   dL_dx = W_1^T p_1, fully written, row- or feature-major as nr3d_mlp_backward's (NULL: not wanted)
+ *   dL_ddLdy [n, out] rows = m_L W_L t_NH, fully written (NULL: not wanted).
+ * x, ddL_dx, dL_dy (gy_stride 0 allowed), packed and the fp32 atomics on dL_dW / dL_db as nr3d_mlp_backward_backward; n == 0 returns 0.
+ * nr3d_mlp_softplus_backward_backward_ok: 1 exactly for softplus hidden layers (valid beta, output none or ReLU) on a shape
+ * nr3d_mlp_backward takes and whose launch plan (per-wave LDS tiles about twice those of nr3d_mlp_backward_backward) fits at least one
+ * wave; a ReLU / linear desc gives 0 and nr3d_mlp_softplus_backward_backward then fails with a message. */
+int nr3d_mlp_softplus_backward_backward_ok(const nr3d_mlp_desc_t *desc);
+int nr3d_mlp_softplus_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, int64_t x_stride, int64_t x_feature_stride,
+                                        const float *dL_dy, int64_t gy_stride, const float *ddL_dx, int64_t v_stride,
+                                        int64_t v_feature_stride, const float *packed, float *dL_ddLdy, int64_t ggy_stride, float *dL_dx,
+                                        int64_t gx_stride, int64_t gx_feature_stride, float *const *dL_dW, float *const *dL_db, void *stream);
 
 /* The same decoder in HALF precision on the f16 MFMA (csrc/mlp_half.hip) -- the contract of the reference's fast decoder,
  * tiny-cuda-nn's FullyFusedMLP behind nr3d_lib/models/tcnn_adapter.py:37-51,74-146 (`use_tcnn_backend`,

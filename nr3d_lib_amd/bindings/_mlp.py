@@ -18,7 +18,8 @@ class _CDesc(C.Structure):
 
 class MLPDesc:
     """dims = [in_features, hidden..., out_features]; beta: of ``hidden_activation=ACT_SOFTPLUS`` (torch.nn.Softplus(beta,
-    threshold=20) after every hidden layer; forward and first backward of both precisions, no fused double backward), not read otherwise"""
+    threshold=20) after every hidden layer; forward and first backward of both precisions; its fused double backward is
+    backward_backward_softplus, ``softplus_second_order_fusable``), not read otherwise"""
 
     def __init__(self, dims, hidden_activation=ACT_RELU, output_activation=ACT_NONE, beta=1.0):
         self.dims = [int(d) for d in dims]
@@ -40,6 +41,8 @@ class MLPDesc:
         self.half_backward_bytes = l.nr3d_mlp_half_backward_packed_bytes(C.byref(c)) if self.half_packed_bytes else 0
         # the fused double backward (nr3d_mlp_backward_backward) on the fp32 packed buffer
         self.second_order_ok = bool(l.nr3d_mlp_backward_backward_ok(C.byref(c))) if self.backward_floats else False
+        # ... of softplus hidden layers (nr3d_mlp_softplus_backward_backward): an entry, a kernel and a launch plan of their own
+        self.softplus_second_order_ok = bool(l.nr3d_mlp_softplus_backward_backward_ok(C.byref(c))) if self.backward_floats else False
 
     @property
     def fusable(self) -> bool:
@@ -52,6 +55,10 @@ class MLPDesc:
     @property
     def second_order_fusable(self) -> bool:
         return self.second_order_ok
+
+    @property
+    def softplus_second_order_fusable(self) -> bool:
+        return self.softplus_second_order_ok
 
     @property
     def half_fusable(self) -> bool:
@@ -177,7 +184,7 @@ def backward_backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, ddL_d
                       has_bias=None):
     """The double backward: gradients of <dL/dx, ddL_dx> (dL/dx = backward()'s, a function of the parameters and dL_dy) ->
     (dL/d(dL_dy) | None, [dL/dW_l], [dL/db_l | None]).  ReLU / linear networks only (softplus hidden layers: desc.second_order_fusable is
-    False and the caller differentiates its torch route).  dL/dx and dL/db_l are zero (the network is piecewise linear): dL/dx is not
+    False, backward_backward_softplus takes them).  dL/dx and dL/db_l are zero (the network is piecewise linear): dL/dx is not
     produced, dL/db_l are zero views of the dW pool for the layers has_bias marks (default: none).  x and ddL_dx row-major with any
     row stride or feature-major, dL_dy rows with any row stride (0 included: an expanded ones); `packed` from
     pack(..., with_backward=True).  dL/d(dL_dy) has dL_dy's shape."""
@@ -201,6 +208,41 @@ def backward_backward(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, ddL_d
             C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(g2), gs, H.ptr(v2), vs, vf,
             H.ptr(packed), H.ptr(dgy), desc.dims[-1], _ptr_array(dWs), H.stream_of(x)))
     return (None if dgy is None else dgy.view(dL_dy.shape)), dWs, dbs
+
+
+def backward_backward_softplus(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tensor, ddL_dx: torch.Tensor, packed: torch.Tensor,
+                               need_dgy=True, need_dx=True, has_bias=None):
+    """The double backward of a network with softplus hidden layers (desc.softplus_second_order_fusable): gradients of <dL/dx, ddL_dx> ->
+    (dL/d(dL_dy) | None, dL/dx | None, [dL/dW_l], [dL/db_l | None]).  Softplus is not piecewise linear, so x and the hidden biases get
+    a gradient: dL/dx has the layout of x (feature-major for a feature-major x, as backward()'s); dL/db_l for the layers has_bias marks
+    (default: all) -- the output layer's entry stays zero, its bias does not reach dL/dx.  Layout rules as backward_backward."""
+    H.require_gpu(x, dL_dy, ddL_dx, packed)
+    if desc.hidden_activation != ACT_SOFTPLUS:
+        raise RuntimeError("mlp.backward_backward_softplus: softplus hidden layers only (ReLU / linear networks: backward_backward)")
+    if not desc.softplus_second_order_fusable:
+        raise RuntimeError("mlp.backward_backward_softplus: the fused double backward does not apply to this network")
+    x2 = x.reshape(-1, desc.dims[0])
+    v2 = ddL_dx.reshape(-1, desc.dims[0])
+    g2 = dL_dy.reshape(-1, desc.dims[-1])
+    if (x2.dtype != torch.float32 or g2.dtype != torch.float32 or v2.dtype != torch.float32 or x2.shape[0] != g2.shape[0]
+            or v2.shape[0] != x2.shape[0]):
+        raise RuntimeError("mlp.backward_backward_softplus: expected fp32 x [n, in], dL_dy [n, out] and ddL_dx [n, in]")
+    x2, xs, xf = _layout(x2)
+    v2, vs, vf = _layout(v2)
+    g2, gs = _rows(g2)
+    n, dev = x2.shape[0], x.device
+    dWs, dbs = _grad_pool(desc, [True] * (len(desc.dims) - 1) if has_bias is None else list(has_bias), dev)
+    dgy = H.empty((n, desc.dims[-1]), dtype=torch.float32, device=dev) if need_dgy else None
+    dx, gxs, gxf = None, desc.dims[0], 1
+    if need_dx and xf != 1:
+        dx, gxs, gxf = H.empty((desc.dims[0], n), dtype=torch.float32, device=dev).t(), 1, n
+    elif need_dx:
+        dx = H.empty((n, desc.dims[0]), dtype=torch.float32, device=dev)
+    with H.on_device(dev):
+        H.check(H.lib().nr3d_mlp_softplus_backward_backward(
+            C.byref(desc._c), n, H.ptr(x2), xs, xf, H.ptr(g2), gs, H.ptr(v2), vs, vf, H.ptr(packed), H.ptr(dgy), desc.dims[-1],
+            H.ptr(dx), gxs, gxf, _ptr_array(dWs), _ptr_array(dbs), H.stream_of(x)))
+    return (None if dgy is None else dgy.view(dL_dy.shape)), (None if dx is None else dx.reshape(x.shape)), dWs, dbs
 
 
 # ------------------------------------------------------------------------------------------------

@@ -15,8 +15,10 @@ backward is the same fused kernel, wrapped as ``FusedMLPBackwardFunction``, and 
 double backward (csrc/mlp.hip k_mlp_bwd2, ``FUSED_SECOND_ORDER``) for both the fp32 and the half block (the half block's second order
 is evaluated in fp32 from the fp32 parameters, as its torch route does).  The double backward gives x no gradient (ReLU / linear
 networks: it is zero), so ``x.grad`` stays None when the eikonal term is x's only consumer.  A softplus network is not piecewise
-linear -- the eikonal term does give x and the biases a gradient -- and has no fused double backward (``desc.second_order_fusable`` is
-False): its create_graph backward differentiates the layer-by-layer torch evaluation of the same network."""
+linear -- the eikonal term does give x and the hidden biases a gradient, and there is a sigma'' chain -- so it has a double backward
+kernel of its own (csrc/mlp_softplus2.hip k_mlp_bwd2_sp, ``desc.softplus_second_order_fusable``; ``desc.second_order_fusable`` stays False for
+it), taken when ``FUSED_SOFTPLUS_SECOND_ORDER`` is on: the nablas are then the fused first backward's dL/dx bit for bit.  With the switch
+off its create_graph backward differentiates the layer-by-layer torch evaluation of the same network."""
 from typing import List, Union
 
 import torch
@@ -32,6 +34,14 @@ USE_FUSED = True                       # False: always the layer-by-layer path (
 # False: a create_graph backward of a fused block differentiates the layer-by-layer torch evaluation (the route before the fused double
 # backward; A/B measurements, tests)
 FUSED_SECOND_ORDER = True
+# True: softplus networks take the fused route above too, through their own double backward kernel (k_mlp_bwd2_sp).  Needs
+# FUSED_SECOND_ORDER.  False: their create_graph backward differentiates the torch evaluation.  DESIGN 7b has the measurements behind the default.
+FUSED_SOFTPLUS_SECOND_ORDER = True
+
+
+def _fused_second_order(desc):
+    """does a create_graph backward of this network return the fused first backward (FusedMLPBackwardFunction)?"""
+    return FUSED_SECOND_ORDER and (desc.second_order_fusable or (FUSED_SOFTPLUS_SECOND_ORDER and desc.softplus_second_order_fusable))
 # nn.Softplus hidden layers run on the fused kernels from this beta up (threshold 20, one beta for all hidden layers); below it they
 # keep the layer-by-layer path.  The line is the one at which get_nonlinearity (models/layers.py; the reference's layers.py:212) already
 # treats softplus as ReLU-like; every softplus of the reference has beta = 100, and the default nn.Softplus (beta = 1) stays on torch.
@@ -61,7 +71,8 @@ class FusedMLPFunction(torch.autograd.Function):
 
     Higher order (``create_graph=True``, e.g. the eikonal term on nablas = d sdf / dx): backward() then runs with grad
     mode on and returns the outputs of ``FusedMLPBackwardFunction`` -- the same fused kernel, whose own backward is the fused
-    double backward (or, with ``FUSED_SECOND_ORDER = False`` / outside its range -- softplus hidden layers among it --, the gradients
+    double backward (or, with ``FUSED_SECOND_ORDER = False`` / outside its range -- softplus hidden layers with
+    ``FUSED_SOFTPLUS_SECOND_ORDER = False`` among it --, the gradients
     of a layer-by-layer PyTorch evaluation of the same network on the saved inputs, which autograd can differentiate again).  First-order training never
     takes that branch."""
 
@@ -92,7 +103,7 @@ class FusedMLPFunction(torch.autograd.Function):
         x, packed, *flat = ctx.saved_tensors
         n_layers = len(ctx.has_bias)
         if torch.is_grad_enabled():
-            if FUSED_SECOND_ORDER and ctx.desc.second_order_fusable:
+            if _fused_second_order(ctx.desc):
                 return (None, None, *FusedMLPBackwardFunction.apply(ctx.desc, packed, tuple(ctx.has_bias), tuple(ctx.needs_input_grad[2:]),
                                                                     x, dL_dy.float(), *flat))
             return (None, None, *FusedMLPFunction._differentiable_backward(ctx, x, flat, dL_dy))
@@ -163,7 +174,7 @@ class FusedMLPHalfFunction(torch.autograd.Function):
             # differentiable form: ONE dtype for x, the (fp32) parameters and dL/dy -- F.linear(half, float) raises outside
             # autocast; the casts are differentiable, so the graph reaches the caller's x whatever its dtype.  Fused: the same fp32
             # network through the fp32 kernels (the fp32 parameters packed here), so the semantics do not change
-            if FUSED_SECOND_ORDER and ctx.desc.second_order_fusable:
+            if _fused_second_order(ctx.desc):
                 ws, bs = FusedMLPBackwardFunction._params(ctx.has_bias, flat)
                 packed32 = _mlp.pack(ctx.desc, ws, bs, with_backward=True)
                 out = list(FusedMLPBackwardFunction.apply(ctx.desc, packed32, tuple(ctx.has_bias), tuple(ctx.needs_input_grad[2:]),
@@ -191,8 +202,10 @@ class FusedMLPBackwardFunction(torch.autograd.Function):
     third order is asked for (grad mode off) and desc.second_order_fusable -- dL/dW_l from the kernel, dL/db_l zeros (views of the
     same pool, as the torch route's), dL/d(dL/dy) when asked for, and None for x: its gradient is zero (piecewise linear network), and
     an [n, in] tensor of zeros would cost a full write for nothing -- so x.grad stays None when the eikonal term is x's only
-    consumer.  Every other case differentiates the layer-by-layer torch evaluation of the network, as the route before this one;
-    softplus hidden layers always do (not piecewise linear: there x and the biases DO get a gradient from the eikonal term)."""
+    consumer.  Softplus hidden layers (FUSED_SOFTPLUS_SECOND_ORDER, desc.softplus_second_order_fusable) take
+    nr3d_mlp_softplus_backward_backward under the same conditions: not piecewise linear, so x (when it needs one) and the hidden
+    biases DO get a gradient from the eikonal term.  Every other case differentiates the layer-by-layer torch evaluation of the
+    network, as the route before this one."""
 
     @staticmethod
     def _params(has_bias, flat):
@@ -235,6 +248,16 @@ class FusedMLPBackwardFunction(torch.autograd.Function):
                 reach = ctx.desc.output_activation == relu or (l + 1 < n_l and ctx.desc.hidden_activation == relu)
                 gp += [dWs[l], dbs[l] if reach else None] if hb else [dWs[l]]
             return (None, None, None, None, None, dgy, *[g if n else None for g, n in zip(gp, need_p)])
+        if (grads[0] is not None and all(g is None for g in grads[1:]) and not torch.is_grad_enabled()
+                and FUSED_SOFTPLUS_SECOND_ORDER and ctx.desc.softplus_second_order_fusable):
+            dgy, dx, dWs, dbs = _mlp.backward_backward_softplus(ctx.desc, x, dL_dy, grads[0].float(), packed, need_dgy=need_gy,
+                                                                need_dx=ctx.needs_input_grad[4], has_bias=ctx.has_bias)
+            # hidden biases: the kernel's sums; the output bias reaches dL/dx only through an output ReLU's mask (zeros), else not at all
+            n_l, gp = len(ctx.has_bias), []
+            for l, hb in enumerate(ctx.has_bias):
+                reach = l + 1 < n_l or ctx.desc.output_activation == _mlp.ACT_RELU
+                gp += [dWs[l], dbs[l] if reach else None] if hb else [dWs[l]]
+            return (None, None, None, None, dx, dgy, *[g if n else None for g, n in zip(gp, need_p)])
         return (None, None, None, None, *FusedMLPBackwardFunction._torch_backward(ctx, x, dL_dy, flat, grads))
 
     @staticmethod
