@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 21
+#define NR3D_ABI_VERSION 22
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -456,14 +456,25 @@ int nr3d_occ_apply_max(uint64_t n_voxels, float ema_decay, const float *vmax, fl
  * first backward of both precisions: as output_activation, or with a softplus_beta that is not finite or not > 0, every size query
  * below returns 0 (the caller keeps its unfused path).  A valid softplus network has the sizes of the same dims with ReLU.
  * nr3d_mlp_backward_backward does not take it (nr3d_mlp_backward_backward_ok returns 0: the network is not piecewise linear); its
- * double backward is nr3d_mlp_softplus_backward_backward (ABI 21), which also produces dL/db and dL/dx. */
-enum { NR3D_MLP_ACT_NONE = 0, NR3D_MLP_ACT_RELU = 1, NR3D_MLP_ACT_SOFTPLUS = 2 };
+ * double backward is nr3d_mlp_softplus_backward_backward (ABI 21), which also produces dL/db and dL/dx.
+ *
+ * NR3D_MLP_ACT_SIGMOID (ABI 22): y = 1 / (1 + exp(-z)) on the fp32 accumulator z of the OUTPUT layer -- in the half kernels before the
+ * result is rounded to half -- the output activation of the reference's radiance decoders (nr3d_lib/models/fields/nerf/mlp_nerf.py:196,
+ * lotd_nerf.py:219-224: 32 -> 64 -> 64 -> 3, ReLU hidden layers).  An OUTPUT activation only, with any hidden activation the kernels
+ * take (none, ReLU, softplus), on the forward and the first backward of both precisions; the backward recomputes z and scales dL/dy by
+ * sigmoid'(z), no y is kept.  A sigmoid network has the sizes of the same dims with a ReLU output.  Neither double backward takes it
+ * (both _ok queries return 0, both entries fail with a message): the caller differentiates its unfused path.
+ *
+ * Any other combination -- sigmoid as hidden_activation, softplus as output_activation, a code outside this enum in either field -- is
+ * refused: every size query returns 0 and every entry fails with a message (ABI 22; before, an unknown code ran as the identity). */
+enum { NR3D_MLP_ACT_NONE = 0, NR3D_MLP_ACT_RELU = 1, NR3D_MLP_ACT_SOFTPLUS = 2, NR3D_MLP_ACT_SIGMOID = 3 };
 
 typedef struct nr3d_mlp_desc {
 	uint32_t n_layers;                          /* linear layers: hidden layers + 1 */
 	uint32_t dims[NR3D_MLP_MAX_LAYERS + 1];
-	uint32_t hidden_activation;                 /* NR3D_MLP_ACT_* after every hidden layer */
-	uint32_t output_activation;                 /* NR3D_MLP_ACT_NONE or NR3D_MLP_ACT_RELU */
+	uint32_t hidden_activation;                 /* after every hidden layer: NR3D_MLP_ACT_NONE, _RELU or _SOFTPLUS */
+	uint32_t output_activation;                 /* NR3D_MLP_ACT_NONE, _RELU or _SIGMOID (ABI 22: y = 1 / (1 + exp(-z)) on the output layer's
+	                                             * fp32 accumulator; half kernels: before the rounding to half) */
 	float softplus_beta;                        /* read only when hidden_activation == NR3D_MLP_ACT_SOFTPLUS (ABI 19; at the end: a
 	                                             * zero-initialised desc with ReLU / no activations means what it meant before) */
 } nr3d_mlp_desc_t;
@@ -494,8 +505,8 @@ int nr3d_mlp_forward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, in
  * packed comes from nr3d_mlp_pack(..., with_backward = 1); the forward is recomputed with nr3d_mlp_backward's route under the same
  * options (NR3D_OPT_MLP_X3), so the masks are bit for bit the ones its dL/dx used.  nr3d_mlp_backward_backward_ok: 1 when the
  * fused double backward applies (the shapes of nr3d_mlp_backward with ReLU / no hidden activation), else 0: the caller differentiates
- * its unfused path.  Softplus hidden layers are outside it (the network is not piecewise linear: dL/db_l and dL/dx are not zero);
- * nr3d_mlp_backward_backward then fails with a message. */
+ * its unfused path.  Softplus hidden layers are outside it (the network is not piecewise linear: dL/db_l and dL/dx are not zero), and
+ * so is a sigmoid output (ABI 22); nr3d_mlp_backward_backward then fails with a message. */
 int nr3d_mlp_backward_backward_ok(const nr3d_mlp_desc_t *desc);
 int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, int64_t x_stride, int64_t x_feature_stride,
                                const float *dL_dy, int64_t gy_stride, const float *ddL_dx, int64_t v_stride, int64_t v_feature_stride,
@@ -509,7 +520,7 @@ int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const fl
  *   dL_dx = W_1^T p_1, fully written, row- or feature-major as nr3d_mlp_backward's (NULL: not wanted)
  *   dL_ddLdy [n, out] rows = m_L W_L t_NH, fully written (NULL: not wanted).
  * x, ddL_dx, dL_dy (gy_stride 0 allowed), packed and the fp32 atomics on dL_dW / dL_db as nr3d_mlp_backward_backward; n == 0 returns 0.
- * nr3d_mlp_softplus_backward_backward_ok: 1 exactly for softplus hidden layers (valid beta, output none or ReLU) on a shape
+ * nr3d_mlp_softplus_backward_backward_ok: 1 exactly for softplus hidden layers (valid beta, output none or ReLU, not sigmoid) on a shape
  * nr3d_mlp_backward takes and whose launch plan (per-wave LDS tiles about twice those of nr3d_mlp_backward_backward) fits at least one
  * wave; a ReLU / linear desc gives 0 and nr3d_mlp_softplus_backward_backward then fails with a message. */
 int nr3d_mlp_softplus_backward_backward_ok(const nr3d_mlp_desc_t *desc);

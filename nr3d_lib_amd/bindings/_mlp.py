@@ -8,7 +8,7 @@ import torch
 from .. import _hip as H
 
 MAX_LAYERS = 8
-ACT_NONE, ACT_RELU, ACT_SOFTPLUS = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_SOFTPLUS, ACT_SIGMOID = 0, 1, 2, 3
 
 
 class _CDesc(C.Structure):
@@ -19,7 +19,9 @@ class _CDesc(C.Structure):
 class MLPDesc:
     """dims = [in_features, hidden..., out_features]; beta: of ``hidden_activation=ACT_SOFTPLUS`` (torch.nn.Softplus(beta,
     threshold=20) after every hidden layer; forward and first backward of both precisions; its fused double backward is
-    backward_backward_softplus, ``softplus_second_order_fusable``), not read otherwise"""
+    backward_backward_softplus, ``softplus_second_order_fusable``), not read otherwise.  ``output_activation=ACT_SIGMOID``: 1 / (1 + exp(-z))
+    on the output layer (output only; forward and first backward of both precisions; neither double backward takes it: both
+    ``..._second_order_fusable`` are False).  Any other code, sigmoid hidden or softplus output: every size is 0, nothing is fusable"""
 
     def __init__(self, dims, hidden_activation=ACT_RELU, output_activation=ACT_NONE, beta=1.0):
         self.dims = [int(d) for d in dims]

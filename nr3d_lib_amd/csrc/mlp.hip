@@ -107,7 +107,10 @@ struct FwdArgs {
 // (X3, one input and one output tile, hidden layers up to 64 wide: two workgroups per CU = two waves per SIMD -- the piece splitting is VALU work, the products MFMA work, and
 // only ANOTHER wave's instructions overlap them; at 260 registers the first version ran one wave per SIMD and the two added up)
 // SP: the hidden activation is softplus (mlp_device.h hidden_layer); a.hidden_act is not read
-template <int IN_T, int W_T, int OUT_T, int XF, bool X3 = false, bool SP = false>
+// SG: the output activation is sigmoid (mlp_act.h), applied to the accumulators before store_rows; a.out_act is not read.  Instantiations
+// of their own, like SP: as a third run-time case next to dense's ReLU test the sigmoid moved the registers of 187 of the 324 existing
+// forward kernels (up to + 96 VGPRs on the 128-wide outputs) and of 80 of the 108 k_mlp_bwd (profiles/mlp_sigmoid_resources.txt)
+template <int IN_T, int W_T, int OUT_T, int XF, bool X3 = false, bool SP = false, bool SG = false>
 __global__ __launch_bounds__(kThreads, (X3 && IN_T == 1 && W_T <= 2 && OUT_T == 1) ? 2 : 1) void k_mlp_fwd(FwdArgs a) {
 	extern __shared__ __attribute__((aligned(16))) float lds[];
 	stage_weights(a.packed, a.packed_floats, lds);          // (X3: a.packed points at the x3 region, a.packed_floats is its size)
@@ -143,8 +146,9 @@ __global__ __launch_bounds__(kThreads, (X3 && IN_T == 1 && W_T <= 2 && OUT_T == 
 #pragma unroll
 			for (int t = 0; t < W_T; ++t) hcur[t] = hn[t];
 		}
-		if constexpr (X3) dense_x3<W_T, OUT_T, true>(wl + off_hidden + (a.n_layers - 2) * sz_hidden, hcur, yo, a.out_act, lane);
-		else dense<W_T, OUT_T, true>(wl + off_hidden + (a.n_layers - 2) * sz_hidden, hcur, yo, a.out_act, lane);
+		if constexpr (X3) dense_x3<W_T, OUT_T, true>(wl + off_hidden + (a.n_layers - 2) * sz_hidden, hcur, yo, SG ? (int)NR3D_MLP_ACT_NONE : a.out_act, lane);
+		else dense<W_T, OUT_T, true>(wl + off_hidden + (a.n_layers - 2) * sz_hidden, hcur, yo, SG ? (int)NR3D_MLP_ACT_NONE : a.out_act, lane);
+		if constexpr (SG) mlp_act::sigmoid_tiles<OUT_T>(yo);
 		store_rows<OUT_T>(a.y, a.ys, a.out_dim, row, valid, a.y_vec != 0, lane, yo);
 	}
 }
@@ -256,7 +260,9 @@ template <int IN_T, int W_T, int OUT_T, int NH> struct BwdCfg { static constexpr
 // SP: softplus hidden layers (hidden_layer / bwd_layer<..., MASK = 2>): the H_l tiles kept for dW also give the derivative.
 // (the ReLU / linear instantiations call dense / dense_x3 directly, not through hidden_layer: the extra inlining level alone moved the
 // register allocation of four of them by 1 - 8 VGPRs and 7 spilled dwords)
-template <int IN_T, int W_T, int OUT_T, int NH, int FAST, bool X3 = false, bool SP = false>
+// SG: sigmoid output (see k_mlp_fwd): the output pre-activations z are recomputed as for an output ReLU's mask, and dL/dy takes the factor
+// sigmoid'(z) -- after the zeroing of the rows past n, which therefore stay zero; a.out_act is not read
+template <int IN_T, int W_T, int OUT_T, int NH, int FAST, bool X3 = false, bool SP = false, bool SG = false>
 __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T, NH>::kMaxWaves * 64)) void k_mlp_bwd(BwdArgs a) {
 	extern __shared__ __attribute__((aligned(16))) float lds[];
 	// FAST: the next tile's rows are requested before a tile's LAST step, not at its top: their 32 - 64 registers then overlap one
@@ -343,7 +349,15 @@ __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T, NH>::kMaxWaves * 64)) voi
 			write_tile<W_T>(TH1 + l * 32 * W_T * kTS, W_T, hcur, lane);
 		}
 		if (FAST && !valid) zero_tiles<OUT_T>(g_out);                    // rows past n were clamped, not zeroed
-		if (a.out_act == NR3D_MLP_ACT_RELU) {
+		if constexpr (SG) {
+			f16v yo[OUT_T];
+			if constexpr (X3) dense_x3<W_T, OUT_T, true, true>(wf + f0 + (NH - 1) * fh, hcur, yo, NR3D_MLP_ACT_NONE, lane);
+			else dense<W_T, OUT_T, true, true>(wf + f0 + (NH - 1) * fh, hcur, yo, NR3D_MLP_ACT_NONE, lane);
+#pragma unroll
+			for (int t = 0; t < OUT_T; ++t)
+#pragma unroll
+				for (int j = 0; j < 16; ++j) g_out[t][j] *= mlp_act::sigmoid_grad(yo[t][j]);
+		} else if (a.out_act == NR3D_MLP_ACT_RELU) {
 			f16v yo[OUT_T];
 			if constexpr (X3) dense_x3<W_T, OUT_T, true, true>(wf + f0 + (NH - 1) * fh, hcur, yo, NR3D_MLP_ACT_NONE, lane);
 			else dense<W_T, OUT_T, true, true>(wf + f0 + (NH - 1) * fh, hcur, yo, NR3D_MLP_ACT_NONE, lane);
@@ -634,26 +648,27 @@ extern "C" int nr3d_mlp_forward(const nr3d_mlp_desc_t *desc, uint64_t n, const f
 	const uint32_t grid = (uint32_t)(n_tiles / 4 + 1 < 1024 ? n_tiles / 4 + 1 : 1024);
 	const int xf = fast_of(lx);
 	int rc = 0;
-	const bool sp = mlp_act::softplus_hidden(desc);
+	const bool sp = mlp_act::softplus_hidden(desc), sg = mlp_act::sigmoid_output(desc);
 	a.beta = desc->softplus_beta;
 	dispatch_tiles(s, [&](auto I, auto W, auto O) {
 		constexpr int IN_T = decltype(I)::value, W_T = decltype(W)::value, OUT_T = decltype(O)::value;
-		// the (bf16 route, softplus) variant of the tile class: the LDS limit of its three XF kernels once per device, then the launch
-		auto go = [&](auto X3c, auto SPc) {
-			constexpr bool X3 = decltype(X3c)::value, SP = decltype(SPc)::value;
+		// the (bf16 route, softplus, sigmoid) variant of the tile class: the LDS limit of its three XF kernels once per device, then the launch
+		auto go = [&](auto X3c, auto SPc, auto SGc) {
+			constexpr bool X3 = decltype(X3c)::value, SP = decltype(SPc)::value, SG = decltype(SGc)::value;
 			static LdsOnce once;
 			int dev = -1;
-			if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlp_fwd<IN_T, W_T, OUT_T, 0, X3, SP>, k_mlp_fwd<IN_T, W_T, OUT_T, 1, X3, SP>,
-			                         k_mlp_fwd<IN_T, W_T, OUT_T, 2, X3, SP>))) return;
+			if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlp_fwd<IN_T, W_T, OUT_T, 0, X3, SP, SG>, k_mlp_fwd<IN_T, W_T, OUT_T, 1, X3, SP, SG>,
+			                         k_mlp_fwd<IN_T, W_T, OUT_T, 2, X3, SP, SG>))) return;
 			if (xf == 2)
-				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 2, X3, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 2, X3, SP, SG>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 			else if (xf == 1)
-				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 1, X3, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 1, X3, SP, SG>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 			else
-				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 0, X3, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+				hipLaunchKernelGGL((k_mlp_fwd<IN_T, W_T, OUT_T, 0, X3, SP, SG>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 		};
-		if (x3) { if (sp) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{}); }
-		else { if (sp) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
+		auto go_sg = [&](auto X3c, auto SPc) { if (sg) go(X3c, SPc, std::true_type{}); else go(X3c, SPc, std::false_type{}); };
+		if (x3) { if (sp) go_sg(std::true_type{}, std::true_type{}); else go_sg(std::true_type{}, std::false_type{}); }
+		else { if (sp) go_sg(std::false_type{}, std::true_type{}); else go_sg(std::false_type{}, std::false_type{}); }
 	});
 	if (rc) return rc;
 	NR3D_LAUNCH_CHECK();
@@ -690,7 +705,7 @@ extern "C" int nr3d_mlp_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const 
 	a.x_vec = lx.vec; a.gy_vec = lgy.vec; a.gx_vec = lgx.vec;
 	a.tile_floats = bwd_tile_floats(s);
 	a.beta = desc->softplus_beta;
-	const bool sp = mlp_act::softplus_hidden(desc);
+	const bool sp = mlp_act::softplus_hidden(desc), sg = mlp_act::sigmoid_output(desc);
 	const BwdPlan plan = bwd_plan_of(s, x3, n);
 	const uint32_t nh = desc->n_layers - 1;
 	const int fast = fast_of(lx, lgy);
@@ -700,14 +715,17 @@ extern "C" int nr3d_mlp_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const 
 		return 0;
 	};
 	int rc = 0;
-#define BWD_FAST(I, W, O, H, X, S) (fast == 2 ? launch(k_mlp_bwd<I, W, O, H, 2, X, S>) : fast == 1 ? launch(k_mlp_bwd<I, W, O, H, 1, X, S>) : launch(k_mlp_bwd<I, W, O, H, 0, X, S>))
+#define BWD_FAST(I, W, O, H, X, S, G) (fast == 2 ? launch(k_mlp_bwd<I, W, O, H, 2, X, S, G>) : fast == 1 ? launch(k_mlp_bwd<I, W, O, H, 1, X, S, G>) : launch(k_mlp_bwd<I, W, O, H, 0, X, S, G>))
+#define BWD_ACT(I, W, O, H, X) (sp ? (sg ? BWD_FAST(I, W, O, H, X, true, true) : BWD_FAST(I, W, O, H, X, true, false)) \
+                                   : (sg ? BWD_FAST(I, W, O, H, X, false, true) : BWD_FAST(I, W, O, H, X, false, false)))
 #define BWD_CASE(I, W, O, H) if (s.in_t == I && s.w_t == W && s.out_t == O && nh == H) { \
-		if (x3) { if constexpr (bwd_has_x3(I, W, O, H)) rc = sp ? BWD_FAST(I, W, O, H, true, true) : BWD_FAST(I, W, O, H, true, false); \
+		if (x3) { if constexpr (bwd_has_x3(I, W, O, H)) rc = BWD_ACT(I, W, O, H, true); \
 		          else rc = ::nr3d::fail("mlp_backward: no bf16 MFMA backward for this shape"); } \
-		else rc = sp ? BWD_FAST(I, W, O, H, false, true) : BWD_FAST(I, W, O, H, false, false); } else
+		else rc = BWD_ACT(I, W, O, H, false); } else
 	NR3D_MLP_BWD_SHAPES(BWD_CASE)
 	rc = ::nr3d::fail("mlp_backward: no kernel for this shape");
 #undef BWD_CASE
+#undef BWD_ACT
 #undef BWD_FAST
 	if (rc) return rc;
 	NR3D_LAUNCH_CHECK();
@@ -715,9 +733,10 @@ extern "C" int nr3d_mlp_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const 
 }
 
 // the double backward runs on every shape the fused backward runs on (same LDS plan, same waves) -- with ReLU / no hidden activation: a
-// softplus network is not piecewise linear (its double backward has bias and x terms and a third chain: csrc/mlp_softplus2.hip)
+// softplus network is not piecewise linear (its double backward has bias and x terms and a third chain: csrc/mlp_softplus2.hip), and
+// neither is a sigmoid output (no fused double backward: a radiance decoder is differentiated once)
 extern "C" int nr3d_mlp_backward_backward_ok(const nr3d_mlp_desc_t *desc) {
-	return desc && !mlp_act::softplus_hidden(desc) && nr3d_mlp_backward_packed_floats(desc) != 0 ? 1 : 0;
+	return desc && !mlp_act::softplus_hidden(desc) && !mlp_act::sigmoid_output(desc) && nr3d_mlp_backward_packed_floats(desc) != 0 ? 1 : 0;
 }
 
 extern "C" int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const float *x, int64_t x_stride, int64_t x_feature_stride,
@@ -726,6 +745,8 @@ extern "C" int nr3d_mlp_backward_backward(const nr3d_mlp_desc_t *desc, uint64_t 
                                           float *const *dL_dW, void *stream) {
 	Shape s;
 	NR3D_CHECK(!(desc && mlp_act::softplus_hidden(desc)), "mlp_backward_backward: the fused double backward does not take softplus hidden layers "
+	           "(differentiate the unfused path)");
+	NR3D_CHECK(!(desc && mlp_act::sigmoid_output(desc)), "mlp_backward_backward: the fused double backward does not take a sigmoid output "
 	           "(differentiate the unfused path)");
 	NR3D_CHECK(shape_of(desc, s) && nr3d_mlp_backward_backward_ok(desc), "mlp_backward_backward: the fused double backward does not apply to this network");
 	if (n == 0) return 0;

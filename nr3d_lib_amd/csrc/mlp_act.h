@@ -1,6 +1,7 @@
-// nr3d_lib_amd/csrc/mlp_act.h -- the softplus hidden activation of the fused decoder (NR3D_MLP_ACT_SOFTPLUS), shared by mlp.hip
-// (fp32) and mlp_half.hip (half): torch.nn.Softplus(beta, threshold = 20), the activation of the reference's SDF decoders
-// (nr3d_lib/models/fields/sdf/mlp_sdf.py:30, beta = 100).
+// nr3d_lib_amd/csrc/mlp_act.h -- the activations of the fused decoder beyond ReLU, shared by mlp.hip (fp32) and mlp_half.hip (half):
+// the softplus HIDDEN activation (NR3D_MLP_ACT_SOFTPLUS): torch.nn.Softplus(beta, threshold = 20), the activation of the reference's SDF
+// decoders (nr3d_lib/models/fields/sdf/mlp_sdf.py:30, beta = 100); and the sigmoid OUTPUT activation (NR3D_MLP_ACT_SIGMOID, below), the
+// one every radiance decoder of the reference ends in (nr3d_lib/models/fields/nerf/mlp_nerf.py:196, lotd_nerf.py:219-224).
 //
 // Forward, on the fp32 accumulator z of a hidden unit: h = z where beta z > 20, else log1p(exp(beta z)) / beta.
 // Backward: the kernels keep every hidden layer's activations h for dW anyway, and h alone gives the derivative:
@@ -21,11 +22,16 @@ namespace mlp_act {
 
 constexpr float kSoftplusThreshold = 20.0f;
 
-// which activations the fused kernels take: softplus on the hidden layers only, with a beta that is finite and > 0
+// which activations the fused kernels take: none / ReLU / softplus (with a beta that is finite and > 0) on the hidden layers, none /
+// ReLU / sigmoid on the output layer.  Every other code -- softplus as output, sigmoid as hidden, a value outside the enum -- is refused:
+// the kernels' run-time tests know these codes only and would run anything else as the identity
 static inline bool softplus_hidden(const nr3d_mlp_desc_t *d) { return d->hidden_activation == NR3D_MLP_ACT_SOFTPLUS; }
+static inline bool sigmoid_output(const nr3d_mlp_desc_t *d) { return d->output_activation == NR3D_MLP_ACT_SIGMOID; }
 static inline bool activations_ok(const nr3d_mlp_desc_t *d) {
-	if (d->output_activation == NR3D_MLP_ACT_SOFTPLUS) return false;
-	if (d->hidden_activation == NR3D_MLP_ACT_SOFTPLUS) return d->softplus_beta > 0.0f && d->softplus_beta <= 3.0e38f;   // (false for NaN)
+	const uint32_t h = d->hidden_activation, o = d->output_activation;
+	if (h != NR3D_MLP_ACT_NONE && h != NR3D_MLP_ACT_RELU && h != NR3D_MLP_ACT_SOFTPLUS) return false;
+	if (o != NR3D_MLP_ACT_NONE && o != NR3D_MLP_ACT_RELU && o != NR3D_MLP_ACT_SIGMOID) return false;
+	if (h == NR3D_MLP_ACT_SOFTPLUS) return d->softplus_beta > 0.0f && d->softplus_beta <= 3.0e38f;   // (false for NaN)
 	return true;
 }
 
@@ -49,6 +55,37 @@ __device__ __forceinline__ void softplus_tiles(V (&r)[NT], float beta) {
 	for (int t = 0; t < NT; ++t)
 #pragma unroll
 		for (int j = 0; j < 16; ++j) r[t][j] = softplus(r[t][j], beta, inv_beta);
+}
+
+// ---- the sigmoid output activation ----
+// y = 1 / (1 + exp(-z)) on the fp32 accumulator z of the output layer (the half kernels: before the result is rounded to half).  With
+// E = exp(-|z|) in (0, 1] and D = 1 / (1 + E) in [1/2, 1): y = D for z >= 0 and E D for z < 0, d y / dz = E D^2 -- no cancellation, so
+// both tails keep their relative accuracy (the hardware exp as above: <= |z| 2^-24 + 1 ulp relative on E; the hardware reciprocal of a
+// value in [1, 2]: 1 ulp, and exactly 1 for 1), and no inf * 0 for any finite z: at z = +-1e4 E is 0, y exactly 1 / 0, the derivative
+// exactly 0.  The backward kernels recompute z (as they do for an output ReLU's mask) and never see a stored y.
+//
+// A PADDED output column (zero weights, zero bias: out_dim no multiple of 32, i.e. nearly always) holds 0.5 with derivative 0.25.
+// Nothing reads it: store_rows / store_cols stop at out_dim; dL/dy is loaded as 0 beyond out_dim, or (branch-free loads) as a copy of
+// real columns that meets W^T's zero rows in the dH chain -- which is what happens without an output activation too -- and the dW / db
+// reductions stop at the real widths.  Rows past n of the branch-free backward paths are clamped rows (finite z) whose dL/dy was zeroed
+// BEFORE it meets the derivative.
+__device__ __forceinline__ float sigmoid(float z) {
+	const float e = __expf(-__builtin_fabsf(z));
+	const float d = __builtin_amdgcn_rcpf(1.0f + e);
+	return z >= 0.0f ? d : e * d;
+}
+__device__ __forceinline__ float sigmoid_grad(float z) {
+	const float e = __expf(-__builtin_fabsf(z));
+	const float d = __builtin_amdgcn_rcpf(1.0f + e);
+	return e * d * d;
+}
+
+template <int NT, class V>
+__device__ __forceinline__ void sigmoid_tiles(V (&r)[NT]) {
+#pragma unroll
+	for (int t = 0; t < NT; ++t)
+#pragma unroll
+		for (int j = 0; j < 16; ++j) r[t][j] = sigmoid(r[t][j]);
 }
 
 }  // namespace mlp_act

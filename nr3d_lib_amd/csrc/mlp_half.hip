@@ -307,7 +307,10 @@ __device__ __forceinline__ void prefetch_x(const __half *__restrict__ p, int64_t
 
 // SP: softplus hidden layers (mlp_act.h), evaluated on the fp32 accumulators before they are rounded to half -- instantiations of their
 // own, so that the ReLU / linear kernels keep their code; a.hidden_act is not read
-template <int IN_T, int W_T, int OUT_T, int XF, bool SP = false>
+// SG: sigmoid output (mlp_act.h) on the fp32 accumulators of the output layer, before store_rows rounds them -- instantiations of their
+// own as well: as a run-time case next to dense's ReLU test it moved the registers of 120 of the 162 existing forward kernels (up to
+// 152 -> 276 VGPRs), 33 of the 60 split backward kernels and one k_mlph_bwd (profiles/mlp_sigmoid_resources.txt); a.out_act is not read
+template <int IN_T, int W_T, int OUT_T, int XF, bool SP = false, bool SG = false>
 __global__ __launch_bounds__(kThreads) void k_mlph_fwd(FwdArgs a) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 	stage_weights(a.packed, a.packed_bytes, lds);
@@ -343,7 +346,8 @@ __global__ __launch_bounds__(kThreads) void k_mlph_fwd(FwdArgs a) {
 			if constexpr (SP) mlp_act::softplus_tiles<W_T>(hacc, a.beta);
 			to_operand<W_T>(hacc, hop);
 		}
-		dense<W_T, OUT_T, true>(wl + off_hidden + (a.n_layers - 2) * sz_hidden, hop, yo, a.out_act, lane);
+		dense<W_T, OUT_T, true>(wl + off_hidden + (a.n_layers - 2) * sz_hidden, hop, yo, SG ? (int)NR3D_MLP_ACT_NONE : a.out_act, lane);
+		if constexpr (SG) mlp_act::sigmoid_tiles<OUT_T>(yo);
 		store_rows<OUT_T>(a.y, a.ys, a.out_dim, row, valid, a.y_vec != 0, lane, yo);
 	}
 }
@@ -392,6 +396,16 @@ __device__ __forceinline__ h8 read_op(const _Float16 *__restrict__ T, int t, int
 	const h4 l4 = __builtin_bit_cast(h4, lo), h4_ = __builtin_bit_cast(h4, hi);
 	const h8 v = {l4[0], l4[1], l4[2], l4[3], h4_[0], h4_[1], h4_[2], h4_[3]};
 	return v;
+}
+
+// dL/dy (operand form) times sigmoid'(z) of the recomputed output pre-activations z (fp32 accumulators): the product in fp32, one
+// rounding to half -- the SG instantiations of the two backward kernels
+template <int NT>
+__device__ __forceinline__ void scale_sigmoid_grad(h8 (&g)[NT][2], const f16v (&z)[NT]) {
+#pragma unroll
+	for (int t = 0; t < NT; ++t)
+#pragma unroll
+		for (int j = 0; j < 16; ++j) g[t][j >> 3][j & 7] = (_Float16)((float)g[t][j >> 3][j & 7] * mlp_act::sigmoid_grad(z[t][j]));
 }
 
 struct BwdArgs {
@@ -512,7 +526,8 @@ __device__ __forceinline__ void zero_tiles(f16v (&r)[NT]) {
 // lane).  64-wide hidden layers keep four waves and the whole register file (at 256 registers 32 -> 64 -> 64 -> 16 spills 300-400 dwords).
 template <int IN_T, int W_T, int OUT_T> struct BwdCfg { static constexpr int kMaxWaves = bwd_max_waves_half(IN_T, W_T, OUT_T); };
 // SP: softplus hidden layers; the derivative comes from the activations in operand form (never the bit masks)
-template <int IN_T, int W_T, int OUT_T, int NH, int FAST, bool SP = false>
+// SG: sigmoid output (see k_mlph_fwd); a.out_act is not read
+template <int IN_T, int W_T, int OUT_T, int NH, int FAST, bool SP = false, bool SG = false>
 __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T>::kMaxWaves * 64)) void k_mlph_bwd(BwdArgs a) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 	stage_weights(a.packed, a.total_bytes, lds);
@@ -583,7 +598,13 @@ __global__ __launch_bounds__((BwdCfg<IN_T, W_T, OUT_T>::kMaxWaves * 64)) void k_
 			to_operand<W_T>(hacc, hop[l]);
 			write_tile<W_T>(TH1 + l * 32 * W_T * kTSH, hop[l], lane);
 			}
-		if (a.out_act == NR3D_MLP_ACT_RELU) {
+		// an output activation: the output pre-activations z are recomputed; dL/dy takes the ReLU mask z > 0, or (SG) the factor sigmoid'(z)
+		// in fp32 (mlp_act.h) and one rounding to half -- rows past n were zeroed above and stay zero
+		if constexpr (SG) {
+			f16v yo[OUT_T];
+			dense<W_T, OUT_T, true>(wf + f0 + (NH - 1) * fh, hop[NH - 1], yo, NR3D_MLP_ACT_NONE, lane);
+			scale_sigmoid_grad<OUT_T>(g_out, yo);
+		} else if (a.out_act == NR3D_MLP_ACT_RELU) {
 			f16v yo[OUT_T];
 			dense<W_T, OUT_T, true>(wf + f0 + (NH - 1) * fh, hop[NH - 1], yo, NR3D_MLP_ACT_NONE, lane);
 #pragma unroll
@@ -747,7 +768,7 @@ __device__ __forceinline__ void dx_layer(const h8 (&g)[NO][2], const unsigned ch
 	}
 }
 
-template <int IN_T, int W_T, int OUT_T, int NH, int FAST, int NW, bool SP = false>
+template <int IN_T, int W_T, int OUT_T, int NH, int FAST, int NW, bool SP = false, bool SG = false>
 __global__ __launch_bounds__(NW * 64) void k_mlph_bwd_split(BwdArgs a) {
 	static_assert(W_T == 2 && NH >= 1 && NH <= 2, "the shapes whose dW does not fit one wave: 64-wide hidden layers");
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -833,7 +854,11 @@ __global__ __launch_bounds__(NW * 64) void k_mlph_bwd_split(BwdArgs a) {
 			write_tile<W_T>(mine + oH1 + szH, hop, lane);
 			signs(hmask[1]);
 		}
-		if (a.out_act == NR3D_MLP_ACT_RELU) {
+		if constexpr (SG) {                                // sigmoid'(z) on dL/dy, as k_mlph_bwd
+			f16v yo[OUT_T];
+			dense<W_T, OUT_T, true>(wf + f0 + (NH - 1) * fh, hop, yo, NR3D_MLP_ACT_NONE, lane);
+			scale_sigmoid_grad<OUT_T>(g_out, yo);
+		} else if (a.out_act == NR3D_MLP_ACT_RELU) {
 			f16v yo[OUT_T];
 			dense<W_T, OUT_T, true>(wf + f0 + (NH - 1) * fh, hop, yo, NR3D_MLP_ACT_NONE, lane);
 #pragma unroll
@@ -963,20 +988,22 @@ extern "C" int nr3d_mlp_half_forward(const nr3d_mlp_desc_t *desc, uint64_t n, co
 	int rc = 0;
 	dispatch_tiles(s, [&](auto I, auto W, auto O) {
 		constexpr int IN_T = decltype(I)::value, W_T = decltype(W)::value, OUT_T = decltype(O)::value;
-		auto go = [&](auto SPc) {
-			constexpr bool SP = decltype(SPc)::value;
+		auto go = [&](auto SPc, auto SGc) {
+			constexpr bool SP = decltype(SPc)::value, SG = decltype(SGc)::value;
 			static LdsOnce once;
 			int dev = -1;
-			if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlph_fwd<IN_T, W_T, OUT_T, 0, SP>, k_mlph_fwd<IN_T, W_T, OUT_T, 1, SP>,
-			                         k_mlph_fwd<IN_T, W_T, OUT_T, 2, SP>))) return;
+			if ((rc = NR3D_LDS_LIMIT(once, dev, kMaxLds, k_mlph_fwd<IN_T, W_T, OUT_T, 0, SP, SG>, k_mlph_fwd<IN_T, W_T, OUT_T, 1, SP, SG>,
+			                         k_mlph_fwd<IN_T, W_T, OUT_T, 2, SP, SG>))) return;
 			if (xf == 2)
-				hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 2, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+				hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 2, SP, SG>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 			else if (xf == 1)
-				hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 1, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+				hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 1, SP, SG>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 			else
-				hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 0, SP>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+				hipLaunchKernelGGL((k_mlph_fwd<IN_T, W_T, OUT_T, 0, SP, SG>), dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
 		};
-		if (mlp_act::softplus_hidden(desc)) go(std::true_type{}); else go(std::false_type{});
+		const bool sp = mlp_act::softplus_hidden(desc), sg = mlp_act::sigmoid_output(desc);
+		if (sp) { if (sg) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{}); }
+		else { if (sg) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
 	});
 	if (rc) return rc;
 	NR3D_LAUNCH_CHECK();
@@ -1012,7 +1039,7 @@ extern "C" int nr3d_mlp_half_backward(const nr3d_mlp_desc_t *desc, uint64_t n, c
 	a.x_vec = lx.vec; a.gy_vec = lgy.vec; a.gx_vec = lgx.vec;
 	a.tile_halfs = bwd_tile_halfs(s);
 	a.beta = desc->softplus_beta;
-	const bool sp = mlp_act::softplus_hidden(desc);
+	const bool sp = mlp_act::softplus_hidden(desc), sg = mlp_act::sigmoid_output(desc);
 	const uint32_t nh = desc->n_layers - 1;
 	const int fast = fast_of(lx, lgy);
 	const BwdPlan plan = bwd_plan_of(s, n);
@@ -1023,8 +1050,9 @@ extern "C" int nr3d_mlp_half_backward(const nr3d_mlp_desc_t *desc, uint64_t n, c
 	};
 	int rc = 0;
 	if (s.w_t == 2) {
-#define SPLIT_FAST(I, O, H, NW_, S) (fast == 2 ? launch(k_mlph_bwd_split<I, 2, O, H, 2, NW_, S>) : fast == 1 ? launch(k_mlph_bwd_split<I, 2, O, H, 1, NW_, S>) : launch(k_mlph_bwd_split<I, 2, O, H, 0, NW_, S>))
-#define SPLIT_LAUNCH(I, O, H, NW_) (sp ? SPLIT_FAST(I, O, H, NW_, true) : SPLIT_FAST(I, O, H, NW_, false))
+#define SPLIT_FAST(I, O, H, NW_, S, G) (fast == 2 ? launch(k_mlph_bwd_split<I, 2, O, H, 2, NW_, S, G>) : fast == 1 ? launch(k_mlph_bwd_split<I, 2, O, H, 1, NW_, S, G>) : launch(k_mlph_bwd_split<I, 2, O, H, 0, NW_, S, G>))
+#define SPLIT_LAUNCH(I, O, H, NW_) (sp ? (sg ? SPLIT_FAST(I, O, H, NW_, true, true) : SPLIT_FAST(I, O, H, NW_, true, false)) \
+                                       : (sg ? SPLIT_FAST(I, O, H, NW_, false, true) : SPLIT_FAST(I, O, H, NW_, false, false)))
 #define SPLIT_CASE(I, O, H) if (s.in_t == I && s.out_t == O && nh == H) { \
 		if constexpr (split_max_waves(I, O) == 8) rc = plan.nw == 8 ? SPLIT_LAUNCH(I, O, H, 8) : SPLIT_LAUNCH(I, O, H, 4); \
 		else rc = SPLIT_LAUNCH(I, O, H, 4); } else
@@ -1035,9 +1063,10 @@ extern "C" int nr3d_mlp_half_backward(const nr3d_mlp_desc_t *desc, uint64_t n, c
 #undef SPLIT_FAST
 #undef SPLIT_CASE
 	} else {
-#define BWD_FAST(I, W, O, H, S) (fast == 2 ? launch(k_mlph_bwd<I, W, O, H, 2, S>) : fast == 1 ? launch(k_mlph_bwd<I, W, O, H, 1, S>) : launch(k_mlph_bwd<I, W, O, H, 0, S>))
+#define BWD_FAST(I, W, O, H, S, G) (fast == 2 ? launch(k_mlph_bwd<I, W, O, H, 2, S, G>) : fast == 1 ? launch(k_mlph_bwd<I, W, O, H, 1, S, G>) : launch(k_mlph_bwd<I, W, O, H, 0, S, G>))
 #define BWD_CASE(I, W, O, H) if (s.in_t == I && s.w_t == W && s.out_t == O && nh == H) \
-		rc = sp ? BWD_FAST(I, W, O, H, true) : BWD_FAST(I, W, O, H, false); else
+		rc = sp ? (sg ? BWD_FAST(I, W, O, H, true, true) : BWD_FAST(I, W, O, H, true, false)) \
+		        : (sg ? BWD_FAST(I, W, O, H, false, true) : BWD_FAST(I, W, O, H, false, false)); else
 		BWD_CASE(1, 1, 1, 1) BWD_CASE(1, 1, 1, 2) BWD_CASE(1, 1, 1, 3)
 		rc = ::nr3d::fail("mlp_half_backward: no kernel for this shape");
 #undef BWD_CASE

@@ -373,7 +373,7 @@ static BwdPlan sp2_plan_of(const Shape &s, bool x3, uint64_t n = 0) {
 
 extern "C" int nr3d_mlp_softplus_backward_backward_ok(const nr3d_mlp_desc_t *desc) {
 	Shape s;
-	return desc && shape_of(desc, s) && mlp_act::softplus_hidden(desc) && nr3d_mlp_backward_packed_floats(desc) != 0 &&
+	return desc && shape_of(desc, s) && mlp_act::softplus_hidden(desc) && !mlp_act::sigmoid_output(desc) && nr3d_mlp_backward_packed_floats(desc) != 0 &&
 	       sp2_plan_of(s, false).nw != 0 ? 1 : 0;
 }
 
@@ -385,6 +385,8 @@ extern "C" int nr3d_mlp_softplus_backward_backward(const nr3d_mlp_desc_t *desc, 
 	Shape s;
 	NR3D_CHECK(!(desc && !mlp_act::softplus_hidden(desc)), "mlp_softplus_backward_backward: softplus hidden layers only (ReLU / linear networks: "
 	           "nr3d_mlp_backward_backward)");
+	NR3D_CHECK(!(desc && mlp_act::sigmoid_output(desc)), "mlp_softplus_backward_backward: the fused double backward does not take a sigmoid output "
+	           "(differentiate the unfused path)");
 	NR3D_CHECK(shape_of(desc, s) && nr3d_mlp_softplus_backward_backward_ok(desc), "mlp_softplus_backward_backward: the fused double backward does "
 	           "not apply to this network");
 	if (n == 0) return 0;

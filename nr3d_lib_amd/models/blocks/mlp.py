@@ -6,7 +6,8 @@ Where the reference runs one GEMM + one activation kernel per layer (or hands th
 runs the whole network in ONE kernel on the fp32 MFMA (csrc/mlp.hip) -- or, for ``dtype=torch.half`` (the reference's autocast
 layers / its tcnn FullyFusedMLP), on the f16 MFMA (csrc/mlp_half.hip) -- whenever it can: on a GPU, ReLU / no
 activations or softplus hidden layers with beta >= ``FUSED_SOFTPLUS_MIN_BETA`` (the reference's SDF decoders:
-``{'type': 'softplus', 'beta': 100.}``), no skips / weight norm / equal_lr, every width <= 128.  Forward: activations stay in registers.  Backward
+``{'type': 'softplus', 'beta': 100.}``), a ReLU, sigmoid (the reference's radiance decoders: ``output_activation='sigmoid'``) or no
+output activation, no skips / weight norm / equal_lr, every width <= 128.  Forward: activations stay in registers.  Backward
 (hidden width <= 64): the forward is recomputed from x inside the backward kernel, so autograd keeps x and nothing else.
 Everything else takes the layer-by-layer torch path below, with identical semantics.
 
@@ -18,7 +19,8 @@ networks: it is zero), so ``x.grad`` stays None when the eikonal term is x's onl
 linear -- the eikonal term does give x and the hidden biases a gradient, and there is a sigma'' chain -- so it has a double backward
 kernel of its own (csrc/mlp_softplus2.hip k_mlp_bwd2_sp, ``desc.softplus_second_order_fusable``; ``desc.second_order_fusable`` stays False for
 it), taken when ``FUSED_SOFTPLUS_SECOND_ORDER`` is on: the nablas are then the fused first backward's dL/dx bit for bit.  With the switch
-off its create_graph backward differentiates the layer-by-layer torch evaluation of the same network."""
+off its create_graph backward differentiates the layer-by-layer torch evaluation of the same network -- which is also the route of a
+block with a sigmoid output, whatever its hidden layers: no double backward kernel takes it (both ``..._second_order_fusable`` are False)."""
 from typing import List, Union
 
 import torch
@@ -62,6 +64,8 @@ def _torch_activation(h, desc, hidden):
         return torch.relu(h)
     if act == _mlp.ACT_SOFTPLUS:
         return torch.nn.functional.softplus(h, desc.beta, 20.0)
+    if act == _mlp.ACT_SIGMOID:
+        return torch.sigmoid(h)
     return h
 
 
@@ -365,6 +369,8 @@ class MLP(nn.Module):
             return _mlp.ACT_NONE
         if isinstance(a, nn.Softplus):
             return _mlp.ACT_SOFTPLUS if (a.threshold == 20 and a.beta >= FUSED_SOFTPLUS_MIN_BETA) else None
+        if isinstance(a, nn.Sigmoid):
+            return _mlp.ACT_SIGMOID          # (the output layer only: fused_desc)
         return _mlp.ACT_RELU if isinstance(a, nn.ReLU) else None
 
     def fused_desc(self):
@@ -374,9 +380,9 @@ class MLP(nn.Module):
             ok = self._plain and self.D >= 1 and self.dtype in (None, torch.float32, torch.float16)
             hid = {self._act_code(l) for l in self.layers[:-1]}
             out = self._act_code(self.layers[-1])
-            # softplus: hidden layers only, and all of them with one beta
+            # softplus: hidden layers only, and all of them with one beta; sigmoid: the output layer only
             betas = {float(l.activation.beta) for l in self.layers[:-1] if isinstance(l.activation, nn.Softplus)}
-            ok = ok and out != _mlp.ACT_SOFTPLUS and len(betas) <= 1
+            ok = ok and out != _mlp.ACT_SOFTPLUS and _mlp.ACT_SIGMOID not in hid and len(betas) <= 1
             if ok and len(hid) == 1 and None not in hid and out is not None and len(self.layers) <= _mlp.MAX_LAYERS:
                 d = _mlp.MLPDesc([self.in_features, *self.Ws, self.out_features], hid.pop(), out, beta=betas.pop() if betas else 1.0)
                 self._desc = d if (d.half_fusable if self.dtype == torch.float16 else d.fusable) else False
