@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 22
+#define NR3D_ABI_VERSION 23
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -1015,6 +1015,44 @@ int nr3d_neus_upsample_stage_packed(uint32_t P, uint64_t N, uint32_t m, const fl
                                     const float *u, int64_t u_stride, float inv_s, int use_estimate, int merge, int need_sdf,
                                     float *cdf_workspace, float *fine, float *merged, float *sdf_merged, int64_t *pidx_fine,
                                     int64_t *pack_infos_out, void *stream);
+
+/* =================================================================================================
+ * NeuS opacity: the SDF of consecutive samples -> alpha, one launch each way (csrc/neus_alpha.hip)
+ *   reference         the torch op chain of nr3d_lib/graphics/neus/neus_utils.py:48-117 (neus_ray_sdf_to_alpha,
+ *                     neus_packed_sdf_to_alpha: sdf * inv_s, sigmoid, diff | packed_diff, negate, + 1e-5, divide, clamp_min) and its
+ *                     autograd; no native twin there
+ *   c_i = sigmoid(sdf_i inv_s), alpha_i = max(0, (c_i - c_next) / (c_i + 1e-5)); c_next = the next sample of the same pack or row,
+ *   for the last sample by append_mode: NONE -- no interval, alpha = 0 (packed) / no output element (rows); ONE -- c_next = 1;
+ *   SDF (packed only) -- c_next = sigmoid(pack_sdf_appends[p] inv_s), pack_sdf_appends float32 [P].
+ * layout PACKED: sdf [S], pack_infos int64 [P, 2] = (first, len), alpha [S]; n is ignored.  One wave per pack; a pack is clipped to
+ *   [0, S); zero-length packs are allowed; rows outside every pack are 0: ordered_packs as for nr3d_packed_diff (!= 0: the kernel zeroes
+ *   them itself, the outputs may be uninitialised; == 0: pass zeroed alpha / grad_sdf).
+ * layout ROWS: sdf [P, n] (S = P n, n >= 1; pack_infos NULL, ordered_packs ignored), alpha [P, n_out], n_out = n - 1 (NONE) or n (ONE),
+ *   fully written; n_out == 0 launches nothing.
+ * inv_s: read from inv_s_dev[0] (one float in device memory) when inv_s_dev != NULL, else the value inv_s.  No host wait either way.
+ * S < 2^32.  fp32; the sigmoid as E = exp(-|z|), c = 1 / (1 + E) | E / (1 + E) by the sign of z, c' = E / (1 + E)^2.  The same data
+ * gives the same bits in both layouts.
+ * ============================================================================================== */
+#define NR3D_NEUS_ALPHA_PACKED 0
+#define NR3D_NEUS_ALPHA_ROWS 1
+#define NR3D_NEUS_ALPHA_APPEND_NONE 0
+#define NR3D_NEUS_ALPHA_APPEND_ONE 1
+#define NR3D_NEUS_ALPHA_APPEND_SDF 2
+int nr3d_neus_alpha_fwd(int layout, uint32_t P, uint64_t S, uint32_t n, const float *sdf, const int64_t *pack_infos, int append_mode,
+                        const float *pack_sdf_appends, float inv_s, const float *inv_s_dev, int ordered_packs, float *alpha, void *stream);
+/* The gradients, recomputed from the forward's inputs (nothing else is kept).  grad_alpha = dL/dalpha, alpha's shape.  With
+ * m_i = [(c_i - c_next) / (c_i + 1e-5) >= 0] (the gradient passes at equality, as torch's clamp_min):
+ *   u_i = c'_i (grad_alpha_i m_i (c_next + 1e-5) / (c_i + 1e-5)^2 - grad_alpha_{i-1} m_{i-1} / (c_{i-1} + 1e-5)), the second term inside
+ *   the same pack or row only;  grad_sdf_i = inv_s u_i (sdf's shape; 0 outside the packs);  append_mode SDF: grad_appends [P] =
+ *   inv_s u_append, u_append = -c'_append grad_alpha_last m_last / (c_last + 1e-5) (0 for a zero-length pack), else grad_appends is unused.
+ * grad_inv_s (optional, one float in device memory) = sum_i sdf_i u_i + sum_p append_p u_append,p: WRITTEN, not accumulated.  Every
+ *   workgroup writes one partial into `workspace` (nr3d_neus_alpha_bwd_workspace_bytes(layout, P, S) bytes, contents undefined on
+ *   return) and a second launch of one workgroup adds them in a fixed order -- no float atomics, the same bits run after run.  Without
+ *   grad_inv_s: one launch, no workspace. */
+uint64_t nr3d_neus_alpha_bwd_workspace_bytes(int layout, uint32_t P, uint64_t S);
+int nr3d_neus_alpha_bwd(int layout, uint32_t P, uint64_t S, uint32_t n, const float *sdf, const int64_t *pack_infos, int append_mode,
+                        const float *pack_sdf_appends, float inv_s, const float *inv_s_dev, int ordered_packs, const float *grad_alpha,
+                        float *grad_sdf, float *grad_appends, float *grad_inv_s, void *workspace, uint64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

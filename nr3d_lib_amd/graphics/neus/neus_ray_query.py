@@ -13,7 +13,9 @@ opacity -> ``packed_alpha_to_vw`` -> exclusive ``packed_cumsum`` normalised with
 ``neus_ray_query_coarse_multi_upsample`` (:132-356) is the vanilla NeuS query that needs no occupancy grid: coarse boundaries on
 every ray between ``near`` and ``far``, the up-sampling on fixed-length rows, one query at the mid-points.  Its stage runs in one
 launch (``bindings._neus_upsample.upsample_stage``) while ``FUSED_UPSAMPLE`` is set.  The stage of the march-occ drivers runs in
-one launch on the packs (``upsample_stage_packed``) while ``FUSED_UPSAMPLE_PACKED`` is set, in place of the pack-op chain above."""
+one launch on the packs (``upsample_stage_packed``) while ``FUSED_UPSAMPLE_PACKED`` is set, in place of the pack-op chain above.
+The opacity of the final samples (``neus_ray_sdf_to_alpha`` / ``neus_packed_sdf_to_alpha``) is one launch each way while
+``neus_utils.FUSED_SDF_TO_ALPHA`` is set; the op chains of the two switches above, when off, pass ``fused=False``."""
 from types import SimpleNamespace
 from typing import Dict, List, Tuple
 
@@ -172,7 +174,7 @@ def _upsample(q, marched, upsample_inv_s_factors, upsample_use_estimate_alpha, p
                 depth_samples, sdf, pack_infos = merged, sdf_m, pinfo
             continue
         alpha = (neus_packed_sdf_to_upsample_alpha(sdf, depth_samples, inv_s, pack_infos) if upsample_use_estimate_alpha
-                 else neus_packed_sdf_to_alpha(sdf, inv_s, pack_infos))
+                 else neus_packed_sdf_to_alpha(sdf, inv_s, pack_infos, fused=False))     # this route stays the reference's op chain
         cdf = packed_cumsum(packed_alpha_to_vw(alpha, pack_infos), pack_infos, exclusive=True)
         last = cdf[pack_infos[..., 0] + pack_infos[..., 1] - 1]
         cdf = packed_div(cdf, last.clamp_min(1e-5), pack_infos)
@@ -207,7 +209,8 @@ def _row_stage(depth, sdf, num_fine, inv_s, use_estimate_alpha, perturb):
             and depth.shape[-1] + num_fine <= _neus_upsample.MAX_ROW:
         u = cdf_positions(depth, depth.shape[:-1], num_fine, perturb)
         return _neus_upsample.upsample_stage(depth.contiguous(), sdf.contiguous(), u, inv_s, use_estimate_alpha)
-    alpha = neus_ray_sdf_to_upsample_alpha(sdf, depth, inv_s) if use_estimate_alpha else neus_ray_sdf_to_alpha(sdf, inv_s)
+    # this route stays the reference's op chain (fused=False: no kernel of neus_utils.FUSED_SDF_TO_ALPHA either)
+    alpha = neus_ray_sdf_to_upsample_alpha(sdf, depth, inv_s) if use_estimate_alpha else neus_ray_sdf_to_alpha(sdf, inv_s, fused=False)
     fine = batch_sample_pdf(depth, ray_alpha_to_vw(alpha), num_fine, perturb=perturb)
     merged, order = torch.sort(torch.cat([depth, fine], dim=-1), dim=-1)
     return fine, merged, order

@@ -8,12 +8,19 @@ from typing import Union
 import torch
 import torch.nn.functional as F
 
+from nr3d_lib_amd.bindings import _neus_alpha as _backend
 from nr3d_lib_amd.graphics.nerf.nerf_utils import ray_alpha_to_vw
 from nr3d_lib_amd.graphics.pack_ops import packed_alpha_to_vw, packed_diff
 
 __all__ = ['neus_pdf', 'neus_cdf', 'neus_ray_cdf_to_alpha', 'neus_ray_sdf_to_tau', 'neus_ray_sdf_to_alpha', 'neus_ray_sdf_to_vw',
            'neus_packed_cdf_to_alpha', 'neus_packed_sdf_to_tau', 'neus_packed_sdf_to_alpha', 'neus_packed_sdf_to_vw',
            'neus_estimate_sdf_nablas_to_alpha', 'neus_packed_sdf_to_upsample_alpha', 'neus_ray_sdf_to_upsample_alpha']
+
+
+# neus_ray_sdf_to_alpha / neus_packed_sdf_to_alpha (and the _vw helpers on top of them): True = one launch of the HIP kernel each way
+# (bindings._neus_alpha) for a float32 GPU sdf with a scalar inv_s; False (and every other input) = the reference's torch op chain.
+# Same semantics.  A call's own ``fused=False`` always takes the chain.
+FUSED_SDF_TO_ALPHA = True
 
 
 def neus_pdf(x: torch.Tensor, inv_s):
@@ -34,7 +41,98 @@ def neus_ray_cdf_to_alpha(cdf: torch.Tensor, append_cdf_1=False):
     return (drop / (ref + 1e-5)).clamp_min(0)
 
 
-def neus_ray_sdf_to_alpha(sdf: torch.Tensor, inv_s, append_cdf_1=False):
+class _SdfToAlpha(torch.autograd.Function):
+    """alpha of consecutive SDF samples as one kernel each way (the chain below: 7 launches forward and 25 backward in eager
+    PyTorch with a learnable inv_s, profiles/neus_alpha.json).  Only sdf, inv_s and the appends are kept; the backward recomputes the rest.  ``layout`` = (pack_infos | None,
+    append_cdf_1): not tensors for autograd, so pack_infos keeps its ``mark_ordered`` tag."""
+
+    @staticmethod
+    def forward(ctx, sdf, inv_s, appends, layout):
+        ctx.layout = layout
+        ctx.inv_s = None if isinstance(inv_s, torch.Tensor) else inv_s
+        ctx.save_for_backward(sdf, inv_s if ctx.inv_s is None else None, appends)
+        return _backend.sdf_to_alpha_forward(sdf, inv_s, layout[0], layout[1], appends)
+
+    @staticmethod
+    def backward(ctx, grad_alpha):
+        sdf, inv_s_t, appends = ctx.saved_tensors
+        inv_s = inv_s_t if ctx.inv_s is None else ctx.inv_s
+        pack_infos, append_cdf_1 = ctx.layout
+        need = ctx.needs_input_grad
+        if torch.is_grad_enabled():
+            # create_graph=True: a higher-order graph is wanted -> the gradient as differentiable torch ops on the saved inputs: the
+            # autograd of the chain's own ops (rows) or of their restatement by indexing (packs: the chain's packed_diff is
+            # differentiable once); first-order training never takes this branch
+            wrt = [t for t, n in zip((sdf, inv_s_t, appends), need) if n]
+            with torch.enable_grad():
+                alpha = (neus_ray_cdf_to_alpha(neus_cdf(sdf, inv_s), append_cdf_1) if pack_infos is None else
+                         _packed_sdf_to_alpha_by_index(sdf, inv_s, pack_infos, append_cdf_1, appends))
+                got = iter(torch.autograd.grad(alpha, wrt, grad_alpha, create_graph=True, allow_unused=True))
+            return tuple(next(got) if n else None for n in need[:3]) + (None,)
+        g_sdf, g_app, g_inv_s = _backend.sdf_to_alpha_backward(sdf, inv_s, grad_alpha.contiguous(), pack_infos, append_cdf_1, appends,
+                                                               need_inv_s=need[1])
+        return (g_sdf if need[0] else None, g_inv_s.reshape(inv_s_t.shape) if need[1] else None,
+                g_app if need[2] else None, None)
+
+
+def _packed_sdf_to_alpha_by_index(sdf, inv_s, pack_infos, append_cdf_1, appends):
+    """neus_packed_sdf_to_alpha in torch ops that can be differentiated twice, without a host wait: c_next by a shift, the packs'
+    last samples and the rows outside the packs by scattered marks (packs in any order, with gaps, of any length)"""
+    S = sdf.shape[0]
+    first, lens = pack_infos[:, 0], pack_infos[:, 1]
+    some = lens > 0
+    cdf = neus_cdf(sdf, inv_s)
+    if S == 0:
+        return cdf
+    edges = torch.zeros(S + 1, dtype=torch.int32, device=sdf.device)
+    edges.index_add_(0, first, some.int()).index_add_(0, first + lens, -some.int())
+    in_pack = edges.cumsum(0)[:S] > 0
+    at = (first + lens - 1).clamp(0, max(S - 1, 0))
+    is_last = torch.zeros(S, dtype=torch.int32, device=sdf.device).index_add_(0, at, some.int()) > 0
+    if append_cdf_1:
+        tail = cdf.new_ones(S)
+    elif appends is not None:
+        tail = cdf.new_zeros(S).index_add(0, at, torch.where(some, neus_cdf(appends, inv_s), cdf.new_zeros(())))
+    else:
+        tail = None
+    c_next = torch.where(is_last, tail if tail is not None else cdf, cdf.roll(-1))
+    closes = in_pack if tail is not None else in_pack & ~is_last
+    return (torch.where(closes, cdf - c_next, cdf.new_zeros(())) / (cdf + 1e-5)).clamp_min(0)
+
+
+def _fused_sdf_to_alpha(fused, sdf, inv_s, pack_infos, append_cdf_1, appends):
+    """alpha through the kernel, or None when the chain has to run: the switch (or the call) is off, or the inputs are not a float32
+    GPU sdf with inv_s a Python number, a one-element CPU tensor without grad or a one-element float32 GPU tensor.  Only the route
+    is decided here; shapes, devices and the other dtypes are the binding's to check (it raises)."""
+    if not (FUSED_SDF_TO_ALPHA if fused is None else fused):
+        return None
+    if not (isinstance(sdf, torch.Tensor) and sdf.is_cuda and sdf.dtype == torch.float32):
+        return None
+    if isinstance(inv_s, torch.Tensor):
+        if inv_s.numel() != 1 or (inv_s.is_cuda and inv_s.dtype != torch.float32) or (not inv_s.is_cuda and inv_s.requires_grad):
+            return None
+        if not inv_s.is_cuda:
+            inv_s = float(inv_s.item())             # host memory: no device wait
+    elif isinstance(inv_s, bool) or not isinstance(inv_s, (int, float)):
+        return None
+    if append_cdf_1 or pack_infos is None:
+        appends = None                              # as the chain: append_cdf_1 overrides the appends; rows have none
+    elif appends is not None:
+        appends = appends.contiguous()
+    sdf = sdf.contiguous()
+    if pack_infos is not None:
+        pack_infos = pack_infos.contiguous()        # itself when it is contiguous: the mark_ordered tag stays
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (sdf, inv_s, appends)):
+        return _SdfToAlpha.apply(sdf, inv_s, appends, (pack_infos, bool(append_cdf_1)))
+    detach = lambda t: t.detach() if isinstance(t, torch.Tensor) else t     # noqa: E731
+    return _backend.sdf_to_alpha_forward(sdf.detach(), detach(inv_s), pack_infos, bool(append_cdf_1), detach(appends))
+
+
+def neus_ray_sdf_to_alpha(sdf: torch.Tensor, inv_s, append_cdf_1=False, fused: bool = None):
+    """``fused``: None follows FUSED_SDF_TO_ALPHA, False always takes the chain"""
+    alpha = _fused_sdf_to_alpha(fused, sdf, inv_s, None, append_cdf_1, None)
+    if alpha is not None:
+        return alpha
     return neus_ray_cdf_to_alpha(neus_cdf(sdf, inv_s), append_cdf_1=append_cdf_1)
 
 
@@ -58,7 +156,11 @@ def neus_packed_cdf_to_alpha(cdf: torch.Tensor, pack_infos: torch.Tensor, append
 
 
 def neus_packed_sdf_to_alpha(sdf: torch.Tensor, inv_s, pack_infos: torch.Tensor, append_cdf_1=False,
-                             pack_sdf_appends: torch.Tensor = None):
+                             pack_sdf_appends: torch.Tensor = None, fused: bool = None):
+    """``fused``: None follows FUSED_SDF_TO_ALPHA, False always takes the chain"""
+    alpha = _fused_sdf_to_alpha(fused, sdf, inv_s, pack_infos, append_cdf_1, pack_sdf_appends)
+    if alpha is not None:
+        return alpha
     appends = None if pack_sdf_appends is None else neus_cdf(pack_sdf_appends, inv_s)
     return neus_packed_cdf_to_alpha(neus_cdf(sdf, inv_s), pack_infos, append_cdf_1=append_cdf_1, pack_cdf_appends=appends)
 
