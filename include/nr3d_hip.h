@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 23
+#define NR3D_ABI_VERSION 24
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -1053,6 +1053,69 @@ uint64_t nr3d_neus_alpha_bwd_workspace_bytes(int layout, uint32_t P, uint64_t S)
 int nr3d_neus_alpha_bwd(int layout, uint32_t P, uint64_t S, uint32_t n, const float *sdf, const int64_t *pack_infos, int append_mode,
                         const float *pack_sdf_appends, float inv_s, const float *inv_s_dev, int ordered_packs, const float *grad_alpha,
                         float *grad_sdf, float *grad_appends, float *grad_inv_s, void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* =================================================================================================
+ * NeRF march + up-sample ray query: its two packed stages, one launch each (csrc/nerf_upsample.hip)
+ *   reference         the torch op chains of nr3d_lib/graphics/nerf/nerf_ray_query.py:289-302 (merge_two_packs_sorted_a_includes_b, the
+ *                     index-puts, addcmul, packed_diff) and :332-360 (tau_to_alpha, packed_cumsum, packed_div, packed_sample_cdf, the
+ *                     second merge with its sort, packed_diff); no native twin there
+ * One 64-lane wave per ray or pack, four per workgroup, no workgroup barrier; no atomics, no host wait; every output element is written
+ * once by a fixed lane, so the result is the same bits run after run.
+ * ============================================================================================== */
+
+/* Rows up to this many elements are staged in LDS (4 * 2 * this many floats per workgroup, both kernels): num_coarse + len for the
+ * merge, len + m + num_coarse for the stage; longer ones run the same code on global memory (the stage with its CDF in the caller's
+ * workspace).  A compile-time choice (-DNR3D_NERF_UPSAMPLE_LDS_ROW=256|512|1024). */
+#ifndef NR3D_NERF_UPSAMPLE_LDS_ROW
+#define NR3D_NERF_UPSAMPLE_LDS_ROW 512
+#endif
+int nr3d_nerf_upsample_lds_row(void);
+
+/* The union of every ray's coarse row with its marched pack.  coarse float32 [R, num_coarse] (non-decreasing per row, num_coarse >= 1);
+ * depth float32 [N], the marched depths, non-decreasing inside a pack; pack_infos_all int64 [R, 2] = (first_r, len_r), the marched pack
+ * of EVERY ray: len_r = 0 for a ray the marcher missed, and first_r = the sum of the lengths before r for all of them (the packs tile
+ * [0, N) in ray order; a pack is clipped to [0, N), so no access leaves the buffers whatever it holds); rays_o, rays_d float32 [R, 3].
+ * Outputs, fully written, [R num_coarse + N] each, ray r's pack starting at r num_coarse + first_r:
+ *   depths_all  the sorted union of the row and the pack -- a marched depth BEFORE a coarse one of equal value, as
+ *               try_merge_two_packs_sorted_aligned(a = coarse, b = marched) places them (the values are the same either way);
+ *   deltas_all  packed_diff without appends: d[i+1] - d[i], 0 for the last element of a pack;
+ *   ridx_all    int64, r;
+ *   samples_all [., 3] = rays_o + rays_d t per component, the product rounded before the sum (what torch.addcmul computes);
+ *   pack_infos_out int64 [R, 2] = (r num_coarse + first_r, num_coarse + len_r).
+ * No arithmetic touches a depth but that subtraction, that product and that sum: every output equals the op chain's bit for bit.
+ * N + R num_coarse < 2^31, otherwise an error before any launch.  R == 0 is a no-op. */
+int nr3d_nerf_merge_rows_packs(uint32_t R, uint32_t num_coarse, uint64_t N, const float *coarse, const float *depth,
+                               const int64_t *pack_infos_all, const float *rays_o, const float *rays_d, float *depths_all,
+                               float *deltas_all, int64_t *ridx_all, float *samples_all, int64_t *pack_infos_out, void *stream);
+
+/* One importance-resampling stage on the density.  depth, sigma, delta float32 [N], packed, pack_infos int64 [P, 2] = (first_p, len_p);
+ * depth is non-decreasing inside a pack.  PRECONDITION: the packs tile [0, N) in order with len_p >= 1, as for
+ * nr3d_neus_upsample_stage_packed; a pack is clipped to [0, N) and one without elements gets fine = 0.
+ * Per pack of n elements, float32, in this order of operations:
+ *   alpha_i = 1 - exp(-(sigma_i delta_i)), evaluated as -expm1(-(sigma_i delta_i)): the same quantity to full float32 precision, where
+ *   the literal expression keeps a multiple of 2^-24 of a small optical depth;
+ *   c_i = the inclusive sum of alpha up to i (it associates as a scan tree over chunks of 64);
+ *   cdf_i = c_i / max(c_{n-1}, 1e-5): summed first, divided afterwards -- the CDF is the sum of the OPACITIES, not of weights, and has
+ *   no leading zero;
+ *   inversion (packed_invert_cdf) at u_j: pos = min(first k with cdf_k >= u_j, n - 1); pos == 0 -> depth_0; else pmf = cdf_pos - cdf_{pos-1},
+ *     pmf < 1e-5 -> depth_{pos-1}, otherwise fmaf((u_j - cdf_{pos-1}) / pmf, depth_pos - depth_{pos-1}, depth_{pos-1}).  A pack of one
+ *     element therefore gives depth_0 and one without mass depth_{n-2}, for every u;
+ *   then fine_j is raised to the running maximum over j.  DEVIATION: the reference sorts the row instead (b_sorted = False in its second
+ *     merge).  The two give the same values wherever the expression above is monotone in u, which it is up to the last rounding of
+ *     the fma; where that rounding breaks the order by an ulp, the sort permutes two values and the maximum repeats the larger one.
+ * u: m = num_fine + 1 >= 1 CDF positions per pack, non-decreasing; pack p reads u + p * u_stride, u_stride 0 (one shared row) or m.
+ * Outputs, fully written: fine [P, m], and
+ *   num_coarse > 0: coarse float32 [n_coarse_rows, num_coarse], non-decreasing per row; pack p takes row coarse_row[p] (int64 [P],
+ *     clipped to the rows there are; NULL: row p).  merged [P, num_coarse + m] = the sorted union of that row and fine;
+ *     deltas [P, num_coarse + m] = packed_diff of merged: the last column 0;
+ *   num_coarse == 0: deltas [P, m - 1] = fine_{j+1} - fine_j and merged [P, m - 1] = fine_j + deltas_j.  This keeps the reference's own
+ *     arithmetic (nerf_ray_query.py:357 adds the WHOLE difference, not half of it: the depths are the upper ends of the intervals).
+ * cdf_workspace: float32 [N], contents undefined on return; always required (packs longer than the LDS row keep their CDF there).
+ * m >= 1, u_stride in {0, m}, N < 2^31, P (m + num_coarse) < 2^31, otherwise an error before any launch.  P == 0 is a no-op. */
+int nr3d_nerf_upsample_stage_packed(uint32_t P, uint64_t N, uint32_t m, uint32_t num_coarse, uint64_t n_coarse_rows, const float *depth,
+                                    const float *sigma, const float *delta, const int64_t *pack_infos, const float *u, int64_t u_stride,
+                                    const float *coarse, const int64_t *coarse_row, float *cdf_workspace, float *fine, float *merged,
+                                    float *deltas, void *stream);
 
 #ifdef __cplusplus
 }

@@ -9,19 +9,28 @@ signature, ``ray_tested`` keys, model attribute protocol (``use_ts`` / ``use_fid
 Data flow on the device (no host sync except the marcher's single total readback and the two nonzero() compactions of
 the pruning stage):  occ-grid march (HIP) -> density query on all marched samples under no_grad (LoTD forward, HIP) ->
 alpha -> packed_volume_render_compression (HIP alpha_to_vw in compaction mode) keeps the samples that are still
-visible (T >= early_stop_eps) -> the differentiable query runs only on those -> alpha -> caller composites."""
+visible (T >= early_stop_eps) -> the differentiable query runs only on those -> alpha -> caller composites.
+
+``nerf_ray_query_march_occ_multi_upsample_compressed`` (:190-441) is the density-field counterpart of the NeuS march + up-sample
+queries: coarse samples and marched samples, ONE importance-resampling pass on the density, a compressed packed buffer.  Its two
+packed stages between the density queries run in one launch each (``bindings._nerf_upsample``) while ``FUSED_UPSAMPLE_NERF`` is set,
+in place of the pack-op chain."""
 from typing import Callable, Dict, Optional, Tuple
 
 import torch
 
+from nr3d_lib_amd.bindings import _nerf_upsample
 from nr3d_lib_amd.graphics.nerf.nerf_utils import (packed_alpha_to_vw, packed_volume_render_compression, sigma_delta_to_alpha,
                                                     tau_to_alpha)
-from nr3d_lib_amd.graphics.pack_ops import (packed_composite, packed_div, packed_sum,
+from nr3d_lib_amd.graphics.pack_ops import (get_pack_infos_from_batch, get_pack_infos_from_n, merge_two_packs_sorted_a_includes_b,
+                                            packed_composite, packed_cumsum, packed_diff, packed_div, packed_sum,
                                             packed_volume_render_compression_gather)
+from nr3d_lib_amd.graphics.raysample import (batch_sample_step_linear, batch_sample_step_wrt_depth, batch_sample_step_wrt_sqrt_depth,
+                                             cdf_positions, packed_sample_cdf)
 from nr3d_lib_amd.profile import profile
 from nr3d_lib_amd import _hip as _H
 
-__all__ = ['nerf_ray_query_march_occ', 'composite_packed_volume_buffer']
+__all__ = ['nerf_ray_query_march_occ', 'nerf_ray_query_march_occ_multi_upsample_compressed', 'composite_packed_volume_buffer']
 
 _PER_RAY_KEYS = (('ts', 'rays_ts'), ('fidx', 'rays_fidx'), ('bidx', 'rays_bidx'), ('pix', 'rays_pix'),
                  ('h_appear', 'rays_h_appear'))
@@ -224,6 +233,222 @@ def nerf_ray_query_march_occ(model, ray_tested: Dict[str, torch.Tensor], with_rg
     if with_rgb:
         volume_buffer['rgb'] = net_out['rgb'].to(dtype)
     volume_buffer['deltas'] = deltas.to(dtype)
+    volume_buffer['sigma'] = net_out['sigma'].to(dtype)
+    volume_buffer['opacity_alpha'] = sigma_delta_to_alpha(volume_buffer['sigma'], volume_buffer['deltas'])
+    for k in _PASSTHROUGH:
+        if k in net_out:
+            volume_buffer[k] = net_out[k].to(dtype)
+    return volume_buffer, details
+
+
+# The two packed stages of nerf_ray_query_march_occ_multi_upsample_compressed between its density queries: True = one launch each of
+# the HIP kernels (bindings._nerf_upsample: merge_rows_packs, upsample_stage_packed) for float32 samples on the GPU; False (and every
+# other input) = the reference's pack-op chain.  Same semantics; the kernel sums the CDF as a scan tree, evaluates the opacity behind
+# it as -expm1(-sigma delta) where the chain's float32 1 - exp(-x) cancels, and raises the new depths to their running maximum where
+# the chain sorts them.  Default by profiles/nerf_upsample.json: the fused route is faster in every row.
+FUSED_UPSAMPLE_NERF = True
+
+_COARSE_SAMPLERS = dict(linear=batch_sample_step_linear, depth=batch_sample_step_wrt_depth,
+                        sqrt_depth=batch_sample_step_wrt_sqrt_depth)
+
+
+def _chunked(fn, kwargs: dict, chunk: int) -> torch.Tensor:
+    """fn(**kwargs) evaluated on slices of at most `chunk` rows (every tensor argument is sliced along dim 0)"""
+    n = next(iter(kwargs.values())).shape[0]
+    if n <= chunk:
+        return fn(**kwargs)
+    return torch.cat([fn(**{k: v[i:i + chunk] for k, v in kwargs.items()}) for i in range(0, n, chunk)], 0)
+
+
+def _rows_into_packs(rows_a, sel_a, rows_b, sel_b, pack_first):
+    """rows_a [len(sel_a), wa] into the packs sel_a and rows_b [len(sel_b), wb] into the packs sel_b of one packed buffer whose packs
+    start at pack_first: plain index copies (the two selections cover every pack once)"""
+    wa, wb = rows_a.shape[1], rows_b.shape[1]
+    out = rows_a.new_empty(rows_a.numel() + rows_b.numel())
+    out[(pack_first[sel_a].unsqueeze(-1) + torch.arange(wa, device=out.device)).flatten()] = rows_a.flatten()
+    out[(pack_first[sel_b].unsqueeze(-1) + torch.arange(wb, device=out.device)).flatten()] = rows_b.flatten()
+    return out
+
+
+def nerf_ray_query_march_occ_multi_upsample_compressed(
+        model, ray_tested: Dict[str, torch.Tensor], with_rgb: bool = True, perturb: bool = False, num_coarse: int = 32,
+        coarse_step_cfg=dict(step_mode='linear'), num_fine: int = 32, march_cfg=dict(), chunksize_query: int = 2 ** 24,
+        combine_marched_and_coarse: bool = True, bypass_sigma_fn: Optional[Callable] = None,
+        bypass_alpha_fn: Optional[Callable] = None, forward_params: dict = {}) -> Tuple[dict, dict]:
+    """Coarse samples on every ray + occupancy-marched samples -> one up-sampling pass on the density (num_fine + 1 depths from the
+    CDF of the opacities) -> density query -> packed_volume_render_compression -> the differentiable query on what is left.
+    Signature, ``ray_tested`` keys, model protocol, ``volume_buffer`` and ``details`` keys of the reference (:190-441).  Where the
+    reference indexes inconsistently, this driver keeps every quantity per ray: with ``num_coarse > 0`` the packs are those of ALL
+    rays, so ``rays_inds_hit`` lists all rays that keep a sample (the reference keeps the marcher's hit list beside packs of all rays
+    when ``combine_marched_and_coarse`` is off), ``rays_bidx_hit`` is taken at those rays, and the per-ray attributes of the density
+    query are read at ``ridx_all`` of the full ray list.  ``num_coarse == 0`` with no marched sample returns the empty buffer."""
+    assert hasattr(model, 'forward'), "model.forward() is requried"
+    assert getattr(model, 'accel', None) is not None, "model.accel is required"
+    if not with_rgb:
+        assert hasattr(model, 'forward_density'), "model.forward_density() is requried"
+    assert hasattr(model, 'query_density'), "model.query_density() is requried"
+    assert (bypass_sigma_fn is None) or (bypass_alpha_fn is None), \
+        "Please pass at most one of bypass_sigma_fn or bypass_alpha_fn"
+
+    density_uses = {k: _flag(model, 'use_' + k) if k in ('ts', 'fidx', 'bidx') else _flag(model, 'fwd_density_use_' + k)
+                    for k, _ in _PER_RAY_KEYS}
+    full_uses = {k: density_uses[k] or (_flag(model, 'use_' + k) and with_rgb) for k, _ in _PER_RAY_KEYS}
+    density_view = _flag(model, 'fwd_density_use_view_dirs')
+    full_view = density_view or (_flag(model, 'use_view_dirs') and with_rgb)
+
+    empty = dict(type='empty', rays_inds_hit=[])
+    num_rays = ray_tested['num_rays']
+    if num_rays == 0:
+        return empty, {}
+    rays_o, rays_d = ray_tested['rays_o'], ray_tested['rays_d']
+    near, far, rays_inds = ray_tested['near'], ray_tested['far'], ray_tested['rays_inds']
+    assert rays_o.dim() == 2 and rays_d.dim() == 2
+    device, dtype = rays_o.device, rays_o.dtype
+    view_dirs = None
+    if full_view:
+        view_dirs = rays_d / rays_d.detach().norm(dim=-1, keepdim=True).clamp_min(1.0e-10)
+
+    def query_kwargs(samples, ridx, uses, use_view):
+        kw = dict(x=samples)
+        for k, src in _PER_RAY_KEYS:
+            if uses[k]:
+                kw[k] = ray_tested[src][ridx]
+        if use_view:
+            kw['v'] = view_dirs[ridx]
+        return kw
+
+    def points(ridx, depths):
+        return torch.addcmul(rays_o[ridx], rays_d[ridx], depths.unsqueeze(-1))
+
+    m = num_fine + 1
+    all_rays = torch.arange(rays_inds.numel(), device=device)
+    if num_coarse > 0:
+        cfg = dict(coarse_step_cfg)
+        mode = cfg.pop('step_mode')
+        if mode not in _COARSE_SAMPLERS:
+            raise RuntimeError(f"Invalid step_mode={mode}")
+        depths_1, deltas_1 = _COARSE_SAMPLERS[mode](near, far, num_coarse + 1, perturb=perturb, return_dt=True, **cfg)
+        deltas_coarse = deltas_1[..., :num_coarse]
+        depths_coarse = (depths_1[..., :num_coarse] + deltas_coarse / 2.).contiguous()      # the mid-points of the coarse steps
+        pack_infos_coarse = get_pack_infos_from_batch(rays_inds.numel(), num_coarse, device=device)
+
+    with profile("Ray marching"):
+        marched = _march(model, ray_tested, rays_o, rays_d, near, far, perturb, march_cfg)
+
+    if marched.ridx_hit is not None:
+        with profile("Upsampling"), torch.no_grad():
+            hit, n_hit = marched.ridx_hit, marched.ridx_hit.numel()
+            marched_depths = marched.depth_samples.view(-1)
+            fused = (FUSED_UPSAMPLE_NERF and marched_depths.is_cuda and marched_depths.dtype == torch.float32
+                     and rays_o.dtype == torch.float32 and rays_d.dtype == torch.float32
+                     and (num_coarse == 0 or depths_coarse.dtype == torch.float32))
+            combine = bool(num_coarse > 0 and combine_marched_and_coarse)
+            if combine and fused:
+                # the marched pack of EVERY ray: none for a missed one, all of them tiling the marched samples in ray order
+                n_marched = marched.pack_infos.new_zeros(rays_inds.numel())
+                n_marched[hit] = marched.pack_infos[:, 1]
+                depths_all, deltas_all, ridx_all, samples_all, pack_infos = _nerf_upsample.merge_rows_packs(
+                    depths_coarse, marched_depths.contiguous(), get_pack_infos_from_n(n_marched), rays_o.contiguous(),
+                    rays_d.contiguous())
+                ridx_hit = all_rays
+            elif combine:
+                pidx0, pidx1, pack_infos = merge_two_packs_sorted_a_includes_b(
+                    depths_coarse.flatten(), pack_infos_coarse, all_rays, marched_depths, marched.pack_infos, hit, b_sorted=True)
+                num_samples = marched_depths.numel() + depths_coarse.numel()
+                depths_all, ridx_all = marched_depths.new_zeros([num_samples]), hit.new_zeros([num_samples])
+                ridx_all[pidx0], ridx_all[pidx1] = all_rays.unsqueeze(-1).expand(-1, num_coarse).flatten(), marched.ridx
+                depths_all[pidx0], depths_all[pidx1] = depths_coarse.flatten(), marched_depths
+                samples_all = points(ridx_all, depths_all)
+                deltas_all = packed_diff(depths_all, pack_infos)
+                ridx_hit = all_rays
+            else:
+                samples_all, depths_all, ridx_all = marched.samples, marched_depths, marched.ridx
+                deltas_all, pack_infos, ridx_hit = marched.deltas.view(-1), marched.pack_infos, hit
+
+            kw = query_kwargs(samples_all, ridx_all, density_uses, density_view)
+            sigma = _chunked(lambda **k: model.query_density(**k), kw, chunksize_query).view(-1)
+            fused = fused and sigma.dtype == torch.float32 and deltas_all.dtype == torch.float32
+            if fused:
+                u = cdf_positions(depths_all, (pack_infos.shape[0],), m, perturb)
+                fine, merged, deltas_m = _nerf_upsample.upsample_stage_packed(
+                    depths_all.contiguous(), sigma.contiguous(), deltas_all.contiguous(), pack_infos.contiguous(), u,
+                    coarse=depths_coarse if num_coarse > 0 else None, coarse_row=None if (combine or num_coarse == 0) else hit)
+            else:
+                cdf = packed_cumsum(tau_to_alpha(sigma * deltas_all), pack_infos)
+                last = cdf[pack_infos[..., 0] + pack_infos[..., 1] - 1]
+                cdf = packed_div(cdf, last.clamp_min(1e-5), pack_infos)
+                fine = packed_sample_cdf(depths_all, cdf.to(depths_all.dtype), pack_infos, m, perturb=perturb)[0]
+
+            if num_coarse == 0:
+                if fused:
+                    depths_all, deltas_all = merged.flatten(), deltas_m.flatten()
+                else:
+                    deltas_m = fine.diff(dim=-1)
+                    depths_all, deltas_all = (fine[..., :num_fine] + deltas_m).flatten(), deltas_m.flatten()
+                ridx_all = ridx_hit.unsqueeze(-1).expand(n_hit, num_fine).flatten()
+                pack_infos = get_pack_infos_from_batch(n_hit, num_fine, device=device)
+            elif fused:
+                if combine:
+                    depths_all, deltas_all = merged.flatten(), deltas_m.flatten()
+                    ridx_all = all_rays.unsqueeze(-1).expand(-1, num_coarse + m).flatten()
+                    pack_infos = get_pack_infos_from_batch(rays_inds.numel(), num_coarse + m, device=device)
+                else:
+                    # the [n_hit, nc + m] rows of the hit rays and the untouched coarse rows of the others into one packed layout
+                    is_hit = torch.zeros(rays_inds.numel(), dtype=torch.bool, device=device)
+                    is_hit[hit] = True
+                    n_per_ray = num_coarse + m * is_hit.long()
+                    pack_infos = get_pack_infos_from_n(n_per_ray)
+                    missed = all_rays[~is_hit]
+                    coarse_diff = torch.cat([depths_coarse.diff(dim=-1), depths_coarse.new_zeros(rays_inds.numel(), 1)], -1)
+                    depths_all = _rows_into_packs(merged, hit, depths_coarse[missed], missed, pack_infos[:, 0])
+                    deltas_all = _rows_into_packs(deltas_m, hit, coarse_diff[missed], missed, pack_infos[:, 0])
+                    ridx_all = torch.repeat_interleave(all_rays, n_per_ray, output_size=depths_all.numel())
+                ridx_hit = all_rays
+            else:
+                ridx_fine = ridx_hit.unsqueeze(-1).expand(fine.size(0), fine.size(1)).flatten()
+                pinfo_fine = get_pack_infos_from_batch(fine.size(0), fine.size(1), device=device)
+                pidx0, pidx1, pack_infos = merge_two_packs_sorted_a_includes_b(
+                    depths_coarse.flatten(), pack_infos_coarse, all_rays, fine.flatten(), pinfo_fine, ridx_hit, b_sorted=False)
+                num_samples = fine.numel() + depths_coarse.numel()
+                depths_all, ridx_all = fine.new_zeros([num_samples]), ridx_hit.new_zeros([num_samples])
+                ridx_all[pidx0], ridx_all[pidx1] = all_rays.unsqueeze(-1).expand(-1, num_coarse).flatten(), ridx_fine
+                depths_all[pidx0], depths_all[pidx1] = depths_coarse.flatten(), fine.flatten()
+                deltas_all = packed_diff(depths_all, pack_infos)
+                ridx_hit = all_rays
+    elif num_coarse > 0:                      # no marched samples, only coarse samples
+        deltas_all, depths_all = deltas_coarse.flatten(), depths_coarse.flatten()
+        ridx_hit = all_rays
+        ridx_all = all_rays.unsqueeze(-1).expand(-1, num_coarse).flatten()
+        pack_infos = pack_infos_coarse
+    else:
+        return empty, {}
+
+    details = {'render.num_per_ray0': pack_infos[:, 1]}
+    if marched.ridx_hit is not None:
+        details['march.num_per_ray'] = marched.pack_infos[:, 1].clone()
+
+    with profile("Acquire volume buffer"), torch.no_grad():
+        kw = query_kwargs(points(ridx_all, depths_all), ridx_all, density_uses, density_view)
+        if bypass_alpha_fn is not None:
+            alphas = bypass_alpha_fn(**kw)
+        else:
+            sigmas = bypass_sigma_fn(**kw) if bypass_sigma_fn is not None else model.query_density(**kw)
+            alphas = sigma_delta_to_alpha(sigmas.view(-1), deltas_all.view(-1))
+        nidx_useful, pack_infos, pidx_useful = packed_volume_render_compression(alphas.view(-1), pack_infos)
+        if nidx_useful.numel() == 0:
+            return empty, {}
+        ridx_hit, ridx_all = ridx_hit[nidx_useful], ridx_all[pidx_useful]
+        depths_all, deltas_all = depths_all[pidx_useful], deltas_all[pidx_useful]
+    details['render.num_per_ray'] = pack_infos[:, 1]
+
+    volume_buffer = dict(type='packed', rays_inds_hit=rays_inds[ridx_hit], pack_infos_hit=pack_infos, t=depths_all.to(dtype))
+    if full_uses['bidx']:
+        volume_buffer['rays_bidx_hit'] = ray_tested['rays_bidx'][ridx_hit]
+    kw = query_kwargs(points(ridx_all, depths_all), ridx_all, full_uses, full_view)
+    net_out = (model.forward if with_rgb else model.forward_density)(**kw, **forward_params)
+    if with_rgb:
+        volume_buffer['rgb'] = net_out['rgb'].to(dtype)
+    volume_buffer['deltas'] = deltas_all.to(dtype)
     volume_buffer['sigma'] = net_out['sigma'].to(dtype)
     volume_buffer['opacity_alpha'] = sigma_delta_to_alpha(volume_buffer['sigma'], volume_buffer['deltas'])
     for k in _PASSTHROUGH:
