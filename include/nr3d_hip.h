@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 24
+#define NR3D_ABI_VERSION 25
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -1053,6 +1053,48 @@ uint64_t nr3d_neus_alpha_bwd_workspace_bytes(int layout, uint32_t P, uint64_t S)
 int nr3d_neus_alpha_bwd(int layout, uint32_t P, uint64_t S, uint32_t n, const float *sdf, const int64_t *pack_infos, int append_mode,
                         const float *pack_sdf_appends, float inv_s, const float *inv_s_dev, int ordered_packs, const float *grad_alpha,
                         float *grad_sdf, float *grad_appends, float *grad_inv_s, void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* =================================================================================================
+ * NeuS render: the volume buffer -> vw, mask, depth, rgb and the rendered normal of every ray, one launch each way (csrc/neus_composite.hip)
+ *   reference         the torch op chain at the end of NeusRendererMixin.ray_query (nr3d_lib/models/fields/neus/renderer_mixin.py:396-439:
+ *                     ray_alpha_to_vw | packed_alpha_to_vw, then sum | packed_sum, div | packed_div, mul and index-put per output) and its
+ *                     autograd; no native twin there
+ * layout ROWS ('batched' buffers): alphas, t [P, n] (S = P n, n >= 1; pack_infos NULL), row r = samples [r n, (r + 1) n).  The semantics of
+ *   ray_alpha_to_vw: w_i = a_i T_i, T_0 = 1, T_{i+1} = T_i (1 - a_i) over EVERY sample; early_stop_eps and alpha_thre are ignored.  G = the
+ *   power of two >= n (at most 64) lanes work on a row; T is a prefix product, so vw equals the chain's up to rounding.
+ * layout PACKED: alphas, t [S], pack_infos int64 [P, 2] = (first, len); n is ignored.  Forward and backward are those of
+ *   nr3d_pack_composite_fwd / _bwd in every respect (early_stop_eps, alpha_thre with `<=` forward and `<` backward, the backward's
+ *   max(1 - a, 1e-10) divisor, NR3D_OPT_PACK_SCAN and its serial replay of ambiguous packs), and without nablas the call is forwarded to
+ *   them: the same bits.  With nablas one wave works on a pack at every pack count.
+ * rgb [S, 3] or NULL; nablas [S, 3] or NULL, composited like rgb into normals_out by normals_mode:
+ *   0 (training)    normals_out = sum_i w_i nablas_i;
+ *   1 (evaluation)  normals_out = sum_i w_i c_i / max(|c_i|, 1e-12), c_i = clamp(nablas_i, -1, 1), and c_i is STORED BACK into nablas (the
+ *                   reference's clamp_ is in place) for every sample of a row or pack; a zero vector contributes zero; forward only.
+ * ray_index int64 [P] or NULL: the per-ray results go to element ray_index[p] of mask / depth [num_rays], rgb_out / normals_out
+ *   [num_rays, 3], which the caller ZERO-INITs when ray_index is given.  depth = sum(w t) / (mask + 1e-10) when normalize_depth, else
+ *   sum(w t).  vw [S] is fully written over the rows or packs; samples outside every pack are the caller's.
+ * Errors before any launch: an unknown layout or normals_mode, rows with pack_infos or with n == 0 and P > 0 or P n != S, S >= 2^32,
+ *   rgb / nablas without their output.  P == 0 is a no-op.  fp32; nothing is accumulated across waves: the same bits run after run.
+ * ============================================================================================== */
+#define NR3D_NEUS_COMPOSITE_ROWS 0
+#define NR3D_NEUS_COMPOSITE_PACKED 1
+int nr3d_neus_composite_fwd(int layout, uint32_t P, uint64_t S, uint32_t n, const float *alphas, const float *t, const float *rgb,
+                            float *nablas, const int64_t *pack_infos, const int64_t *ray_index, float early_stop_eps, float alpha_thre,
+                            int normalize_depth, int normals_mode, float *vw, float *mask, float *depth, float *rgb_out, float *normals_out,
+                            void *stream);
+/* The gradients.  vw, mask, depth = the forward's outputs; g_mask / g_depth [num_rays], g_rgb / g_normals [num_rays, 3], g_vw [S] (each may
+ * be NULL = zero).  With g_i = dL/dw_i = g_mask + the depth term + g_rgb . rgb_i + g_normals . nablas_i + g_vw_i:
+ *   ROWS    grad_alphas_i = T_i (g_i - R_i), R_i = g_{i+1} a_{i+1} + (1 - a_{i+1}) R_{i+1}, R_{n-1} = 0: the derivative of the product with
+ *           the sample's own factor left out (torch's cumprod backward), no division -- exact where some a_i == 1;
+ *   PACKED  as nr3d_pack_composite_bwd.
+ * grad_alphas [S] fully written over the rows or packs; grad_t [S], grad_rgb [S, 3], grad_nablas [S, 3] = w_i g_normals optional (NULL:
+ * not computed).  normals_mode 1 together with g_normals or grad_nablas is an error (the normalised normals are forward only); nablas is
+ * read only where g_normals is given. */
+int nr3d_neus_composite_bwd(int layout, uint32_t P, uint64_t S, uint32_t n, const float *alphas, const float *t, const float *rgb,
+                            const float *nablas, const int64_t *pack_infos, const int64_t *ray_index, float early_stop_eps, float alpha_thre,
+                            int normalize_depth, int normals_mode, const float *vw, const float *mask, const float *depth,
+                            const float *g_mask, const float *g_depth, const float *g_rgb, const float *g_normals, const float *g_vw,
+                            float *grad_alphas, float *grad_t, float *grad_rgb, float *grad_nablas, void *stream);
 
 /* =================================================================================================
  * NeRF march + up-sample ray query: its two packed stages, one launch each (csrc/nerf_upsample.hip)

@@ -24,5 +24,16 @@ int launch_composite_rays_bwd(uint32_t n_rays, const int32_t *packed_info, const
                               float *grad_rgb, const float *sigma, const float *delta, uint64_t sigma_rows, float *grad_sigma,
                               hipStream_t st);
 
+// the packed composite with the samples' normals composited next to rgb (neus_composite.hip: nr3d_neus_composite_fwd / _bwd with nablas):
+// the device bodies of nr3d_pack_composite_fwd / _bwd, one wave per pack; normals_mode 1 clamps nablas in place
+int launch_neus_composite_packs_fwd(uint32_t P, const float *alphas, const float *ts, const float *rgb, float *nablas, int normals_mode,
+                                    const int64_t *pack_infos, const int64_t *ray_index, float eps, float thre, int normalize, float *vw,
+                                    float *mask, float *depth, float *rgb_out, float *normals_out, hipStream_t st);
+int launch_neus_composite_packs_bwd(uint32_t P, const float *alphas, const float *vw, const float *ts, const float *rgb, const float *nablas,
+                                    const int64_t *pack_infos, const int64_t *ray_index, float eps, float thre, int normalize,
+                                    const float *mask, const float *depth, const float *g_mask, const float *g_depth, const float *g_rgb,
+                                    const float *g_normals, const float *g_vw, float *grad_alphas, float *grad_t, float *grad_rgb,
+                                    float *grad_nablas, hipStream_t st);
+
 }  // namespace pk
 }  // namespace nr3d

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "scan.h"
 #include "pack_launch.h"
+#include "unit_normal.h"
 #include <stdlib.h>
 
 namespace nr3d {
@@ -849,14 +850,25 @@ static inline bool lane_per_pack(uint32_t P) { return P >= kLanePerPackMin; }
 // normalised depth as sum(vw * t) / (mask + 1e-10) -- the chain's values up to summation order (<= 1e-5 rel).
 // `ray_index` (optional) scatters the per-ray results into [num_rays] outputs (rays_inds_hit) and gathers their grads.
 // ------------------------------------------------------------------------------------------------
-template <bool RGB>
+// NeuS normals riding along (template parameter NRM; the pack kernels of nr3d_neus_composite_fwd / _bwd at the end of this section): the
+// samples' nablas [S,3] are composited like rgb.  mode 1 (evaluation) clamps them to [-1, 1] IN PLACE, as the reference's clamp_ does, and
+// composites the unit vectors c / max(|c|, 1e-12) (F.normalize); a NaN stays one.  With NRM = false none of this leaves an instruction.
+struct NrmFwd { float *nablas; int mode; float *out; };
+struct NrmBwd { const float *nablas; const float *g_normals; float *grad_nablas; };
+template <bool NRM>
+__device__ __forceinline__ V3 nrm_load(const NrmFwd &nf, size_t i, bool mine) {
+	if (NRM && mine) return load_normal(nf.nablas, i, nf.mode);      // unit_normal.h: the rows' kernels read theirs the same way
+	return V3{0.0f, 0.0f, 0.0f};
+}
+
+template <bool RGB, bool NRM = false>
 __device__ __forceinline__ void composite_fwd_serial(const Pack &k, const float *__restrict__ alphas, const float *__restrict__ ts,
                                                      const float *__restrict__ rgb, const int64_t *__restrict__ ray_index, float eps,
                                                      float thre, int normalize, float *__restrict__ vw, float *__restrict__ mask,
-                                                     float *__restrict__ depth, float *__restrict__ rgb_out) {
+                                                     float *__restrict__ depth, float *__restrict__ rgb_out, NrmFwd nf = NrmFwd()) {
 	float T = 1.0f;
 	bool stopped = false;
-	float s = 0.0f, dt = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+	float s = 0.0f, dt = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, m0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
 	for (uint32_t base = 0; base < k.len; base += 64) {
 		const uint32_t n = min(64u, k.len - base);
 		const bool mine = (uint32_t)k.lane < n;
@@ -865,6 +877,7 @@ __device__ __forceinline__ void composite_fwd_serial(const Pack &k, const float 
 		const float t_mine = mine ? ts[i] : 0.0f;
 		float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
 		if (RGB && mine) { r0 = rgb[3 * i]; r1 = rgb[3 * i + 1]; r2 = rgb[3 * i + 2]; }
+		const V3 x = nrm_load<NRM>(nf, i, mine);
 		float w_mine = 0.0f;
 		if (!stopped) {
 			for (uint32_t j = 0; j < n; ++j) {
@@ -878,17 +891,20 @@ __device__ __forceinline__ void composite_fwd_serial(const Pack &k, const float 
 		if (mine) vw[i] = w_mine;
 		s += w_mine; dt += w_mine * t_mine;
 		if (RGB) { c0 += w_mine * r0; c1 += w_mine * r1; c2 += w_mine * r2; }
+		if (NRM) { m0 += w_mine * x.x; m1 += w_mine * x.y; m2 += w_mine * x.z; }
 	}
 #pragma unroll
 	for (int off = 32; off >= 1; off >>= 1) {
 		s += shfl_xor_t<float>(s, off); dt += shfl_xor_t<float>(dt, off);
 		if (RGB) { c0 += shfl_xor_t<float>(c0, off); c1 += shfl_xor_t<float>(c1, off); c2 += shfl_xor_t<float>(c2, off); }
+		if (NRM) { m0 += shfl_xor_t<float>(m0, off); m1 += shfl_xor_t<float>(m1, off); m2 += shfl_xor_t<float>(m2, off); }
 	}
 	if (k.lane == 0) {
 		const size_t o = ray_index ? (size_t)ray_index[k.p] : (size_t)k.p;
 		mask[o] = s;
 		depth[o] = normalize ? dt / (s + 1e-10f) : dt;
 		if (RGB) { rgb_out[3 * o] = c0; rgb_out[3 * o + 1] = c1; rgb_out[3 * o + 2] = c2; }
+		if (NRM) { nf.out[3 * o] = m0; nf.out[3 * o + 1] = m1; nf.out[3 * o + 2] = m2; }
 	}
 }
 
@@ -921,7 +937,28 @@ __device__ __forceinline__ CompGrad comp_grad(size_t o, int normalize, const flo
 	return c;
 }
 
-template <bool RGB>
+// the normals' share of dL/dvw and the per-pack g_normals (NRM)
+struct NrmG { float n0, n1, n2; };
+__device__ __forceinline__ NrmG nrm_grad(const NrmBwd &nb, size_t o) {
+	NrmG g;
+	g.n0 = nb.g_normals ? nb.g_normals[3 * o] : 0.0f; g.n1 = nb.g_normals ? nb.g_normals[3 * o + 1] : 0.0f;
+	g.n2 = nb.g_normals ? nb.g_normals[3 * o + 2] : 0.0f;
+	return g;
+}
+// gw of comp_gw plus g_normals . nablas_i; the nablas are read only where g_normals is given
+template <bool NRM>
+__device__ __forceinline__ float nrm_gw(float gw, const NrmBwd &nb, const NrmG &g, size_t i, bool mine) {
+	if (NRM && mine && nb.g_normals) {
+		gw = __fmaf_rn(g.n0, nb.nablas[3 * i], gw); gw = __fmaf_rn(g.n1, nb.nablas[3 * i + 1], gw); gw = __fmaf_rn(g.n2, nb.nablas[3 * i + 2], gw);
+	}
+	return gw;
+}
+template <bool NRM>
+__device__ __forceinline__ void nrm_store_grad(const NrmBwd &nb, const NrmG &g, size_t i, float w) {
+	if (NRM && nb.grad_nablas) { nb.grad_nablas[3 * i] = w * g.n0; nb.grad_nablas[3 * i + 1] = w * g.n1; nb.grad_nablas[3 * i + 2] = w * g.n2; }
+}
+
+template <bool RGB, bool NRM = false>
 __device__ __forceinline__ void composite_bwd_serial(const Pack &k, const float *__restrict__ alphas, const float *__restrict__ vw,
                                                      const float *__restrict__ ts, const float *__restrict__ rgb,
                                                      const int64_t *__restrict__ ray_index, float eps, float thre, int normalize,
@@ -929,9 +966,11 @@ __device__ __forceinline__ void composite_bwd_serial(const Pack &k, const float 
                                                      const float *__restrict__ g_mask, const float *__restrict__ g_depth,
                                                      const float *__restrict__ g_rgb, const float *__restrict__ g_vw,
                                                      float *__restrict__ grad_alphas, float *__restrict__ grad_t,
-                                                     float *__restrict__ grad_rgb) {
+                                                     float *__restrict__ grad_rgb, NrmBwd nb = NrmBwd()) {
 	const size_t o = ray_index ? (size_t)ray_index[k.p] : (size_t)k.p;
 	const CompGrad cg = comp_grad(o, normalize, mask, depth, g_mask, g_depth, g_rgb);
+	NrmG ng = {0.0f, 0.0f, 0.0f};
+	if (NRM) ng = nrm_grad(nb, o);
 	// accum = sum_j gw_j * w_j, serial fma chain like packed_alpha_to_vw_backward (the sweep below divides by
 	// max(1 - alpha, 1e-10), which amplifies any difference in accum)
 	float accum = 0.0f;
@@ -942,7 +981,7 @@ __device__ __forceinline__ void composite_bwd_serial(const Pack &k, const float 
 		const float w_mine = mine ? vw[i] : 0.0f;
 		float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
 		if (RGB && mine) { r0 = rgb[3 * i]; r1 = rgb[3 * i + 1]; r2 = rgb[3 * i + 2]; }
-		const float gw_mine = mine ? comp_gw(cg, ts[i], r0, r1, r2, g_vw ? g_vw[i] : 0.0f) : 0.0f;
+		const float gw_mine = nrm_gw<NRM>(mine ? comp_gw(cg, ts[i], r0, r1, r2, g_vw ? g_vw[i] : 0.0f) : 0.0f, nb, ng, i, mine);
 		for (uint32_t j = 0; j < n; ++j)
 			accum = __fmaf_rn(shfl_t<float>(gw_mine, (int)j), shfl_t<float>(w_mine, (int)j), accum);
 	}
@@ -956,7 +995,7 @@ __device__ __forceinline__ void composite_bwd_serial(const Pack &k, const float 
 		const float w_mine = mine ? vw[i] : 0.0f;
 		float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
 		if (RGB && mine) { r0 = rgb[3 * i]; r1 = rgb[3 * i + 1]; r2 = rgb[3 * i + 2]; }
-		const float gw_mine = mine ? comp_gw(cg, ts[i], r0, r1, r2, g_vw ? g_vw[i] : 0.0f) : 0.0f;
+		const float gw_mine = nrm_gw<NRM>(mine ? comp_gw(cg, ts[i], r0, r1, r2, g_vw ? g_vw[i] : 0.0f) : 0.0f, nb, ng, i, mine);
 		float ga_mine = 0.0f;
 		if (!stopped) {
 			for (uint32_t j = 0; j < n; ++j) {
@@ -972,6 +1011,7 @@ __device__ __forceinline__ void composite_bwd_serial(const Pack &k, const float 
 			grad_alphas[i] = ga_mine;
 			if (grad_t) grad_t[i] = cg.cd * w_mine;
 			if (RGB && grad_rgb) { grad_rgb[3 * i] = w_mine * cg.g0; grad_rgb[3 * i + 1] = w_mine * cg.g1; grad_rgb[3 * i + 2] = w_mine * cg.g2; }
+			nrm_store_grad<NRM>(nb, ng, i, w_mine);
 		}
 	}
 }
@@ -1035,13 +1075,13 @@ __device__ __forceinline__ ChunkT chunk_transmittance(float a, bool mine, bool c
 // body of the prefix-product forward for the pack `k`.  FROM_SIGMA: the opacity is alpha = 1 - exp(-(sigma * delta)) (the expression of
 // k_tau_to_alpha_fwd, ray_glue.hip: bit-identical), computed here and stored to `alphas` (an OUTPUT then: not restrict-qualified, the
 // serial replay below reads back what this wave's own lanes stored); rows >= sigma_rows read sigma as 0 (the host raises afterwards).
-template <bool RGB, bool FROM_SIGMA>
+template <bool RGB, bool FROM_SIGMA, bool NRM = false>
 __device__ __forceinline__ void composite_fwd_scan_body(const Pack &k, float *alphas, const float *__restrict__ sigma,
                                                         const float *__restrict__ delta, uint64_t sigma_rows, const float *__restrict__ ts,
                                                         const float *__restrict__ rgb, const int64_t *__restrict__ ray_index, float eps,
                                                         float thre, int normalize, float *__restrict__ vw, float *__restrict__ mask,
-                                                        float *__restrict__ depth, float *__restrict__ rgb_out) {
-	float Tc = 1.0f, s = 0.0f, dt = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+                                                        float *__restrict__ depth, float *__restrict__ rgb_out, NrmFwd nf = NrmFwd()) {
+	float Tc = 1.0f, s = 0.0f, dt = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, m0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
 	bool stopped = false, ambiguous = false;
 	auto alpha_at = [&](size_t i) -> float {
 		if (!FROM_SIGMA) return alphas[i];
@@ -1058,29 +1098,34 @@ __device__ __forceinline__ void composite_fwd_scan_body(const Pack &k, float *al
 		const float t = mine ? ts[i] : 0.0f;
 		float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
 		if (RGB && mine) { r0 = rgb[3 * i]; r1 = rgb[3 * i + 1]; r2 = rgb[3 * i + 2]; }
+		const V3 x = nrm_load<NRM>(nf, i, mine);
 		const bool counts = !(a <= thre);
 		const ChunkT ct = chunk_transmittance(a, mine, counts, eps, k.lane, Tc, stopped, ambiguous);
 		const float w = (mine && counts && !ct.cut) ? a * ct.Tin : 0.0f;
 		if (mine) vw[i] = w;
 		s += w; dt += w * t;
 		if (RGB) { c0 += w * r0; c1 += w * r1; c2 += w * r2; }
+		if (NRM) { m0 += w * x.x; m1 += w * x.y; m2 += w * x.z; }
 	}
 	if (ambiguous) {        // wave-uniform
 		if (FROM_SIGMA)     // the chunks the loop above did not reach: their opacities first
 			for (; base < k.len; base += 64) if ((uint32_t)k.lane < min(64u, k.len - base)) alpha_at((size_t)k.begin + base + k.lane);
-		composite_fwd_serial<RGB>(k, alphas, ts, rgb, ray_index, eps, thre, normalize, vw, mask, depth, rgb_out);
+		// NRM, mode 1: the replay reads back the nablas this wave's own lanes have clamped (the clamp gives the same value again)
+		composite_fwd_serial<RGB, NRM>(k, alphas, ts, rgb, ray_index, eps, thre, normalize, vw, mask, depth, rgb_out, nf);
 		return;
 	}
 #pragma unroll
 	for (int off = 32; off >= 1; off >>= 1) {
 		s += shfl_xor_t<float>(s, off); dt += shfl_xor_t<float>(dt, off);
 		if (RGB) { c0 += shfl_xor_t<float>(c0, off); c1 += shfl_xor_t<float>(c1, off); c2 += shfl_xor_t<float>(c2, off); }
+		if (NRM) { m0 += shfl_xor_t<float>(m0, off); m1 += shfl_xor_t<float>(m1, off); m2 += shfl_xor_t<float>(m2, off); }
 	}
 	if (k.lane == 0) {
 		const size_t o = ray_index ? (size_t)ray_index[k.p] : (size_t)k.p;
 		mask[o] = s;
 		depth[o] = normalize ? dt / (s + 1e-10f) : dt;
 		if (RGB) { rgb_out[3 * o] = c0; rgb_out[3 * o + 1] = c1; rgb_out[3 * o + 2] = c2; }
+		if (NRM) { nf.out[3 * o] = m0; nf.out[3 * o + 1] = m1; nf.out[3 * o + 2] = m2; }
 	}
 }
 
@@ -1160,7 +1205,7 @@ __global__ __launch_bounds__(kBlock) void k_emit_composite_rays_fwd(uint32_t n_r
 	                                   rgb_out);
 }
 
-template <bool RGB>
+template <bool RGB, bool NRM = false>
 __device__ __forceinline__ void composite_bwd_scan_body(const Pack &k, const float *__restrict__ alphas, const float *__restrict__ vw,
                                                         const float *__restrict__ ts, const float *__restrict__ rgb,
                                                         const int64_t *__restrict__ ray_index, float eps, float thre, int normalize,
@@ -1168,9 +1213,11 @@ __device__ __forceinline__ void composite_bwd_scan_body(const Pack &k, const flo
                                                         const float *__restrict__ g_mask, const float *__restrict__ g_depth,
                                                         const float *__restrict__ g_rgb, const float *__restrict__ g_vw,
                                                         float *__restrict__ grad_alphas, float *__restrict__ grad_t,
-                                                        float *__restrict__ grad_rgb) {
+                                                        float *__restrict__ grad_rgb, NrmBwd nb = NrmBwd()) {
 	const size_t o = ray_index ? (size_t)ray_index[k.p] : (size_t)k.p;
 	const CompGrad cg = comp_grad(o, normalize, mask, depth, g_mask, g_depth, g_rgb);
+	NrmG ng = {0.0f, 0.0f, 0.0f};
+	if (NRM) ng = nrm_grad(nb, o);
 	// total = sum_j gw_j * w_j; the sample's own "still to come" sum is total minus the prefix before it
 	float total = 0.0f;
 	for (uint32_t base = 0; base < k.len; base += 64) {
@@ -1179,7 +1226,7 @@ __device__ __forceinline__ void composite_bwd_scan_body(const Pack &k, const flo
 		if (mine) {
 			float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
 			if (RGB) { r0 = rgb[3 * i]; r1 = rgb[3 * i + 1]; r2 = rgb[3 * i + 2]; }
-			total = __fmaf_rn(comp_gw(cg, ts[i], r0, r1, r2, g_vw ? g_vw[i] : 0.0f), vw[i], total);
+			total = __fmaf_rn(nrm_gw<NRM>(comp_gw(cg, ts[i], r0, r1, r2, g_vw ? g_vw[i] : 0.0f), nb, ng, i, true), vw[i], total);
 		}
 	}
 #pragma unroll
@@ -1194,7 +1241,7 @@ __device__ __forceinline__ void composite_bwd_scan_body(const Pack &k, const flo
 		const float w = mine ? vw[i] : 0.0f;
 		float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
 		if (RGB && mine) { r0 = rgb[3 * i]; r1 = rgb[3 * i + 1]; r2 = rgb[3 * i + 2]; }
-		const float gw = mine ? comp_gw(cg, ts[i], r0, r1, r2, g_vw ? g_vw[i] : 0.0f) : 0.0f;
+		const float gw = nrm_gw<NRM>(mine ? comp_gw(cg, ts[i], r0, r1, r2, g_vw ? g_vw[i] : 0.0f) : 0.0f, nb, ng, i, mine);
 		const bool counts = !(a < thre);
 		const ChunkT ct = chunk_transmittance(a, mine, counts, eps, k.lane, Tc, stopped, ambiguous);
 		const float q = gw * w;
@@ -1205,11 +1252,12 @@ __device__ __forceinline__ void composite_bwd_scan_body(const Pack &k, const flo
 			grad_alphas[i] = (counts && !ct.cut) ? __fmaf_rn(gw, ct.Tin, -accum) / fmaxf(1.0f - a, 1e-10f) : 0.0f;
 			if (grad_t) grad_t[i] = cg.cd * w;
 			if (RGB && grad_rgb) { grad_rgb[3 * i] = w * cg.g0; grad_rgb[3 * i + 1] = w * cg.g1; grad_rgb[3 * i + 2] = w * cg.g2; }
+			nrm_store_grad<NRM>(nb, ng, i, w);
 		}
 	}
 	if (ambiguous)
-		composite_bwd_serial<RGB>(k, alphas, vw, ts, rgb, ray_index, eps, thre, normalize, mask, depth, g_mask, g_depth, g_rgb, g_vw,
-		                          grad_alphas, grad_t, grad_rgb);
+		composite_bwd_serial<RGB, NRM>(k, alphas, vw, ts, rgb, ray_index, eps, thre, normalize, mask, depth, g_mask, g_depth, g_rgb, g_vw,
+		                               grad_alphas, grad_t, grad_rgb, nb);
 }
 
 
@@ -1716,6 +1764,78 @@ int launch_composite_rays_bwd(uint32_t n_rays, const int32_t *packed_info, const
 		hipLaunchKernelGGL(k_composite_rays_bwd<false>, grid_for(n_rays), dim3(kBlock), 0, st, n_rays, packed_info, alphas, vw, ts, rgb, eps,
 		                   thre, normalize, mask, depth, g_mask, g_depth, g_rgb, grad_alphas, grad_t, grad_rgb, sigma, delta, sigma_rows,
 		                   grad_sigma);
+	NR3D_LAUNCH_CHECK();
+	return 0;
+}
+
+// ---- NeuS: the packed composite with the samples' normals (nr3d_neus_composite_fwd / _bwd, packs with nablas; the entries and the rows'
+// kernels are in neus_composite.hip).  The bodies above with NRM = true: SCAN = the prefix-product body with its serial replay of ambiguous
+// packs, else the serial body (NR3D_OPT_PACK_SCAN = 0: wave per pack at every pack count, there is no lane-per-pack form with normals).
+template <bool RGB, bool SCAN>
+__global__ __launch_bounds__(kBlock) void k_neus_composite_fwd(uint32_t P, const float *__restrict__ alphas, const float *__restrict__ ts,
+                                                               const float *__restrict__ rgb, float *nablas, int normals_mode,
+                                                               const int64_t *__restrict__ pi, const int64_t *__restrict__ ray_index,
+                                                               float eps, float thre, int normalize, float *__restrict__ vw,
+                                                               float *__restrict__ mask, float *__restrict__ depth,
+                                                               float *__restrict__ rgb_out, float *__restrict__ normals_out) {
+	const Pack k = my_pack(P, pi);
+	if (!k.valid) return;
+	const NrmFwd nf = {nablas, normals_mode, normals_out};
+	if (SCAN)
+		composite_fwd_scan_body<RGB, false, true>(k, const_cast<float *>(alphas), nullptr, nullptr, 0, ts, rgb, ray_index, eps, thre, normalize,
+		                                          vw, mask, depth, rgb_out, nf);
+	else
+		composite_fwd_serial<RGB, true>(k, alphas, ts, rgb, ray_index, eps, thre, normalize, vw, mask, depth, rgb_out, nf);
+}
+
+template <bool RGB, bool SCAN>
+__global__ __launch_bounds__(kBlock) void k_neus_composite_bwd(uint32_t P, const float *__restrict__ alphas, const float *__restrict__ vw,
+                                                               const float *__restrict__ ts, const float *__restrict__ rgb,
+                                                               const float *__restrict__ nablas, const int64_t *__restrict__ pi,
+                                                               const int64_t *__restrict__ ray_index, float eps, float thre, int normalize,
+                                                               const float *__restrict__ mask, const float *__restrict__ depth,
+                                                               const float *__restrict__ g_mask, const float *__restrict__ g_depth,
+                                                               const float *__restrict__ g_rgb, const float *__restrict__ g_normals,
+                                                               const float *__restrict__ g_vw, float *__restrict__ grad_alphas,
+                                                               float *__restrict__ grad_t, float *__restrict__ grad_rgb,
+                                                               float *__restrict__ grad_nablas) {
+	const Pack k = my_pack(P, pi);
+	if (!k.valid) return;
+	const NrmBwd nb = {nablas, g_normals, grad_nablas};
+	if (SCAN)
+		composite_bwd_scan_body<RGB, true>(k, alphas, vw, ts, rgb, ray_index, eps, thre, normalize, mask, depth, g_mask, g_depth, g_rgb, g_vw,
+		                                   grad_alphas, grad_t, grad_rgb, nb);
+	else
+		composite_bwd_serial<RGB, true>(k, alphas, vw, ts, rgb, ray_index, eps, thre, normalize, mask, depth, g_mask, g_depth, g_rgb, g_vw,
+		                                grad_alphas, grad_t, grad_rgb, nb);
+}
+
+int launch_neus_composite_packs_fwd(uint32_t P, const float *alphas, const float *ts, const float *rgb, float *nablas, int normals_mode,
+                                    const int64_t *pack_infos, const int64_t *ray_index, float eps, float thre, int normalize, float *vw,
+                                    float *mask, float *depth, float *rgb_out, float *normals_out, hipStream_t st) {
+	if (P == 0) return 0;
+	prof::Scope ps(NR3D_PROF_COMPOSITE_FWD, st);
+#define NR3D_NCOMP_FWD(K) hipLaunchKernelGGL(K, grid_for(P), dim3(kBlock), 0, st, P, alphas, ts, rgb, nablas, normals_mode, pack_infos, \
+	ray_index, eps, thre, normalize, vw, mask, depth, rgb_out, normals_out)
+	if (composite_scan()) { if (rgb) NR3D_NCOMP_FWD((k_neus_composite_fwd<true, true>)); else NR3D_NCOMP_FWD((k_neus_composite_fwd<false, true>)); }
+	else { if (rgb) NR3D_NCOMP_FWD((k_neus_composite_fwd<true, false>)); else NR3D_NCOMP_FWD((k_neus_composite_fwd<false, false>)); }
+#undef NR3D_NCOMP_FWD
+	NR3D_LAUNCH_CHECK();
+	return 0;
+}
+
+int launch_neus_composite_packs_bwd(uint32_t P, const float *alphas, const float *vw, const float *ts, const float *rgb, const float *nablas,
+                                    const int64_t *pack_infos, const int64_t *ray_index, float eps, float thre, int normalize,
+                                    const float *mask, const float *depth, const float *g_mask, const float *g_depth, const float *g_rgb,
+                                    const float *g_normals, const float *g_vw, float *grad_alphas, float *grad_t, float *grad_rgb,
+                                    float *grad_nablas, hipStream_t st) {
+	if (P == 0) return 0;
+	prof::Scope ps(NR3D_PROF_COMPOSITE_BWD, st);
+#define NR3D_NCOMP_BWD(K) hipLaunchKernelGGL(K, grid_for(P), dim3(kBlock), 0, st, P, alphas, vw, ts, rgb, nablas, pack_infos, ray_index, \
+	eps, thre, normalize, mask, depth, g_mask, g_depth, g_rgb, g_normals, g_vw, grad_alphas, grad_t, grad_rgb, grad_nablas)
+	if (composite_scan()) { if (rgb) NR3D_NCOMP_BWD((k_neus_composite_bwd<true, true>)); else NR3D_NCOMP_BWD((k_neus_composite_bwd<false, true>)); }
+	else { if (rgb) NR3D_NCOMP_BWD((k_neus_composite_bwd<true, false>)); else NR3D_NCOMP_BWD((k_neus_composite_bwd<false, false>)); }
+#undef NR3D_NCOMP_BWD
 	NR3D_LAUNCH_CHECK();
 	return 0;
 }

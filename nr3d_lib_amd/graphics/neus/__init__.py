@@ -1,2 +1,3 @@
 from .neus_utils import *
 from .neus_ray_query import *
+from .neus_render import *
