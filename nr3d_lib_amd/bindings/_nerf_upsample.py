@@ -9,6 +9,7 @@ A CPU tensor raises RuntimeError; there is no fallback here."""
 import torch
 
 from .. import _hip as H
+from ._args import chk, same_device, u_rows
 
 __all__ = ["LDS_ROW", "merge_rows_packs", "upsample_stage_packed"]
 
@@ -21,25 +22,6 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-def _chk(name, t, shape, fn, dtype=torch.float32):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"{fn}: `{name}` must be a tensor, got {type(t).__name__}")
-    H.require_gpu(t)
-    if t.dtype != dtype:
-        raise RuntimeError(f"{fn}: `{name}` must be {str(dtype).split('.')[-1]}, got {t.dtype}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{fn}: `{name}` must be {list(shape)}, got {list(t.shape)}")
-    if not t.is_contiguous():
-        raise RuntimeError(f"{fn}: `{name}` must be contiguous")
-    return t
-
-
-def _same_device(fn, dev, first, **tensors):
-    for name, t in tensors.items():
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"{fn}: `{name}` is on {t.device}, {first} on {dev}")
-
-
 def merge_rows_packs(coarse, depth, pack_infos_all, rays_o, rays_d):
     """coarse float32 [R, nc] (non-decreasing per row, nc >= 1); depth float32 [N], the marched depths (non-decreasing inside a pack);
     pack_infos_all int64 [R, 2] = (first, len), the marched pack of EVERY ray in ray order: len 0 for a ray the marcher missed,
@@ -50,19 +32,19 @@ def merge_rows_packs(coarse, depth, pack_infos_all, rays_o, rays_d):
     Every output equals the op chain's (``merge_two_packs_sorted_a_includes_b`` -> index-puts -> addcmul -> ``packed_diff``) bit for
     bit.  Packs of any length are served: those with nc + len <= LDS_ROW in LDS, longer ones on global memory."""
     fn = "merge_rows_packs"
-    _chk("coarse", coarse, None, fn)
+    chk(fn, "coarse", coarse)
     if coarse.dim() != 2 or coarse.shape[1] < 1:
         raise RuntimeError(f"{fn}: `coarse` must be [R, nc] with nc >= 1, got {list(coarse.shape)}")
     R, nc = coarse.shape
-    _chk("depth", depth, None, fn)
+    chk(fn, "depth", depth)
     if depth.dim() != 1:
         raise RuntimeError(f"{fn}: `depth` must be [N], got {list(depth.shape)}")
     N = depth.shape[0]
-    _chk("pack_infos_all", pack_infos_all, (R, 2), fn, torch.int64)
-    _chk("rays_o", rays_o, (R, 3), fn)
-    _chk("rays_d", rays_d, (R, 3), fn)
+    chk(fn, "pack_infos_all", pack_infos_all, (R, 2), torch.int64)
+    chk(fn, "rays_o", rays_o, (R, 3))
+    chk(fn, "rays_d", rays_d, (R, 3))
     dev = coarse.device
-    _same_device(fn, dev, "coarse", depth=depth, pack_infos_all=pack_infos_all, rays_o=rays_o, rays_d=rays_d)
+    same_device(fn, dev, "coarse", depth=depth, pack_infos_all=pack_infos_all, rays_o=rays_o, rays_d=rays_d)
     total = R * nc + N
     if total >= 2 ** 31:
         raise RuntimeError(f"{fn}: R nc + N = {total}, the merged buffer holds at most 2^31 - 1 elements (split the batch)")
@@ -96,40 +78,34 @@ def upsample_stage_packed(depth, sigma, delta, pack_infos, u, coarse=None, coars
     column 0); without: merged [P, m - 1] = fine[:, :-1] + deltas and deltas [P, m - 1] = fine.diff(dim=-1)).
     Packs of any length are served: those with len + m + nc <= LDS_ROW in LDS, longer ones on global memory."""
     fn = "upsample_stage_packed"
-    _chk("depth", depth, None, fn)
+    chk(fn, "depth", depth)
     if depth.dim() != 1:
         raise RuntimeError(f"{fn}: `depth` must be [N], got {list(depth.shape)}")
     N = depth.shape[0]
-    _chk("sigma", sigma, (N,), fn)
-    _chk("delta", delta, (N,), fn)
-    _chk("pack_infos", pack_infos, None, fn, torch.int64)
+    chk(fn, "sigma", sigma, (N,))
+    chk(fn, "delta", delta, (N,))
+    chk(fn, "pack_infos", pack_infos, None, torch.int64)
     if pack_infos.dim() != 2 or pack_infos.shape[1] != 2:
         raise RuntimeError(f"{fn}: `pack_infos` must be [P, 2], got {list(pack_infos.shape)}")
     P = pack_infos.shape[0]
-    _chk("u", u, None, fn)
-    if u.dim() == 1 and u.shape[0] >= 1:
-        m, u_stride = u.shape[0], 0
-    elif u.dim() == 2 and u.shape[0] == P and u.shape[1] >= 1:
-        m, u_stride = u.shape[1], u.shape[1]
-    else:
-        raise RuntimeError(f"{fn}: `u` must be [m] or [{P}, m] with m >= 1, got {list(u.shape)}")
+    m, u_stride = u_rows(fn, u, P)
     nc = n_rows = 0
     if coarse is None:
         if coarse_row is not None:
             raise RuntimeError(f"{fn}: `coarse_row` without `coarse`")
     else:
-        _chk("coarse", coarse, None, fn)
+        chk(fn, "coarse", coarse)
         if coarse.dim() != 2 or coarse.shape[1] < 1:
             raise RuntimeError(f"{fn}: `coarse` must be [Rc, nc] with nc >= 1, got {list(coarse.shape)}")
         n_rows, nc = coarse.shape
         if coarse_row is not None:
-            _chk("coarse_row", coarse_row, (P,), fn, torch.int64)
+            chk(fn, "coarse_row", coarse_row, (P,), torch.int64)
         elif n_rows != P:
             raise RuntimeError(f"{fn}: `coarse` must be [{P}, nc] without `coarse_row`, got {list(coarse.shape)}")
         if P and n_rows == 0:
             raise RuntimeError(f"{fn}: `coarse` has no rows for {P} packs")
     dev = depth.device
-    _same_device(fn, dev, "depth", sigma=sigma, delta=delta, pack_infos=pack_infos, u=u, coarse=coarse, coarse_row=coarse_row)
+    same_device(fn, dev, "depth", sigma=sigma, delta=delta, pack_infos=pack_infos, u=u, coarse=coarse, coarse_row=coarse_row)
     if N >= 2 ** 31 or P * (m + nc) >= 2 ** 31:
         raise RuntimeError(f"{fn}: N = {N}, P (m + nc) = {P * (m + nc)}: at most 2^31 - 1 elements each (split the batch)")
     width = nc + m if nc else m - 1

@@ -8,6 +8,7 @@ A CPU tensor raises RuntimeError; there is no fallback here."""
 import torch
 
 from .. import _hip as H
+from ._args import chk, same_device
 
 __all__ = ["PACKED", "ROWS", "APPEND_NONE", "APPEND_ONE", "APPEND_SDF", "sdf_to_alpha_forward", "sdf_to_alpha_backward"]
 
@@ -15,26 +16,11 @@ PACKED, ROWS = 0, 1                              # NR3D_NEUS_ALPHA_PACKED / _ROW
 APPEND_NONE, APPEND_ONE, APPEND_SDF = 0, 1, 2    # NR3D_NEUS_ALPHA_APPEND_*
 
 
-def _chk(fn, name, t, dtype=torch.float32, shape=None, dev=None):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"{fn}: `{name}` must be a tensor, got {type(t).__name__}")
-    H.require_gpu(t)
-    if t.dtype != dtype:
-        raise RuntimeError(f"{fn}: `{name}` must be {str(dtype).split('.')[-1]}, got {t.dtype}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{fn}: `{name}` must be {list(shape)}, got {list(t.shape)}")
-    if not t.is_contiguous():
-        raise RuntimeError(f"{fn}: `{name}` must be contiguous")
-    if dev is not None and t.device != dev:
-        raise RuntimeError(f"{fn}: `{name}` is on {t.device}, sdf on {dev}")
-    return t
-
-
 class _Call:
     """the arguments both directions share, checked: layout, sizes, append mode, inv_s as (value, device tensor | None)"""
 
     def __init__(self, fn, sdf, inv_s, pack_infos, append_cdf_1, pack_sdf_appends):
-        _chk(fn, "sdf", sdf)
+        chk(fn, "sdf", sdf)
         self.dev = dev = sdf.device
         if pack_infos is None:
             if sdf.dim() < 1 or sdf.shape[-1] < 1:
@@ -49,7 +35,8 @@ class _Call:
         else:
             if sdf.dim() != 1:
                 raise RuntimeError(f"{fn}: packed `sdf` must be [S], got {list(sdf.shape)}")
-            _chk(fn, "pack_infos", pack_infos, torch.int64, dev=dev)
+            chk(fn, "pack_infos", pack_infos, None, torch.int64)
+            same_device(fn, dev, "sdf", pack_infos=pack_infos)
             if pack_infos.dim() != 2 or pack_infos.shape[1] != 2:
                 raise RuntimeError(f"{fn}: `pack_infos` must be [P, 2], got {list(pack_infos.shape)}")
             self.layout, self.n = PACKED, 0
@@ -62,13 +49,15 @@ class _Call:
             self.mode = APPEND_ONE                 # as the chain: append_cdf_1 overrides the appends
             pack_sdf_appends = None
         elif pack_sdf_appends is not None:
-            _chk(fn, "pack_sdf_appends", pack_sdf_appends, shape=(self.P,), dev=dev)
+            chk(fn, "pack_sdf_appends", pack_sdf_appends, (self.P,))
+            same_device(fn, dev, "sdf", pack_sdf_appends=pack_sdf_appends)
             self.mode = APPEND_SDF
         else:
             self.mode = APPEND_NONE
         self.appends = pack_sdf_appends
         if isinstance(inv_s, torch.Tensor):
-            _chk(fn, "inv_s", inv_s, dev=dev)
+            chk(fn, "inv_s", inv_s)
+            same_device(fn, dev, "sdf", inv_s=inv_s)
             if inv_s.numel() != 1:
                 raise RuntimeError(f"{fn}: `inv_s` must hold one element, got {list(inv_s.shape)}")
             self.inv_s, self.inv_s_dev = 0.0, inv_s
@@ -110,7 +99,8 @@ def sdf_to_alpha_backward(sdf, inv_s, grad_alpha, pack_infos=None, append_cdf_1=
     after run."""
     fn = "sdf_to_alpha_backward"
     c = _Call(fn, sdf, inv_s, pack_infos, append_cdf_1, pack_sdf_appends)
-    _chk(fn, "grad_alpha", grad_alpha, shape=c.out_shape, dev=c.dev)
+    chk(fn, "grad_alpha", grad_alpha, c.out_shape)
+    same_device(fn, c.dev, "sdf", grad_alpha=grad_alpha)
     g_app = H.empty((c.P,), dtype=torch.float32, device=c.dev) if c.mode == APPEND_SDF else None
     if c.S == 0 or (c.layout == PACKED and c.P == 0) or grad_alpha.numel() == 0:      # no interval anywhere: nothing to launch
         return (torch.zeros_like(sdf), None if g_app is None else g_app.zero_(),

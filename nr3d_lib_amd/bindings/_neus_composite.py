@@ -8,6 +8,7 @@ A CPU tensor raises RuntimeError; there is no fallback here."""
 import torch
 
 from .. import _hip as H
+from ._args import chk, same_device
 
 __all__ = ["ROWS", "PACKED", "NORMALS_RAW", "NORMALS_UNIT", "neus_composite_forward", "neus_composite_backward"]
 
@@ -15,19 +16,9 @@ ROWS, PACKED = 0, 1                     # NR3D_NEUS_COMPOSITE_ROWS / _PACKED
 NORMALS_RAW, NORMALS_UNIT = 0, 1        # normals_mode: sum w nablas | sum w normalize(clamp(nablas, -1, 1)), nablas clamped in place
 
 
-def _chk(fn, name, t, shape, dtype=torch.float32, dev=None):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"{fn}: `{name}` must be a tensor, got {type(t).__name__}")
-    H.require_gpu(t)
-    if t.dtype != dtype:
-        raise RuntimeError(f"{fn}: `{name}` must be {str(dtype).split('.')[-1]}, got {t.dtype}")
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{fn}: `{name}` must be {list(shape)}, got {list(t.shape)}")
-    if not t.is_contiguous():
-        raise RuntimeError(f"{fn}: `{name}` must be contiguous")
-    if dev is not None and t.device != dev:
-        raise RuntimeError(f"{fn}: `{name}` is on {t.device}, alphas on {dev}")
-    return t
+def _on(fn, dev, name, t, shape, dtype=torch.float32):
+    chk(fn, name, t, shape, dtype)
+    same_device(fn, dev, "alphas", **{name: t})
 
 
 class _Call:
@@ -46,21 +37,21 @@ class _Call:
                 raise RuntimeError(f"{fn}: packed `alphas` must be [S], got {list(alphas.shape)}")
             self.layout, self.P, self.n = PACKED, pack_infos.shape[0] if pack_infos.dim() else -1, 0
         self.shape, self.S = tuple(alphas.shape), alphas.numel()
-        _chk(fn, "alphas", alphas, self.shape)
+        chk(fn, "alphas", alphas, self.shape)
         self.dev = dev = alphas.device
         if pack_infos is not None:
-            _chk(fn, "pack_infos", pack_infos, (max(self.P, 0), 2), torch.int64, dev)
-        _chk(fn, "t", t, self.shape, dev=dev)
+            _on(fn, dev, "pack_infos", pack_infos, (max(self.P, 0), 2), torch.int64)
+        _on(fn, dev, "t", t, self.shape)
         if rgb is not None:
-            _chk(fn, "rgb", rgb, (*self.shape, 3), dev=dev)
+            _on(fn, dev, "rgb", rgb, (*self.shape, 3))
         if nablas is not None:
-            _chk(fn, "nablas", nablas, (*self.shape, 3), dev=dev)
+            _on(fn, dev, "nablas", nablas, (*self.shape, 3))
         if self.S >= 2 ** 32 or self.P >= 2 ** 32:
             raise RuntimeError(f"{fn}: {self.S} samples in {self.P} packs or rows, the limit is 2^32 - 1 each (split the batch)")
         if normals_mode not in (NORMALS_RAW, NORMALS_UNIT):
             raise RuntimeError(f"{fn}: normals_mode = {normals_mode!r}, must be 0 (raw) or 1 (clamped and normalised)")
         if rays_inds_hit is not None:
-            _chk(fn, "rays_inds_hit", rays_inds_hit, (self.P,), torch.int64, dev)
+            _on(fn, dev, "rays_inds_hit", rays_inds_hit, (self.P,), torch.int64)
             self.num_rays = int(num_rays)
         else:
             if num_rays is not None and int(num_rays) != self.P:
@@ -117,11 +108,11 @@ def neus_composite_backward(alphas, t, rgb, nablas, pack_infos, rays_inds_hit, e
     c = _Call(fn, alphas, t, rgb, nablas, pack_infos, rays_inds_hit, mask.shape[0] if isinstance(mask, torch.Tensor) else None,
               early_stop_eps, alpha_thre, normalize_depth, normals_mode)
     nr, dev = c.num_rays, c.dev
-    _chk(fn, "vw", vw, c.shape, dev=dev)
+    _on(fn, dev, "vw", vw, c.shape)
     for name, g, shape in (("mask", mask, (nr,)), ("depth", depth, (nr,)), ("g_mask", g_mask, (nr,)), ("g_depth", g_depth, (nr,)),
                            ("g_rgb", g_rgb, (nr, 3)), ("g_normals", g_normals, (nr, 3)), ("g_vw", g_vw, c.shape)):
         if g is not None or name in ("mask", "depth"):
-            _chk(fn, name, g, shape, dev=dev)
+            _on(fn, dev, name, g, shape)
     with H.on_device(dev):
         ga = c.per_sample(None, packs_tile)
         gt = c.per_sample(None, packs_tile) if need_t else None

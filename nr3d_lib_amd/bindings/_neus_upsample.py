@@ -9,6 +9,7 @@ A CPU tensor raises RuntimeError; there is no fallback here."""
 import torch
 
 from .. import _hip as H
+from ._args import chk, same_device, u_rows
 
 __all__ = ["MAX_ROW", "PACKED_LDS_ROW", "upsample_stage", "upsample_stage_packed"]
 
@@ -22,19 +23,6 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-def _chk(name, t, shape, fn="upsample_stage", dtype=torch.float32):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"{fn}: `{name}` must be a tensor, got {type(t).__name__}")
-    H.require_gpu(t)
-    if t.dtype != dtype:
-        raise RuntimeError(f"{fn}: `{name}` must be {str(dtype).split('.')[-1]}, got {t.dtype}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{fn}: `{name}` must be {list(shape)}, got {list(t.shape)}")
-    if not t.is_contiguous():
-        raise RuntimeError(f"{fn}: `{name}` must be contiguous")
-    return t
-
-
 def upsample_stage(depth, sdf, u, inv_s, use_estimate):
     """depth, sdf float32 [R, n] (depth non-decreasing per row, n >= 2); u float32 [m] (one row of CDF positions for every ray) or
     [R, m] (per ray), non-decreasing, m >= 1; n + m <= MAX_ROW.
@@ -42,22 +30,14 @@ def upsample_stage(depth, sdf, u, inv_s, use_estimate):
     fine; order int32 [R, n + m]: merged == cat([depth, fine], -1).gather(-1, order), depth elements first on equal values).
     ``use_estimate``: the NeuS paper's slope estimate (neus_ray_sdf_to_upsample_alpha) instead of neus_ray_sdf_to_alpha."""
     fn = "upsample_stage"
-    _chk("depth", depth, None)
+    chk(fn, "depth", depth)
     if depth.dim() != 2 or depth.shape[1] < 2:
         raise RuntimeError(f"{fn}: `depth` must be [R, n] with n >= 2, got {list(depth.shape)}")
     R, n = depth.shape
-    _chk("sdf", sdf, (R, n))
-    _chk("u", u, None)
-    if u.dim() == 1 and u.shape[0] >= 1:
-        m, u_stride = u.shape[0], 0
-    elif u.dim() == 2 and u.shape[0] == R and u.shape[1] >= 1:
-        m, u_stride = u.shape[1], u.shape[1]
-    else:
-        raise RuntimeError(f"{fn}: `u` must be [m] or [{R}, m] with m >= 1, got {list(u.shape)}")
+    chk(fn, "sdf", sdf, (R, n))
+    m, u_stride = u_rows(fn, u, R)
     dev = depth.device
-    for name, t in (("sdf", sdf), ("u", u)):
-        if t.device != dev:
-            raise RuntimeError(f"{fn}: `{name}` is on {t.device}, depth on {dev}")
+    same_device(fn, dev, "depth", sdf=sdf, u=u)
     max_row = __getattr__("MAX_ROW")
     if n + m > max_row:
         raise RuntimeError(f"{fn}: n + m = {n + m}, rows of at most MAX_ROW = {max_row} are served")
@@ -91,26 +71,18 @@ def upsample_stage_packed(depth, sdf, pack_infos, u, inv_s, use_estimate, merge=
     ``merge=False`` returns None for the last four (and needs no ``need_sdf``), ``need_sdf=False`` None for sdf_merged.
     Packs of any length are served: those with len + m <= PACKED_LDS_ROW in LDS, longer ones on global memory."""
     fn = "upsample_stage_packed"
-    _chk("depth", depth, None, fn)
+    chk(fn, "depth", depth)
     if depth.dim() != 1:
         raise RuntimeError(f"{fn}: `depth` must be [N], got {list(depth.shape)}")
     N = depth.shape[0]
-    _chk("sdf", sdf, (N,), fn)
-    _chk("pack_infos", pack_infos, None, fn, torch.int64)
+    chk(fn, "sdf", sdf, (N,))
+    chk(fn, "pack_infos", pack_infos, None, torch.int64)
     if pack_infos.dim() != 2 or pack_infos.shape[1] != 2:
         raise RuntimeError(f"{fn}: `pack_infos` must be [P, 2], got {list(pack_infos.shape)}")
     P = pack_infos.shape[0]
-    _chk("u", u, None, fn)
-    if u.dim() == 1 and u.shape[0] >= 1:
-        m, u_stride = u.shape[0], 0
-    elif u.dim() == 2 and u.shape[0] == P and u.shape[1] >= 1:
-        m, u_stride = u.shape[1], u.shape[1]
-    else:
-        raise RuntimeError(f"{fn}: `u` must be [m] or [{P}, m] with m >= 1, got {list(u.shape)}")
+    m, u_stride = u_rows(fn, u, P)
     dev = depth.device
-    for name, t in (("sdf", sdf), ("pack_infos", pack_infos), ("u", u)):
-        if t.device != dev:
-            raise RuntimeError(f"{fn}: `{name}` is on {t.device}, depth on {dev}")
+    same_device(fn, dev, "depth", sdf=sdf, pack_infos=pack_infos, u=u)
     if N + P * m >= 2 ** 31:
         raise RuntimeError(f"{fn}: N + P m = {N + P * m}, the merged buffer holds at most 2^31 - 1 elements (split the batch)")
     need_sdf = bool(merge and need_sdf)

@@ -4,11 +4,11 @@
 // The reference runs both between two density queries as chains of small torch ops (nr3d_lib/graphics/nerf/nerf_ray_query.py:289-302:
 // merge_two_packs_sorted_a_includes_b, four index-puts, addcmul, packed_diff; :332-360: tau_to_alpha, packed_cumsum, a gather,
 // packed_div, packed_sample_cdf, a second merge with its sort, four more index-puts, packed_diff) on packs of a few dozen to a few
-// hundred floats.  Here, as in neus_upsample.hip, one 64-lane wave owns one ray or pack: short rows are staged in LDS, sums and maxima
-// are wave scans over 64-element chunks with a carry, the inverse CDF is a binary search, and -- both lists being sorted -- a union is
-// a merge-path search per output slot instead of a sort.  No atomics, no workgroup barrier, no host wait; every output element is
-// written exactly once by a fixed lane in a fixed order, so the result is the same bits run after run.
+// hundred floats.  Here one 64-lane wave owns one ray or pack, with the building blocks of wave_row.h; short rows are staged in LDS,
+// longer ones stay in global memory.  No host wait; every output element is written exactly once by a fixed lane in a fixed order, so
+// the result is the same bits run after run.
 #include "common.h"
+#include "wave_row.h"
 
 namespace nr3d {
 namespace nerf_upsample {
@@ -16,45 +16,7 @@ namespace nerf_upsample {
 constexpr int kLdsRow = NR3D_NERF_UPSAMPLE_LDS_ROW;    // rows up to this are staged: kWaves * 2 L floats of LDS per workgroup, both kernels
 constexpr int kWaves = 4;                              // rays or packs per workgroup
 
-// Memory written by some lanes of the wave is read by others: order the traffic of the wave (no other wave shares these rows).  That
-// holds for the global rows of the long packs too: a wave's vector memory instructions reach its compute unit's L1 in program order,
-// the L1 is write-through and nothing else writes these rows, so a load issued after a store of the same wave returns the stored
-// value; the wavefront-scope fence keeps the compiler from moving the accesses across it.
-__device__ __forceinline__ void wave_sync() {
-	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ float wave_incl_add(float v, int lane) {
-#pragma unroll
-	for (int off = 1; off < 64; off <<= 1) {
-		const float t = __shfl_up(v, off, 64);
-		if (lane >= off) v += t;
-	}
-	return v;
-}
-__device__ __forceinline__ float wave_incl_max(float v, int lane) {
-#pragma unroll
-	for (int off = 1; off < 64; off <<= 1) {
-		const float t = __shfl_up(v, off, 64);
-		if (lane >= off) v = fmaxf(v, t);
-	}
-	return v;
-}
-
-// The sorted union of A [na] and B [nb] (both non-decreasing), an element of B BEFORE an equal one of A (k_merge of pack_ops.hip: the
-// lower bound of b among a): output slot q takes A[i] or B[q - i], i = the number of A's elements among the first q outputs.  Every
-// index is in range by construction of the search interval, whatever the values are.
-__device__ __forceinline__ float union_at(int q, int na, int nb, const float *A, const float *B) {
-	int lo = max(0, q - nb), hi = min(q, na);
-	while (lo < hi) {
-		const int mid = (lo + hi) >> 1;                        // lo <= mid < hi: mid < na, 1 <= q - mid <= nb
-		if (A[mid] < B[q - mid - 1]) lo = mid + 1; else hi = mid;
-	}
-	const int i = lo, j = q - lo;
-	const bool from_a = i < na && (j >= nb || A[i] < B[j]);
-	return from_a ? A[i] : B[j];
-}
+using namespace wave_row;    // wave_sync() and its visibility argument, the scans, running_max, merge_value (B first on ties)
 
 // ---- (a) coarse rows U marched packs -------------------------------------------------------------------------------------------------
 // A = the ray's coarse row [nc], B = its marched pack [n], M = the union [nc + n]: LDS rows (STAGED, then d_out receives a copy) or the
@@ -65,7 +27,7 @@ __device__ __forceinline__ void merge_body(int nc, int n, int lane, const float 
                                            int64_t *__restrict__ r_out, float *__restrict__ x_out) {
 	const int nm = nc + n;
 	for (int q = lane; q < nm; q += 64) {
-		const float t = union_at(q, nc, n, A, B);
+		const float t = merge_value<false>(q, nc, n, A, B);      // a marched depth before an equal coarse one
 		M[q] = t;
 		if (STAGED) d_out[q] = t;
 		r_out[q] = r;
@@ -129,7 +91,7 @@ __device__ __forceinline__ void stage_body(int n, int m, int nc, int lane, const
 	for (int b = 0; b < n; b += 64) {
 		const int i = b + lane;
 		const float alpha = i < n ? -expm1f(-(sigma[i] * delta[i])) : 0.0f;
-		const float incl = carry + wave_incl_add(alpha, lane);
+		const float incl = carry + incl_add(alpha, lane);
 		if (i < n) C[i] = incl;
 		carry = __shfl(incl, 63, 64);
 	}
@@ -138,7 +100,8 @@ __device__ __forceinline__ void stage_body(int n, int m, int nc, int lane, const
 	for (int i = lane; i < n; i += 64) C[i] = C[i] / norm;
 	wave_sync();
 
-	// ---- inverse CDF at every u_j (k_invert_cdf, pack_ops.hip) ----
+	// ---- inverse CDF at every u_j (k_invert_cdf, pack_ops.hip), raised to its running maximum: the union below needs a sorted row (the
+	// reference sorts it) ----
 	float carry_f = -INFINITY;
 	for (int b = 0; b < m; b += 64) {
 		const int j = b + lane;
@@ -160,11 +123,7 @@ __device__ __forceinline__ void stage_body(int n, int m, int nc, int lane, const
 				}
 			}
 		}
-		// d0 + t (d1 - d0) with t <= 1 can round one ulp above d1, where the next bin's samples start: the running maximum keeps the row
-		// non-decreasing, which the union below relies on (the reference sorts the row instead: the same values wherever the expression
-		// is monotone in u, which it is up to its last rounding)
-		f = fmaxf(wave_incl_max(f, lane), carry_f);
-		carry_f = __shfl(f, 63, 64);
+		f = running_max(f, lane, carry_f);
 		if (j < m) {
 			F[j] = f;
 			if (STAGED) fine_row[j] = f;
@@ -184,7 +143,7 @@ __device__ __forceinline__ void stage_body(int n, int m, int nc, int lane, const
 	// ---- the sorted union of the coarse row and the new depths, then its differences ----
 	const int nm = nc + m;
 	for (int q = lane; q < nm; q += 64) {
-		const float t = union_at(q, nc, m, K, F);
+		const float t = merge_value<false>(q, nc, m, K, F);       // a new depth before an equal coarse one
 		M[q] = t;
 		if (STAGED) m_row[q] = t;
 	}

@@ -11,7 +11,7 @@
 // ROWS follow ray_alpha_to_vw: w_i = a_i T_i, T_{i+1} = T_i (1 - a_i) over EVERY sample -- no early stop, no threshold (the chain's
 // (1 + 1e-10) - a is 1 - a in float32).  A row of n samples is the work of G = min(64, the power of two >= n) neighbouring lanes, 64 / G
 // rows per wave, so that the one-sample rows of a sphere-traced buffer fill a wave as the 128-sample rows of an up-sampled one do; rows
-// longer than 64 walk in chunks of 64 with T carried.  T is a prefix product (shuffle scan inside the G lanes).
+// longer than 64 walk in chunks of 64 with T carried.  T is a prefix product (wave_row.h's scan at width G).
 // Backward, with g_i = dL/dw_i (comp_gw of pack_ops.hip plus g_normals . nablas_i):
 //   dL/da_i = T_i (g_i - R_i),   R_i = g_{i+1} a_{i+1} + (1 - a_{i+1}) R_{i+1},   R_{n-1} = 0
 // -- the derivative of the product with the sample's own factor left out, as torch's cumprod backward gives it: no division, so a sample
@@ -23,17 +23,13 @@
 #include "common.h"
 #include "pack_launch.h"
 #include "unit_normal.h"
+#include "wave_row.h"
 
 namespace nr3d {
 namespace neus_composite {
 
 constexpr int kBlock = 256;
 
-template <int G> __device__ __forceinline__ float group_inclusive_mul(float v, int gl) {
-#pragma unroll
-	for (int off = 1; off < G; off <<= 1) { const float t = __shfl_up(v, off, G); if (gl >= off) v *= t; }
-	return v;
-}
 template <int G> __device__ __forceinline__ float group_mul(float v) {
 #pragma unroll
 	for (int off = G / 2; off >= 1; off >>= 1) v *= __shfl_xor(v, off, G);
@@ -62,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_fwd(uint32_t R, uint32_t n, con
 		const size_t i = begin + base + gl;
 		const float a = mine ? alphas[i] : 0.0f;
 		const float t = mine ? ts[i] : 0.0f;
-		const float inc = group_inclusive_mul<G>(1.0f - a, gl);
+		const float inc = wave_row::incl_mul<G>(1.0f - a, gl);
 		float exc = __shfl_up(inc, 1, G);
 		if (gl == 0) exc = 1.0f;
 		const float w = a * (Tc * exc);
@@ -141,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_bwd(uint32_t R, uint32_t n, con
 				if (g_normals) { g = __fmaf_rn(n0, nablas[3 * i], g); g = __fmaf_rn(n1, nablas[3 * i + 1], g); g = __fmaf_rn(n2, nablas[3 * i + 2], g); }
 				if (g_vw) g += g_vw[i];
 			}
-			const float inc = group_inclusive_mul<G>(1.0f - a, gl);
+			const float inc = wave_row::incl_mul<G>(1.0f - a, gl);
 			float exc = __shfl_up(inc, 1, G);
 			if (gl == 0) exc = 1.0f;
 			const float Tin = __shfl(Tstart, (int)(c - c_first), G) * exc;

@@ -3,50 +3,21 @@
 //
 // The reference runs a stage between two SDF queries as a chain of small torch ops (nr3d_lib/graphics/neus/neus_ray_query.py:258-270:
 // neus_ray_sdf_to_alpha | neus_ray_sdf_to_upsample_alpha -> ray_alpha_to_vw -> batch_sample_pdf -> cat -> sort).  Rows hold tens to a
-// few hundred floats, so launches and the sort dominate.  Here one 64-lane wave owns one ray: the row (depths, SDF, CDF, new depths)
-// is staged in LDS, products and sums are wave scans over 64-element chunks with a carry, the inverse CDF is a binary search in LDS,
-// and -- both lists being sorted -- the merge is a merge-path search per output slot instead of a sort.  No atomics, no workspace;
-// every output element is written exactly once by a fixed lane in a fixed order, so the result is the same bits run after run.
+// few hundred floats, so launches and the sort dominate.  Here one 64-lane wave owns one ray, with the building blocks of wave_row.h:
+// the row (depths, SDF, CDF, new depths) is staged in LDS.  No workspace; every output element is written exactly once by a fixed lane
+// in a fixed order, so the result is the same bits run after run.
 #include "common.h"
+#include "wave_row.h"
 
 namespace nr3d {
 namespace neus_upsample {
 
+using namespace wave_row;    // wave_sync() and its visibility argument, the scans, running_max, merge_slot
+
 constexpr int kMaxRow = NR3D_NEUS_UPSAMPLE_MAX_ROW;   // cap on n + m: 3 n + m floats of LDS per wave stay below 12 KiB
 constexpr int kWaves = 4;                              // rays per workgroup
 
-// LDS written by some lanes of the wave is read by others: order the DS traffic of the wave (no other wave shares these rows)
-__device__ __forceinline__ void wave_sync() {
-	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-}
-
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ float wave_incl_mul(float v, int lane) {
-#pragma unroll
-	for (int off = 1; off < 64; off <<= 1) {
-		const float t = __shfl_up(v, off, 64);
-		if (lane >= off) v *= t;
-	}
-	return v;
-}
-__device__ __forceinline__ float wave_incl_add(float v, int lane) {
-#pragma unroll
-	for (int off = 1; off < 64; off <<= 1) {
-		const float t = __shfl_up(v, off, 64);
-		if (lane >= off) v += t;
-	}
-	return v;
-}
-__device__ __forceinline__ float wave_incl_max(float v, int lane) {
-#pragma unroll
-	for (int off = 1; off < 64; off <<= 1) {
-		const float t = __shfl_up(v, off, 64);
-		if (lane >= off) v = fmaxf(v, t);
-	}
-	return v;
-}
 
 template <bool ESTIMATE>
 __global__ __launch_bounds__(kWaves * 64) void k_stage(uint32_t R, int n, int m, const float *__restrict__ depth,
@@ -89,12 +60,12 @@ __global__ __launch_bounds__(kWaves * 64) void k_stage(uint32_t R, int n, int m,
 			alpha = fmaxf((c_prev - c_next) / (c_prev + 1e-5f), 0.0f);
 		}
 		// (1 + 1e-10) - alpha in fp32 is 1 - alpha; lanes past the row multiply by 1
-		const float incl = wave_incl_mul(1.0f - alpha, lane);
+		const float incl = incl_mul(1.0f - alpha, lane);
 		float excl = __shfl_up(incl, 1, 64);
 		if (lane == 0) excl = 1.0f;
 		const float w = alpha * (carry_T * excl);
 		carry_T *= __shfl(incl, 63, 64);
-		total += __shfl(wave_incl_add(w, lane), 63, 64);
+		total += __shfl(incl_add(w, lane), 63, 64);
 		if (i < n) C[i] = w;
 	}
 	wave_sync();
@@ -105,7 +76,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_stage(uint32_t R, int n, int m,
 	for (int b = 0; b < n; b += 64) {
 		const int i = b + lane;
 		const float pdf = i < n ? C[i] / norm : 0.0f;
-		const float incl = wave_incl_add(pdf, lane);
+		const float incl = incl_add(pdf, lane);
 		float before = __shfl_up(incl, 1, 64);
 		if (i < n) C[i] = lane == 0 ? carry_c : carry_c + before;      // the inclusive sum up to interval i - 1
 		carry_c += __shfl(incl, 63, 64);
@@ -130,10 +101,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_stage(uint32_t R, int n, int m,
 			if (den < 1e-5f) den = 1.0f;
 			f = d0 + (uj - c0) / den * (D[above] - d0);
 		}
-		// d0 + t (d1 - d0) with t <= 1 can round one ulp above d1, where the next interval's samples start: a running maximum keeps the
-		// row non-decreasing, which the merge below relies on (it changes nothing wherever the formula is monotone already)
-		f = fmaxf(wave_incl_max(f, lane), carry_f);
-		carry_f = __shfl(f, 63, 64);
+		f = running_max(f, lane, carry_f);                    // the merge below needs a sorted row
 		if (j < m) {
 			F[j] = f;
 			fine[(size_t)r * m + j] = f;
@@ -141,21 +109,14 @@ __global__ __launch_bounds__(kWaves * 64) void k_stage(uint32_t R, int n, int m,
 	}
 	wave_sync();
 
-	// ---- merge path: output slot p takes D[i] or F[p - i], i = the number of depths among the first p outputs (depths first on ties);
-	// every index below is in range by construction of the search interval, whatever the values are ----
+	// ---- the sorted union of D and F, depths first on ties ----
 	const int nm = n + m;
 	float *m_row = merged + (size_t)r * nm;
 	int32_t *o_row = order + (size_t)r * nm;
 	for (int p = lane; p < nm; p += 64) {
-		int lo = max(0, p - m), hi = min(p, n);
-		while (lo < hi) {
-			const int mid = (lo + hi) >> 1;                    // lo <= mid < hi: mid < n, 1 <= p - mid <= m
-			if (D[mid] <= F[p - mid - 1]) lo = mid + 1; else hi = mid;
-		}
-		const int i = lo, j = p - lo;
-		const bool from_depth = i < n && (j >= m || D[i] <= F[j]);
-		m_row[p] = from_depth ? D[i] : F[j];
-		o_row[p] = from_depth ? i : n + j;
+		const Slot s = merge_slot<true>(p, n, m, D, F);
+		m_row[p] = s.from_a ? D[s.i] : F[s.j];
+		o_row[p] = s.from_a ? s.i : n + s.j;
 	}
 }
 
@@ -169,11 +130,7 @@ constexpr int kPackedLdsRow = NR3D_NEUS_UPSAMPLE_PACKED_LDS_ROW;   // packs with
 
 // The body over the pack's four arrays: D, S = depths and SDF [n], C = the CDF [n], F = the new depths [m].  Called once with LDS
 // pointers and once with global ones; inlined, each call resolves to DS or global instructions.  Only this wave touches these rows, in
-// both address spaces: what its lanes store is read back by other lanes of the same wave after wave_sync().  That is enough for the
-// global arrays too: a wave's vector memory instructions reach its compute unit's L1 in program order, the L1 is write-through and
-// shared by nothing that writes these rows, so a load issued after a store of the same wave returns the stored value; the
-// wavefront-scope fence keeps the compiler from moving the accesses across it, and no wider scope is needed because no other wave,
-// workgroup or atomic is involved.
+// both address spaces, which is what wave_sync() needs (wave_row.h).
 template <bool ESTIMATE, bool STAGED>
 __device__ __forceinline__ void packed_body(int n, int m, int lane, const float *D, const float *S, float *C, float *F,
                                             const float *__restrict__ u_row, float inv_s, float *__restrict__ fine_row, bool merge,
@@ -204,7 +161,7 @@ __device__ __forceinline__ void packed_body(int n, int m, int lane, const float 
 		}
 		// packed_alpha_to_vw(early_stop_eps = 1e-4, alpha_thre = 0): an alpha <= 0 leaves T as it is; w = alpha T while T >= 1e-4 and
 		// 0 from the first T below on (decided on the scanned T: the product associates as a tree)
-		const float incl = wave_incl_mul(alpha <= 0.0f ? 1.0f : 1.0f - alpha, lane);
+		const float incl = incl_mul(alpha <= 0.0f ? 1.0f : 1.0f - alpha, lane);
 		float excl = __shfl_up(incl, 1, 64);
 		if (lane == 0) excl = 1.0f;
 		const float T = carry_T * excl;
@@ -213,7 +170,7 @@ __device__ __forceinline__ void packed_body(int n, int m, int lane, const float 
 		const float w = (stopped || lane >= first) ? 0.0f : alpha * T;
 		stopped = stopped || below != 0ull;
 		carry_T *= __shfl(incl, 63, 64);
-		const float incl_w = carry_c + wave_incl_add(w, lane);
+		const float incl_w = carry_c + incl_add(w, lane);
 		const float before_w = __shfl_up(incl_w, 1, 64);
 		if (i < n) C[i] = lane == 0 ? carry_c : before_w;
 		carry_c = __shfl(incl_w, 63, 64);
@@ -226,7 +183,7 @@ __device__ __forceinline__ void packed_body(int n, int m, int lane, const float 
 	for (int i = lane; i < n; i += 64) C[i] = C[i] / norm;
 	wave_sync();
 
-	// ---- inverse CDF at every u_j (k_invert_cdf, pack_ops.hip) ----
+	// ---- inverse CDF at every u_j, raised to its running maximum: the merge needs a sorted row ----
 	float carry_f = -INFINITY;
 	for (int b = 0; b < m; b += 64) {
 		const int j = b + lane;
@@ -234,8 +191,10 @@ __device__ __forceinline__ void packed_body(int n, int m, int lane, const float 
 		if (j < m) {
 			f = 0.0f;                                         // a pack without elements (outside the contract) has nothing to read
 			if (n > 0) {
+				// packed_invert_cdf's rule (k_invert_cdf, pack_ops.hip).  Written out on purpose: behind a shared function this kernel measured
+				// 0.2 - 0.5 % slower at 65 536 packs, and nerf_upsample.hip's stage likewise (profiles/wave_row.md)
 				const float uj = u_row[j];
-				int lo = 0, hi = n;                           // first k with C[k] >= uj, n when there is none
+				int lo = 0, hi = n;
 				while (lo < hi) {
 					const int mid = (lo + hi) >> 1;
 					if (C[mid] < uj) lo = mid + 1; else hi = mid;
@@ -248,10 +207,7 @@ __device__ __forceinline__ void packed_body(int n, int m, int lane, const float 
 				}
 			}
 		}
-		// as in k_stage: the running maximum keeps the new depths non-decreasing, which the merge relies on; it changes nothing
-		// wherever the expression is monotone in u already
-		f = fmaxf(wave_incl_max(f, lane), carry_f);
-		carry_f = __shfl(f, 63, 64);
+		f = running_max(f, lane, carry_f);
 		if (j < m) {
 			F[j] = f;
 			if (STAGED) fine_row[j] = f;
@@ -260,20 +216,13 @@ __device__ __forceinline__ void packed_body(int n, int m, int lane, const float 
 	if (!merge) return;
 	wave_sync();
 
-	// ---- merge path, a new depth before an equal old one (k_merge: the lower bound of the new value among the old ones): output slot
-	// q takes D[i] or F[q - i], i = the number of old depths among the first q outputs; every index is in range by construction ----
+	// ---- the sorted union of D and F, a new depth before an equal old one ----
 	const int nm = n + m;
 	for (int q = lane; q < nm; q += 64) {
-		int lo = max(0, q - m), hi = min(q, n);
-		while (lo < hi) {
-			const int mid = (lo + hi) >> 1;                    // lo <= mid < hi: mid < n, 1 <= q - mid <= m
-			if (D[mid] < F[q - mid - 1]) lo = mid + 1; else hi = mid;
-		}
-		const int i = lo, j = q - lo;
-		const bool old = i < n && (j >= m || D[i] < F[j]);
-		m_row[q] = old ? D[i] : F[j];
-		if (!old) pidx_row[j] = out_begin + q;
-		else if (s_row) s_row[q] = S[i];
+		const Slot s = merge_slot<false>(q, n, m, D, F);
+		m_row[q] = s.from_a ? D[s.i] : F[s.j];
+		if (!s.from_a) pidx_row[s.j] = out_begin + q;
+		else if (s_row) s_row[q] = S[s.i];
 	}
 }
 
@@ -289,6 +238,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_stage_packed(uint32_t P, int64_
 	const uint32_t p = blockIdx.x * kWaves + wave;
 	if (p >= P) return;                                   // wave-uniform; nothing below synchronises across waves
 	// the pack, clipped to [0, N): whatever pack_infos holds, every access below stays inside the buffers
+	// (these three lines stay written out for the same reason as the inverse CDF of packed_body)
 	const int64_t b64 = pack_infos[2 * (size_t)p], n64 = pack_infos[2 * (size_t)p + 1];
 	const int64_t first = b64 < 0 ? 0 : (b64 > N ? N : b64);
 	const int n = (int)(n64 < 0 ? 0 : (n64 > N - first ? N - first : n64));

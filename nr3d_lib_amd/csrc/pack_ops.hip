@@ -17,6 +17,7 @@
 #include "scan.h"
 #include "pack_launch.h"
 #include "unit_normal.h"
+#include "wave_row.h"
 #include <stdlib.h>
 
 namespace nr3d {
@@ -1033,30 +1034,19 @@ __global__ __launch_bounds__(kBlock) void k_composite_bwd(uint32_t P, const floa
 
 // ------------------------------------------------------------------------------------------------
 // Prefix-product forms (wave per pack, few to some thousand packs): the transmittance before sample i is the running
-// product of (1 - alpha) over the samples that count, so a 64-sample chunk needs one 6-step wave scan instead of 64
+// product of (1 - alpha) over the samples that count, so a 64-sample chunk needs one 6-step wave scan (wave_row.h) instead of 64
 // dependent broadcast-multiply steps.  The products are associated as a tree instead of left to right: T differs from the
 // serial recurrence by rounding only (<= ~n * 2^-24 relative, typically 1e-6 at 512 samples; the contract's tolerance is
 // 1e-5).  What must NOT depend on rounding is WHICH samples early_stop_eps cuts: a pack where some T lands within
 // 2e-4 * eps of the threshold is replayed with the serial kernel body (wave-uniform branch; ~1 pack in 10^4).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_inclusive_mul(float v, int lane) {
-#pragma unroll
-	for (int off = 1; off < 64; off <<= 1) { const float t = shfl_up_t<float>(v, off); if (lane >= off) v *= t; }
-	return v;
-}
-__device__ __forceinline__ float wave_inclusive_add(float v, int lane) {
-#pragma unroll
-	for (int off = 1; off < 64; off <<= 1) { const float t = shfl_up_t<float>(v, off); if (lane >= off) v += t; }
-	return v;
-}
-
 // transmittance of one chunk: `counts` = the sample multiplies T; returns T before my sample, whether my sample lies behind
 // the early stop, and flags a pack whose stop decision could hinge on rounding.  Tc / stopped carry across chunks.
 struct ChunkT { float Tin; bool cut; };
 __device__ __forceinline__ ChunkT chunk_transmittance(float a, bool mine, bool counts, float eps, int lane, float &Tc, bool &stopped,
                                                       bool &ambiguous) {
 	const float f = (mine && counts) ? (1.0f - a) : 1.0f;
-	const float inc = wave_inclusive_mul(f, lane);
+	const float inc = wave_row::incl_mul(f, lane);
 	float exc = shfl_up_t<float>(inc, 1);
 	if (lane == 0) exc = 1.0f;
 	ChunkT r;
@@ -1245,7 +1235,7 @@ __device__ __forceinline__ void composite_bwd_scan_body(const Pack &k, const flo
 		const bool counts = !(a < thre);
 		const ChunkT ct = chunk_transmittance(a, mine, counts, eps, k.lane, Tc, stopped, ambiguous);
 		const float q = gw * w;
-		const float incq = wave_inclusive_add(q, k.lane);
+		const float incq = wave_row::incl_add(q, k.lane);
 		const float accum = total - (qc + (incq - q));            // sum over the samples from mine on
 		qc += shfl_t<float>(incq, 63);
 		if (mine) {

@@ -20,6 +20,7 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from nr3d_lib_amd.bindings import _nerf_upsample
+from nr3d_lib_amd.graphics._ray_query import _chunked, _flag, _march
 from nr3d_lib_amd.graphics.nerf.nerf_utils import (packed_alpha_to_vw, packed_volume_render_compression, sigma_delta_to_alpha,
                                                     tau_to_alpha)
 from nr3d_lib_amd.graphics.pack_ops import (get_pack_infos_from_batch, get_pack_infos_from_n, merge_two_packs_sorted_a_includes_b,
@@ -110,22 +111,6 @@ def _from_spatial_order(order, net_out, n):
         else:
             out[pair[0]] = _MoveRows.apply(order, net_out[pair[0]], None, True)
     return out
-
-
-def _flag(model, name):
-    return bool(getattr(model, name, False))
-
-
-def _march(model, ray_tested, rays_o, rays_d, near, far, perturb, march_cfg):
-    """dispatch on what the accel's ray_march accepts (single / dynamic / batched / batched-dynamic accels of the
-    reference differ only in the extra per-ray arguments, nerf_ray_query.py:84-104)"""
-    accel = model.accel
-    if hasattr(accel, 'cur_batch__ray_march'):
-        extra = [ray_tested['rays_bidx']] + ([ray_tested['rays_ts']] if getattr(accel, 'is_dynamic', False) else [])
-        return accel.cur_batch__ray_march(rays_o, rays_d, *extra, near=near, far=far, perturb=perturb, **march_cfg)
-    if getattr(accel, 'is_dynamic', False):
-        return accel.ray_march(rays_o, rays_d, ray_tested['rays_ts'], near=near, far=far, perturb=perturb, **march_cfg)
-    return accel.ray_march(rays_o, rays_d, near=near, far=far, perturb=perturb, **march_cfg)
 
 
 def nerf_ray_query_march_occ(model, ray_tested: Dict[str, torch.Tensor], with_rgb: bool = True, perturb: bool = False,
@@ -250,14 +235,6 @@ FUSED_UPSAMPLE_NERF = True
 
 _COARSE_SAMPLERS = dict(linear=batch_sample_step_linear, depth=batch_sample_step_wrt_depth,
                         sqrt_depth=batch_sample_step_wrt_sqrt_depth)
-
-
-def _chunked(fn, kwargs: dict, chunk: int) -> torch.Tensor:
-    """fn(**kwargs) evaluated on slices of at most `chunk` rows (every tensor argument is sliced along dim 0)"""
-    n = next(iter(kwargs.values())).shape[0]
-    if n <= chunk:
-        return fn(**kwargs)
-    return torch.cat([fn(**{k: v[i:i + chunk] for k, v in kwargs.items()}) for i in range(0, n, chunk)], 0)
 
 
 def _rows_into_packs(rows_a, sel_a, rows_b, sel_b, pack_first):

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from nr3d_lib_amd.bindings import _neus_upsample
+from nr3d_lib_amd.graphics._ray_query import _chunked, _flag, _march
 from nr3d_lib_amd.graphics.nerf.nerf_utils import packed_alpha_to_vw, ray_alpha_to_vw
 from nr3d_lib_amd.graphics.neus.neus_utils import (neus_packed_sdf_to_alpha, neus_packed_sdf_to_upsample_alpha,
                                                    neus_ray_sdf_to_alpha, neus_ray_sdf_to_upsample_alpha)
@@ -47,28 +48,6 @@ _RAY_ATTRS = (('ts', 'rays_ts'), ('fidx', 'rays_fidx'), ('bidx', 'rays_bidx'), (
               ('h_appear', 'rays_h_appear'))
 _COARSE_SAMPLERS = dict(linear=batch_sample_step_linear, depth=batch_sample_step_wrt_depth,
                         sqrt_depth=batch_sample_step_wrt_sqrt_depth)
-
-
-def _flag(model, name):
-    return bool(getattr(model, name, False))
-
-
-def _chunked(fn, kwargs: dict, chunk: int) -> torch.Tensor:
-    """fn(**kwargs) evaluated on slices of at most `chunk` rows (every tensor argument is sliced along dim 0)"""
-    n = next(iter(kwargs.values())).shape[0]
-    if n <= chunk:
-        return fn(**kwargs)
-    return torch.cat([fn(**{k: v[i:i + chunk] for k, v in kwargs.items()}) for i in range(0, n, chunk)], 0)
-
-
-def _march(model, ray_tested, rays_o, rays_d, near, far, perturb, march_cfg):
-    accel = model.accel
-    if hasattr(accel, 'cur_batch__ray_march'):
-        extra = [ray_tested['rays_bidx']] + ([ray_tested['rays_ts']] if getattr(accel, 'is_dynamic', False) else [])
-        return accel.cur_batch__ray_march(rays_o, rays_d, *extra, near=near, far=far, perturb=perturb, **march_cfg)
-    if getattr(accel, 'is_dynamic', False):
-        return accel.ray_march(rays_o, rays_d, ray_tested['rays_ts'], near=near, far=far, perturb=perturb, **march_cfg)
-    return accel.ray_march(rays_o, rays_d, near=near, far=far, perturb=perturb, **march_cfg)
 
 
 def _check_model(model, need_accel=True):
