@@ -4,6 +4,7 @@ float32 run is pinned to the reference's own results by tests/test_neus_coarse_c
 is what the HIP kernel's error is measured against, and the distance between the two runs is the yardstick for that error.
 
 Also the analytic model and the ray fan the coarse-query tests share."""
+import numpy as np
 import torch
 
 RADIUS, FORWARD_INV_S = 0.62, 48.0
@@ -49,9 +50,22 @@ def shared_u(m, dtype=torch.float32):
     return torch.linspace(0., 1., m + 2, dtype=dtype)[1:-1]
 
 
-def stage(depth, sdf, u, inv_s, use_estimate, dtype=torch.float32):
+def _cumsum(x, dim):
+    return torch.from_numpy(np.cumsum(x.numpy(), axis=dim, dtype=x.numpy().dtype))
+
+
+def _cumprod(x, dim):
+    return torch.from_numpy(np.cumprod(x.numpy(), axis=dim, dtype=x.numpy().dtype))
+
+
+def stage(depth, sdf, u, inv_s, use_estimate, dtype=torch.float32, *, slope_clamp=-10.0, slope_eps=1e-5, alpha_eps=1e-5,
+          mass_min=1e-5, den_min=1e-5, sums_in_dtype=False):
     """depth, sdf [R, n], u [m] or [R, m] (all taken as they are and converted to `dtype`) ->
-    dict(fine [R, m], wsum [R] = the sum of the weights, cdf [R, n])"""
+    dict(fine [R, m], wsum [R] = the sum of the weights, cdf [R, n])
+    The keyword arguments are the stage's literals (the kernel's values by default): tests/test_upsample_decisions_cpu.py moves them.
+    sums_in_dtype: the product and the sums run in order IN `dtype` (torch's CPU cumsum / cumprod / sum keep a float32 row's running
+    value in double; next to cdf = 1 the difference is an ulp of the CDF, which an inverted bin with a pmf of 1e-4 turns into 1e-3
+    of the bin -- tests/upsample_decision_inputs.py inverts such bins and sets it)"""
     d, s, u = depth.to(dtype), sdf.to(dtype), u.to(dtype)
     u = u.expand(d.shape[0], u.shape[-1]).contiguous()
     n = d.shape[-1]
@@ -61,21 +75,22 @@ def stage(depth, sdf, u, inv_s, use_estimate, dtype=torch.float32):
     else:
         delta = d[:, 1:] - d[:, :-1]
         mid = (s[:, :-1] + s[:, 1:]) * 0.5
-        slope = (s[:, 1:] - s[:, :-1]) / (delta + 1e-5)
+        slope = (s[:, 1:] - s[:, :-1]) / (delta + slope_eps)
         before = torch.cat([torch.zeros_like(slope[:, :1]), slope[:, :-1]], -1)
-        slope = torch.minimum(before, slope).clamp(-10.0, 0.0)
+        slope = torch.minimum(before, slope).clamp(slope_clamp, 0.0)
         c_prev = torch.sigmoid((mid + slope * (delta * -0.5)) * inv_s)
         c_next = torch.sigmoid((mid + slope * (delta * 0.5)) * inv_s)
-    alpha = ((c_prev - c_next) / (c_prev + 1e-5)).clamp_min(0)
+    alpha = ((c_prev - c_next) / (c_prev + alpha_eps)).clamp_min(0)
     keep = torch.cat([torch.ones_like(alpha[:, :1]), (1 + 1e-10) - alpha[:, :-1]], -1)
-    w = alpha * torch.cumprod(keep, -1)
-    wsum = w.sum(-1, keepdim=True)
-    cdf = torch.cat([torch.zeros_like(w[:, :1]), torch.cumsum(w / wsum.clamp_min(1e-5), -1)], -1)
+    cumprod, cumsum = (_cumprod, _cumsum) if sums_in_dtype else (torch.cumprod, torch.cumsum)
+    w = alpha * cumprod(keep, -1)
+    wsum = cumsum(w, -1)[:, -1:] if sums_in_dtype else w.sum(-1, keepdim=True)
+    cdf = torch.cat([torch.zeros_like(w[:, :1]), cumsum(w / wsum.clamp_min(mass_min), -1)], -1)
     k = torch.searchsorted(cdf, u, right=False)
     lo, hi = (k - 1).clamp_min(0), k.clamp_max(n - 1)
     c_lo, c_hi, d_lo, d_hi = cdf.gather(-1, lo), cdf.gather(-1, hi), d.gather(-1, lo), d.gather(-1, hi)
     den = c_hi - c_lo
-    den = torch.where(den < 1e-5, torch.ones_like(den), den)
+    den = torch.where(den < den_min, torch.ones_like(den), den)
     fine = d_lo + (u - c_lo) / den * (d_hi - d_lo)
     return dict(fine=fine, wsum=wsum[:, 0], cdf=cdf)
 

@@ -5,11 +5,19 @@ the float32 run is pinned to the CPU oracle's pack ops by tests/test_neus_packed
 inputs is what the HIP kernel's error is measured against, and the distance between the two runs is the yardstick for that error.
 
 Also the packs on the analytic sphere of tests/neus_coarse_ref.py that the packed tests share."""
+import numpy as np
 import torch
 
 import neus_coarse_ref as cref
 
 EARLY_STOP, PMF_MIN, MASS_MIN = 1e-4, 1e-5, 1e-5
+SLOPE_CLAMP, SLOPE_EPS, ALPHA_EPS = -10.0, 1e-5, 1e-5
+# a wrong kernel, for tests/test_upsample_decisions_cpu.py alone: the early stop is honoured in the first chunk of 64 elements only
+STOP_FIRST_CHUNK_ONLY = False
+# torch's CPU cumsum / cumprod keep a float32 row's running value in double.  True: the product and the sum run in order IN the dtype,
+# as the oracle's pack ops do.  Next to cdf = 1 the difference is an ulp of the CDF, which an inverted bin with a pmf of 1e-4 turns
+# into 1e-3 of the bin: tests/upsample_decision_inputs.py, which inverts such bins, sets it; the parity inputs do not notice.
+SUMS_IN_DTYPE = False
 
 
 def _fma(a, b, c):
@@ -17,6 +25,14 @@ def _fma(a, b, c):
     if a.dtype == torch.float32:
         return (a.double() * b.double() + c.double()).float()
     return a * b + c
+
+
+def _cumsum(x):
+    return torch.from_numpy(np.cumsum(x.numpy(), dtype=x.numpy().dtype)) if SUMS_IN_DTYPE else torch.cumsum(x, 0)
+
+
+def _cumprod(x):
+    return torch.from_numpy(np.cumprod(x.numpy(), dtype=x.numpy().dtype)) if SUMS_IN_DTYPE else torch.cumprod(x, 0)
 
 
 def alpha_of(d, s, inv_s, use_estimate):
@@ -30,12 +46,12 @@ def alpha_of(d, s, inv_s, use_estimate):
         c_prev, c_next = c[:-1], c[1:]
     else:
         d_sdf, delta = s[1:] - s[:-1], d[1:] - d[:-1]
-        slope = d_sdf / (delta + 1e-5)
+        slope = d_sdf / (delta + SLOPE_EPS)
         before = torch.cat([torch.zeros_like(slope[:1]), slope[:-1]])
-        sl = torch.minimum(before, slope).clamp(-10.0, 0.0)
+        sl = torch.minimum(before, slope).clamp(SLOPE_CLAMP, 0.0)
         mid, half = s[:-1] + d_sdf * 0.5, sl * delta * 0.5
         c_prev, c_next = torch.sigmoid((mid - half) * inv_s), torch.sigmoid((mid + half) * inv_s)
-    alpha[:-1] = ((c_prev - c_next) / (c_prev + 1e-5)).clamp_min(0)
+    alpha[:-1] = ((c_prev - c_next) / (c_prev + ALPHA_EPS)).clamp_min(0)
     return alpha
 
 
@@ -45,12 +61,14 @@ def pack_stage(d, alpha, u):
     every inverted bin (inf where none is read))"""
     n = d.shape[0]
     keep = torch.where(alpha <= 0, torch.ones_like(alpha), 1.0 - alpha)
-    T = torch.cat([torch.ones_like(keep[:1]), torch.cumprod(keep, 0)[:-1]])
+    T = torch.cat([torch.ones_like(keep[:1]), _cumprod(keep)[:-1]])
     below = (T < EARLY_STOP).nonzero()
     stop = int(below[0]) if below.numel() else n
+    if STOP_FIRST_CHUNK_ONLY and stop >= 64:
+        stop = n
     w = alpha * T
     w[stop:] = 0
-    cdf = torch.cat([torch.zeros_like(w[:1]), torch.cumsum(w, 0)[:-1]])
+    cdf = torch.cat([torch.zeros_like(w[:1]), _cumsum(w)[:-1]])
     cdf = cdf / cdf[-1].clamp_min(MASS_MIN)
     pos = torch.searchsorted(cdf, u.contiguous(), right=False).clamp_max(n - 1)
     lo = (pos - 1).clamp_min(0)
