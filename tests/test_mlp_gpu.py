@@ -8,6 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+from mlp_half_ref import (assert_rows, check_rows_against_twin, double_twin, fill_parameters, flip_band, half_contract, max_excused,
+                          rows_in_band)
+
 pytestmark = pytest.mark.gpu
 
 CASES = [
@@ -226,32 +229,66 @@ def test_second_order_through_the_fused_block(dev):
 def test_second_order_through_the_half_block(dev, x_dtype):
     """MLP(dtype=half) under create_graph (round-4 advisor: the differentiable branch mixed half x with fp32 parameters and raised,
     and for float x it differentiated a detached copy, so nothing of the second order reached the caller's x): nablas with
-    create_graph, a loss on them, gradients to the parameters AND to x, against the same network evaluated in fp32"""
+    create_graph, a loss on them, gradients to the parameters AND to x.
+
+    Row by row (tests/mlp_half_ref.py check_rows_against_twin) against an fp64 twin of the module -- parameters and x rounded to half,
+    everything else double -- with the USE_FUSED = False run of the same module as the yardstick: every row OUTSIDE the kink band
+    (flip_band: no ReLU unit of the row within the kernels' rounding of zero; at least 90 % of the rows, 96.4 % here) is within
+    max(2e-2, 4 x the USE_FUSED = False run's worst such row) of the tensor's scale, no exceptions; rows inside the band may switch a
+    unit differently, so a whole weight path enters or leaves that row's gradient: those keep the earlier share rule (below 5 % of
+    all rows off).  x.grad comes from the half kernels alone (the eikonal term gives a piecewise linear network's x nothing).  The
+    nablas under create_graph are the FP32 network's, on the fp32 parameters as they are (FusedMLPHalfFunction.backward): against
+    the rounded twin a layer-0 unit within 2^-11 of its scale of zero switches although it is far outside the kernels' band -- on the
+    CPU, fp32 torch against the rounded twin: 5 of 777 such rows (x fp32; 2 for half x), off by up to 0.16 of scale -- so the nablas
+    are judged twice: against the rounded twin with the band widened by that operand rounding (flip_band(unrounded_operands=True)),
+    and, in all rows outside the kernels' own band, against the twin on the operands the route really uses.
+    Measured on an MI355X, worst judged row as a fraction of scale, fused (USE_FUSED = False), for x fp32 / x half: x.grad 3.8e-4
+    (3.8e-4) / 3.8e-4 (3.8e-4); nablas against the rounded twin, 58.4 % of the rows outside the widened band, 2.8e-4 (3.9e-4) / 4.7e-4
+    (3.9e-4); nablas against the twin on the fp32 parameters 7.1e-8 / 2.9e-4 -- so 2e-2 is the bound in force everywhere, and no row
+    inside a band missed it either.  The earlier comparison with the same network in fp32 stays beside the new one."""
     from nr3d_lib_amd.models.blocks import MLP
+    from nr3d_lib_amd.models.blocks import mlp as mlp_mod
     torch.manual_seed(11)
-    m = MLP(16, 4, D=2, W=32, dtype=torch.half, device=dev)
+    m = MLP(16, 4, D=2, W=32, dtype=torch.half, device=torch.device("cpu")).to(dev)       # drawn on the CPU: the same net on every machine
     ref = MLP(16, 4, D=2, W=32, dtype=torch.float, device=dev)
     ref.load_state_dict(m.state_dict())
+    twin, twin_exact = double_twin(m), double_twin(m, rounded=False)
     g = torch.Generator(device="cpu").manual_seed(4)
     x0 = torch.randn(777, 16, generator=g).to(dev)
 
-    def run(net, dt):
+    def run(net, dt, x_in=None):
         net.zero_grad(set_to_none=True)
-        x = x0.to(dt).clone().requires_grad_(True)
+        x = (x0.to(dt) if x_in is None else x_in).clone().requires_grad_(True)
+        up = (lambda t: t) if dt == torch.float64 else (lambda t: t.float())
         y = net(x)
-        nablas, = torch.autograd.grad(y[:, 0].float().sum(), x, create_graph=True)
+        nablas, = torch.autograd.grad(up(y[:, 0]).sum(), x, create_graph=True)
         assert nablas.dtype == dt and nablas.requires_grad
         # sums, not means: a half network's backward carries dL/dy and every dL/d(pre-activation) in half -- gradients of 1e-5
         # would sit in half's subnormal range (the reference's half decoders run under a loss scale for the same reason)
-        loss = ((nablas.float().norm(dim=-1) - 1.0) ** 2).sum() + y.float().square().sum()
+        loss = ((up(nablas).norm(dim=-1) - 1.0) ** 2).sum() + up(y).square().sum()
         loss.backward()
-        return nablas.detach().float(), [p.grad.float().clone() for p in net.parameters()], x.grad.float().clone()
+        return up(nablas.detach()), [up(p.grad).clone() for p in net.parameters()], up(x.grad).clone()
     nh, gh, xh = run(m, x_dtype)
     nr, gr, xr = run(ref, torch.float32)
-    # half against fp32: values agree to half precision EXCEPT in samples where a hidden unit sits within half rounding of its ReLU
-    # kink -- there the two networks switch the unit differently and a whole weight path enters or leaves that sample's gradient
-    # (test_half_fused_forward_backward moves its inputs off the kinks; here the fp32 network is the reference, so such rows are
-    # counted instead: a few per cent at most).  Parameter gradients are sums over all samples: compared as a whole.
+    mlp_mod.USE_FUSED = False
+    try:
+        nu, _, xu = run(m, x_dtype)
+    finally:
+        mlp_mod.USE_FUSED = True
+    n64, _, x64 = run(twin, torch.float64, x0.half().double())
+    ne64, _, _ = run(twin_exact, torch.float64, x0.to(x_dtype).double())
+    zs = half_contract(m, x0, torch.zeros(777, 4, device=dev))[4]
+    outside = ~rows_in_band(zs, flip_band(m, x0))
+    outside_wide = ~rows_in_band(zs, flip_band(m, x0, unrounded_operands=True))
+    print(f"rows outside the kink band: {float(outside.float().mean()):.3f}, with the operand rounding: {float(outside_wide.float().mean()):.3f}")
+    assert float(outside.float().mean()) >= 0.9
+    assert float(xh.abs().max()) > 0
+    check_rows_against_twin("x.grad", xh, xu, x64, outside)
+    check_rows_against_twin("nablas (rounded twin, band with the operand rounding)", nh, nu, n64, outside_wide)
+    check_rows_against_twin("nablas (twin on the fp32 parameters)", nh, nu, ne64, outside, unfused_twin=n64)
+    # half against fp32, as before: values agree to half precision EXCEPT in samples where a hidden unit sits within half rounding of
+    # its ReLU kink -- there the two networks switch the unit differently; counted over all rows.  Parameter gradients are sums over
+    # all samples: compared as a whole.
     def rows_off(a, b, tol=2e-2):
         return float(((a - b).abs().amax(1) > tol * float(b.abs().max())).float().mean())
     assert torch.isfinite(nh).all() and torch.isfinite(xh).all() and float(xh.abs().max()) > 0
@@ -367,32 +404,6 @@ HALF_CASES = CASES + [([32, 128, 128, 16], 3001, "relu", None, True), ([128, 64,
                       ([33, 64, 50], 66000, None, None, True)]
 
 
-def _half_reference(m, x, gy):
-    """the half contract in fp64: weights / biases / x rounded to half, every layer's output rounded to half (straight-through
-    for the gradient) -> (y, dx, [dW], [db]) as fp64 tensors"""
-    rnd = lambda t: t.half().double()
-
-    class _Round(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, t):
-            return rnd(t)
-
-        @staticmethod
-        def backward(ctx, g):
-            return g
-    h0 = rnd(x.detach()).requires_grad_(True)
-    h = h0
-    ws = [rnd(l.weight.detach()).requires_grad_(True) for l in m.layers]
-    bs = [None if l.bias is None else rnd(l.bias.detach()).requires_grad_(True) for l in m.layers]
-    for l, W, b in zip(m.layers, ws, bs):
-        h = torch.nn.functional.linear(h, W, b)
-        if l.activation is not None:
-            h = torch.relu(h)
-        h = _Round.apply(h)
-    h.backward(rnd(gy))
-    return h.detach(), h0.grad, [w.grad for w in ws], [None if b is None else b.grad for b in bs]
-
-
 def _check_half(name, got, ref64, tol):
     scale = float(ref64.abs().max()) or 1.0
     err = float((got.double() - ref64).abs().max()) / scale
@@ -404,17 +415,18 @@ def _check_half(name, got, ref64, tol):
 def test_half_fused_forward_backward(dev, dims, n, hidden, out, bias, layout):
     """MLP(dtype=half) runs on the f16-MFMA kernels: y against the half contract evaluated in fp64 at 2^-9 of the output scale
     (one half rounding of the result + the odd activation that rounds the other way after fp32 instead of exact accumulation),
-    gradients at 2^-7 (dL/d(pre-activation) is rounded to half between the layers, as in the reference's half networks; a
-    pre-activation within half rounding of a ReLU kink flips a unit -- the inputs are moved off the kinks below); parameters
-    stay fp32 and so do their gradients.  Row-major and feature-major x, fused backward where the shape allows it, the torch
-    autocast path otherwise."""
+    gradients at 2^-7 (dL/d(pre-activation) is rounded to half between the layers, as in the reference's half networks);
+    parameters stay fp32 and so do their gradients.  dL/dx row by row (tests/mlp_half_ref.py assert_rows): every row is finite and
+    within 2^-7 of the scale, or it is PROVEN to sit on a ReLU kink -- the contract re-evaluated on that row with some of its
+    near-zero units switched the other way gives the kernel's gradient within the same 2^-7 -- and at most max(2, n // 2000) rows
+    may need that; no row of a network without ReLU layers may.  Weights from a CPU generator: tests/test_mlp_half_rows_cpu.py
+    sees the same nets.  Row-major and feature-major x, fused backward where the shape allows it, the torch autocast path
+    otherwise."""
     from nr3d_lib_amd.models.blocks import MLP
     torch.manual_seed(0)
     m = MLP(dims[0], dims[-1], D=len(dims) - 2, W=dims[1:-1], activation=hidden or "none", output_activation=out, bias=bias,
             dtype=torch.half, device=dev)
-    with torch.no_grad():
-        for p in m.parameters():
-            p.copy_(torch.randn_like(p) * (0.4 if p.dim() > 1 else 0.2))
+    fill_parameters(m, 0)
     desc = m.fused_desc()
     assert desc is not None and desc.half_fusable
     g = torch.Generator(device="cpu").manual_seed(1)
@@ -425,7 +437,8 @@ def test_half_fused_forward_backward(dev, dims, n, hidden, out, bias, layout):
     else:
         xt = x = xs.clone().requires_grad_(True)
     gy = torch.randn(n, dims[-1], generator=g).to(dev)
-    y64, dx64, dW64, db64 = _half_reference(m, x, gy)
+    contract = half_contract(m, x, gy)
+    y64, dx64, dW64, db64, _ = contract
     y = m(x)
     assert y.dtype == torch.float16
     fused_bwd = desc.half_backward_fusable
@@ -436,13 +449,10 @@ def test_half_fused_forward_backward(dev, dims, n, hidden, out, bias, layout):
         yn = m(x)
         assert yn.dtype == torch.float16
         _check_half("y (no_grad: fused forward for every shape)", yn, y64, 2.0 ** -9)
-    # rows whose ReLU pattern differs between the kernel and the fp64 reference (a pre-activation within rounding of zero) are
-    # excluded from the gradient comparison by construction: compare on the sum over rows, where a flipped unit is O(1/n)
     tol = 2.0 ** -7
     gx = (xt.grad.t() if layout == "feature_major" else xt.grad)
     assert gx.dtype == torch.float32 and gx.shape == dx64.shape
-    bad = ((gx.double() - dx64).abs().amax(1) > tol * float(dx64.abs().max()))
-    assert float(bad.float().mean()) <= 0.02, f"dL_dx: {int(bad.sum())} of {n} rows off"
+    assert_rows("dL_dx", gx, m, x, gy, tol, max_excused=max_excused(n), contract=contract)
     for l, layer in enumerate(m.layers):
         assert layer.weight.grad.dtype == torch.float32
         _check_half(f"dL_dW{l}", layer.weight.grad, dW64[l], 4 * tol if n < 100 else tol)
@@ -615,21 +625,19 @@ def test_every_half_backward_table_entry(dev, shape, fast):
     dims = _table_dims(shape, fast)
     torch.manual_seed(23)
     m = MLP(dims[0], dims[-1], D=len(dims) - 2, W=dims[1:-1], activation="relu", bias=True, dtype=torch.half, device=dev)
-    with torch.no_grad():
-        for p in m.parameters():
-            p.copy_(torch.randn_like(p) * (0.4 if p.dim() > 1 else 0.2))
+    fill_parameters(m, 23)
     desc = m.fused_desc()
     assert desc is not None and desc.half_backward_fusable
     packed = _mlp.pack_half(desc, [l.weight for l in m.layers], [l.bias for l in m.layers], with_backward=True)
     tol = 2.0 ** -7
     for n in TABLE_NS:
         x, gy = _table_inputs(dims, n, fast, dev, torch.half)
-        y64, dx64, dW64, db64 = _half_reference(m, x, gy)
+        contract = half_contract(m, x, gy)
+        y64, dx64, dW64, db64, _ = contract
         _check_half(f"n={n} y", _mlp.forward_half(desc, x, packed), y64, 2.0 ** -9)
         dx, dWs, dbs = _mlp.backward_half(desc, x, gy, packed, need_dx=True)
         assert dx.dtype == torch.float16 and dx.shape == dx64.shape and (n == 1 or fast != 2 or dx.stride() == (1, n))
-        bad = ((dx.double() - dx64).abs().amax(1) > tol * float(dx64.abs().max()))
-        assert torch.isfinite(dx).all() and float(bad.float().mean()) <= 0.02, f"n={n} dL_dx: {int(bad.sum())} of {n} rows off"
+        assert_rows(f"n={n} dL_dx", dx, m, x, gy, tol, max_excused=max_excused(n), contract=contract)
         for l in range(len(dims) - 1):
             assert dWs[l].dtype == torch.float32
             _check_half(f"n={n} dL_dW{l}", dWs[l], dW64[l], 4 * tol if n < 100 else tol)
