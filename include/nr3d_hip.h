@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 25
+#define NR3D_ABI_VERSION 26
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -1158,6 +1158,48 @@ int nr3d_nerf_upsample_stage_packed(uint32_t P, uint64_t N, uint32_t m, uint32_t
                                     const float *sigma, const float *delta, const int64_t *pack_infos, const float *u, int64_t u_stride,
                                     const float *coarse, const int64_t *coarse_row, float *cdf_workspace, float *fine, float *merged,
                                     float *deltas, void *stream);
+
+/* =================================================================================================
+ * NeRF++ distant-view shell marcher: the samples of every ray on N (+ 1) concentric shells, packed, two launches (csrc/nerfpp_march.hip)
+ *   reference         the torch op chain of NeRFRendererMixinDistant._ray_marching
+ *                     (nr3d_lib/models/fields_distant/nerf/renderer_mixin.py:170-288, ray_sphere_intersect :31-50, ray_box_intersect
+ *                     :53-82); no native twin there
+ * rays_o, rays_d float32 [R, 3] in object space, t_min float32 [R]; aabb float32 [2, 3], READ ON THE DEVICE: c = (aabb[1] + aabb[0]) / 2,
+ * h = (aabb[1] - aabb[0]) / 2, s = min_k (aabb[1] - aabb[0])_k; normalised ray o_n = (o - c) / h, d_n = d / h.
+ * radii float32 [N] (N >= 1): the table of the chain's torch.arange; noise float32 [R, N] or NULL; step, last_radius floats.
+ * Shell j < N of a ray, float32, in this order of operations:
+ *   interval_type INVERSE:            r_reci = radii[j], with noise clamp_min(radii[j] + noise[ray, j] * step, 1e-5); r = 1 / r_reci
+ *   LOGARITHM, LOGARITHM_INV_INPUT:   r_log = radii[j] (+ noise[ray, j] * step); r = powf(10, r_log); r_reci = 1 / r
+ *   r_ext[j] = r[j], r_ext[N] = last_radius.
+ *   sample_mode BOX:       t_ext = box(o_n, d_n, r_ext)        ELLIPSOID: t_ext = sphere(o_n, d_n, r_ext)
+ *               CUBE:      t_ext = box(o, d, r_ext * s)        SPHERICAL: t_ext = sphere(o, d, r_ext * s)
+ *     box(o, d, r):    a_k = (-r - o_k) / d_k, b_k = (r - o_k) / d_k; t_near = max_k min(a_k, b_k), t_far = min_k max(a_k, b_k), both
+ *                      NaN-PROPAGATING as torch.minimum / maximum / max(dim) / min(dim) (a 0/0 slab term makes the shell invalid; the
+ *                      infinities of a zero direction component are ordinary values); (t_far > t_near) & (t_far > 0) ? t_far : NaN
+ *     sphere(o, d, r): pp = o.o, vv = d.d, pv = o.d; (sqrt(pv pv - vv (pp - r r)) - pv) / vv  (a negative discriminant gives NaN)
+ *   t = t_ext[j], delta = t_ext[j + 1] - t_ext[j] (written even when it is NaN); the shell is valid iff !(isnan(t) | (t < t_min[ray]))
+ *   -- exactly that boolean: a NaN t_min keeps the sample.
+ *   network input x [4]:
+ *     BOX, ELLIPSOID:   p = o_n + d_n t (one fma per component); x_0..2 = p r_reci; q = r_reci, l = r_log
+ *     CUBE, SPHERICAL:  p = ((o + d t) - c) / h; n = |p|; x_0..2 = p / max(n, 1e-12); q = 1 / n, l = log10f(n)
+ *     x_3 = q 2 - 1 (INVERSE, LOGARITHM_INV_INPUT) or (l - log_min) / (log_max - log_min) 2 - 1 (LOGARITHM).
+ * nr3d_nerfpp_march_count: counts int64 [R] = the valid shells of every ray, fully written.  The caller turns them into begin_all
+ *   (the exclusive sum) and the sample total S with nr3d_prune_compact_packs.
+ * nr3d_nerfpp_march_emit: the same inputs and begin_all int64 [R]; the valid shells in (ray, shell) ascending order -- the order of the
+ *   chain's nonzero() -- into x float32 [S, 4] (16-byte aligned), t float32 [S], deltas float32 [S], ridx int64 [S], each fully
+ *   written when begin_all and S come from the count of the same inputs; no row >= S is ever written.
+ * One wave per ray, lane = shell in chunks of 64, four rays per workgroup; a lane computes t_ext[j] and t_ext[j + 1] itself; position =
+ * begin_all[ray] + the chunks before + the valid lanes below (ballot).  No LDS, no atomics.  R < 2^28 (nr3d_prune_compact_packs),
+ * R N < 2^40; R == 0 is a no-op. */
+enum { NR3D_NERFPP_BOX = 0, NR3D_NERFPP_ELLIPSOID = 1, NR3D_NERFPP_CUBE = 2, NR3D_NERFPP_SPHERICAL = 3 };
+enum { NR3D_NERFPP_INVERSE = 0, NR3D_NERFPP_LOGARITHM = 1, NR3D_NERFPP_LOGARITHM_INV_INPUT = 2 };
+int nr3d_nerfpp_march_count(uint32_t R, const float *rays_o, const float *rays_d, const float *t_min, const float *aabb, uint32_t N,
+                            const float *radii, const float *noise, float step, float last_radius, int sample_mode, int interval_type,
+                            float log_min, float log_max, int64_t *counts, void *stream);
+int nr3d_nerfpp_march_emit(uint32_t R, const float *rays_o, const float *rays_d, const float *t_min, const float *aabb, uint32_t N,
+                           const float *radii, const float *noise, float step, float last_radius, int sample_mode, int interval_type,
+                           float log_min, float log_max, const int64_t *begin_all, uint64_t S, float *x, float *t, float *deltas,
+                           int64_t *ridx, void *stream);
 
 #ifdef __cplusplus
 }

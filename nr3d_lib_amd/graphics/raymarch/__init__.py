@@ -57,3 +57,9 @@ class RaymarchRetForest(RaymarchRetBase):
     blidx_pack_infos: Optional[torch.Tensor]
     gidx: Optional[torch.Tensor]
     gidx_pack_infos: Optional[torch.Tensor]
+
+
+# the NeRF++ distant-view sampler (below the records: nerfpp_raymarch's own imports may come back to this package).  The function
+# shadows its module as an attribute of this package: reach the module and its switch FUSED_NERFPP_MARCH with
+# importlib.import_module("nr3d_lib_amd.graphics.raymarch.nerfpp_raymarch") or a `from ... import`.
+from .nerfpp_raymarch import nerfpp_raymarch, nerfpp_raymarch_ret, ray_box_intersect, ray_sphere_intersect  # noqa: E402,F401
