@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import neus_packed_ref as packed_ref
+
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +86,22 @@ def _reference_fine_depths(oracle, o, d, near, far, occ, step, radius, stages, n
     return hit, np.stack(out), pi
 
 
+def _float64_restatement(model, rays, factors, use_estimate, num_fine):
+    """-> (e_ref, the largest marched depth, the float64 interval mid-points [n_hit, 3 m - 1]) of the up-sampling loop on the depths the
+    device marched; e_ref is never taken from the code under test"""
+    from nr3d_lib_amd.graphics.neus import neus_ray_query as rq
+    with torch.no_grad():
+        marched = rq._march(model, rays, rays["rays_o"], rays["rays_d"], rays["near"], rays["far"], False, {})
+    hit, pi = marched.ridx_hit, marched.pack_infos.cpu()
+    assert pi[0, 0] == 0 and torch.equal(pi[1:, 0], (pi[:, 0] + pi[:, 1])[:-1]) and (pi[:, 1] >= 1).all(), "the marcher's packs tile"
+    args = (rays["rays_o"][hit], rays["rays_d"][hit], marched.depth_samples, pi, num_fine, factors, 64.0, use_estimate)
+    d32 = packed_ref.upsample_loop(*args, dtype=torch.float32, radius=model.radius)
+    d64 = packed_ref.upsample_loop(*args, dtype=torch.float64, radius=model.radius)
+    e_ref = (d32.double() - d64).abs().max().item()
+    mids = (d64[:, :-1] + d64.diff(dim=-1) / 2).numpy()
+    return e_ref, marched.depth_samples.abs().max().item(), mids
+
+
 @pytest.mark.parametrize("use_estimate", [False, True])
 def test_fine_buffer_matches_per_ray_restatement(oracle, dev, use_estimate):
     from nr3d_lib_amd.graphics.neus import neus_ray_query_march_occ_multi_upsample
@@ -102,6 +120,16 @@ def test_fine_buffer_matches_per_ray_restatement(oracle, dev, use_estimate):
     # the chain is fp32 on both sides; a last-bit difference in an sdf can move a sample inside its CDF bin
     close = np.isclose(vb["t"].cpu().numpy(), mids_ref, rtol=0, atol=2e-4)
     assert close.mean() > 0.995, f"only {close.mean():.4f} of the fine depths agree"
+    # and every depth, as tests/test_neus_packed_query_gpu.py judges the two routes: within 4 e_ref + one ulp of the largest depth of the
+    # float64 run of the loop restatement (tests/neus_packed_ref.py) on the marched depths; e_ref = the distance between the float32 and
+    # the float64 run of that restatement, measured here
+    e_ref, d_max, mids64 = _float64_restatement(model, rays, stages, use_estimate, nf)
+    err = np.abs(vb["t"].cpu().numpy().astype(np.float64) - mids64)
+    allowed = 4 * e_ref + float(np.spacing(np.float32(d_max)))
+    msg = (f"use_estimate={use_estimate}: max |t - float64 restatement| {err.max():.3e} at {np.unravel_index(err.argmax(), err.shape)}, "
+           f"{int((err > allowed).sum())} of {err.size} above; e_ref {e_ref:.3e}, allowed {allowed:.3e}")
+    print(msg)
+    assert err.max() <= allowed, msg
     assert vb["rgb"].shape == (*vb["t"].shape, 3) and vb["nablas"].shape == (*vb["t"].shape, 3)
     a = vb["opacity_alpha"].cpu().numpy()
     assert a.shape == mids_ref.shape and (a >= 0).all() and (a <= 1 + 1e-5).all()

@@ -110,7 +110,14 @@ def test_contractions(oracle, dev, ctype):
     far = near + 6.0
     grid = grids(res, 4)["random"]
     got, ref = run_both(oracle, dev, o, d, near, far, ROI * 0.5, grid, ctype, 0.02, 1e10, 0.0, 200)
-    same = (got[0].cpu().numpy() == ref[0]).all(1).mean()
+    pi = got[0].cpu().numpy()
+    same = (pi == ref[0]).all(1).mean()
+    # on the rays with identical packed_info the t values and ray indices are bit-equal, always: they do not depend on the
+    # contraction (tests/test_occ_contract_gpu.py judges every probe's cell)
+    in_same = np.repeat((pi == ref[0]).all(1), pi[:, 1])
+    in_same_ref = np.repeat((pi == ref[0]).all(1), ref[0][:, 1])
+    for k, name in ((1, "t_starts"), (2, "t_ends"), (3, "ridx")):
+        assert_equal(got[k].cpu().numpy().view(np.int32)[in_same], ref[k].view(np.int32)[in_same_ref], name=name)
     assert same >= 0.999, f"only {same:.4f} of rays have identical packed_info"
     if same == 1.0:
         assert (got[4].cpu().numpy() == ref[4]).mean() >= 0.999
