@@ -1,5 +1,6 @@
 // nr3d_lib_amd/csrc/neus_upsample.hip -- one up-sampling stage of the NeuS ray queries in one launch: on the fixed-length rows of the
-// vanilla coarse query (k_stage) and on the packs of the occupancy-march queries (k_stage_packed, further down).
+// vanilla coarse query (k_stage) and on the packs of the occupancy-march queries (k_stage_packed, further down; with LABELS the
+// same body carries the block index of a forest's samples along).
 //
 // The reference runs a stage between two SDF queries as a chain of small torch ops (nr3d_lib/graphics/neus/neus_ray_query.py:258-270:
 // neus_ray_sdf_to_alpha | neus_ray_sdf_to_upsample_alpha -> ray_alpha_to_vw -> batch_sample_pdf -> cat -> sort).  Rows hold tens to a
@@ -131,11 +132,24 @@ constexpr int kPackedLdsRow = NR3D_NEUS_UPSAMPLE_PACKED_LDS_ROW;   // packs with
 // The body over the pack's four arrays: D, S = depths and SDF [n], C = the CDF [n], F = the new depths [m].  Called once with LDS
 // pointers and once with global ones; inlined, each call resolves to DS or global instructions.  Only this wave touches these rows, in
 // both address spaces, which is what wave_sync() needs (wave_row.h).
-template <bool ESTIMATE, bool STAGED>
+//
+// LABELS (nr3d_neus_upsample_stage_packed_blocks): every sample carries an int64 label, the forest's block index, that nothing here
+// interprets.  A new depth takes the label of the inversion's `pos`, the upper end of its CDF bin, before the running maximum; the
+// union carries the labels along.  Labels never enter LDS: `lb.in` is read once per new depth behind its binary search and once per
+// old element in the merge, and a new element's label is read back from `lb.fine`, which this wave alone wrote before the
+// wave_sync() in front of the merge -- the rule that lets the unstaged body read F from global memory.
+template <bool LABELS> struct Labels {};
+template <> struct Labels<true> {
+	const int64_t *in;       // the pack's labels [n]
+	int64_t *fine;           // [m], always written
+	int64_t *merged;         // the pack's place in blidx_merged [n + m], read with merge only
+};
+
+template <bool ESTIMATE, bool STAGED, bool LABELS>
 __device__ __forceinline__ void packed_body(int n, int m, int lane, const float *D, const float *S, float *C, float *F,
                                             const float *__restrict__ u_row, float inv_s, float *__restrict__ fine_row, bool merge,
                                             int64_t out_begin, float *__restrict__ m_row, float *__restrict__ s_row,
-                                            int64_t *__restrict__ pidx_row) {
+                                            int64_t *__restrict__ pidx_row, const Labels<LABELS> lb) {
 	// ---- weights of the n - 1 intervals (w_{n-1} = 0) and, at the same index, their exclusive sum into C ----
 	float carry_T = 1.0f, carry_c = 0.0f;
 	bool stopped = false;
@@ -190,6 +204,7 @@ __device__ __forceinline__ void packed_body(int n, int m, int lane, const float 
 		float f = -INFINITY;
 		if (j < m) {
 			f = 0.0f;                                         // a pack without elements (outside the contract) has nothing to read
+			[[maybe_unused]] int64_t label = -1;
 			if (n > 0) {
 				// packed_invert_cdf's rule (k_invert_cdf, pack_ops.hip).  Written out on purpose: behind a shared function this kernel measured
 				// 0.2 - 0.5 % slower at 65 536 packs, and nerf_upsample.hip's stage likewise (profiles/wave_row.md)
@@ -205,7 +220,9 @@ __device__ __forceinline__ void packed_body(int n, int m, int lane, const float 
 					const float c0 = C[pos - 1], pmf = C[pos] - c0, d0 = D[pos - 1];
 					f = pmf < 1e-5f ? d0 : fmaf((uj - c0) / pmf, D[pos] - d0, d0);
 				}
+				if constexpr (LABELS) label = lb.in[pos];
 			}
+			if constexpr (LABELS) lb.fine[j] = label;
 		}
 		f = running_max(f, lane, carry_f);
 		if (j < m) {
@@ -223,16 +240,18 @@ __device__ __forceinline__ void packed_body(int n, int m, int lane, const float 
 		m_row[q] = s.from_a ? D[s.i] : F[s.j];
 		if (!s.from_a) pidx_row[s.j] = out_begin + q;
 		else if (s_row) s_row[q] = S[s.i];
+		if constexpr (LABELS) lb.merged[q] = s.from_a ? lb.in[s.i] : lb.fine[s.j];
 	}
 }
 
-template <bool ESTIMATE>
+template <bool ESTIMATE, bool LABELS>
 __global__ __launch_bounds__(kWaves * 64) void k_stage_packed(uint32_t P, int64_t N, int m, const float *__restrict__ depth,
                                                                const float *__restrict__ sdf, const int64_t *__restrict__ pack_infos,
                                                                const float *__restrict__ u, int64_t u_stride, float inv_s,
                                                                float *__restrict__ cdf_ws, float *__restrict__ fine,
                                                                float *__restrict__ merged, float *__restrict__ sdf_merged,
-                                                               int64_t *__restrict__ pidx_fine, int64_t *__restrict__ pack_infos_out) {
+                                                               int64_t *__restrict__ pidx_fine, int64_t *__restrict__ pack_infos_out,
+                                                               const Labels<LABELS> labels) {
 	__shared__ __attribute__((aligned(16))) float lds[kWaves * 3 * kPackedLdsRow];
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const uint32_t p = blockIdx.x * kWaves + wave;
@@ -252,6 +271,8 @@ __global__ __launch_bounds__(kWaves * 64) void k_stage_packed(uint32_t P, int64_
 		pack_infos_out[2 * (size_t)p] = out_begin;
 		pack_infos_out[2 * (size_t)p + 1] = (int64_t)n + m;
 	}
+	Labels<LABELS> lb;
+	if constexpr (LABELS) lb = {labels.in + first, labels.fine + (size_t)p * m, merge ? labels.merged + out_begin : nullptr};
 	if (n + m <= kPackedLdsRow) {                         // wave-uniform
 		float *D = lds + (size_t)wave * (3 * kPackedLdsRow), *S = D + n, *C = S + n, *F = C + n;
 		for (int i = lane; i < n; i += 64) {
@@ -259,9 +280,10 @@ __global__ __launch_bounds__(kWaves * 64) void k_stage_packed(uint32_t P, int64_
 			S[i] = s_row[i];
 		}
 		wave_sync();
-		packed_body<ESTIMATE, true>(n, m, lane, D, S, C, F, u_row, inv_s, f_row, merge, out_begin, mo, so, po);
+		packed_body<ESTIMATE, true, LABELS>(n, m, lane, D, S, C, F, u_row, inv_s, f_row, merge, out_begin, mo, so, po, lb);
 	} else {
-		packed_body<ESTIMATE, false>(n, m, lane, d_row, s_row, cdf_ws + first, f_row, u_row, inv_s, nullptr, merge, out_begin, mo, so, po);
+		packed_body<ESTIMATE, false, LABELS>(n, m, lane, d_row, s_row, cdf_ws + first, f_row, u_row, inv_s, nullptr, merge, out_begin, mo, so,
+		                                     po, lb);
 	}
 }
 
@@ -299,30 +321,53 @@ extern "C" int nr3d_neus_upsample_stage(uint32_t R, uint32_t n, uint32_t m, cons
 
 extern "C" int nr3d_neus_upsample_packed_lds_row(void) { return neus_upsample::kPackedLdsRow; }
 
-extern "C" int nr3d_neus_upsample_stage_packed(uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf,
-                                               const int64_t *pack_infos, const float *u, int64_t u_stride, float inv_s, int use_estimate,
-                                               int merge, int need_sdf, float *cdf_workspace, float *fine, float *merged,
-                                               float *sdf_merged, int64_t *pidx_fine, int64_t *pack_infos_out, void *stream) {
-	NR3D_CHECK(m >= 1, "neus_upsample_stage_packed: m = %u, at least 1 new depth per pack", m);
-	NR3D_CHECK(u_stride == 0 || u_stride == (int64_t)m, "neus_upsample_stage_packed: u_stride = %lld, must be 0 (one shared row) or m = %u",
+// the checks and the launch of both packed entries; `fn` names the entry in the messages
+template <bool LABELS>
+static int launch_stage_packed(const char *fn, uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf,
+                               const int64_t *pack_infos, const float *u, int64_t u_stride, float inv_s, int use_estimate, int merge,
+                               int need_sdf, float *cdf_workspace, float *fine, float *merged, float *sdf_merged, int64_t *pidx_fine,
+                               int64_t *pack_infos_out, const neus_upsample::Labels<LABELS> labels, void *stream) {
+	NR3D_CHECK(m >= 1, "%s: m = %u, at least 1 new depth per pack", fn, m);
+	NR3D_CHECK(u_stride == 0 || u_stride == (int64_t)m, "%s: u_stride = %lld, must be 0 (one shared row) or m = %u", fn,
 	           (long long)u_stride, m);
 	NR3D_CHECK(N < (1ull << 31) && N + (uint64_t)P * m < (1ull << 31),
-	           "neus_upsample_stage_packed: N + P m = %llu + %u * %u, the merged buffer holds at most 2^31 - 1 elements",
-	           (unsigned long long)N, P, m);
-	NR3D_CHECK(!need_sdf || merge, "neus_upsample_stage_packed: need_sdf without merge");
+	           "%s: N + P m = %llu + %u * %u, the merged buffer holds at most 2^31 - 1 elements", fn, (unsigned long long)N, P, m);
+	NR3D_CHECK(!need_sdf || merge, "%s: need_sdf without merge", fn);
 	if (P == 0) return 0;
-	NR3D_CHECK(depth && sdf && pack_infos && u && cdf_workspace && fine, "neus_upsample_stage_packed: NULL tensor pointer");
-	NR3D_CHECK(!merge || (merged && pidx_fine && pack_infos_out), "neus_upsample_stage_packed: merge without merged, pidx_fine or pack_infos_out");
-	NR3D_CHECK(!need_sdf || sdf_merged, "neus_upsample_stage_packed: need_sdf without sdf_merged");
+	NR3D_CHECK(depth && sdf && pack_infos && u && cdf_workspace && fine, "%s: NULL tensor pointer", fn);
+	NR3D_CHECK(!merge || (merged && pidx_fine && pack_infos_out), "%s: merge without merged, pidx_fine or pack_infos_out", fn);
+	NR3D_CHECK(!need_sdf || sdf_merged, "%s: need_sdf without sdf_merged", fn);
+	if constexpr (LABELS) {
+		NR3D_CHECK(labels.in && labels.fine, "%s: NULL label pointer", fn);
+		NR3D_CHECK(!merge || labels.merged, "%s: merge without blidx_merged", fn);
+	}
 	const dim3 grid(div_up(P, neus_upsample::kWaves)), block(neus_upsample::kWaves * 64);
 	hipStream_t st = (hipStream_t)stream;
 	float *mg = merge ? merged : nullptr, *sm = need_sdf ? sdf_merged : nullptr;
 	if (use_estimate)
-		hipLaunchKernelGGL(neus_upsample::k_stage_packed<true>, grid, block, 0, st, P, (int64_t)N, (int)m, depth, sdf, pack_infos, u, u_stride,
-		                   inv_s, cdf_workspace, fine, mg, sm, pidx_fine, pack_infos_out);
+		hipLaunchKernelGGL((neus_upsample::k_stage_packed<true, LABELS>), grid, block, 0, st, P, (int64_t)N, (int)m, depth, sdf, pack_infos, u,
+		                   u_stride, inv_s, cdf_workspace, fine, mg, sm, pidx_fine, pack_infos_out, labels);
 	else
-		hipLaunchKernelGGL(neus_upsample::k_stage_packed<false>, grid, block, 0, st, P, (int64_t)N, (int)m, depth, sdf, pack_infos, u, u_stride,
-		                   inv_s, cdf_workspace, fine, mg, sm, pidx_fine, pack_infos_out);
+		hipLaunchKernelGGL((neus_upsample::k_stage_packed<false, LABELS>), grid, block, 0, st, P, (int64_t)N, (int)m, depth, sdf, pack_infos, u,
+		                   u_stride, inv_s, cdf_workspace, fine, mg, sm, pidx_fine, pack_infos_out, labels);
 	NR3D_LAUNCH_CHECK();
 	return 0;
+}
+
+extern "C" int nr3d_neus_upsample_stage_packed(uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf,
+                                               const int64_t *pack_infos, const float *u, int64_t u_stride, float inv_s, int use_estimate,
+                                               int merge, int need_sdf, float *cdf_workspace, float *fine, float *merged,
+                                               float *sdf_merged, int64_t *pidx_fine, int64_t *pack_infos_out, void *stream) {
+	return launch_stage_packed<false>("neus_upsample_stage_packed", P, N, m, depth, sdf, pack_infos, u, u_stride, inv_s, use_estimate, merge,
+	                                  need_sdf, cdf_workspace, fine, merged, sdf_merged, pidx_fine, pack_infos_out, {}, stream);
+}
+
+extern "C" int nr3d_neus_upsample_stage_packed_blocks(uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf,
+                                                      const int64_t *blidx, const int64_t *pack_infos, const float *u, int64_t u_stride,
+                                                      float inv_s, int use_estimate, int merge, int need_sdf, float *cdf_workspace,
+                                                      float *fine, int64_t *blidx_fine, float *merged, float *sdf_merged,
+                                                      int64_t *blidx_merged, int64_t *pidx_fine, int64_t *pack_infos_out, void *stream) {
+	return launch_stage_packed<true>("neus_upsample_stage_packed_blocks", P, N, m, depth, sdf, pack_infos, u, u_stride, inv_s, use_estimate,
+	                                 merge, need_sdf, cdf_workspace, fine, merged, sdf_merged, pidx_fine, pack_infos_out,
+	                                 {blidx, blidx_fine, merge ? blidx_merged : nullptr}, stream);
 }

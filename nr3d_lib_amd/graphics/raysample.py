@@ -1,15 +1,18 @@
 """Depth samplers on rays -- counterpart of the parts of nr3d_lib/graphics/raysample.py the hot-path drivers use:
 ``packed_sample_cdf`` / ``packed_sample_pdf`` (:38-84, on the HIP ``packed_invert_cdf``), the batched inverse-CDF samplers
-``batch_sample_cdf`` / ``batch_sample_pdf`` (:221-282, plain torch) and the three ``batch_sample_step_*`` ladders (:285-383).
+``batch_sample_cdf`` / ``batch_sample_pdf`` (:221-282, plain torch), the three ``batch_sample_step_*`` ladders (:285-383) and the
+linear stepper inside packed segments (:161-205, ``_v1``) that ``ForestBlockSpace.ray_step_coarse(step_mode='linear')`` calls.
 Same names, arguments and return conventions."""
-from typing import Tuple
+from typing import Tuple, Union
 
 import torch
 
-from nr3d_lib_amd.graphics.pack_ops import packed_cumsum, packed_div, packed_invert_cdf
+from nr3d_lib_amd.graphics.pack_ops import (get_pack_infos_from_n, interleave_arange_simple, interleave_linstep, packed_cumsum,
+                                            packed_diff, packed_div, packed_invert_cdf)
 
 __all__ = ['packed_sample_cdf', 'packed_sample_pdf', 'batch_sample_cdf', 'batch_sample_pdf', 'batch_sample_step_linear',
-           'batch_sample_step_wrt_depth', 'batch_sample_step_wrt_sqrt_depth']
+           'batch_sample_step_wrt_depth', 'batch_sample_step_wrt_sqrt_depth',
+           'interleave_sample_step_linear_in_packed_segments']
 
 
 def _per_ray(near, far, prefix_shape):
@@ -123,3 +126,42 @@ def batch_sample_pdf(bins: torch.Tensor, weights: torch.Tensor, num_to_sample: i
     pdf = weights / torch.sum(weights, -1, keepdim=True).clamp_min(eps)
     cdf = torch.cat([pdf.new_zeros((*pdf.shape[:-1], 1)), torch.cumsum(pdf, -1)], -1)
     return batch_sample_cdf(bins, cdf, num_to_sample, perturb, eps)
+
+
+@torch.no_grad()
+def interleave_sample_step_linear_in_packed_segments(
+        near: Union[torch.Tensor, float], far: Union[torch.Tensor, float], entry: torch.Tensor, exit: torch.Tensor,
+        seg_pack_infos: torch.Tensor, step_size: float = 0.01, step_size_factor: float = 1.0, min_steps: int = 2,
+        max_steps: int = 512, perturb=False):
+    """equal steps inside every (entry, exit) segment of every ray, on the ray's own ladder near + k step_size
+    (raysample.py:161-205, ``interleave_sample_step_linear_in_packed_segments_v1``): a segment takes the rungs from
+    trunc((entry - near) / step) up to and including trunc((exit - near) / step) -- without the last one when perturbing, every
+    sample then moves by U(0, 1) steps -- clamped to [min_steps, max_steps] rungs counted from the first.  ``far`` is not used, as
+    in the reference.
+    -> (t_samples, deltas, ridx, ray_pack_infos, sidx, out_seg_pack_infos): flat per sample the depth, the step to the next sample
+    (``step_size`` without perturb, and for the last sample of a segment), the ray and the segment; the packs per ray and per
+    segment"""
+    num_rays = seg_pack_infos.shape[0]
+    near = entry.new_full([num_rays], near) if not isinstance(near, torch.Tensor) else near
+    step_size = step_size * step_size_factor
+    _, seg_ridx = interleave_arange_simple(seg_pack_infos[..., 1].contiguous())
+    _near = near[seg_ridx]
+    entry_ind = (entry - _near).div_(step_size, rounding_mode='trunc').long()
+    exit_ind = (exit - _near).div_(step_size, rounding_mode='trunc').long()
+    if not perturb:
+        exit_ind.add_(1)
+    n_per_seg = (exit_ind - entry_ind).clamp_(min_steps, max_steps)
+    out_seg_pack_infos = get_pack_infos_from_n(n_per_seg)
+    indexing, sidx = interleave_linstep(entry_ind, n_per_seg, 1, return_idx=True)
+    if not perturb:
+        t_samples = _near[sidx] + indexing.to(near.dtype) * step_size
+        deltas = near.new_full(sidx.shape, step_size)
+    else:
+        indexing = indexing.to(near.dtype) + torch.rand_like(indexing, dtype=near.dtype, device=near.device)
+        t_samples = _near[sidx] + indexing * step_size
+        last_inds = out_seg_pack_infos[..., 0] + out_seg_pack_infos[..., 1] - 1
+        deltas = packed_diff(t_samples, out_seg_pack_infos).index_fill_(0, last_inds, step_size)
+    ridx = seg_ridx[sidx]
+    n_per_ray = seg_pack_infos.new_zeros([num_rays])
+    n_per_ray.index_add_(0, seg_ridx, n_per_seg)
+    return t_samples, deltas, ridx, get_pack_infos_from_n(n_per_ray), sidx, out_seg_pack_infos

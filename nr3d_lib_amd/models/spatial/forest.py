@@ -21,6 +21,7 @@ import torch.nn as nn
 from nr3d_lib_amd.bindings._forest import ForestMeta, forest_identify
 from nr3d_lib_amd.graphics.pack_ops import (get_pack_infos_from_first, interleave_sample_step_wrt_depth_in_packed_segments,
                                             mark_pack_boundaries, packed_sort_inplace)
+from nr3d_lib_amd.graphics.raysample import interleave_sample_step_linear_in_packed_segments
 
 __all__ = ['ForestBlockSpace', 'octree_from_corners', 'ray_box_intersection']
 
@@ -264,12 +265,16 @@ class ForestBlockSpace(nn.Module):
 
     def ray_step_coarse(self, rays_o, rays_d, near, far, seg_block_inds, seg_entries, seg_exits, seg_pack_infos, *,
                         step_mode: str = 'depth', **step_kwargs):
-        """depth-proportional stepping inside the block segments (forest.py:396-419, 'depth' mode) ->
+        """stepping inside the block segments (forest.py:396-419): 'depth' = steps proportional to depth, 'linear' = equal steps ->
         dict(num_hit_rays, ridx_hit, samples, depth_samples, deltas, ridx, pack_infos, blidx, blidx_pack_infos)"""
-        if step_mode != 'depth':
+        if step_mode == 'depth':
+            stepper = interleave_sample_step_wrt_depth_in_packed_segments
+        elif step_mode == 'linear':
+            stepper = interleave_sample_step_linear_in_packed_segments
+        else:
             raise RuntimeError(f"Invalid step_mode={step_mode}")
-        depths, deltas, ridx, pack_infos, sidx, blidx_pack_infos = interleave_sample_step_wrt_depth_in_packed_segments(
-            near, far, seg_entries, seg_exits, seg_pack_infos, **step_kwargs)
+        depths, deltas, ridx, pack_infos, sidx, blidx_pack_infos = stepper(near, far, seg_entries, seg_exits, seg_pack_infos,
+                                                                           **step_kwargs)
         ridx_hit = ridx[pack_infos[:, 0]]
         return dict(num_hit_rays=ridx_hit.numel(), ridx_hit=ridx_hit,
                     samples=torch.addcmul(rays_o[ridx], rays_d[ridx], depths.unsqueeze(-1)), depth_samples=depths,
