@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 27
+#define NR3D_ABI_VERSION 28
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -971,7 +971,8 @@ int nr3d_neus_upsample_stage(uint32_t R, uint32_t n, uint32_t m, const float *de
                              float inv_s, int use_estimate, float *fine, float *merged, int32_t *order, void *stream);
 
 /* -------------------------------------------------------------------------------------------------
- * The same stage on the packs of a marcher: the up-sampling of neus_ray_query_march_occ_multi_upsample[_compressed] in one launch
+ * The same stage on the packs of a marcher: the up-sampling of neus_ray_query_march_occ_multi_upsample[_compressed], and with a label
+ * per sample of the forest's march-occ queries, in one launch
  *   reference         the packed op chain of nr3d_lib/graphics/neus/neus_ray_query.py (neus_packed_sdf_to_alpha |
  *                     neus_packed_sdf_to_upsample_alpha, packed_alpha_to_vw, packed_cumsum, packed_div, packed_sample_cdf,
  *                     merge_two_packs_sorted_aligned and the index-puts of the driver); no native twin there
@@ -1010,29 +1011,23 @@ int nr3d_neus_upsample_packed_lds_row(void);
  * merged of every new depth.  With need_sdf != 0 (needs merge) sdf_merged [N + P m] holds every old SDF value at its depth's index in
  * merged; the elements at pidx_fine are NOT written, the caller fills them with the SDF at the new depths.
  * cdf_workspace: float32 [N], contents undefined on return; always required (packs longer than the LDS row keep their CDF there).
- * Unused outputs may be NULL.  m >= 1, u_stride in {0, m}, N + P m < 2^31, otherwise an error before any launch.  P == 0 is a no-op. */
-int nr3d_neus_upsample_stage_packed(uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf, const int64_t *pack_infos,
-                                    const float *u, int64_t u_stride, float inv_s, int use_estimate, int merge, int need_sdf,
-                                    float *cdf_workspace, float *fine, float *merged, float *sdf_merged, int64_t *pidx_fine,
-                                    int64_t *pack_infos_out, void *stream);
-
-/* The packed stage on samples that carry a label each -- the block index of a forest's samples (the up-sampling of the reference's
- * NeuSRendererMixinForest, nr3d_lib/models/fields_forest/neus/renderer_mixin.py: `blidx[pidx_fine_iter]` and the index-puts of blidx).
- * Everything of nr3d_neus_upsample_stage_packed holds, on the same kernel body: fine, merged, sdf_merged (at the old places), pidx_fine
- * and pack_infos_out are the same bits as that entry gives on the same inputs, and the checks and the clipping of a pack are the same.
- * blidx int64 [N]: one label per sample; any value, nothing interprets it.
- * blidx_fine int64 [P, m], always fully written: blidx_fine[p, j] = blidx[first_p + pos_j], pos_j the inversion's own
- *   pos = min(first k with cdf_k >= u_j, n - 1) -- the upper end of the bin, packed_invert_cdf's bin index -- taken before fine_j is
- *   raised to the running maximum and whether or not that raise changes it.  A pack without elements (outside the contract) gets -1.
- * blidx_merged int64 [N + P m], fully written with merge != 0 (may be NULL otherwise): an old depth's place holds its old label,
- *   blidx_merged[pidx_fine[p, j]] = blidx_fine[p, j].
- * Labels are not staged in LDS (the workgroup's footprint is that of the unlabelled stage): blidx is read once per new depth and once
- * per old element of the union. */
-int nr3d_neus_upsample_stage_packed_blocks(uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf, const int64_t *blidx,
-                                           const int64_t *pack_infos, const float *u, int64_t u_stride, float inv_s, int use_estimate,
-                                           int merge, int need_sdf, float *cdf_workspace, float *fine, int64_t *blidx_fine, float *merged,
-                                           float *sdf_merged, int64_t *blidx_merged, int64_t *pidx_fine, int64_t *pack_infos_out,
-                                           void *stream);
+ * Labels, optional: blidx int64 [N] gives every sample a label -- the block index of a forest's samples (the up-sampling of the
+ * reference's NeuSRendererMixinForest, nr3d_lib/models/fields_forest/neus/renderer_mixin.py: `blidx[pidx_fine_iter]` and the index-puts
+ * of blidx); any value, nothing interprets it.  blidx == NULL runs the stage without labels, and blidx_fine and blidx_merged must be
+ * NULL too; with blidx, blidx_fine is required, and so is blidx_merged with merge != 0.  The other outputs are the same bits either way.
+ *   blidx_fine int64 [P, m], fully written: blidx_fine[p, j] = blidx[first_p + pos_j], pos_j the inversion's own pos -- the upper end
+ *     of the bin, packed_invert_cdf's bin index -- taken before fine_j is raised to the running maximum and whether or not that raise
+ *     changes it.  A pack without elements (outside the contract) gets -1.
+ *   blidx_merged int64 [N + P m], fully written with merge != 0: an old depth's place holds its old label,
+ *     blidx_merged[pidx_fine[p, j]] = blidx_fine[p, j].
+ *   Labels are not staged in LDS (the workgroup's footprint is the same with and without them): blidx is read once per new depth and
+ *   once per old element of the union.
+ * Unused outputs may be NULL.  m >= 1, u_stride in {0, m}, N + P m < 2^31, need_sdf only with merge and the label rules above, otherwise
+ * an error before any launch.  P == 0 is a no-op. */
+int nr3d_neus_upsample_stage_packed(uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf, const int64_t *blidx,
+                                    const int64_t *pack_infos, const float *u, int64_t u_stride, float inv_s, int use_estimate, int merge,
+                                    int need_sdf, float *cdf_workspace, float *fine, int64_t *blidx_fine, float *merged,
+                                    float *sdf_merged, int64_t *blidx_merged, int64_t *pidx_fine, int64_t *pack_infos_out, void *stream);
 
 /* =================================================================================================
  * NeuS opacity: the SDF of consecutive samples -> alpha, one launch each way (csrc/neus_alpha.hip)

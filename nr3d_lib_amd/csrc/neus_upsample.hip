@@ -133,7 +133,7 @@ constexpr int kPackedLdsRow = NR3D_NEUS_UPSAMPLE_PACKED_LDS_ROW;   // packs with
 // pointers and once with global ones; inlined, each call resolves to DS or global instructions.  Only this wave touches these rows, in
 // both address spaces, which is what wave_sync() needs (wave_row.h).
 //
-// LABELS (nr3d_neus_upsample_stage_packed_blocks): every sample carries an int64 label, the forest's block index, that nothing here
+// LABELS (nr3d_neus_upsample_stage_packed with blidx): every sample carries an int64 label, the forest's block index, that nothing here
 // interprets.  A new depth takes the label of the inversion's `pos`, the upper end of its CDF bin, before the running maximum; the
 // union carries the labels along.  Labels never enter LDS: `lb.in` is read once per new depth behind its binary search and once per
 // old element in the merge, and a new element's label is read back from `lb.fine`, which this wave alone wrote before the
@@ -321,53 +321,48 @@ extern "C" int nr3d_neus_upsample_stage(uint32_t R, uint32_t n, uint32_t m, cons
 
 extern "C" int nr3d_neus_upsample_packed_lds_row(void) { return neus_upsample::kPackedLdsRow; }
 
-// the checks and the launch of both packed entries; `fn` names the entry in the messages
+// LABELS picks the instantiation; `labels` is the kernel argument as the entry filled it
 template <bool LABELS>
-static int launch_stage_packed(const char *fn, uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf,
-                               const int64_t *pack_infos, const float *u, int64_t u_stride, float inv_s, int use_estimate, int merge,
-                               int need_sdf, float *cdf_workspace, float *fine, float *merged, float *sdf_merged, int64_t *pidx_fine,
-                               int64_t *pack_infos_out, const neus_upsample::Labels<LABELS> labels, void *stream) {
-	NR3D_CHECK(m >= 1, "%s: m = %u, at least 1 new depth per pack", fn, m);
-	NR3D_CHECK(u_stride == 0 || u_stride == (int64_t)m, "%s: u_stride = %lld, must be 0 (one shared row) or m = %u", fn,
-	           (long long)u_stride, m);
-	NR3D_CHECK(N < (1ull << 31) && N + (uint64_t)P * m < (1ull << 31),
-	           "%s: N + P m = %llu + %u * %u, the merged buffer holds at most 2^31 - 1 elements", fn, (unsigned long long)N, P, m);
-	NR3D_CHECK(!need_sdf || merge, "%s: need_sdf without merge", fn);
-	if (P == 0) return 0;
-	NR3D_CHECK(depth && sdf && pack_infos && u && cdf_workspace && fine, "%s: NULL tensor pointer", fn);
-	NR3D_CHECK(!merge || (merged && pidx_fine && pack_infos_out), "%s: merge without merged, pidx_fine or pack_infos_out", fn);
-	NR3D_CHECK(!need_sdf || sdf_merged, "%s: need_sdf without sdf_merged", fn);
-	if constexpr (LABELS) {
-		NR3D_CHECK(labels.in && labels.fine, "%s: NULL label pointer", fn);
-		NR3D_CHECK(!merge || labels.merged, "%s: merge without blidx_merged", fn);
-	}
+static void launch_stage_packed(uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf, const int64_t *pack_infos,
+                                const float *u, int64_t u_stride, float inv_s, int use_estimate, float *cdf_workspace, float *fine,
+                                float *merged, float *sdf_merged, int64_t *pidx_fine, int64_t *pack_infos_out,
+                                const neus_upsample::Labels<LABELS> labels, hipStream_t st) {
 	const dim3 grid(div_up(P, neus_upsample::kWaves)), block(neus_upsample::kWaves * 64);
-	hipStream_t st = (hipStream_t)stream;
-	float *mg = merge ? merged : nullptr, *sm = need_sdf ? sdf_merged : nullptr;
 	if (use_estimate)
 		hipLaunchKernelGGL((neus_upsample::k_stage_packed<true, LABELS>), grid, block, 0, st, P, (int64_t)N, (int)m, depth, sdf, pack_infos, u,
-		                   u_stride, inv_s, cdf_workspace, fine, mg, sm, pidx_fine, pack_infos_out, labels);
+		                   u_stride, inv_s, cdf_workspace, fine, merged, sdf_merged, pidx_fine, pack_infos_out, labels);
 	else
 		hipLaunchKernelGGL((neus_upsample::k_stage_packed<false, LABELS>), grid, block, 0, st, P, (int64_t)N, (int)m, depth, sdf, pack_infos, u,
-		                   u_stride, inv_s, cdf_workspace, fine, mg, sm, pidx_fine, pack_infos_out, labels);
-	NR3D_LAUNCH_CHECK();
-	return 0;
+		                   u_stride, inv_s, cdf_workspace, fine, merged, sdf_merged, pidx_fine, pack_infos_out, labels);
 }
 
 extern "C" int nr3d_neus_upsample_stage_packed(uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf,
-                                               const int64_t *pack_infos, const float *u, int64_t u_stride, float inv_s, int use_estimate,
-                                               int merge, int need_sdf, float *cdf_workspace, float *fine, float *merged,
-                                               float *sdf_merged, int64_t *pidx_fine, int64_t *pack_infos_out, void *stream) {
-	return launch_stage_packed<false>("neus_upsample_stage_packed", P, N, m, depth, sdf, pack_infos, u, u_stride, inv_s, use_estimate, merge,
-	                                  need_sdf, cdf_workspace, fine, merged, sdf_merged, pidx_fine, pack_infos_out, {}, stream);
-}
-
-extern "C" int nr3d_neus_upsample_stage_packed_blocks(uint32_t P, uint64_t N, uint32_t m, const float *depth, const float *sdf,
-                                                      const int64_t *blidx, const int64_t *pack_infos, const float *u, int64_t u_stride,
-                                                      float inv_s, int use_estimate, int merge, int need_sdf, float *cdf_workspace,
-                                                      float *fine, int64_t *blidx_fine, float *merged, float *sdf_merged,
-                                                      int64_t *blidx_merged, int64_t *pidx_fine, int64_t *pack_infos_out, void *stream) {
-	return launch_stage_packed<true>("neus_upsample_stage_packed_blocks", P, N, m, depth, sdf, pack_infos, u, u_stride, inv_s, use_estimate,
-	                                 merge, need_sdf, cdf_workspace, fine, merged, sdf_merged, pidx_fine, pack_infos_out,
-	                                 {blidx, blidx_fine, merge ? blidx_merged : nullptr}, stream);
+                                               const int64_t *blidx, const int64_t *pack_infos, const float *u, int64_t u_stride,
+                                               float inv_s, int use_estimate, int merge, int need_sdf, float *cdf_workspace, float *fine,
+                                               int64_t *blidx_fine, float *merged, float *sdf_merged, int64_t *blidx_merged,
+                                               int64_t *pidx_fine, int64_t *pack_infos_out, void *stream) {
+	NR3D_CHECK(m >= 1, "neus_upsample_stage_packed: m = %u, at least 1 new depth per pack", m);
+	NR3D_CHECK(u_stride == 0 || u_stride == (int64_t)m, "neus_upsample_stage_packed: u_stride = %lld, must be 0 (one shared row) or m = %u",
+	           (long long)u_stride, m);
+	NR3D_CHECK(N < (1ull << 31) && N + (uint64_t)P * m < (1ull << 31),
+	           "neus_upsample_stage_packed: N + P m = %llu + %u * %u, the merged buffer holds at most 2^31 - 1 elements",
+	           (unsigned long long)N, P, m);
+	NR3D_CHECK(!need_sdf || merge, "neus_upsample_stage_packed: need_sdf without merge");
+	NR3D_CHECK(!blidx || blidx_fine, "neus_upsample_stage_packed: blidx without blidx_fine");
+	NR3D_CHECK(blidx || (!blidx_fine && !blidx_merged), "neus_upsample_stage_packed: blidx_fine or blidx_merged without blidx");
+	NR3D_CHECK(!(merge && blidx) || blidx_merged, "neus_upsample_stage_packed: merge with blidx but without blidx_merged");
+	if (P == 0) return 0;
+	NR3D_CHECK(depth && sdf && pack_infos && u && cdf_workspace && fine, "neus_upsample_stage_packed: NULL tensor pointer");
+	NR3D_CHECK(!merge || (merged && pidx_fine && pack_infos_out),
+	           "neus_upsample_stage_packed: merge without merged, pidx_fine or pack_infos_out");
+	NR3D_CHECK(!need_sdf || sdf_merged, "neus_upsample_stage_packed: need_sdf without sdf_merged");
+	float *mg = merge ? merged : nullptr, *sm = need_sdf ? sdf_merged : nullptr;
+	if (!blidx)   // (named first: the kernels stand in the code object in the order they are instantiated in)
+		launch_stage_packed<false>(P, N, m, depth, sdf, pack_infos, u, u_stride, inv_s, use_estimate, cdf_workspace, fine, mg, sm, pidx_fine,
+		                           pack_infos_out, {}, (hipStream_t)stream);
+	else
+		launch_stage_packed<true>(P, N, m, depth, sdf, pack_infos, u, u_stride, inv_s, use_estimate, cdf_workspace, fine, mg, sm, pidx_fine,
+		                          pack_infos_out, {blidx, blidx_fine, merge ? blidx_merged : nullptr}, (hipStream_t)stream);
+	NR3D_LAUNCH_CHECK();
+	return 0;
 }

@@ -11,9 +11,9 @@ Model protocol: ``space`` (ForestBlockSpace), ``accel`` (OccGridAccelForest; the
 What sets the forest apart from the single-block drivers of ``neus_ray_query``: every sample carries the index of the block it is
 evaluated in.  A new depth inherits the block of the CDF bin it was drawn from, the block indices are merged along with the
 depths, and every SDF query takes ``(x, block_inds)``.  The multi-factor loops -- the march-occ pair's and 'multistep_estimate'
-of the coarse driver -- share ``_upsample_loop``.  While ``FUSED_UPSAMPLE_FOREST`` is set it runs one launch of
-``bindings._neus_upsample.upsample_stage_packed_blocks`` per factor for float32 samples on the GPU; otherwise, and for every
-other input, the reference's pack-op chain.  Both draw the same CDF positions (``cdf_positions``).
+of the coarse driver -- are ``_packed_upsample.upsample_loop``, the loop of the single-block drivers, given the block indices as
+labels.  While ``FUSED_UPSAMPLE_FOREST`` is set it runs one launch of ``bindings._neus_upsample.upsample_stage_packed_blocks`` per
+factor for float32 samples on the GPU; otherwise, and for every other input, the reference's pack-op chain.
 
 Against the reference: ``space.ray_step_coarse`` returns a dict here and the drivers use its keys; the one-factor branch of the
 march-occ pair takes ``blidxs_1[0]`` where the reference has ``depths_1[0]`` (:377, :579); the final ``forward`` of the march-occ
@@ -24,22 +24,19 @@ from typing import Dict, List, Tuple
 
 import torch
 
-from nr3d_lib_amd.bindings import _neus_upsample
 from nr3d_lib_amd.graphics._ray_query import _chunked
-from nr3d_lib_amd.graphics.nerf.nerf_utils import packed_alpha_to_vw
-from nr3d_lib_amd.graphics.neus.neus_utils import (neus_packed_sdf_to_alpha, neus_packed_sdf_to_upsample_alpha,
-                                                   neus_ray_sdf_to_alpha)
-from nr3d_lib_amd.graphics.pack_ops import (get_pack_infos_from_batch, merge_two_packs_sorted_a_includes_b,
-                                            merge_two_packs_sorted_aligned, packed_cumsum, packed_diff, packed_div,
-                                            packed_invert_cdf, packed_volume_render_compression)
-from nr3d_lib_amd.graphics.raysample import cdf_positions
+from nr3d_lib_amd.graphics.neus._packed_upsample import union, upsample_loop
+from nr3d_lib_amd.graphics.neus.neus_utils import neus_packed_sdf_to_alpha, neus_ray_sdf_to_alpha
+from nr3d_lib_amd.graphics.pack_ops import (get_pack_infos_from_batch, merge_two_packs_sorted_a_includes_b, packed_diff,
+                                            packed_volume_render_compression)
 from nr3d_lib_amd.profile import profile
 
 __all__ = ['neus_forest_ray_query_coarse_multi_upsample', 'neus_forest_ray_query_march_occ_multi_upsample',
            'neus_forest_ray_query_march_occ_multi_upsample_compressed']
 
-# One up-sampling stage of _upsample_loop: True = one launch of the block-carrying packed HIP kernel per factor for float32 samples on
-# the GPU, no union on the last factor; False (and every other input) = the reference's pack-op chain.  Same semantics.
+# One up-sampling stage of the loop (read at call time and handed to it as `fused`): True = one launch of the block-carrying packed
+# HIP kernel per factor for float32 samples on the GPU, no union on the last factor; False (and every other input) = the reference's
+# pack-op chain.  Same semantics.
 # Measured (profiles/neus_forest_query.json, tools/exp_neus_forest_query.py): the fused route's median is below the chain's in every row.
 FUSED_UPSAMPLE_FOREST = True
 
@@ -85,69 +82,21 @@ def _setup(model, ray_tested, forward_inv_s, upsample_inv_s, with_rgb, with_norm
     return q
 
 
-def _union(depth, blidx, pack_infos, fine, blidx_fine):
-    """the new depths [P, m] and their block indices joined to the packed ones, sorted per pack (a new depth before an equal old one)
-    -> (depth, blidx, pack_infos, pidx of the old, pidx of the new elements)"""
-    pinfo_fine = get_pack_infos_from_batch(fine.shape[0], fine.shape[1], device=fine.device)
-    pidx0, pidx1, pinfo = merge_two_packs_sorted_aligned(depth, pack_infos, fine.flatten(), pinfo_fine, b_sorted=True, return_val=False)
-    total = depth.numel() + fine.numel()
-    d_new, b_new = depth.new_empty([total]), blidx.new_empty([total])
-    d_new[pidx0], d_new[pidx1] = depth, fine.flatten()
-    b_new[pidx0], b_new[pidx1] = blidx, blidx_fine.flatten()
-    return d_new, b_new, pinfo, pidx0, pidx1
-
-
-@torch.no_grad()
-def _upsample_loop(q, o_packs, d_packs, depth, sdf, blidx, pack_infos, num_fine, factors, use_estimate_alpha, perturb):
-    """the multi-factor up-sampling on packed samples: o_packs, d_packs [P, 3] the ray of every pack; depth, sdf, blidx [N] packed by
-    pack_infos [P, 2], which tile [0, N).  Per factor ``num_fine`` new depths per pack from the up-sampling CDF at
-    ``upsample_inv_s * factor``, each with the block index of the upper end of its CDF bin; between factors they join the packed
-    buffer and ``model.forward_sdf(x_fine, blidx_fine)`` fills in their SDF.  The union behind the last factor is left to the caller.
-    -> (the new depths per factor [P, num_fine], their block indices likewise, (depth, blidx, pack_infos) as the last factor saw them)"""
-    n_stages, P = len(factors), pack_infos.shape[0]
-    o_packs, d_packs = o_packs.unsqueeze(-2), d_packs.unsqueeze(-2)
-    fines, blidx_fines = [], []
-    fused = FUSED_UPSAMPLE_FOREST and depth.is_cuda and depth.dtype == torch.float32 and sdf.dtype == torch.float32 \
-        and blidx.dtype == torch.int64
-    for i, factor in enumerate(factors):
-        inv_s, more = q.upsample_inv_s * factor, i < n_stages - 1
-        u = cdf_positions(depth, (P,), num_fine, perturb)
-        if fused:
-            fine, blidx_fine, merged, sdf_m, blidx_m, pidx1, pinfo = _neus_upsample.upsample_stage_packed_blocks(
-                depth.contiguous(), sdf.contiguous(), blidx.contiguous(), pack_infos, u, inv_s, use_estimate_alpha, merge=more,
-                need_sdf=more)
-        else:
-            # the reference's op chain (fused=False: no kernel of neus_utils.FUSED_SDF_TO_ALPHA either)
-            alpha = (neus_packed_sdf_to_upsample_alpha(sdf, depth, inv_s, pack_infos) if use_estimate_alpha
-                     else neus_packed_sdf_to_alpha(sdf, inv_s, pack_infos, fused=False))
-            cdf = packed_cumsum(packed_alpha_to_vw(alpha, pack_infos), pack_infos, exclusive=True)
-            last = cdf[pack_infos[..., 0] + pack_infos[..., 1] - 1]
-            cdf = packed_div(cdf, last.clamp_min(1e-5), pack_infos)
-            fine, pidx_bin = packed_invert_cdf(depth, cdf.to(depth.dtype), u.expand(P, num_fine).contiguous(), pack_infos)
-            blidx_fine = blidx[pidx_bin]
-        fines.append(fine)
-        blidx_fines.append(blidx_fine)
-        if not more:
-            break
-        x_fine = torch.addcmul(o_packs, d_packs, fine.unsqueeze(-1)).flatten(0, -2)
-        sdf_fine = q.sdf(x_fine, blidx_fine.flatten()).flatten()
-        if fused:
-            sdf_m[pidx1.flatten()] = sdf_fine.to(sdf_m.dtype)
-        else:
-            merged, blidx_m, pinfo, pidx0, pidx1 = _union(depth, blidx, pack_infos, fine, blidx_fine)
-            sdf_m = sdf.new_empty([merged.numel()])
-            sdf_m[pidx0], sdf_m[pidx1] = sdf, sdf_fine.to(sdf.dtype)
-        depth, sdf, blidx, pack_infos = merged, sdf_m, blidx_m, pinfo
-    return fines, blidx_fines, (depth, blidx, pack_infos)
+def _upsample_loop(q, hit, depth, sdf, blidx, pack_infos, num_fine, factors, use_estimate_alpha, perturb):
+    """``_packed_upsample.upsample_loop`` on the packs of the rays `hit`, every sample with its block index: ``num_fine`` new depths per
+    factor, ``model.forward_sdf(x_fine, blidx_fine)`` between factors"""
+    return upsample_loop(q.rays_o[hit], q.rays_d[hit], depth, sdf, pack_infos, blidx, [num_fine] * len(factors), factors, q.upsample_inv_s,
+                         use_estimate_alpha, perturb, FUSED_UPSAMPLE_FOREST,
+                         lambda x, blidx_fine: q.sdf(x.flatten(0, -2), blidx_fine.flatten()))
 
 
 def _one_stage(q, ret, num_fine, use_estimate_alpha, perturb, chunk=None):
     """'direct_use' / 'direct_more': one stage of ``num_fine`` new depths on the stepped samples `ret`, joined to them
     -> (depth, blidx, pack_infos, the ray of every pack)"""
     sdf = q.sdf(ret['samples'], ret['blidx'], chunk)
-    fines, blidx_fines, _ = _upsample_loop(q, q.rays_o[ret['ridx_hit']], q.rays_d[ret['ridx_hit']], ret['depth_samples'], sdf,
-                                           ret['blidx'], ret['pack_infos'], num_fine, [1], use_estimate_alpha, perturb)
-    return (*_union(ret['depth_samples'], ret['blidx'], ret['pack_infos'], fines[0], blidx_fines[0])[:3], ret['ridx_hit'])
+    fines, blidx_fines, _ = _upsample_loop(q, ret['ridx_hit'], ret['depth_samples'], sdf, ret['blidx'], ret['pack_infos'], num_fine, [1],
+                                           use_estimate_alpha, perturb)
+    return (*union(ret['depth_samples'], ret['blidx'], ret['pack_infos'], fines[0], blidx_fines[0])[:3], ret['ridx_hit'])
 
 
 def neus_forest_ray_query_coarse_multi_upsample(
@@ -178,10 +127,10 @@ def neus_forest_ray_query_coarse_multi_upsample(
         if upsample_mode == 'multistep_estimate':
             hit = coarse['ridx_hit']
             fines, blidx_fines, state = _upsample_loop(
-                q, q.rays_o[hit], q.rays_d[hit], coarse['depth_samples'], q.sdf(coarse['samples'], coarse['blidx']), coarse['blidx'],
-                coarse['pack_infos'], num_fine // 2 * 2 + 1, upsample_inv_s_factors, upsample_use_estimate_alpha, perturb)
+                q, hit, coarse['depth_samples'], q.sdf(coarse['samples'], coarse['blidx']), coarse['blidx'], coarse['pack_infos'],
+                num_fine // 2 * 2 + 1, upsample_inv_s_factors, upsample_use_estimate_alpha, perturb)
             if len(upsample_inv_s_factors) > 1:
-                return (*_union(*state, fines[-1], blidx_fines[-1])[:3], hit)
+                return (*union(*state, fines[-1], blidx_fines[-1])[:3], hit)
             return (*state, hit)
         raise RuntimeError(f"Invalid upsample_mode={upsample_mode}")
 
@@ -212,8 +161,8 @@ def _march_and_upsample(q, perturb, coarse_step_cfg, chunksize_query, march_cfg,
         hit = marched.ridx_hit
         sdf = _chunked(lambda x, block_inds: model.forward_sdf(x, block_inds)['sdf'],
                        dict(x=marched.samples, block_inds=marched.blidx), chunksize_query)
-        fines, blidx_fines, _ = _upsample_loop(q, q.rays_o[hit], q.rays_d[hit], marched.depth_samples, sdf, marched.blidx,
-                                               marched.pack_infos.clone(), num_fine // 2 * 2 + 1, factors, use_estimate_alpha, perturb)
+        fines, blidx_fines, _ = _upsample_loop(q, hit, marched.depth_samples, sdf, marched.blidx, marched.pack_infos.clone(),
+                                               num_fine // 2 * 2 + 1, factors, use_estimate_alpha, perturb)
         if len(factors) > 1:
             depths_1, order = torch.cat(fines, dim=-1).sort(dim=-1)
             blidxs_1 = torch.cat(blidx_fines, dim=-1).gather(-1, order)

@@ -13,7 +13,8 @@ opacity -> ``packed_alpha_to_vw`` -> exclusive ``packed_cumsum`` normalised with
 ``neus_ray_query_coarse_multi_upsample`` (:132-356) is the vanilla NeuS query that needs no occupancy grid: coarse boundaries on
 every ray between ``near`` and ``far``, the up-sampling on fixed-length rows, one query at the mid-points.  Its stage runs in one
 launch (``bindings._neus_upsample.upsample_stage``) while ``FUSED_UPSAMPLE`` is set.  The stage of the march-occ drivers runs in
-one launch on the packs (``upsample_stage_packed``) while ``FUSED_UPSAMPLE_PACKED`` is set, in place of the pack-op chain above.
+one launch on the packs (``upsample_stage_packed``) while ``FUSED_UPSAMPLE_PACKED`` is set, in place of the pack-op chain above;
+the loop itself is ``_packed_upsample.upsample_loop``, which the forest drivers of ``neus_forest_ray_query`` share.
 The opacity of the final samples (``neus_ray_sdf_to_alpha`` / ``neus_packed_sdf_to_alpha``) is one launch each way while
 ``neus_utils.FUSED_SDF_TO_ALPHA`` is set; the op chains of the two switches above, when off, pass ``fused=False``."""
 from types import SimpleNamespace
@@ -24,14 +25,13 @@ import torch.nn.functional as F
 
 from nr3d_lib_amd.bindings import _neus_upsample
 from nr3d_lib_amd.graphics._ray_query import _chunked, _flag, _march
-from nr3d_lib_amd.graphics.nerf.nerf_utils import packed_alpha_to_vw, ray_alpha_to_vw
-from nr3d_lib_amd.graphics.neus.neus_utils import (neus_packed_sdf_to_alpha, neus_packed_sdf_to_upsample_alpha,
-                                                   neus_ray_sdf_to_alpha, neus_ray_sdf_to_upsample_alpha)
-from nr3d_lib_amd.graphics.pack_ops import (get_pack_infos_from_batch, merge_two_batch_a_includes_b,
-                                            merge_two_packs_sorted_aligned, packed_cumsum, packed_diff, packed_div,
+from nr3d_lib_amd.graphics.nerf.nerf_utils import ray_alpha_to_vw
+from nr3d_lib_amd.graphics.neus._packed_upsample import upsample_loop
+from nr3d_lib_amd.graphics.neus.neus_utils import neus_packed_sdf_to_alpha, neus_ray_sdf_to_alpha, neus_ray_sdf_to_upsample_alpha
+from nr3d_lib_amd.graphics.pack_ops import (get_pack_infos_from_batch, merge_two_batch_a_includes_b, packed_diff,
                                             packed_volume_render_compression)
 from nr3d_lib_amd.graphics.raysample import (batch_sample_pdf, batch_sample_step_linear, batch_sample_step_wrt_depth,
-                                             batch_sample_step_wrt_sqrt_depth, cdf_positions, packed_sample_cdf)
+                                             batch_sample_step_wrt_sqrt_depth, cdf_positions)
 from nr3d_lib_amd.profile import profile
 
 __all__ = ['neus_ray_query_sphere_trace', 'neus_ray_query_coarse_multi_upsample', 'neus_ray_query_march_occ_multi_upsample',
@@ -40,8 +40,9 @@ __all__ = ['neus_ray_query_sphere_trace', 'neus_ray_query_coarse_multi_upsample'
 # The stage of neus_ray_query_coarse_multi_upsample between two SDF queries: True = one launch of the HIP kernel for rows that are
 # float32, on the GPU and within _neus_upsample.MAX_ROW; False (and every other row) = the reference's torch op chain.  Same semantics.
 FUSED_UPSAMPLE = True
-# The stage of the march-occ drivers (_upsample): True = one launch of the packed HIP kernel per stage for float32 samples on the GPU,
-# no merge on the last stage; False (and every other input) = the reference's pack-op chain.  Same semantics.
+# The stage of the march-occ drivers (read at call time and handed to _packed_upsample.upsample_loop as `fused`): True = one launch of the
+# packed HIP kernel per stage for float32 samples on the GPU, no merge on the last stage; False (and every other input) = the
+# reference's pack-op chain.  Same semantics.
 FUSED_UPSAMPLE_PACKED = True
 
 _RAY_ATTRS = (('ts', 'rays_ts'), ('fidx', 'rays_fidx'), ('bidx', 'rays_bidx'), ('pix', 'rays_pix'),
@@ -105,7 +106,16 @@ def _setup(model, ray_tested, with_rgb, with_normal, nablas_has_grad, forward_in
                 buf[k] = out[k].to(q.dtype)
         return buf
 
-    q.attrs, q.spread, q.query_sdf, q.full_query = attrs, spread, query_sdf, full_query
+    def finish(vb, rays_sel, pts, pick):
+        """the last two steps of every volume buffer: ``rays_bidx_hit`` of its rays (`rays_sel` indexes the tested rays, None: all of
+        them) and the full query at ``pts()`` with the per-ray extras laid out by `pick`"""
+        if q.full_uses['bidx']:
+            vb['rays_bidx_hit'] = ray_tested['rays_bidx'] if rays_sel is None else ray_tested['rays_bidx'][rays_sel]
+        if with_rgb or with_normal:
+            vb.update(full_query(pts(), q.full_attrs(pick)))
+        return vb
+
+    q.attrs, q.spread, q.query_sdf, q.full_query, q.finish = attrs, spread, query_sdf, full_query, finish
     q.sdf_attrs = lambda pick: attrs(q.sdf_uses, q.sdf_view, pick)
     q.full_attrs = lambda pick: attrs(q.full_uses, q.full_view, pick)
     return q
@@ -126,59 +136,49 @@ def _sdf_maybe_chunked(q, x, extra, chunksize_query):
     return _chunked(lambda x, **kw: q.query_sdf(x, kw), dict(x=x, **extra), chunksize_query)
 
 
-@torch.no_grad()
-def _upsample(q, marched, upsample_inv_s_factors, upsample_use_estimate_alpha, perturb, chunksize_query):
-    """the multi-stage up-sampling on the marched samples -> (fine depths [n_hit, sum(num_fine)] sorted per ray,
-    the stage (1-based) every fine depth came from)"""
-    hit, n_hit, device = marched.ridx_hit, marched.num_hit_rays, q.device
-    o_hit, d_hit = q.rays_o[hit].unsqueeze(-2), q.rays_d[hit].unsqueeze(-2)
-    pack_infos = marched.pack_infos.clone()
-    depth_samples = marched.depth_samples
-    sdf = _chunked(lambda x, **kw: q.query_sdf(x, kw),
-                   dict(x=marched.samples, **q.sdf_attrs(lambda t: t[marched.ridx])), chunksize_query)
-    stage_depths = []
-    fused = FUSED_UPSAMPLE_PACKED and depth_samples.is_cuda and depth_samples.dtype == torch.float32 and sdf.dtype == torch.float32
-    for i, factor in enumerate(upsample_inv_s_factors):
-        inv_s = q.upsample_inv_s * factor
-        if fused:
-            more = i < q.n_stages - 1                      # the last stage's union is read by nobody
-            u = cdf_positions(depth_samples, (n_hit,), q.num_fine[i], perturb)
-            fine, merged, sdf_m, pidx1, pinfo = _neus_upsample.upsample_stage_packed(
-                depth_samples.contiguous(), sdf.contiguous(), pack_infos, u, inv_s, upsample_use_estimate_alpha, merge=more, need_sdf=more)
-            stage_depths.append(fine)
-            if more:
-                x_fine = torch.addcmul(o_hit, d_hit, fine.unsqueeze(-1)).flatten(0, -2)
-                extra = {k: v.flatten(0, 1) for k, v in q.sdf_attrs(q.spread(hit, q.num_fine[i])).items()}
-                sdf_m[pidx1.flatten()] = q.query_sdf(x_fine, extra).to(sdf_m.dtype)
-                depth_samples, sdf, pack_infos = merged, sdf_m, pinfo
-            continue
-        alpha = (neus_packed_sdf_to_upsample_alpha(sdf, depth_samples, inv_s, pack_infos) if upsample_use_estimate_alpha
-                 else neus_packed_sdf_to_alpha(sdf, inv_s, pack_infos, fused=False))     # this route stays the reference's op chain
-        cdf = packed_cumsum(packed_alpha_to_vw(alpha, pack_infos), pack_infos, exclusive=True)
-        last = cdf[pack_infos[..., 0] + pack_infos[..., 1] - 1]
-        cdf = packed_div(cdf, last.clamp_min(1e-5), pack_infos)
-        fine = packed_sample_cdf(depth_samples, cdf.to(depth_samples.dtype), pack_infos, q.num_fine[i], perturb=perturb)[0]
-        stage_depths.append(fine)
-        if q.n_stages > 1:
-            # the new depths join the packed buffer (sorted merge per ray) for the next, sharper stage
-            pinfo_fine = get_pack_infos_from_batch(n_hit, q.num_fine[i], device=device)
-            pidx0, pidx1, pack_infos = merge_two_packs_sorted_aligned(depth_samples, pack_infos, fine.flatten(), pinfo_fine,
-                                                                      b_sorted=True, return_val=False)
-            merged = depth_samples.new_empty(depth_samples.numel() + fine.numel())
-            merged[pidx0], merged[pidx1] = depth_samples, fine.flatten()
-            if i < q.n_stages - 1:
-                x_fine = torch.addcmul(o_hit, d_hit, fine.unsqueeze(-1)).flatten(0, -2)
-                extra = {k: v.flatten(0, 1) for k, v in q.sdf_attrs(q.spread(hit, q.num_fine[i])).items()}
-                sdf_m = sdf.new_empty(merged.numel())
-                sdf_m[pidx0], sdf_m[pidx1] = sdf, q.query_sdf(x_fine, extra)
-                sdf = sdf_m
-            depth_samples = merged
-    if q.n_stages > 1:
-        order = torch.cat(stage_depths, dim=-1).sort(dim=-1)
-        stage_of = torch.repeat_interleave(1 + torch.arange(q.n_stages, device=device),
-                                           torch.tensor(q.num_fine, device=device))
-        return order.values, stage_of[order.indices]
-    return stage_depths[0], torch.ones_like(stage_depths[0], dtype=torch.long)
+def _march_and_upsample(q, perturb, num_coarse, coarse_step_cfg, chunksize_query, march_cfg, factors, use_estimate_alpha,
+                        want_stages=False):
+    """the front half of the march-occ pair -> (coarse boundaries [num_rays, num_coarse + 1] and their spacings | None, None, the marcher's
+    record, and for hit rays the new depths [num_hit, sum(num_fine)] sorted per ray, with `want_stages` the factor (1-based) each came
+    from | None)"""
+    depths_coarse_1, deltas_coarse_1 = _coarse_boundaries(q, num_coarse, coarse_step_cfg, perturb) if num_coarse > 0 else (None, None)
+    with profile("Ray marching"):
+        marched = _march(q.model, q.ray_tested, q.rays_o, q.rays_d, q.near, q.far, perturb, march_cfg)
+    if marched.ridx_hit is None:
+        return depths_coarse_1, deltas_coarse_1, marched, None, None
+    with profile("Upsampling"), torch.no_grad():
+        hit = marched.ridx_hit
+        sdf = _chunked(lambda x, **kw: q.query_sdf(x, kw),
+                       dict(x=marched.samples, **q.sdf_attrs(lambda t: t[marched.ridx])), chunksize_query)
+
+        def sdf_at(x, _):
+            extra = {k: v.flatten(0, 1) for k, v in q.sdf_attrs(q.spread(hit, x.shape[1])).items()}
+            return q.query_sdf(x.flatten(0, -2), extra)
+
+        fines, _, _ = upsample_loop(q.rays_o[hit], q.rays_d[hit], marched.depth_samples, sdf, marched.pack_infos.clone(), None, q.num_fine,
+                                    factors, q.upsample_inv_s, use_estimate_alpha, perturb, FUSED_UPSAMPLE_PACKED, sdf_at)
+        depths_1, order = torch.cat(fines, dim=-1).sort(dim=-1) if q.n_stages > 1 else (fines[0], None)
+        stages = None
+        if want_stages:                                    # only debug_query_data reads them, and repeat_interleave waits for the host
+            stage_of = torch.repeat_interleave(1 + torch.arange(q.n_stages, device=q.device), torch.tensor(q.num_fine, device=q.device))
+            stages = stage_of.expand_as(depths_1) if order is None else stage_of[order]
+    return depths_coarse_1, deltas_coarse_1, marched, depths_1, stages
+
+
+def _join_coarse(depths_coarse_1, hit, depths_1, stages=None):
+    """coarse boundaries of every ray + the new depths of the hit rays, sorted per ray -> (ridx, depth, pack_infos, the factor every
+    element came from: 0 for a coarse boundary | None without `stages`), packed over ALL tested rays"""
+    all_rays = torch.arange(depths_coarse_1.shape[0], device=depths_1.device)
+    pidx0, pidx1, pack_infos = merge_two_batch_a_includes_b(depths_coarse_1, all_rays, depths_1, hit, a_sorted=True)
+    total = depths_1.numel() + depths_coarse_1.numel()
+    depth, ridx = depths_1.new_zeros(total), hit.new_zeros(total)
+    ridx[pidx0], ridx[pidx1] = all_rays.unsqueeze(-1), hit.unsqueeze(-1)
+    depth[pidx0], depth[pidx1] = depths_coarse_1, depths_1
+    stages_p = None
+    if stages is not None:
+        stages_p = stages.new_zeros(total)
+        stages_p[pidx0], stages_p[pidx1] = 0, stages
+    return ridx, depth, pack_infos, stages_p
 
 
 def _row_stage(depth, sdf, num_fine, inv_s, use_estimate_alpha, perturb):
@@ -255,10 +255,7 @@ def neus_ray_query_coarse_multi_upsample(
         if not compression:
             vb = dict(type='batched', rays_inds_hit=rays_inds, num_per_hit=d_mid.size(-1), t=d_mid.to(dtype),
                       opacity_alpha=alpha.to(dtype))
-            if q.full_uses['bidx']:
-                vb['rays_bidx_hit'] = ray_tested['rays_bidx']
-            if with_rgb or with_normal:
-                vb.update(q.full_query(pts(d_mid), q.full_attrs(q.spread(None, d_mid.shape[-1]))))
+            q.finish(vb, None, lambda: pts(d_mid), q.spread(None, d_mid.shape[-1]))
             return vb, {'render.num_per_ray': d_mid.size(-1)}
 
         # `pack_infos` is over all tested rays
@@ -269,12 +266,10 @@ def neus_ray_query_coarse_multi_upsample(
         depths_packed = d_mid.flatten()[pidx_useful]
         vb = dict(type='packed', rays_inds_hit=rays_inds[nidx_useful], pack_infos_hit=pack_infos_useful, t=depths_packed.to(dtype),
                   opacity_alpha=alpha.flatten()[pidx_useful].to(dtype))
-        if q.full_uses['bidx']:
-            vb['rays_bidx_hit'] = ray_tested['rays_bidx'][nidx_useful]
+        ridx = None                                                       # the ray of every kept sample: only the full query asks
         if with_rgb or with_normal:
             ridx = torch.arange(alpha.shape[0], device=device).unsqueeze(-1).expand_as(alpha).flatten()[pidx_useful]
-            vb.update(q.full_query(torch.addcmul(rays_o[ridx], rays_d[ridx], depths_packed.unsqueeze(-1)),
-                                   q.full_attrs(lambda t: t[ridx])))
+        q.finish(vb, nidx_useful, lambda: torch.addcmul(rays_o[ridx], rays_d[ridx], depths_packed.unsqueeze(-1)), lambda t: t[ridx])
         return vb, {'render.num_per_ray0': d_mid.size(-1), 'render.num_per_ray': pack_infos_useful[:, 1]}
 
 
@@ -292,46 +287,32 @@ def neus_ray_query_march_occ_multi_upsample(
         return empty, {}
     q = _setup(model, ray_tested, with_rgb, with_normal, nablas_has_grad, forward_inv_s, num_fine, upsample_inv_s,
                upsample_s_divisor, upsample_inv_s_factors)
-    rays_o, rays_d, rays_inds, device, dtype = q.rays_o, q.rays_d, q.rays_inds, q.device, q.dtype
-    forward_inv_s = q.forward_inv_s
+    rays_o, rays_d, rays_inds, dtype, forward_inv_s = q.rays_o, q.rays_d, q.rays_inds, q.dtype, q.forward_inv_s
+    depths_coarse_1, deltas_coarse_1, marched, depths_1, upsample_stages = _march_and_upsample(
+        q, perturb, num_coarse, coarse_step_cfg, chunksize_query, march_cfg, upsample_inv_s_factors, upsample_use_estimate_alpha,
+        want_stages=debug_query_data is not None)
+    hit = marched.ridx_hit
 
-    if num_coarse > 0:
-        depths_coarse_1, deltas_coarse_1 = _coarse_boundaries(q, num_coarse, coarse_step_cfg, perturb)
-
-    with profile("Ray marching"):
-        marched = _march(model, ray_tested, rays_o, rays_d, q.near, q.far, perturb, march_cfg)
-
-    if marched.ridx_hit is None:
-        if num_coarse == 0:
-            return empty, {}
-        # nothing marched: a batched buffer of the coarse samples on every ray
-        with profile("Acquire volume buffer"):
+    with profile("Acquire volume buffer"):
+        if hit is None:
+            if num_coarse == 0:
+                return empty, {}
+            # nothing marched: a batched buffer of the coarse samples on every ray
             pts = lambda d: torch.addcmul(rays_o[..., None, :], rays_d[..., None, :], d[..., None])
             sdf = q.query_sdf(pts(depths_coarse_1), q.sdf_attrs(q.spread(None, num_coarse + 1)))
             depths = depths_coarse_1[..., :num_coarse] + deltas_coarse_1[..., :num_coarse] / 2.
             vb = dict(type='batched', rays_inds_hit=rays_inds, num_per_hit=num_coarse, t=depths.to(dtype),
                       opacity_alpha=neus_ray_sdf_to_alpha(sdf, forward_inv_s).to(dtype))
-            if q.full_uses['bidx']:
-                vb['rays_bidx_hit'] = ray_tested['rays_bidx']
-            if with_rgb or with_normal:
-                vb.update(q.full_query(pts(depths), q.full_attrs(q.spread(None, num_coarse))))
-        return vb, {'render.num_per_ray': num_coarse}
+            q.finish(vb, None, lambda: pts(depths), q.spread(None, num_coarse))
+            return vb, {'render.num_per_ray': num_coarse}
 
-    hit = marched.ridx_hit
-    rays_inds_hit = rays_inds[hit]
-    o_hit, d_hit = rays_o[hit].unsqueeze(-2), rays_d[hit].unsqueeze(-2)
-    with profile("Upsampling"):
-        depths_1, upsample_stages = _upsample(q, marched, upsample_inv_s_factors, upsample_use_estimate_alpha, perturb,
-                                              chunksize_query)
-
-    details = {'march.num_per_ray': marched.pack_infos[:, 1]}
-    with profile("Acquire volume buffer"):
+        details = {'march.num_per_ray': marched.pack_infos[:, 1]}
         if num_coarse == 0:
             # batched buffer: the fine depths are interval boundaries, samples sit at the interval mid-points
-            k1 = depths_1.shape[-1]
-            x1 = torch.addcmul(o_hit, d_hit, depths_1.unsqueeze(-1))
-            extra1 = q.sdf_attrs(q.spread(hit, k1))
-            sdf = _sdf_maybe_chunked(q, x1, extra1, chunksize_query)
+            rays_inds_hit = rays_inds[hit]
+            o_hit, d_hit = rays_o[hit].unsqueeze(-2), rays_d[hit].unsqueeze(-2)
+            sdf = _sdf_maybe_chunked(q, torch.addcmul(o_hit, d_hit, depths_1.unsqueeze(-1)), q.sdf_attrs(q.spread(hit, depths_1.shape[-1])),
+                                     chunksize_query)
             depths = depths_1[..., :-1] + depths_1.diff(dim=-1) / 2.
             if debug_query_data is not None:
                 debug_query_data["fine"] = dict(ridx=rays_inds_hit[..., None].expand_as(depths).flatten(),
@@ -339,22 +320,12 @@ def neus_ray_query_march_occ_multi_upsample(
                                                 upsample_stages=upsample_stages.flatten())
             vb = dict(type='batched', rays_inds_hit=rays_inds_hit, num_per_hit=depths.size(-1), t=depths.to(dtype),
                       opacity_alpha=neus_ray_sdf_to_alpha(sdf, forward_inv_s).to(dtype))
-            if q.full_uses['bidx']:
-                vb['rays_bidx_hit'] = ray_tested['rays_bidx'][hit]
-            if with_rgb or with_normal:
-                vb.update(q.full_query(torch.addcmul(o_hit, d_hit, depths[..., None]),
-                                       q.full_attrs(q.spread(hit, depths.shape[-1]))))
+            q.finish(vb, hit, lambda: torch.addcmul(o_hit, d_hit, depths[..., None]), q.spread(hit, depths.shape[-1]))
             details['render.num_per_ray'] = depths.size(-1)
             return vb, details
 
         # packed buffer over ALL tested rays: coarse boundaries of every ray + fine depths of the hit rays
-        all_rays = torch.arange(rays_inds.numel(), device=device)
-        pidx0, pidx1, pack_infos = merge_two_batch_a_includes_b(depths_coarse_1, all_rays, depths_1, hit, a_sorted=True)
-        total = depths_1.numel() + depths_coarse_1.numel()
-        depths_1p, stages_p, ridx_all = depths_1.new_zeros(total), upsample_stages.new_zeros(total), hit.new_zeros(total)
-        ridx_all[pidx0], ridx_all[pidx1] = all_rays.unsqueeze(-1), hit.unsqueeze(-1)
-        depths_1p[pidx0], depths_1p[pidx1] = depths_coarse_1, depths_1
-        stages_p[pidx0], stages_p[pidx1] = 0, upsample_stages
+        ridx_all, depths_1p, pack_infos, stages_p = _join_coarse(depths_coarse_1, hit, depths_1, upsample_stages)
         o_p, d_p = rays_o[ridx_all], rays_d[ridx_all]
         sdf_p = q.query_sdf(torch.addcmul(o_p, d_p, depths_1p.unsqueeze(-1)), q.sdf_attrs(lambda t: t[ridx_all]))
         depths_p = depths_1p + packed_diff(depths_1p, pack_infos) / 2.
@@ -366,10 +337,7 @@ def neus_ray_query_march_occ_multi_upsample(
             debug_query_data["fine"]["upsample_stages"] = stages_p[(stages_p > 0).nonzero(as_tuple=True)[0]]
         vb = dict(type='packed', rays_inds_hit=rays_inds, pack_infos_hit=pack_infos, t=depths_p.to(dtype),
                   opacity_alpha=neus_packed_sdf_to_alpha(sdf_p, forward_inv_s, pack_infos).to(dtype))
-        if q.full_uses['bidx']:
-            vb['rays_bidx_hit'] = ray_tested['rays_bidx']
-        if with_rgb or with_normal:
-            vb.update(q.full_query(torch.addcmul(o_p, d_p, depths_p.unsqueeze(-1)), q.full_attrs(lambda t: t[ridx_all])))
+        q.finish(vb, None, lambda: torch.addcmul(o_p, d_p, depths_p.unsqueeze(-1)), lambda t: t[ridx_all])
         details['render.num_per_ray'] = pack_infos[:, 1]
         return vb, details
 
@@ -392,76 +360,57 @@ def neus_ray_query_march_occ_multi_upsample_compressed(
         return empty, {}
     q = _setup(model, ray_tested, with_rgb, with_normal, nablas_has_grad, forward_inv_s, num_fine, upsample_inv_s,
                upsample_s_divisor, upsample_inv_s_factors)
-    rays_o, rays_d, rays_inds, device, dtype = q.rays_o, q.rays_d, q.rays_inds, q.device, q.dtype
-    forward_inv_s = q.forward_inv_s
+    rays_o, rays_d, rays_inds, device, dtype, forward_inv_s = q.rays_o, q.rays_d, q.rays_inds, q.device, q.dtype, q.forward_inv_s
+    depths_coarse_1, deltas_coarse_1, marched, depths_1, _ = _march_and_upsample(
+        q, perturb, num_coarse, coarse_step_cfg, chunksize_query, march_cfg, upsample_inv_s_factors, upsample_use_estimate_alpha)
+    hit = marched.ridx_hit
 
-    if num_coarse > 0:
-        depths_coarse_1, deltas_coarse_1 = _coarse_boundaries(q, num_coarse, coarse_step_cfg, perturb)
-
-    with profile("Ray marching"):
-        marched = _march(model, ray_tested, rays_o, rays_d, q.near, q.far, perturb, march_cfg)
-
-    def compressed_buffer(alpha, depths, ridx, pack_infos, rays_of_packs, bidx_of_packs, details):
-        """alpha / depths / ridx: flat per sample (ridx = index into the tested rays), packs described by pack_infos"""
+    def compressed_buffer(alpha, depths, ridx, pack_infos, rays_of_packs, details):
+        """alpha / depths / ridx: flat per sample (ridx = index into the tested rays), packs described by pack_infos;
+        rays_of_packs: the tested ray of every pack (None: pack p is ray p)"""
         nidx_useful, pack_infos_useful, pidx_useful = packed_volume_render_compression(alpha, pack_infos)
         if nidx_useful.numel() == 0:
             return empty, {}
         depths, alpha, ridx = depths[pidx_useful], alpha[pidx_useful], ridx[pidx_useful]
-        vb = dict(type='packed', rays_inds_hit=rays_of_packs[nidx_useful], pack_infos_hit=pack_infos_useful,
+        rays_useful = nidx_useful if rays_of_packs is None else rays_of_packs[nidx_useful]
+        vb = dict(type='packed', rays_inds_hit=rays_inds[rays_useful], pack_infos_hit=pack_infos_useful,
                   t=depths.to(dtype), opacity_alpha=alpha.to(dtype))
-        if q.full_uses['bidx']:
-            vb['rays_bidx_hit'] = bidx_of_packs()[nidx_useful]
-        if with_rgb or with_normal:
-            vb.update(q.full_query(torch.addcmul(rays_o[ridx], rays_d[ridx], depths.unsqueeze(-1)),
-                                   q.full_attrs(lambda t: t[ridx])))
+        q.finish(vb, rays_useful, lambda: torch.addcmul(rays_o[ridx], rays_d[ridx], depths.unsqueeze(-1)), lambda t: t[ridx])
         details['render.num_per_ray'] = pack_infos_useful[:, 1]
         return vb, details
 
-    if marched.ridx_hit is None:
-        if num_coarse == 0:
-            return empty, {}
-        with profile("Acquire volume buffer"):
+    with profile("Acquire volume buffer"):
+        if hit is None:
+            if num_coarse == 0:
+                return empty, {}
             x = torch.addcmul(rays_o[..., None, :], rays_d[..., None, :], depths_coarse_1[..., None])
             sdf = _sdf_maybe_chunked(q, x, q.sdf_attrs(q.spread(None, num_coarse + 1)), chunksize_query)
             alpha = neus_ray_sdf_to_alpha(sdf, forward_inv_s)
             depths = depths_coarse_1[..., :num_coarse] + deltas_coarse_1[..., :num_coarse] / 2.
             n = rays_inds.numel()
             ridx = torch.arange(n, device=device).unsqueeze(-1).expand_as(depths).flatten()
-            return compressed_buffer(alpha.flatten(), depths.flatten(), ridx,
-                                     get_pack_infos_from_batch(n, depths.size(-1), device=device), rays_inds,
-                                     lambda: ray_tested['rays_bidx'], {'render.num_per_ray0': depths.size(-1)})
+            return compressed_buffer(alpha.flatten(), depths.flatten(), ridx, get_pack_infos_from_batch(n, depths.size(-1), device=device),
+                                     None, {'render.num_per_ray0': depths.size(-1)})
 
-    hit = marched.ridx_hit
-    with profile("Upsampling"):
-        depths_1, _ = _upsample(q, marched, upsample_inv_s_factors, upsample_use_estimate_alpha, perturb, chunksize_query)
-
-    details = {'march.num_per_ray': marched.pack_infos[:, 1]}
-    with profile("Acquire volume buffer"):
+        details = {'march.num_per_ray': marched.pack_infos[:, 1]}
         if num_coarse == 0:
             o_hit, d_hit = rays_o[hit].unsqueeze(-2), rays_d[hit].unsqueeze(-2)
-            k1 = depths_1.shape[-1]
-            sdf = _sdf_maybe_chunked(q, torch.addcmul(o_hit, d_hit, depths_1.unsqueeze(-1)), q.sdf_attrs(q.spread(hit, k1)),
+            sdf = _sdf_maybe_chunked(q, torch.addcmul(o_hit, d_hit, depths_1.unsqueeze(-1)), q.sdf_attrs(q.spread(hit, depths_1.shape[-1])),
                                      chunksize_query)
             alpha = neus_ray_sdf_to_alpha(sdf, forward_inv_s)
             depths = depths_1[..., :-1] + depths_1.diff(dim=-1) / 2.
             details['render.num_per_ray0'] = depths.size(-1)
             return compressed_buffer(alpha.flatten(), depths.flatten(), hit.unsqueeze(-1).expand_as(depths).flatten(),
-                                     get_pack_infos_from_batch(marched.num_hit_rays, depths.size(-1), device=device),
-                                     rays_inds[hit], lambda: ray_tested['rays_bidx'][hit], details)
+                                     get_pack_infos_from_batch(marched.num_hit_rays, depths.size(-1), device=device), hit, details)
 
         # coarse boundaries of every ray + fine depths of the hit rays, merged per ray; then compressed
-        all_rays = torch.arange(rays_inds.numel(), device=device)
-        pidx0, pidx1, pack_infos = merge_two_batch_a_includes_b(depths_coarse_1, all_rays, depths_1, hit, a_sorted=True)
-        total = depths_1.numel() + depths_coarse_1.numel()
-        depths_1p, ridx_all = depths_1.new_zeros(total), hit.new_zeros(total)
-        ridx_all[pidx0], ridx_all[pidx1] = all_rays.unsqueeze(-1), hit.unsqueeze(-1)
-        depths_1p[pidx0], depths_1p[pidx1] = depths_coarse_1, depths_1
+        ridx_all, depths_1p, pack_infos, _ = _join_coarse(depths_coarse_1, hit, depths_1)
         depths_p = depths_1p + packed_diff(depths_1p, pack_infos) / 2.
         sdf_p = _sdf_maybe_chunked(q, torch.addcmul(rays_o[ridx_all], rays_d[ridx_all], depths_1p.unsqueeze(-1)),
                                    q.sdf_attrs(lambda t: t[ridx_all]), chunksize_query)
         alpha_p = neus_packed_sdf_to_alpha(sdf_p, forward_inv_s, pack_infos)
         details['render.num_per_ray0'] = pack_infos[:, 1]
-        return compressed_buffer(alpha_p, depths_p, ridx_all, pack_infos, rays_inds, lambda: ray_tested['rays_bidx'], details)
+        return compressed_buffer(alpha_p, depths_p, ridx_all, pack_infos, None, details)
 
 
 def neus_ray_query_march_occ_multi_upsample_compressed_strategy(model, ray_tested: Dict[str, torch.Tensor], **kwargs):

@@ -202,12 +202,11 @@ def test_ray_step_coarse_modes(monkeypatch):
 
 def test_abi_lists_the_blocks_stage():
     assert _abi.ABI_VERSION >= 27
-    ret, args = _abi.SIGNATURES['nr3d_neus_upsample_stage_packed_blocks']
+    # the labelled argument list, under the one packed entry's name since ABI 28: the unlabelled call passes NULL for the three
+    ret, args = _abi.SIGNATURES['nr3d_neus_upsample_stage_packed']
     assert ret == 'int' and args == ['uint32_t', 'uint64_t', 'uint32_t'] + ['ptr'] * 5 + ['int64_t', 'float', 'int', 'int', 'int'] \
         + ['ptr'] * 8 + ['ptr']
-    # the unlabelled entry is as it was
-    assert _abi.SIGNATURES['nr3d_neus_upsample_stage_packed'][1] == ['uint32_t', 'uint64_t', 'uint32_t'] + ['ptr'] * 4 \
-        + ['int64_t', 'float', 'int', 'int', 'int'] + ['ptr'] * 6 + ['ptr']
+    assert 'nr3d_neus_upsample_stage_packed_blocks' not in _abi.SIGNATURES
 
 
 def test_binding_refuses_cpu_tensors_and_non_tensors():

@@ -68,8 +68,10 @@ def test_merge_puts_a_new_depth_before_an_equal_old_one(oracle):
 def test_abi_lists_the_packed_stage():
     assert _abi.ABI_VERSION >= 18
     ret, args = _abi.SIGNATURES['nr3d_neus_upsample_stage_packed']
-    assert ret == 'int' and args == ['uint32_t', 'uint64_t', 'uint32_t'] + ['ptr'] * 4 + ['int64_t', 'float', 'int', 'int', 'int'] \
-        + ['ptr'] * 6 + ['ptr']
+    # one entry for packs with and without labels (ABI 28): blidx after sdf, blidx_fine after fine, blidx_merged after sdf_merged
+    assert ret == 'int' and args == ['uint32_t', 'uint64_t', 'uint32_t'] + ['ptr'] * 5 + ['int64_t', 'float', 'int', 'int', 'int'] \
+        + ['ptr'] * 8 + ['ptr']
+    assert 'nr3d_neus_upsample_stage_packed_blocks' not in _abi.SIGNATURES
     assert _abi.SIGNATURES['nr3d_neus_upsample_packed_lds_row'] == ('int', [])
 
 
@@ -87,3 +89,38 @@ def test_parity_inputs_meet_the_preconditions(lds_row, inv_s, est):
     assert exact[pi[:, 1] <= 2].all(), "packs of one and two elements carry no mass here"
     r32 = ref.stage(depth, sdf, pi, cref.shared_u(m), float(inv_s), est, torch.float32)
     assert torch.equal(r32['fine'][exact].double(), r64['fine'][exact])
+
+
+def test_entry_refuses_before_any_launch(hiplib):
+    """every rule of nr3d_neus_upsample_stage_packed that is checked before a launch, by its nr3d_last_error text.  Pointers that have
+    to be non-NULL point at host scratch: a refused call touches none of them."""
+    import ctypes
+    scratch = (ctypes.c_char * 64)()
+    X = ctypes.addressof(scratch)
+
+    def call(P=1, N=8, m=9, blidx=None, u_stride=0, merge=0, need_sdf=0, blidx_fine=None, blidx_merged=None):
+        # P, N, m, depth, sdf, blidx, pack_infos, u, u_stride, inv_s, use_estimate, merge, need_sdf, cdf_workspace, fine, blidx_fine,
+        # merged, sdf_merged, blidx_merged, pidx_fine, pack_infos_out, stream: every tensor but the labels NULL
+        return hiplib.nr3d_neus_upsample_stage_packed(P, N, m, None, None, blidx, None, None, u_stride, 64.0, 0, merge, need_sdf, None, None,
+                                                      blidx_fine, None, None, blidx_merged, None, None, None)
+
+    def refused(text, **kw):
+        assert call(**kw) != 0
+        assert text in hiplib.nr3d_last_error(), hiplib.nr3d_last_error()
+
+    refused(b"m = 0, at least 1 new depth per pack", m=0)
+    refused(b"u_stride = 3, must be 0 (one shared row) or m = 9", u_stride=3)
+    assert call(u_stride=9) != 0 and b"NULL tensor pointer" in hiplib.nr3d_last_error()          # m itself passes that rule
+    refused(b"need_sdf without merge", need_sdf=1)
+    refused(b"the merged buffer holds at most 2^31 - 1 elements", P=2 ** 20, N=0, m=2 ** 11)
+    refused(b"the merged buffer holds at most 2^31 - 1 elements", P=1, N=2 ** 31 - 9, m=9)
+    refused(b"the merged buffer holds at most 2^31 - 1 elements", P=0, N=2 ** 31, m=9)
+    refused(b"blidx without blidx_fine", blidx=X)
+    refused(b"blidx without blidx_fine", blidx=X, blidx_merged=X, merge=1)
+    refused(b"blidx_fine or blidx_merged without blidx", blidx_fine=X)
+    refused(b"blidx_fine or blidx_merged without blidx", blidx_merged=X, merge=1)
+    refused(b"merge with blidx but without blidx_merged", blidx=X, blidx_fine=X, merge=1)
+    # the label rules come before the pointers are looked at, and P == 0 before that: a no-op with everything NULL
+    assert call(P=0, N=0) == 0 and call(P=0, N=0, merge=1, need_sdf=1) == 0
+    assert call(blidx=X, blidx_fine=X) != 0 and b"NULL tensor pointer" in hiplib.nr3d_last_error()
+    assert all(b == b"\x00" for b in scratch), "a refused call wrote nothing"

@@ -8,7 +8,7 @@ shell), 4096 and 65 536 rays from a pinhole towards the hub, num_fine = 8, facto
 two march step sizes: packs of about 30 and of about 300 samples.  The fused route (FUSED_UPSAMPLE_FOREST = True: one launch per
 factor) and the pack-op chain (False) run in alternated rounds on the same inputs; a round is the mean of ITERS queries between two
 events after a warm-up, the figure is the median of the rounds.  Also the labelled stage alone against the unlabelled one on the
-same marched samples, timed twice: "kernel" = the two C entries on preallocated outputs (the launch and the kernel: the labelled
+same marched samples, timed twice: "kernel" = the one C entry with and without labels on preallocated outputs (the launch and the kernel: the labelled
 stage moves 8 B more per sample each way), "binding" = upsample_stage_packed_blocks against upsample_stage_packed as the drivers
 call them (with the argument checks and 7 against 5 output allocations per call); and the largest |fused - chain| of the query's
 depths.
@@ -62,7 +62,7 @@ def rays_towards_hub(model, dev, n_rays):
 
 
 def stage_kernels(depth, sdf, bl, pi, u):
-    """the two C entries with merge and need_sdf on, on outputs allocated once -> (labelled, unlabelled) callables"""
+    """the C entry with and without labels, merge and need_sdf on, on outputs allocated once -> (labelled, unlabelled) callables"""
     from nr3d_lib_amd import _hip as H
     N, P, m, dev = depth.shape[0], pi.shape[0], u.shape[0], depth.device
     f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
@@ -72,12 +72,12 @@ def stage_kernels(depth, sdf, bl, pi, u):
     lib, st, p = H.lib(), H.stream_of(depth), H.ptr
 
     def labelled():
-        H.check(lib.nr3d_neus_upsample_stage_packed_blocks(P, N, m, p(depth), p(sdf), p(bl), p(pi), p(u), 0, 64.0, 0, 1, 1, p(ws), p(fine),
-                                                           p(bl_fine), p(merged), p(sdf_m), p(bl_m), p(pidx), p(pi_out), st))
+        H.check(lib.nr3d_neus_upsample_stage_packed(P, N, m, p(depth), p(sdf), p(bl), p(pi), p(u), 0, 64.0, 0, 1, 1, p(ws), p(fine),
+                                                    p(bl_fine), p(merged), p(sdf_m), p(bl_m), p(pidx), p(pi_out), st))
 
     def unlabelled():
-        H.check(lib.nr3d_neus_upsample_stage_packed(P, N, m, p(depth), p(sdf), p(pi), p(u), 0, 64.0, 0, 1, 1, p(ws), p(fine), p(merged),
-                                                    p(sdf_m), p(pidx), p(pi_out), st))
+        H.check(lib.nr3d_neus_upsample_stage_packed(P, N, m, p(depth), p(sdf), None, p(pi), p(u), 0, 64.0, 0, 1, 1, p(ws), p(fine), None,
+                                                    p(merged), p(sdf_m), None, p(pidx), p(pi_out), st))
     return labelled, unlabelled
 
 
@@ -136,7 +136,7 @@ def main():
                 labelled = lambda: U.upsample_stage_packed_blocks(depth, sdf, bl, pi, u, 64.0, False)                         # noqa: E731
                 plain = lambda: U.upsample_stage_packed(depth, sdf, pi, u, 64.0, False)                                       # noqa: E731
                 a, b = labelled(), plain()
-                assert torch.equal(a[0], b[0]) and torch.equal(a[2], b[1]) and torch.equal(a[5], b[3]), "the two entries compute the same"
+                assert torch.equal(a[0], b[0]) and torch.equal(a[2], b[1]) and torch.equal(a[5], b[3]), "the two bindings compute the same"
                 res["stage_alone"][key] = {}
                 k_labelled, k_plain = stage_kernels(depth, sdf, bl, pi, u)
                 for what, fns in (("kernel", {"labelled": k_labelled, "unlabelled": k_plain}),

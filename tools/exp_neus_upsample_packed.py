@@ -112,7 +112,7 @@ def scene(dev, n_rays, res=64):
 
 
 def chain_stage(depth, sdf, pack_infos, n_packs, m, inv_s):
-    """one stage of the pack-op chain as _upsample runs it between two SDF queries (without the query)"""
+    """one stage of the pack-op chain as _packed_upsample.upsample_loop runs it between two SDF queries (without the query)"""
     from nr3d_lib_amd.graphics.neus.neus_utils import neus_packed_sdf_to_alpha
     from nr3d_lib_amd.graphics.pack_ops import (get_pack_infos_from_batch, merge_two_packs_sorted_aligned, packed_alpha_to_vw,
                                                 packed_cumsum, packed_div)
