@@ -25,7 +25,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
 /* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
  * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
  * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
-#define NR3D_ABI_VERSION 28
+#define NR3D_ABI_VERSION 29
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -735,6 +735,35 @@ int nr3d_ray_marching_emit_finished(uint32_t n_rays, const float *rays_o, const 
                                     const void *sample_cache, uint32_t cache_max_steps, float *t_starts, float *t_ends,
                                     int32_t *ridx, int32_t *bidx, int32_t *gidx, int64_t *ridx64, float *deltas,
                                     float *samples, void *stream);
+/* Dynamic scenes: the march through TIME-SLICED occupancy, every ray with a timestamp.  No single reference kernel: replaces the
+ * chain of models/accelerations/occgrid_accel/dynamic.py:117-151, :328-364 and batched_dynamic.py:69-110
+ * (torch_consecutive_nearest1d -> `occ_dynamic | occ_static.expand_as(...)` -> batched march -> ts_keyframes[bidx] -> div / sub).
+ *   grid_dynamic uint8 [n_slices, Rx, Ry, Rz], n_slices = (batch_inds ? n_batches : 1) * T; grid_static uint8 [Rx, Ry, Rz] or NULL
+ *   (a cell is occupied when either byte is nonzero); roi [6]; AABB grids only.  ts_keyframes [T] ascending, rays_ts [n_rays].
+ *   Frame of a ray = torch_consecutive_nearest1d (nr3d_lib/utils.py:675-699), the same float32 operations: i = first index with
+ *   key[i] >= t (NaN: T), clamped to [1, T-1]; frame i-1 if |key[i-1] - t| < |key[i] - t| else i; T == 1: frame 0.
+ *   slice = (batch_inds ? batch_inds[i] : 0) * T + frame -> rays_slice int32 [n_rays]; a ray whose batch index is negative or
+ *   >= n_batches gets slice -1, count 0 and is never probed.  n_slices * Rx*Ry*Rz >= 2^31 is refused (gidx is int32).
+ * _count: packed_info / ridx_hit / pack_infos / totals / scan_tmp as nr3d_ray_marching_count_finished; the sample cache
+ * (nr3d_ray_marching_cache_bytes) is required.  _emit (after the caller read totals = {S, n_hit}): per sample t_starts, t_ends,
+ * ridx int64, bidx int64 (= batch_inds of the ray; NULL without batch_inds), ts = ts_keyframes[frame], gidx int32 (cell + slice *
+ * Rx*Ry*Rz; optional), deltas = t_ends - t_starts, samples [S, 3] = rays_o + (rays_d * t_starts) with the product rounded on its own --
+ * torch.addcmul's float32 result on the chain's route (self + value * (t1 * t2)), so the two routes agree bit for bit. */
+int nr3d_dynamic_ray_marching_count(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
+                                    const float *t_max, const float *roi, const int32_t grid_res[3],
+                                    const uint8_t *grid_dynamic, const uint8_t *grid_static, const float *ts_keyframes,
+                                    uint32_t T, const float *rays_ts, const int32_t *batch_inds, uint32_t n_batches,
+                                    float step_size, float max_step_size, float dt_gamma, uint32_t max_steps,
+                                    int32_t *packed_info, int32_t *rays_slice, int64_t *ridx_hit, int64_t *pack_infos,
+                                    int64_t *totals, void *scan_tmp, void *sample_cache, uint64_t sample_cache_bytes,
+                                    void *stream);
+int nr3d_dynamic_ray_marching_emit(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *ts_keyframes,
+                                   uint32_t T, const int32_t *batch_inds, const int32_t *packed_info,
+                                   const int32_t *rays_slice, const void *sample_cache, uint32_t cache_max_steps,
+                                   float *t_starts, float *t_ends, int64_t *ridx, int64_t *bidx, float *ts, int32_t *gidx,
+                                   float *deltas, float *samples, void *stream);
+/* the frame lookup alone: fidx int64 [n] = nearest keyframe of ts [n] (as above) */
+int nr3d_nearest_keyframe(uint64_t n, const float *ts_keyframes, uint32_t T, const float *ts, int64_t *fidx, void *stream);
 /* Visibility pruning (nr3d_lib/graphics/nerf/nerf_utils.py:64-98 packed_volume_render_compression + the index gathers
  * of nerf_ray_query.py:128-137).  counts int64 [P] = kept samples per pack (nr3d_alpha_to_vw_forward's num_steps):
  * begin_all [P] = new begin of EVERY pack; the packs that keep >= 1 sample, ascending: idx_out [P'] (tag[i] if tag is

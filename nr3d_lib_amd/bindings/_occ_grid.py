@@ -179,6 +179,106 @@ def batched_ray_marching(rays_o, rays_d, t_min, t_max, batch_inds_, batch_data_s
                   step_size, max_step_size, dt_gamma, max_steps, return_gidx, True)
 
 
+def nearest_keyframe(ts_keyframes, ts):
+    """fidx int64 (shape of ``ts``) = index of the keyframe nearest to every timestamp: ``torch_consecutive_nearest1d``
+    (nr3d_lib/utils.py:675-699) with the same float32 operations, one launch (nr3d_nearest_keyframe)"""
+    _chk("ts_keyframes", ts_keyframes, 1, torch.float32)
+    _chk("ts", ts, None, torch.float32)
+    if ts_keyframes.shape[0] < 1:
+        raise RuntimeError("ts_keyframes: expected at least one keyframe")
+    dev = ts.device
+    with H.on_device(dev):
+        fidx = H.empty(tuple(ts.shape), dtype=torch.int64, device=dev)
+        H.check(H.lib().nr3d_nearest_keyframe(ts.numel(), H.ptr(ts_keyframes), int(ts_keyframes.shape[0]), H.ptr(ts), H.ptr(fidx),
+                                              H.stream_of(ts)))
+    return fidx
+
+
+def dynamic_cache_fits(n_rays, max_steps):
+    """whether ``dynamic_ray_marching`` can allocate its sample cache (it has no second-march route)"""
+    return _cache_bytes(n_rays, int(max_steps)) <= SAMPLE_CACHE_MAX_BYTES
+
+
+def dynamic_ray_marching(rays_o, rays_d, t_min, t_max, rays_ts, roi, grid_dynamic, ts_keyframes, step_size, max_step_size,
+                         dt_gamma, max_steps, return_gidx, grid_static=None, batch_inds=None, n_batches=0):
+    """The march through time-sliced occupancy in two launches and one readback (nr3d_dynamic_ray_marching_count / _emit):
+    ``grid_dynamic`` bool [n_slices, Rx, Ry, Rz] with n_slices = (n_batches if batch_inds is given else 1) * T, ``grid_static``
+    bool [Rx, Ry, Rz] or None (OR-ed per probe, never materialised), ``ts_keyframes`` f32 [T], ``rays_ts`` f32 [n_rays],
+    ``batch_inds`` int32 [n_rays] or None.  -> dict(n_hit, packed_info int32 [n, 2], rays_slice int32 [n] (-1: ray skipped),
+    ridx_hit int64 [n_hit], pack_infos int64 [n_hit, 2], t_starts / t_ends / deltas / ts f32 [S], ridx int64 [S], bidx int64 [S] |
+    None, gidx int32 [S] | None, samples f32 [S, 3])."""
+    _chk("rays_o", rays_o, 2, torch.float32)
+    _chk("rays_d", rays_d, 2, torch.float32)
+    _chk("t_min", t_min, 1, torch.float32)
+    _chk("t_max", t_max, 1, torch.float32)
+    _chk("rays_ts", rays_ts, 1, torch.float32)
+    _chk("roi", roi, 1, torch.float32)
+    _chk("ts_keyframes", ts_keyframes, 1, torch.float32)
+    _chk("grid_dynamic", grid_dynamic, 4)
+    if grid_dynamic.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError("grid_dynamic: expected a bool tensor")
+    n = rays_o.shape[0]
+    if tuple(rays_o.shape) != (n, 3) or tuple(rays_d.shape) != (n, 3):
+        raise RuntimeError("rays_o / rays_d: expected shape [n_rays, 3]")
+    if t_min.shape[0] != n or t_max.shape[0] != n or rays_ts.shape[0] != n:
+        raise RuntimeError("t_min / t_max / rays_ts: expected shape [n_rays]")
+    if roi.shape[0] != 6:
+        raise RuntimeError("roi: expected shape [6]")
+    T = int(ts_keyframes.shape[0])
+    if T < 1:
+        raise RuntimeError("ts_keyframes: expected at least one keyframe")
+    if batch_inds is not None:
+        _chk("batch_inds", batch_inds, 1, torch.int32)
+        if batch_inds.shape[0] != n:
+            raise RuntimeError("batch_inds: expected shape [n_rays]")
+        if int(n_batches) < 1:
+            raise RuntimeError("dynamic_ray_marching: batch_inds needs n_batches >= 1")
+    nb = int(n_batches) if batch_inds is not None else 0
+    if grid_dynamic.shape[0] != max(nb, 1) * T:
+        raise RuntimeError(f"grid_dynamic: expected {max(nb, 1) * T} slices ({max(nb, 1)} x {T} keyframes), got {grid_dynamic.shape[0]}")
+    if grid_static is not None:
+        _chk("grid_static", grid_static, 3)
+        if grid_static.dtype not in (torch.bool, torch.uint8) or tuple(grid_static.shape) != tuple(grid_dynamic.shape[1:]):
+            raise RuntimeError("grid_static: expected a bool tensor of one slice's shape")
+    cache_bytes = _cache_bytes(n, int(max_steps))
+    if cache_bytes > SAMPLE_CACHE_MAX_BYTES:
+        raise RuntimeError(f"dynamic_ray_marching: the sample cache of {n} rays x {int(max_steps)} steps exceeds "
+                           f"SAMPLE_CACHE_MAX_BYTES; split the rays")
+    dev = rays_o.device
+    res = (C.c_int32 * 3)(*[int(s) for s in grid_dynamic.shape[-3:]])
+    with H.on_device(dev):
+        st = H.stream_of(rays_o)
+        packed_info = H.empty((n, 2), dtype=torch.int32, device=dev)
+        rays_slice = H.empty(n, dtype=torch.int32, device=dev)
+        ridx_hit = H.empty(n, dtype=torch.int64, device=dev)
+        pack_infos = H.empty((n, 2), dtype=torch.int64, device=dev)
+        tmp = H.empty((_scan_tmp_bytes(n) + 7) // 8, dtype=torch.int64, device=dev)
+        cache = H.empty(max((cache_bytes + 3) // 4, 1), dtype=torch.int32, device=dev)
+        totals = H.host_i64(2, dev)
+        H.check(H.lib().nr3d_dynamic_ray_marching_count(
+            n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_dynamic), H.ptr(grid_static),
+            H.ptr(ts_keyframes), T, H.ptr(rays_ts), H.ptr(batch_inds), nb, float(step_size), float(max_step_size), float(dt_gamma),
+            int(max_steps), H.ptr(packed_info), H.ptr(rays_slice), H.ptr(ridx_hit), H.ptr(pack_infos), H.ptr(totals), H.ptr(tmp),
+            H.ptr(cache), max(cache_bytes, 4), st))
+        S, n_hit = H.wait_i64(totals, dev)     # the single device->host sync of this op
+        t_starts = H.empty(S, dtype=torch.float32, device=dev)
+        t_ends = H.empty(S, dtype=torch.float32, device=dev)
+        ridx = H.empty(S, dtype=torch.int64, device=dev)
+        bidx = H.empty(S, dtype=torch.int64, device=dev) if batch_inds is not None else None
+        ts = H.empty(S, dtype=torch.float32, device=dev)
+        gidx = H.empty(S, dtype=torch.int32, device=dev) if return_gidx else None
+        deltas = H.empty(S, dtype=torch.float32, device=dev)
+        samples = H.empty((S, 3), dtype=torch.float32, device=dev)
+        if S > 0:
+            H.check(H.lib().nr3d_dynamic_ray_marching_emit(
+                n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(ts_keyframes), T, H.ptr(batch_inds), H.ptr(packed_info), H.ptr(rays_slice),
+                H.ptr(cache), int(max_steps), H.ptr(t_starts), H.ptr(t_ends), H.ptr(ridx), H.ptr(bidx), H.ptr(ts), H.ptr(gidx),
+                H.ptr(deltas), H.ptr(samples), st))
+    return dict(n_hit=n_hit, packed_info=packed_info, rays_slice=rays_slice, ridx_hit=ridx_hit[:n_hit],
+                pack_infos=H.mark_ordered(pack_infos[:n_hit], total=S), t_starts=t_starts, t_ends=t_ends, ridx=ridx, bidx=bidx,
+                ts=ts, gidx=gidx, deltas=deltas, samples=samples)
+
+
 def forest_ray_marching(forest, rays_o, rays_d, t_min, t_max, seg_block_inds, seg_entries, seg_exits, seg_pack_infos,
                         grid_binary, step_size, max_step_size, dt_gamma, max_steps, return_gidx):
     """-> [packed_info, t_starts, t_ends, ridx, blidx, gidx | None]  (forest_marching.cu:145-303; `forest` is a

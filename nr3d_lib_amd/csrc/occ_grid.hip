@@ -31,6 +31,7 @@ struct Grid {
 	f3 mn, mx;
 	int rx, ry, rz;
 	const uint8_t *cells;
+	const uint8_t *cells2;   // DYN == 2 only (time-sliced march): the static grid OR-ed onto the ray's slice; never read otherwise
 	int type;
 	// POW2 fast path: when the ROI extents and the resolution are powers of two, x / d == x * (1 / d) bit for bit
 	// (1 / d is exact and scaling by a power of two does not round), so the ~12-instruction IEEE division
@@ -70,8 +71,10 @@ __device__ __forceinline__ f3 contract(const Grid &g, f3 p) {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return max(lo, min(v, hi)); }
 
-// returns occupancy; *cell receives the flat voxel index (z contiguous)
-template <bool POW2>
+// returns occupancy; *cell receives the flat voxel index (z contiguous).  DYN (compile-time; the time-sliced marcher below):
+// 0 = g.cells alone (every kernel above the dynamic section), 1 = the same byte of the ray's own slice, 2 = that byte OR the
+// static grid's -- two independent loads from one index, issued together and waited for once.
+template <bool POW2, int DYN = 0>
 __device__ __forceinline__ bool probe(const Grid &g, f3 p, int *cell) {
 	if (g.type == NR3D_CONTRACT_AABB &&
 	    (p.x < g.mn.x || p.x > g.mx.x || p.y < g.mn.y || p.y > g.mx.y || p.z < g.mn.z || p.z > g.mx.z))
@@ -82,6 +85,10 @@ __device__ __forceinline__ bool probe(const Grid &g, f3 p, int *cell) {
 	const int iz = clampi((int)(u.z * (float)g.rz), 0, g.rz - 1);
 	const int idx = ix * (g.ry * g.rz) + iy * g.rz + iz;
 	*cell = idx;
+	if (DYN == 2) {
+		const uint8_t a = g.cells[idx], s = g.cells2[idx];
+		return (a | s) != 0;
+	}
 	return g.cells[idx] != 0;
 }
 
@@ -105,7 +112,7 @@ __device__ __forceinline__ float skip_voxel(const Grid &g, float t, float dt_min
 }
 
 // the serial march of one ray (one lane); returns the number of samples
-template <bool EMIT, bool CACHE, bool POW2>
+template <bool EMIT, bool CACHE, bool POW2, int DYN = 0>
 __device__ __forceinline__ uint32_t march_ray(const Grid &g, uint32_t i, uint32_t b, int32_t grid_offset, f3 o, f3 dir, f3 inv,
                                               float near, float far, float dt_min, float dt_max, float dt_gamma,
                                               uint32_t max_steps, uint32_t base, float *__restrict__ t_starts,
@@ -121,7 +128,7 @@ __device__ __forceinline__ uint32_t march_ray(const Grid &g, uint32_t i, uint32_
 	while (tm < far && j < max_steps) {
 		const f3 p = {__fmaf_rn(tm, dir.x, o.x), __fmaf_rn(tm, dir.y, o.y), __fmaf_rn(tm, dir.z, o.z)};
 		int cell = -1;
-		if (probe<POW2>(g, p, &cell)) {
+		if (probe<POW2, DYN>(g, p, &cell)) {
 			if (EMIT) {
 				t_starts[base + j] = t0;
 				t_ends[base + j] = t1;
@@ -234,7 +241,7 @@ __device__ __forceinline__ unsigned long long group_ballot(bool v) {
 	return (m >> ((threadIdx.x & 63u) / G * G)) & ((1ull << (G & 63)) - 1ull);
 }
 
-template <int G, bool POW2>
+template <int G, bool POW2, int DYN = 0>
 __device__ __forceinline__ uint32_t march_ray_group(const Grid &g, uint32_t lane, int32_t grid_offset, f3 o, f3 dir, f3 inv,
                                                     float near, float far, float dt_min, float dt_max, float dt_gamma,
                                                     uint32_t max_steps, uint32_t *__restrict__ cache_ray) {
@@ -277,11 +284,12 @@ __device__ __forceinline__ uint32_t march_ray_group(const Grid &g, uint32_t lane
 				const int iz = clampi((int)(u.z * (float)g.rz), 0, g.rz - 1);
 				cell = ix * (g.ry * g.rz) + iy * g.rz + iz;
 				occ = g.cells[cell];
+				if (DYN == 2) occ |= g.cells2[cell];
 			}
 			if (in) sk = skip_voxel<POW2>(g, mm, dt_min, p, dir, inv);
 			hit = inside && occ != 0;
 		} else {
-			hit = in && probe<POW2>(g, p, &cell);
+			hit = in && probe<POW2, DYN>(g, p, &cell);
 		}
 		if (aabb) {
 			const bool ok = hit && (j + lane < max_steps);
@@ -312,7 +320,7 @@ __device__ __forceinline__ uint32_t march_ray_group(const Grid &g, uint32_t lane
 					const bool inm = (int)lane < kMissAhead && my < far;
 					const f3 pm = {__fmaf_rn(my, dir.x, o.x), __fmaf_rn(my, dir.y, o.y), __fmaf_rn(my, dir.z, o.z)};
 					int cm2 = -1;
-					const bool hitm = inm && probe<POW2>(g, pm, &cm2);
+					const bool hitm = inm && probe<POW2, DYN>(g, pm, &cm2);
 					const float nxt = skip_voxel<POW2>(g, my, dt_min, pm, dir, inv);       // lane kMissAhead-1: where the run goes on
 					const unsigned long long stop = group_ballot<G>((int)lane < kMissAhead && (hitm || !inm));
 					if (stop == 0ull) { tm = __shfl(nxt, kMissAhead - 1, G); continue; }
@@ -427,6 +435,164 @@ __global__ __launch_bounds__(256) void k_emit_cached(uint32_t n_rays, uint32_t s
 #pragma unroll
 			for (int k = 0; k < 3; ++k) samples[(size_t)(base + j) * 3 + k] = __fmaf_rn(d[k], a, o[k]);
 		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Time-sliced occupancy (dynamic scenes): grid_dynamic is [n_slices, Rx, Ry, Rz] with n_slices = max(n_batches, 1) * T, every ray
+// carries a timestamp and marches through the slice of its nearest keyframe, OR-ed with an optional static grid.  Replaces the
+// reference's chain (models/accelerations/occgrid_accel/dynamic.py:117-151, :328-364, batched_dynamic.py:69-110):
+// torch_consecutive_nearest1d -> `occ_dynamic | occ_static.expand_as(...)` (a whole [T, Rx, Ry, Rz] tensor per march) -> batched
+// march -> ts_keyframes[bidx] (-> div / sub).  The march bodies are the ones above with DYN = 1 | 2; only AABB grids.
+// ---------------------------------------------------------------------------------------------------
+// torch_consecutive_nearest1d (nr3d_lib/utils.py:675-699), the same float32 operations in the same order: i = first index with
+// key[i] >= t (searchsorted; NaN: T) clamped to [1, T-1]; the previous key wins only when strictly closer.  T == 1: frame 0.
+__device__ __forceinline__ int nearest_keyframe(const float *__restrict__ key, int T, float t) {
+	if (T <= 1) return 0;
+	int lo = 0, hi = T;
+	while (lo < hi) {
+		const int mid = (lo + hi) >> 1;
+		if (key[mid] >= t) hi = mid; else lo = mid + 1;
+	}
+	const int i = min(max(lo, 1), T - 1);
+	const float prev = fabsf(key[i - 1] - t), next = fabsf(key[i] - t);
+	return prev < next ? i - 1 : i;
+}
+
+__global__ __launch_bounds__(256) void k_nearest_keyframe(uint64_t n, const float *__restrict__ key, int T,
+                                                          const float *__restrict__ ts, int64_t *__restrict__ fidx) {
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i < n) fidx[i] = (int64_t)nearest_keyframe(key, T, ts[i]);
+}
+
+// the ray's slice (batch * T + frame), or -1 for a ray whose batch index is negative or >= n_batches (never probed)
+__device__ __forceinline__ int32_t dyn_slice(uint32_t i, const float *__restrict__ key, int T, const float *__restrict__ rays_ts,
+                                             const int32_t *__restrict__ batch_inds, uint32_t n_batches) {
+	int32_t b = 0;
+	if (batch_inds) {
+		b = batch_inds[i];
+		if (b < 0 || (uint32_t)b >= n_batches) return -1;
+	}
+	return b * T + nearest_keyframe(key, T, rays_ts[i]);
+}
+
+__device__ __forceinline__ bool dyn_grid(Grid &g, const float *__restrict__ roi, int rx, int ry, int rz,
+                                         const uint8_t *__restrict__ cells, const uint8_t *__restrict__ cells_static, int32_t slice) {
+	const uint32_t vol = (uint32_t)(rx * ry * rz);
+	g.mn = {roi[0], roi[1], roi[2]};
+	g.mx = {roi[3], roi[4], roi[5]};
+	g.rx = rx; g.ry = ry; g.rz = rz;
+	g.cells = cells + (size_t)slice * vol;
+	g.cells2 = cells_static;
+	g.type = NR3D_CONTRACT_AABB;
+	g.inv_ext = {1.0f / (g.mx.x - g.mn.x), 1.0f / (g.mx.y - g.mn.y), 1.0f / (g.mx.z - g.mn.z)};
+	g.inv_res = {1.0f / (float)rx, 1.0f / (float)ry, 1.0f / (float)rz};
+	return is_pow2f(g.mx.x - g.mn.x) && is_pow2f(g.mx.y - g.mn.y) && is_pow2f(g.mx.z - g.mn.z) &&
+	       is_pow2f((float)rx) && is_pow2f((float)ry) && is_pow2f((float)rz);
+}
+
+// count pass, one lane per ray, always with the sample cache
+template <int DYN>
+__global__ __launch_bounds__(kBlock) void k_march_dyn(uint32_t n_rays, const float *__restrict__ rays_o,
+                                                      const float *__restrict__ rays_d, const float *__restrict__ t_min,
+                                                      const float *__restrict__ t_max, const float *__restrict__ roi, int rx,
+                                                      int ry, int rz, const uint8_t *__restrict__ cells,
+                                                      const uint8_t *__restrict__ cells_static, const float *__restrict__ key,
+                                                      int T, const float *__restrict__ rays_ts,
+                                                      const int32_t *__restrict__ batch_inds, uint32_t n_batches,
+                                                      float step_size, float max_step_size, float dt_gamma, uint32_t max_steps,
+                                                      int32_t *__restrict__ counts, int32_t *__restrict__ rays_slice,
+                                                      uint32_t *__restrict__ cache) {
+	const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+	if (i >= n_rays) return;
+	const int32_t slice = dyn_slice(i, key, T, rays_ts, batch_inds, n_batches);
+	rays_slice[i] = slice;
+	if (slice < 0) { counts[i] = 0; return; }
+	Grid g;
+	const bool pow2 = dyn_grid(g, roi, rx, ry, rz, cells, cells_static, slice);
+	const int32_t grid_offset = slice * (rx * ry * rz);
+	const f3 o = {rays_o[3 * (size_t)i], rays_o[3 * (size_t)i + 1], rays_o[3 * (size_t)i + 2]};
+	const f3 dir = {rays_d[3 * (size_t)i], rays_d[3 * (size_t)i + 1], rays_d[3 * (size_t)i + 2]};
+	const f3 inv = {1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z};
+	uint32_t j;
+	if (__all(pow2))
+		j = march_ray<false, true, true, DYN>(g, i, 0u, grid_offset, o, dir, inv, t_min[i], t_max[i], step_size, max_step_size,
+		                                      dt_gamma, max_steps, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, cache);
+	else
+		j = march_ray<false, true, false, DYN>(g, i, 0u, grid_offset, o, dir, inv, t_min[i], t_max[i], step_size, max_step_size,
+		                                       dt_gamma, max_steps, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, cache);
+	counts[i] = (int32_t)j;
+}
+
+// count pass, G lanes per ray (every lane of a group looks the frame up: the same few broadcast loads)
+template <int G, int DYN>
+__global__ __launch_bounds__(256) void k_march_group_dyn(uint32_t n_rays, const float *__restrict__ rays_o,
+                                                         const float *__restrict__ rays_d, const float *__restrict__ t_min,
+                                                         const float *__restrict__ t_max, const float *__restrict__ roi, int rx,
+                                                         int ry, int rz, const uint8_t *__restrict__ cells,
+                                                         const uint8_t *__restrict__ cells_static, const float *__restrict__ key,
+                                                         int T, const float *__restrict__ rays_ts,
+                                                         const int32_t *__restrict__ batch_inds, uint32_t n_batches,
+                                                         float step_size, float max_step_size, float dt_gamma,
+                                                         uint32_t max_steps, int32_t *__restrict__ counts,
+                                                         int32_t *__restrict__ rays_slice, uint32_t *__restrict__ cache) {
+	const uint32_t i = (blockIdx.x * 256u + threadIdx.x) / G, lane = threadIdx.x % G;
+	if (i >= n_rays) return;
+	const int32_t slice = dyn_slice(i, key, T, rays_ts, batch_inds, n_batches);
+	if (lane == 0) rays_slice[i] = slice;
+	if (slice < 0) { if (lane == 0) counts[i] = 0; return; }
+	Grid g;
+	const bool pow2 = dyn_grid(g, roi, rx, ry, rz, cells, cells_static, slice);
+	const int32_t grid_offset = slice * (rx * ry * rz);
+	const f3 o = {rays_o[3 * (size_t)i], rays_o[3 * (size_t)i + 1], rays_o[3 * (size_t)i + 2]};
+	const f3 dir = {rays_d[3 * (size_t)i], rays_d[3 * (size_t)i + 1], rays_d[3 * (size_t)i + 2]};
+	const f3 inv = {1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z};
+	uint32_t *cache_ray = cache + (size_t)i * max_steps * 3;
+	uint32_t j;
+	if (__all(pow2))
+		j = march_ray_group<G, true, DYN>(g, lane, grid_offset, o, dir, inv, t_min[i], t_max[i], step_size, max_step_size, dt_gamma,
+		                                  max_steps, cache_ray);
+	else
+		j = march_ray_group<G, false, DYN>(g, lane, grid_offset, o, dir, inv, t_min[i], t_max[i], step_size, max_step_size, dt_gamma,
+		                                   max_steps, cache_ray);
+	if (lane == 0) counts[i] = (int32_t)j;
+}
+
+// one wave per ray: the ray's cached samples go to their packed position, with the per-sample epilogue of the chain
+// (ridx.long(), ts_keyframes[frame], the batch index, deltas, samples)
+__global__ __launch_bounds__(256) void k_emit_dyn(uint32_t n_rays, uint32_t stride, const float *__restrict__ rays_o,
+                                                  const float *__restrict__ rays_d, const float *__restrict__ key, int T,
+                                                  const int32_t *__restrict__ batch_inds,
+                                                  const int32_t *__restrict__ packed_info,
+                                                  const int32_t *__restrict__ rays_slice, const uint32_t *__restrict__ cache,
+                                                  float *__restrict__ t_starts, float *__restrict__ t_ends,
+                                                  int64_t *__restrict__ ridx, int64_t *__restrict__ bidx, float *__restrict__ ts,
+                                                  int32_t *__restrict__ gidx, float *__restrict__ deltas,
+                                                  float *__restrict__ samples) {
+	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+	if (i >= n_rays) return;
+	const uint32_t base = (uint32_t)packed_info[2 * (size_t)i], cnt = (uint32_t)packed_info[2 * (size_t)i + 1];
+	if (cnt == 0) return;       // also every ray without a slice
+	const int32_t b = batch_inds ? batch_inds[i] : 0;
+	const float t_key = key[rays_slice[i] - b * T];
+	const uint32_t *c = cache + (size_t)i * stride * 3;
+	float o[3], d[3];
+#pragma unroll
+	for (int k = 0; k < 3; ++k) { o[k] = rays_o[3 * (size_t)i + k]; d[k] = rays_d[3 * (size_t)i + k]; }
+	for (uint32_t j = lane; j < cnt; j += 64) {
+		const float a = __uint_as_float(c[3 * j]), e = __uint_as_float(c[3 * j + 1]);
+		t_starts[base + j] = a;
+		t_ends[base + j] = e;
+		ridx[base + j] = (int64_t)i;
+		if (bidx) bidx[base + j] = (int64_t)b;
+		ts[base + j] = t_key;
+		if (gidx) gidx[base + j] = (int32_t)c[3 * j + 2];
+		deltas[base + j] = e - a;
+		// o + (d * t), the product rounded on its own: ATen's addcmul evaluates self + value * (t1 * t2), so the chain's positions are
+		// rounded twice whatever the compiler contracts; both routes of occgrid_raymarch_dynamic return the same bits.  (k_emit_cached
+		// rounds once: there the fused finish follows the reference's CUDA build instead, see nr3d_march_finish_samples.)
+#pragma unroll
+		for (int k = 0; k < 3; ++k) samples[(size_t)(base + j) * 3 + k] = __fadd_rn(o[k], __fmul_rn(d[k], a));
 	}
 }
 
@@ -721,6 +887,93 @@ extern "C" int nr3d_ray_marching_emit_finished(uint32_t n_rays, const float *ray
 	hipLaunchKernelGGL(occ::k_emit_cached, dim3(div_up(n_rays, 4)), dim3(256), 0, (hipStream_t)stream, n_rays, cache_max_steps,
 	                   batched, batch_inds, batch_data_size, packed_info, (const uint32_t *)sample_cache, t_starts, t_ends, ridx,
 	                   bidx, gidx, rays_o, rays_d, ridx64, deltas, samples);
+	NR3D_LAUNCH_CHECK();
+	return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Time-sliced march: count (+ sample cache, + the per-ray slice) -> scan (+ hit rays, totals) | readback | cached emit
+// ---------------------------------------------------------------------------------------------------
+extern "C" int nr3d_nearest_keyframe(uint64_t n, const float *ts_keyframes, uint32_t T, const float *ts, int64_t *fidx,
+                                     void *stream) {
+	if (n == 0) return 0;
+	NR3D_CHECK(ts_keyframes && ts && fidx, "nearest_keyframe: NULL pointer");
+	NR3D_CHECK(T >= 1 && T < (1u << 30), "nearest_keyframe: %u keyframes", T);
+	NR3D_CHECK(n < (1ull << 31) * 256, "nearest_keyframe: %llu values in one call", (unsigned long long)n);
+	hipLaunchKernelGGL(occ::k_nearest_keyframe, dim3((unsigned)div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, n, ts_keyframes,
+	                   (int)T, ts, fidx);
+	NR3D_LAUNCH_CHECK();
+	return 0;
+}
+
+extern "C" int nr3d_dynamic_ray_marching_count(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
+                                               const float *t_max, const float *roi, const int32_t grid_res[3],
+                                               const uint8_t *grid_dynamic, const uint8_t *grid_static,
+                                               const float *ts_keyframes, uint32_t T, const float *rays_ts,
+                                               const int32_t *batch_inds, uint32_t n_batches, float step_size,
+                                               float max_step_size, float dt_gamma, uint32_t max_steps, int32_t *packed_info,
+                                               int32_t *rays_slice, int64_t *ridx_hit, int64_t *pack_infos, int64_t *totals,
+                                               void *scan_tmp, void *sample_cache, uint64_t sample_cache_bytes, void *stream) {
+	NR3D_CHECK(totals && scan_tmp, "dynamic_ray_marching: NULL scratch pointer");
+	hipStream_t st = (hipStream_t)stream;
+	if (n_rays == 0) { NR3D_HIP_CHECK(hipMemsetAsync(totals, 0, 2 * sizeof(int64_t), st)); return 0; }
+	NR3D_CHECK(rays_o && rays_d && t_min && t_max && roi && grid_dynamic && ts_keyframes && rays_ts,
+	           "dynamic_ray_marching: NULL tensor pointer");
+	NR3D_CHECK(packed_info && rays_slice && ridx_hit && pack_infos, "dynamic_ray_marching: NULL output pointer");
+	NR3D_CHECK(grid_res[0] > 0 && grid_res[1] > 0 && grid_res[2] > 0, "dynamic_ray_marching: empty grid");
+	NR3D_CHECK(T >= 1, "dynamic_ray_marching: no keyframes");
+	NR3D_CHECK(!batch_inds || n_batches >= 1, "dynamic_ray_marching: batch_inds without batches");
+	const uint64_t n_slices = (uint64_t)(batch_inds ? n_batches : 1u) * T;
+	const uint64_t vol = (uint64_t)grid_res[0] * grid_res[1] * grid_res[2];
+	NR3D_CHECK(n_slices * vol < (1ull << 31), "dynamic_ray_marching: %llu slices of %llu voxels: gidx is int32 (fewer than 2^31 cells in all)",
+	           (unsigned long long)n_slices, (unsigned long long)vol);
+	NR3D_CHECK(sample_cache && sample_cache_bytes >= nr3d_ray_marching_cache_bytes(n_rays, max_steps),
+	           "dynamic_ray_marching: needs the sample cache (nr3d_ray_marching_cache_bytes)");
+	int32_t *counts = (int32_t *)scan_tmp;
+	void *tiles = (char *)scan_tmp + (((uint64_t)n_rays * sizeof(int64_t) + 7) / 8) * 8;
+	// lanes per ray as in march_count (NR3D_OPT_MARCH_GROUP forces)
+	int group = n_rays <= 8192u ? 32 : (n_rays <= 32768u ? 16 : 1);
+	{ const int64_t v = opt::get(NR3D_OPT_MARCH_GROUP); if (v == 1 || v == 16 || v == 32 || v == 64) group = (int)v; }
+	auto launch = [&](auto kern, int G) {
+		const dim3 grid = G == 1 ? dim3(div_up(n_rays, occ::kBlock)) : dim3((unsigned)div_up((uint64_t)n_rays * G, 256));
+		hipLaunchKernelGGL(kern, grid, dim3(G == 1 ? occ::kBlock : 256), 0, st, n_rays, rays_o, rays_d, t_min, t_max, roi, grid_res[0],
+		                   grid_res[1], grid_res[2], grid_dynamic, grid_static, ts_keyframes, (int)T, rays_ts, batch_inds, n_batches,
+		                   step_size, max_step_size, dt_gamma, max_steps, counts, rays_slice, (uint32_t *)sample_cache);
+	};
+	{
+		prof::Scope ps(NR3D_PROF_MARCH, st);
+		if (grid_static) {
+			if (group == 64) launch(occ::k_march_group_dyn<64, 2>, 64);
+			else if (group == 32) launch(occ::k_march_group_dyn<32, 2>, 32);
+			else if (group == 16) launch(occ::k_march_group_dyn<16, 2>, 16);
+			else launch(occ::k_march_dyn<2>, 1);
+		} else {
+			if (group == 64) launch(occ::k_march_group_dyn<64, 1>, 64);
+			else if (group == 32) launch(occ::k_march_group_dyn<32, 1>, 32);
+			else if (group == 16) launch(occ::k_march_group_dyn<16, 1>, 16);
+			else launch(occ::k_march_dyn<1>, 1);
+		}
+	}
+	NR3D_LAUNCH_CHECK();
+	glue::PackWriter<int32_t, 1> w{counts, nullptr, nullptr, ridx_hit, pack_infos, packed_info};
+	return glue::compact_packs<int32_t, 1>(n_rays, w, totals, tiles, st);
+}
+
+extern "C" int nr3d_dynamic_ray_marching_emit(uint32_t n_rays, const float *rays_o, const float *rays_d,
+                                              const float *ts_keyframes, uint32_t T, const int32_t *batch_inds,
+                                              const int32_t *packed_info, const int32_t *rays_slice, const void *sample_cache,
+                                              uint32_t cache_max_steps, float *t_starts, float *t_ends, int64_t *ridx,
+                                              int64_t *bidx, float *ts, int32_t *gidx, float *deltas, float *samples,
+                                              void *stream) {
+	if (n_rays == 0) return 0;
+	NR3D_CHECK(rays_o && rays_d && ts_keyframes && packed_info && rays_slice && sample_cache, "dynamic_ray_marching_emit: NULL tensor pointer");
+	NR3D_CHECK(t_starts && t_ends && ridx && ts && deltas && samples, "dynamic_ray_marching_emit: NULL output pointer");
+	NR3D_CHECK(!bidx || batch_inds, "dynamic_ray_marching_emit: bidx needs batch_inds");
+	NR3D_CHECK(T >= 1, "dynamic_ray_marching_emit: no keyframes");
+	prof::Scope ps(NR3D_PROF_MARCH, (hipStream_t)stream);
+	hipLaunchKernelGGL(occ::k_emit_dyn, dim3(div_up(n_rays, 4)), dim3(256), 0, (hipStream_t)stream, n_rays, cache_max_steps, rays_o,
+	                   rays_d, ts_keyframes, (int)T, batch_inds, packed_info, rays_slice, (const uint32_t *)sample_cache, t_starts,
+	                   t_ends, ridx, bidx, ts, gidx, deltas, samples);
 	NR3D_LAUNCH_CHECK();
 	return 0;
 }

@@ -1,11 +1,13 @@
 from .aabb import *  # noqa: F401,F403
 from .forest import *  # noqa: F401,F403
 from .batched import *  # noqa: F401,F403
+from .aabb_dynamic import *  # noqa: F401,F403
+from .batched_dynamic import *  # noqa: F401,F403
 
 
 def get_space(space_cfg=None):
     """name or {'type': name, **kwargs} -> space module (nr3d_lib/models/spatial/__init__.py:10-32); the time-varying
-    spaces ('aabb_dynamic', 'batched_dynamic') are not provided"""
+    spaces ('aabb_dynamic', 'batched_dynamic') are constructed directly (AABBDynamicSpace, BatchedDynamicSpace), not by name"""
     if space_cfg is None:
         return None
     cfg = {'type': space_cfg} if isinstance(space_cfg, str) else dict(space_cfg)
@@ -19,7 +21,8 @@ def get_space(space_cfg=None):
     if kind in ('unbounded', 'none'):
         return None
     if kind in ('aabb_dynamic', 'batched_dynamic'):
-        raise NotImplementedError(f"nr3d_lib_amd: space type {kind!r} (time-varying) is not provided")
+        raise NotImplementedError(f"nr3d_lib_amd: space type {kind!r} (time-varying) is not built by name: construct "
+                                  f"AABBDynamicSpace / BatchedDynamicSpace directly")
     raise RuntimeError(f"Invalid space_type={kind}")
 
 
