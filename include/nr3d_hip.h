@@ -22,9 +22,12 @@ extern "C" {
 
 enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3D_U8 = 5, NR3D_I16 = 6, NR3D_I8 = 7 };
 
-/* Bumped whenever an entry point is added, removed or changes its parameters.  nr3d_lib_amd/_abi.py (generated from this header by
- * tools/gen_abi.py at build time) carries the same number next to every entry point's argument types; the Python loader refuses a
- * library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import nor at run time. */
+/* Bumped whenever an entry point is removed or changes its parameters, or an addition touches an existing one.  An addition that leaves
+ * every existing entry untouched keeps the number (nr3d_marching_cubes_*): the Python loader refuses, by name, a library that lacks an
+ * entry its table declares (_hip._declare), so an older build behind newer bindings is still an error at load.  nr3d_lib_amd/_abi.py
+ * (generated from this header by tools/gen_abi.py at build time) carries the same number next to every entry point's argument types;
+ * the loader also refuses a library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import
+ * nor at run time. */
 #define NR3D_ABI_VERSION 29
 
 const char *nr3d_last_error(void);
@@ -1242,6 +1245,32 @@ int nr3d_nerfpp_march_emit(uint32_t R, const float *rays_o, const float *rays_d,
                            const float *radii, const float *noise, float step, float last_radius, int sample_mode, int interval_type,
                            float log_min, float log_max, const int64_t *begin_all, uint64_t S, float *x, float *t, float *deltas,
                            int64_t *ridx, void *stream);
+
+/* ---- marching cubes (csrc/marching_cubes.hip; no reference twin: the reference copies the SDF volume to the host and calls
+ * skimage.measure.marching_cubes, nr3d_lib/graphics/trianglemesh.py:210-214).  The case table is csrc/mc_table.inc, written by
+ * tools/gen_mc_table.py (corner c at offsets (c & 1, (c >> 1) & 1, (c >> 2) & 1); edge e = 4 axis + u + 2 v, owned by the node at its low
+ * end).  volume float32 [Nx, Ny, Nz] contiguous, every dimension >= 2, Nx Ny < 2^28 rows, fewer than 2^36 nodes.
+ *   A node is inside iff v < level, outside iff v >= level; NaN is neither.
+ *   A cell (i, j, k), i < Nx - 1 ..., is ACTIVE iff its 8 corner values are finite; it emits its case's triangles (case = sum of
+ *     inside(c) << c), an inactive cell emits nothing.  NaN marks nodes that were not evaluated; there is no mask argument.
+ *   An edge is LIVE iff one end is inside and the other outside and at least one of its up to four incident cells is active.  One
+ *     vertex per live edge and none otherwise: every vertex is referenced by a face and every face index is valid.
+ *   Vertex order: owner node in linear order (x slowest, z fastest), then axis x, y, z.  Position, in INDEX units (no spacing, no
+ *     origin): the owner's index as float, plus t = (level - v0) / (v1 - v0) on the edge's axis, v0 the owner's value: two float32
+ *     subtractions, one IEEE division, one addition.
+ *   Face order: cells in linear order over the (Nx - 1, Ny - 1, Nz - 1) cell grid, then table order; a face's three indices are the
+ *     vertices of its three edges, normals towards increasing value.
+ * nr3d_marching_cubes_count: scratch >= nr3d_marching_cubes_scratch_bytes(Nx, Ny, Nz) bytes, 8-byte aligned (48 bytes per z-row for the
+ *   counts and their scans, 4 bytes per node for emit's vertex words); totals int64 [2] = {V, F}, stored with system scope (pinned host
+ *   memory + nr3d_wait_host_words, or device memory).
+ * nr3d_marching_cubes_emit: the same volume, level and scratch, V and F as read back; verts float32 [V, 3] and faces int64 [F, 3], both
+ *   fully written, no row >= V / F is ever written.  V < 2^29; V == 0 is a no-op.
+ * One wave per z-row, lane = z in chunks of 64 with two halo lanes; ranks from ballots and popcounts; no LDS, no atomics. */
+uint64_t nr3d_marching_cubes_scratch_bytes(uint32_t Nx, uint32_t Ny, uint32_t Nz);
+int nr3d_marching_cubes_count(const float *volume, uint32_t Nx, uint32_t Ny, uint32_t Nz, float level, void *scratch, int64_t *totals,
+                              void *stream);
+int nr3d_marching_cubes_emit(const float *volume, uint32_t Nx, uint32_t Ny, uint32_t Nz, float level, void *scratch, uint64_t V, uint64_t F,
+                             float *verts, int64_t *faces, void *stream);
 
 #ifdef __cplusplus
 }
