@@ -23,7 +23,7 @@ extern "C" {
 enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3D_U8 = 5, NR3D_I16 = 6, NR3D_I8 = 7 };
 
 /* Bumped whenever an entry point is removed or changes its parameters, or an addition touches an existing one.  An addition that leaves
- * every existing entry untouched keeps the number (nr3d_marching_cubes_*): the Python loader refuses, by name, a library that lacks an
+ * every existing entry untouched keeps the number (nr3d_marching_cubes_*, nr3d_knn_*): the Python loader refuses, by name, a library that lacks an
  * entry its table declares (_hip._declare), so an older build behind newer bindings is still an error at load.  nr3d_lib_amd/_abi.py
  * (generated from this header by tools/gen_abi.py at build time) carries the same number next to every entry point's argument types;
  * the loader also refuses a library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import
@@ -1271,6 +1271,46 @@ int nr3d_marching_cubes_count(const float *volume, uint32_t Nx, uint32_t Ny, uin
                               void *stream);
 int nr3d_marching_cubes_emit(const float *volume, uint32_t Nx, uint32_t Ny, uint32_t Nz, float level, void *scratch, uint64_t V, uint64_t F,
                              float *verts, int64_t *faces, void *stream);
+
+/* ---- k nearest neighbours between two batched point clouds (csrc/knn.hip; the reference's externals/pytorch3d_knn behind
+ * nr3d_lib/maths/pytorch3d_knn.py and maths/chamfer_distance.py).  Brute force, as there; no spatial index.  An addition that touches no
+ * existing entry: the ABI number stays.
+ *   p1 float32 [N, P1, D], p2 float32 [N, P2, D], contiguous.  lengths1 / lengths2: int64 [N] ON THE DEVICE (the kernels read them: no
+ *     host read-back), NULL = every cloud has full length; a value outside [0, P] is clamped into it.
+ *   Distance of a pair, all in float32, d_c = p1[c] - p2[c]:
+ *     norm == 2: dist = d_0 * d_0, then dist = fmaf(d_c, d_c, dist) for c = 1 .. D-1 (the order of the reference's loop, knn.cu:56-62,
+ *                under nvcc's default contraction; this library is built without contraction, so the fmaf is written out);
+ *     norm == 1: dist = |d_0|, then dist = dist + |d_c|.
+ *   Row (n, i) with i < lengths1[n]: the k = min(K, lengths2[n]) smallest pairs (dist, j) in LEXICOGRAPHIC order over j < lengths2[n]:
+ *     ascending distance, equal distances by ascending j, and at the K-th place the lower index wins (one of the outcomes the reference
+ *     can produce: its MinK::add replaces on a strict < only).  The order is fixed: the same bytes run after run.  Slots k .. K-1 hold
+ *     dists = 0, idx = 0.  Rows i >= lengths1[n] are all zero.  Every element of dists float32 [N, P1, K] and idx int64 [N, P1, K] is
+ *     written: they may be allocated uninitialised.
+ *   The output is ALWAYS sorted (the reference's return_sorted=False would return the same set in an unspecified order), and there is
+ *     one implementation per (D, K): the reference's `version` has nothing to select.
+ *   Non-finite coordinates or distances: the neighbours of an affected row (a non-finite p1 row; every row of a cloud whose p2 holds
+ *     a non-finite point; a row with a pair of finite points so far apart that its float32 distance overflows to +inf: such a pair
+ *     never enters a list, since inf < inf is false, so the row can come back with (inf, 0) entries) are unspecified, but every idx
+ *     stays in [0, max(lengths2[n], 1)), no other row changes and nothing is written outside the row.
+ *   Refused with a message: P1 or P2 >= 2^31, N >= 2^31, K == 0, D == 0, norm outside {1, 2}.  N == 0, P1 == 0 or P2 == 0 is a no-op
+ *     (with P2 == 0 NOTHING is written: the caller returns zeros).
+ *   nr3d_knn_fast_path(D, K): 1 when k_knn<D, KB, NORM> serves the pair (D in 1..8, K <= 32 in buckets KB = 1, 4, 8, 16, 32: a lane owns
+ *     1, 2 or 4 queries in registers, p2 streams through LDS in tiles of nr3d_knn_tile_points(D) points read as broadcasts, the top-K is
+ *     a sorted list in statically indexed registers); 0: k_knn_any, one lane per query, p2 from global memory, the list in the row's
+ *     own output slots -- the same contract, CORRECT AND UNOPTIMISED.
+ *   nr3d_knn_tile_points(D): the tile length of the fast kernel for this D, 0 without one (tests place P2 around it).
+ * nr3d_knn_points_backward: idx int64 [N, P1, K] and grad_dists float32 [N, P1, K] as the forward shaped them.  For k < min(K,
+ *   lengths2[n]), i < lengths1[n] and each c:  norm == 2: t = 2 g[n,i,k] (p1 - p2[idx]);  norm == 1: t = g (p1 > p2 ? 1 : -1) (at
+ *   equality -1 for p1, as in the reference).  grad_p1 float32 [N, P1, D]: the lane's own sum over k, fully written without atomics
+ *   (deterministic; rows >= lengths1[n] zero).  grad_p2 float32 [N, P2, D], zero-init: takes -t through float32 atomic adds.  An idx
+ *   outside [0, P2) is skipped.  N == 0, P1 == 0 or P2 == 0 is a no-op.  No double backward (the reference is once_differentiable). */
+int nr3d_knn_points(const float *p1, const float *p2, const int64_t *lengths1, const int64_t *lengths2, uint64_t N, uint64_t P1, uint64_t P2,
+                    uint32_t D, uint32_t K, int norm, float *dists, int64_t *idx, void *stream);
+int nr3d_knn_points_backward(const float *p1, const float *p2, const int64_t *lengths1, const int64_t *lengths2, const int64_t *idx,
+                             const float *grad_dists, uint64_t N, uint64_t P1, uint64_t P2, uint32_t D, uint32_t K, int norm, float *grad_p1,
+                             float *grad_p2, void *stream);
+int nr3d_knn_fast_path(uint32_t D, uint32_t K);
+int nr3d_knn_tile_points(uint32_t D);
 
 #ifdef __cplusplus
 }
