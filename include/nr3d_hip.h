@@ -23,7 +23,7 @@ extern "C" {
 enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3D_U8 = 5, NR3D_I16 = 6, NR3D_I8 = 7 };
 
 /* Bumped whenever an entry point is removed or changes its parameters, or an addition touches an existing one.  An addition that leaves
- * every existing entry untouched keeps the number (nr3d_marching_cubes_*, nr3d_knn_*): the Python loader refuses, by name, a library that lacks an
+ * every existing entry untouched keeps the number (nr3d_marching_cubes_*, nr3d_knn_*, nr3d_forest_ray_test_*): the Python loader refuses, by name, a library that lacks an
  * entry its table declares (_hip._declare), so an older build behind newer bindings is still an error at load.  nr3d_lib_amd/_abi.py
  * (generated from this header by tools/gen_abi.py at build time) carries the same number next to every entry point's argument types;
  * the loader also refuses a library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import
@@ -1311,6 +1311,41 @@ int nr3d_knn_points_backward(const float *p1, const float *p2, const int64_t *le
                              float *grad_p2, void *stream);
 int nr3d_knn_fast_path(uint32_t D, uint32_t K);
 int nr3d_knn_tile_points(uint32_t D);
+
+/* ---- ray test of a forest of blocks (csrc/forest_ray_test.hip; ForestBlockSpace.ray_test, nr3d_lib/models/spatial/forest.py:353-394,
+ * which tests every ray against every block box because the octree traversal it wanted, :302-351, stood on kaolin's SPC ray trace).
+ * One descent of the forest's byte octree per ray, pruning whole subtrees; the result is the dense route's, BIT FOR BIT.  An addition
+ * that touches no existing entry: the ABI number stays.
+ *   forest: octree / exsum as above (both may be NULL on level 0: the root is the only block), level <= 15, world_block_size > 0;
+ *     block_ks is NOT read: a block's coordinates are those of its path through the octree, which is what block_ks holds.
+ *   rays_o, rays_d float32 [R, 3]; near / far: float32 [R] per ray, or NULL and then near_const / far_const for every ray
+ *     (no lower bound: NULL, 0; no upper bound: NULL, +inf -- min(x, +inf) is x, and a NaN stays one).  wb = world_block_size,
+ *     wo = world_origin; all in float32, no contraction:
+ *   Block k:   bmin = float(k) * wb + wo,  bmax = bmin + wb            (an explicit multiply, then an add)
+ *   Per axis:  t0 = (bmin - o) / d,  t1 = (bmax - o) / d               (IEEE subtraction and division: x / 0 = +-inf, 0 / 0 = NaN)
+ *   entry = max(max over the axes of min(t0, t1), near),  exit = min(min over the axes of max(t0, t1), far), where min and max
+ *     PROPAGATE NaN (torch.minimum / torch.maximum; fminf / fmaxf would not).  A ray parallel to a slab with its origin exactly on one
+ *     of the slab's planes gives 0 / 0: that pair is rejected, as by the dense route.
+ *   Hit:       exit > entry && exit > 0.
+ *   Order:     the segments of a ray by (entry, block index) ascending -- a stable sort by entry of the hits in block order; block
+ *     index = node index - level_poffset.  The order is fixed: the same bytes run after run.
+ *   Interior nodes (why no hit is lost, without an epsilon): node k on level l of L is tested on lo = float(k 2^(L-l)) * wb + wo and
+ *     hi = (float((k + 1) 2^(L-l) - 1) * wb + wo) + wb, the planes of its first and last leaf by the expression above.  int -> float,
+ *     * wb (> 0), + wo, - o and / d for a fixed d != 0 are monotone under round-to-nearest, so every leaf's float interval lies inside
+ *     its ancestors' and the non-strict test exit >= entry && exit >= 0 is conservative; with d == 0 on an axis a node accepts
+ *     lo <= o <= hi, the leaf keeps the NaN / inf arithmetic.  Children are visited front to back (c ^ sign mask of d).
+ *   _count: counts int64 [R] = segments per ray, fully written.  Then nr3d_prune_compact_packs(R, counts, ...) gives begin_all, the hit
+ *     rays, their pack_infos and the totals {S, hit rays}: the one device->host wait.
+ *   _emit: seg_block_inds int64 [S], seg_entries / seg_exits float32 [S], fully written (the packs tile [0, S)); a ray whose
+ *     begin_all + counts leaves [0, S] writes nothing.
+ *   Refused with a message: level > 15, n_trees == 0, R >= 2^28 (nr3d_prune_compact_packs), a world_block_size that is not positive,
+ *     S > R * n_trees.  R == 0 (and S == 0 for _emit) is a no-op. */
+int nr3d_forest_ray_test_count(const nr3d_forest_meta_t *forest, uint32_t n_rays, const float *rays_o, const float *rays_d,
+                               const float *near, float near_const, const float *far, float far_const, int64_t *counts, void *stream);
+int nr3d_forest_ray_test_emit(const nr3d_forest_meta_t *forest, uint32_t n_rays, const float *rays_o, const float *rays_d,
+                              const float *near, float near_const, const float *far, float far_const, const int64_t *counts,
+                              const int64_t *begin_all, uint64_t S, int64_t *seg_block_inds, float *seg_entries, float *seg_exits,
+                              void *stream);
 
 #ifdef __cplusplus
 }

@@ -6,14 +6,22 @@
 ``raytrace_cuda_fixed`` (the reference's patched copy of kaolin's SPC ray trace, forest.cpp:40) is third-party code
 outside the path and is not provided; ``forest_identify`` is the octree point query the reference reaches through
 kaolin's ``unbatched_query``.
+
+``forest_ray_test`` has NO reference twin: the reference's ``ForestBlockSpace.ray_test`` tests every ray against every block
+box in torch (forest.py:353-394) because the octree traversal it wanted (:302-351) stood on that kaolin trace.  The kaolin
+trace stays out: it returns (ray, node) pairs in its own order with no entry / exit depths, so the ray test would still need
+the slab test, the sort and the packing behind it; csrc/forest_ray_test.hip descends the byte octree this module already owns
+and emits the dense route's segments directly, bit for bit (the contract is in include/nr3d_hip.h).
 """
 import ctypes as C
+import math
 
 import torch
 
 from .. import _hip as H
+from ._args import chk, same_device
 
-__all__ = ['ForestMeta', 'forest_identify']
+__all__ = ['ForestMeta', 'forest_identify', 'forest_ray_test']
 
 
 class _CForest(C.Structure):
@@ -78,6 +86,66 @@ def forest_identify(forest: ForestMeta, ks: torch.Tensor) -> torch.Tensor:
         c = forest._c()
         H.check(H.lib().nr3d_forest_identify(C.byref(c), k16.shape[0], H.ptr(k16), H.ptr(out), H.stream_of(ks)))
     return out.view(ks.shape[:-1])
+
+
+def forest_ray_test(forest: ForestMeta, rays_o: torch.Tensor, rays_d: torch.Tensor, near=None, far=None):
+    """the (block, entry, exit) segments of float32 rays [R, 3] through the forest's blocks, one octree descent per ray: count ->
+    ``nr3d_prune_compact_packs`` on the counts (the ONE device->host sync) -> emit.  near / far: None, a number, or float32 [R].
+    -> None when no ray hits a block, else dict(rays_inds int64 [P'] ascending, seg_pack_infos int64 [P', 2] marked ordered and tiling
+    [0, S), seg_block_inds int64 [S], seg_entries / seg_exits float32 [S] sorted by (entry, block) in every pack, near / far float32
+    [P']: the given value of the hit ray, or its first entry / its last segment's exit when absent).  A CPU tensor raises
+    RuntimeError; there is no fallback here, and no backward."""
+    from ._pack_ops import _scan_tmp
+    fn = "forest_ray_test"
+    chk(fn, "rays_o", rays_o)
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3:
+        raise RuntimeError(f"{fn}: `rays_o` must be [R, 3], got {list(rays_o.shape)}")
+    R, dev = rays_o.shape[0], rays_o.device
+    chk(fn, "rays_d", rays_d, (R, 3))
+    bounds = []
+    for name, v, absent in (("near", near, 0.0), ("far", far, math.inf)):
+        if v is None:
+            bounds += [None, absent]
+        elif isinstance(v, torch.Tensor):
+            bounds += [chk(fn, name, v, (R,)), 0.0]
+        else:
+            bounds += [None, float(v)]
+    same_device(fn, dev, "rays_o", rays_d=rays_d, near=bounds[0], far=bounds[2])
+    forest._check(fn, rays_o)
+    if R >= 2 ** 28:
+        raise RuntimeError(f"{fn}: {R} rays, the limit is 2^28 - 1 per call (split the batch)")
+    if R == 0:
+        return None
+    with H.on_device(dev):
+        l, st, c = H.lib(), H.stream_of(rays_o), forest._c()
+        head = (C.byref(c), R, H.ptr(rays_o), H.ptr(rays_d), H.ptr(bounds[0]), bounds[1], H.ptr(bounds[2]), bounds[3])
+        counts = H.empty(R, dtype=torch.int64, device=dev)
+        H.check(l.nr3d_forest_ray_test_count(*head, H.ptr(counts), st))
+        begin_all = H.empty(R, dtype=torch.int64, device=dev)
+        ridx_hit = H.empty(R, dtype=torch.int64, device=dev)
+        pack_infos = H.empty((R, 2), dtype=torch.int64, device=dev)
+        totals = H.host_i64(2, dev)
+        H.check(l.nr3d_prune_compact_packs(R, H.ptr(counts), None, H.ptr(begin_all), H.ptr(ridx_hit), H.ptr(pack_infos), H.ptr(totals),
+                                           H.ptr(_scan_tmp(R, dev)), st))
+        S, n_hit = H.wait_i64(totals, dev)                  # the one device->host sync
+        if S == 0:
+            return None
+        seg_block_inds = H.empty(S, dtype=torch.int64, device=dev)
+        seg_entries = H.empty(S, dtype=torch.float32, device=dev)
+        seg_exits = H.empty(S, dtype=torch.float32, device=dev)
+        H.check(l.nr3d_forest_ray_test_emit(*head, H.ptr(counts), H.ptr(begin_all), S, H.ptr(seg_block_inds), H.ptr(seg_entries),
+                                            H.ptr(seg_exits), st))
+    ridx_hit, pack_infos = ridx_hit[:n_hit], pack_infos[:n_hit]
+    if near is None:
+        near = seg_entries[pack_infos[:, 0]]
+    else:
+        near = near[ridx_hit] if isinstance(near, torch.Tensor) else rays_o.new_full([n_hit], float(near))
+    if far is None:
+        far = seg_exits[pack_infos.sum(-1).sub_(1)]
+    else:
+        far = far[ridx_hit] if isinstance(far, torch.Tensor) else rays_o.new_full([n_hit], float(far))
+    return dict(rays_inds=ridx_hit, seg_pack_infos=H.mark_ordered(pack_infos, total=S), seg_block_inds=seg_block_inds,
+                seg_entries=seg_entries, seg_exits=seg_exits, near=near, far=far)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -18,12 +18,32 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from nr3d_lib_amd.bindings._forest import ForestMeta, forest_identify
+from nr3d_lib_amd.bindings._forest import ForestMeta, forest_identify, forest_ray_test
 from nr3d_lib_amd.graphics.pack_ops import (get_pack_infos_from_first, interleave_sample_step_wrt_depth_in_packed_segments,
                                             mark_pack_boundaries, packed_sort_inplace)
 from nr3d_lib_amd.graphics.raysample import interleave_sample_step_linear_in_packed_segments
 
 __all__ = ['ForestBlockSpace', 'octree_from_corners', 'ray_box_intersection']
+
+# ForestBlockSpace.ray_test on float32 GPU rays: one octree descent per ray (csrc/forest_ray_test.hip: three launches and one host
+# wait, work ~ rays x blocks crossed) instead of the dense [R, B] torch chain below.  Same segments bit for bit; equal entries come
+# in block order.  tools/exp_forest_ray_test.py -> profiles/forest_ray_test.json decides the default.
+FUSED_FOREST_RAY_TEST = True
+
+
+def _takes_fused_ray_test(space, rays_o, rays_d, near, far) -> bool:
+    if not FUSED_FOREST_RAY_TEST or space.meta is None or space.meta.level > 15:
+        return False
+    if not (rays_o.is_cuda and rays_o.dtype == torch.float32 and rays_o.dim() == 2 and rays_o.shape[1] == 3
+            and rays_d.shape == rays_o.shape and rays_d.dtype == rays_o.dtype and rays_d.device == rays_o.device):
+        return False
+    for v in (near, far):
+        if isinstance(v, torch.Tensor):
+            if not (v.dtype == torch.float32 and v.device == rays_o.device and tuple(v.shape) == (rays_o.shape[0],)):
+                return False
+        elif v is not None and not isinstance(v, Number):
+            return False
+    return True
 
 
 def _morton(k: torch.Tensor, level: int) -> torch.Tensor:
@@ -225,7 +245,10 @@ class ForestBlockSpace(nn.Module):
     # ---- rays ----------------------------------------------------------------------------------------------------------
     def ray_test(self, rays_o: torch.Tensor, rays_d: torch.Tensor, near=None, far=None, return_rays=True, **extra_ray_data):
         """ray / block-box intersections of every (ray, block) pair, kept as per-ray packs of (block, entry, exit)
-        segments sorted by entry depth (forest.py:353-394)"""
+        segments sorted by entry depth (forest.py:353-394).  float32 GPU rays take one descent of the block octree per ray
+        (``FUSED_FOREST_RAY_TEST``, bindings._forest.forest_ray_test): the same dict, equal entries ordered by block index"""
+        if _takes_fused_ray_test(self, rays_o, rays_d, near, far):
+            return self._ray_test_fused(rays_o, rays_d, near, far, return_rays, extra_ray_data)
         wo, wb = self.world_origin.to(rays_o.dtype), self.world_block_size.to(rays_o.dtype)
         with torch.no_grad():
             bmin = self.block_ks.to(rays_o.dtype) * wb + wo
@@ -258,6 +281,23 @@ class ForestBlockSpace(nn.Module):
         ret = dict(num_rays=num_rays, rays_inds=ridx_hit.long().contiguous(), near=near, far=far,
                    seg_pack_infos=seg_pack_infos.long().contiguous(), seg_block_inds=blidx.long().contiguous(),
                    seg_entries=seg_entries.contiguous(), seg_exits=seg_exits.contiguous())
+        ret.update({k: v[ridx_hit] if isinstance(v, torch.Tensor) else v for k, v in extra_ray_data.items()})
+        if return_rays:
+            ret.update(rays_o=rays_o.index_select(0, ridx_hit), rays_d=rays_d.index_select(0, ridx_hit))
+        return ret
+
+    def _ray_test_fused(self, rays_o, rays_d, near, far, return_rays, extra_ray_data):
+        with torch.no_grad():
+            hit = forest_ray_test(self.meta, rays_o.detach().contiguous(), rays_d.detach().contiguous(),
+                                  near.detach().contiguous() if isinstance(near, torch.Tensor) else near,
+                                  far.detach().contiguous() if isinstance(far, torch.Tensor) else far)
+        if hit is None:
+            ret = dict(num_rays=0, rays_inds=None)
+            if return_rays:
+                ret.update(rays_o=rays_o[:0], rays_d=rays_d[:0])
+            return ret
+        ridx_hit = hit['rays_inds']
+        ret = dict(num_rays=ridx_hit.numel(), **hit)
         ret.update({k: v[ridx_hit] if isinstance(v, torch.Tensor) else v for k, v in extra_ray_data.items()})
         if return_rays:
             ret.update(rays_o=rays_o.index_select(0, ridx_hit), rays_d=rays_d.index_select(0, ridx_hit))
