@@ -1299,6 +1299,10 @@ int nr3d_marching_cubes_emit(const float *volume, uint32_t Nx, uint32_t Ny, uint
  *     a sorted list in statically indexed registers); 0: k_knn_any, one lane per query, p2 from global memory, the list in the row's
  *     own output slots -- the same contract, CORRECT AND UNOPTIMISED.
  *   nr3d_knn_tile_points(D): the tile length of the fast kernel for this D, 0 without one (tests place P2 around it).
+ *   nr3d_knn_launch_plan(N, P1, D, K): what nr3d_knn_points launches for N clouds of P1 query points: 0 when k_knn_any serves (D, K),
+ *     else R | wg << 8, R = query points per lane (1, 2 or 4), wg = lanes per workgroup (64, 128 or 256); a workgroup covers wg R
+ *     consecutive rows of one cloud.  Computed by the function the launcher itself calls, no device is touched (tests assert the
+ *     variant they mean to run before they run it).  An addition that touches no existing entry: the ABI number stays.
  * nr3d_knn_points_backward: idx int64 [N, P1, K] and grad_dists float32 [N, P1, K] as the forward shaped them.  For k < min(K,
  *   lengths2[n]), i < lengths1[n] and each c:  norm == 2: t = 2 g[n,i,k] (p1 - p2[idx]);  norm == 1: t = g (p1 > p2 ? 1 : -1) (at
  *   equality -1 for p1, as in the reference).  grad_p1 float32 [N, P1, D]: the lane's own sum over k, fully written without atomics
@@ -1311,6 +1315,7 @@ int nr3d_knn_points_backward(const float *p1, const float *p2, const int64_t *le
                              float *grad_p2, void *stream);
 int nr3d_knn_fast_path(uint32_t D, uint32_t K);
 int nr3d_knn_tile_points(uint32_t D);
+int nr3d_knn_launch_plan(uint64_t N, uint64_t P1, uint32_t D, uint32_t K);
 
 /* ---- ray test of a forest of blocks (csrc/forest_ray_test.hip; ForestBlockSpace.ray_test, nr3d_lib/models/spatial/forest.py:353-394,
  * which tests every ray against every block box because the octree traversal it wanted, :302-351, stood on kaolin's SPC ray trace).

@@ -12,7 +12,7 @@ import torch
 from .. import _hip as H
 from ._args import chk, same_device
 
-__all__ = ["knn_points_idx", "knn_points_backward", "TILE", "fast_path"]
+__all__ = ["knn_points_idx", "knn_points_backward", "TILE", "fast_path", "launch_plan"]
 
 
 def TILE(D):
@@ -23,6 +23,13 @@ def TILE(D):
 def fast_path(D, K):
     """True: k_knn<D, KB, NORM> serves (D, K); False: the generic, unoptimised k_knn_any"""
     return bool(H.lib().nr3d_knn_fast_path(int(D), int(K)))
+
+
+def launch_plan(N, P1, D, K):
+    """(R, wg) of the k_knn<D, KB, NORM, R> launch for N clouds of P1 query points: R queries per lane, wg lanes per workgroup, from the
+    function the launcher itself calls; None: the generic k_knn_any serves (D, K)"""
+    plan = int(H.lib().nr3d_knn_launch_plan(int(N), int(P1), int(D), int(K)))
+    return (plan & 0xFF, plan >> 8) if plan else None
 
 
 def _clouds(fn, p1, p2, lengths1, lengths2, norm):

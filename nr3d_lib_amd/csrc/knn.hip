@@ -291,24 +291,51 @@ static int launch_r(const Args &a, uint32_t wg) {
 	return 0;
 }
 
+// the launch plan of the fast kernel, pure host arithmetic: what launch_kb launches and what nr3d_knn_launch_plan reports
+struct Plan { uint32_t R, wg; };
+
+// the K bucket of the fast kernel (K in 1 .. kMaxKB)
+static uint32_t bucket_of(uint32_t K) { return K == 1 ? 1u : K <= 4 ? 4u : K <= 8 ? 8u : K <= 16 ? 16u : 32u; }
+
+static uint32_t wide_r(uint32_t KB) {
+	switch (KB) {
+	case 1: return Wide<1>::R;
+	case 4: return Wide<4>::R;
+	case 8: return Wide<8>::R;
+	case 16: return Wide<16>::R;
+	default: return Wide<32>::R;
+	}
+}
+
 // the wide variant (Wide<KB>::R queries per lane, kBlock lanes) when that still gives every CU two workgroups; else one query per lane, and
 // then smaller workgroups, down to one wave
+static Plan plan_of(uint64_t N, uint64_t P1, uint32_t KB) {
+	const uint32_t RW = wide_r(KB);
+	if (RW > 1 && N * div_up(P1, (uint64_t)kBlock * RW) >= kWantGroups) return Plan{RW, (uint32_t)kBlock};
+	uint32_t wg = kBlock;
+	while (wg > 64 && N * div_up(P1, wg) < kWantGroups) wg >>= 1;
+	return Plan{1u, wg};
+}
+
 template <int D, int KB, int NORM>
 static int launch_kb(const Args &a) {
 	constexpr int RW = Wide<KB>::R;
-	if (RW > 1 && a.N * div_up(a.P1, (uint64_t)kBlock * RW) >= kWantGroups) return launch_r<D, KB, NORM, RW>(a, kBlock);
-	uint32_t wg = kBlock;
-	while (wg > 64 && a.N * div_up(a.P1, wg) < kWantGroups) wg >>= 1;
-	return launch_r<D, KB, NORM, 1>(a, wg);
+	const Plan p = plan_of(a.N, a.P1, KB);
+	if constexpr (RW > 1) {
+		if (p.R == (uint32_t)RW) return launch_r<D, KB, NORM, RW>(a, p.wg);
+	}
+	return launch_r<D, KB, NORM, 1>(a, p.wg);
 }
 
 template <int D, int NORM>
 static int launch_d(const Args &a) {
-	if (a.K == 1) return launch_kb<D, 1, NORM>(a);
-	if (a.K <= 4) return launch_kb<D, 4, NORM>(a);
-	if (a.K <= 8) return launch_kb<D, 8, NORM>(a);
-	if (a.K <= 16) return launch_kb<D, 16, NORM>(a);
-	return launch_kb<D, 32, NORM>(a);
+	switch (bucket_of(a.K)) {
+	case 1: return launch_kb<D, 1, NORM>(a);
+	case 4: return launch_kb<D, 4, NORM>(a);
+	case 8: return launch_kb<D, 8, NORM>(a);
+	case 16: return launch_kb<D, 16, NORM>(a);
+	default: return launch_kb<D, 32, NORM>(a);
+	}
 }
 
 template <int NORM>
@@ -345,6 +372,12 @@ extern "C" int nr3d_knn_fast_path(uint32_t D, uint32_t K) {
 }
 
 extern "C" int nr3d_knn_tile_points(uint32_t D) { return D >= 1 && D <= (uint32_t)knn::kMaxD ? knn::kTile : 0; }
+
+extern "C" int nr3d_knn_launch_plan(uint64_t N, uint64_t P1, uint32_t D, uint32_t K) {
+	if (!nr3d_knn_fast_path(D, K)) return 0;
+	const knn::Plan p = knn::plan_of(N, P1, knn::bucket_of(K));
+	return (int)(p.R | p.wg << 8);
+}
 
 extern "C" int nr3d_knn_points(const float *p1, const float *p2, const int64_t *lengths1, const int64_t *lengths2, uint64_t N, uint64_t P1,
                                uint64_t P2, uint32_t D, uint32_t K, int norm, float *dists, int64_t *idx, void *stream) {

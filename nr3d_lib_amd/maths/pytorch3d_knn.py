@@ -101,6 +101,7 @@ def _knn_torch_backward(p1, p2, lengths1, lengths2, idx, norm, grad_dists):
         return torch.zeros((N, P1, D), dtype=torch.float32, device=dev), grad_p2
     live = (torch.arange(K, device=dev)[None, None, :] < lengths2.clamp(0, P2)[:, None, None]) \
         & (torch.arange(P1, device=dev)[None, :, None] < lengths1.clamp(0, P1)[:, None, None])           # [N, P1, K]
+    live = live & (idx >= 0) & (idx < P2)              # an idx outside [0, P2) is skipped: its t is zero, the clamp only keeps the gather in range
     j = idx.clamp(0, P2 - 1)
     nb = torch.gather(p2[:, :, None, :].expand(-1, -1, K, -1), 1, j[..., None].expand(-1, -1, -1, D))   # [N, P1, K, D]
     g = grad_dists[..., None]

@@ -5,7 +5,7 @@ Forward: per-dimension float32 differences; norm 2 accumulates d_0 * d_0 and the
 multiply-add rounded to float32 (the product of two float32 is exact in float64; the float64 sum is rounded once more, a double rounding
 that the lattice never meets and the float tests allow for in their bound) -- norm 1 accumulates |d_c| in float32.  Selection:
 ``np.lexsort((j, dist))``, the first min(K, lengths2[n]) pairs, zeros after them and in the rows past lengths1[n].
-Backward: float64.
+Backward: float64; an idx outside [0, P2) is skipped, as the contract says (no term in either gradient).
 
 lattice(): coordinates k / 256 with integer |k| <= kmax and D (2 kmax)^2 <= 2^24: every difference, square and partial sum is exact in
 float32, so the fmaf chain, separate multiply-add and float64 give the same bits, and the lattice is full of ties.
@@ -32,6 +32,41 @@ def lattice(rng, shape, kmax=None):
 
 def normal(rng, shape):
     return rng.standard_normal(shape).astype(np.float32)
+
+
+I64_MIN, I64_MAX = -2 ** 63, 2 ** 63 - 1
+
+
+def wild_lengths(rng, N, P, at=0):
+    """int64 [N]: -5, P, P + 1, -1, 2^40, INT64_MIN, INT64_MAX and 0 in the clouds at .. at + 7, random values of [1, P] in the others;
+    the contract clamps each into [0, P].  lengths1 with at = 0 and lengths2 with at = 8 put every wild value of one beside a live
+    value of the other."""
+    assert N >= 8 + at
+    l = rng.integers(1, P + 1, N).astype(np.int64)
+    l[at:at + 8] = [-5, P, P + 1, -1, 2 ** 40, I64_MIN, I64_MAX, 0]
+    return l
+
+
+def spoil_idx(rng, idx, P2, share=0.1):
+    """a copy of idx with about `share` of its entries replaced by -1, P2, P2 + 7 and 2^40, none of them an index of knn_points, and the
+    bool mask of the replaced entries"""
+    bad = rng.random(idx.shape) < share
+    out = idx.copy()
+    out[bad] = rng.choice(np.array([-1, P2, P2 + 7, 2 ** 40], np.int64), int(bad.sum()))
+    return out, bad
+
+
+def directed_p2(D, order, P2=1025):
+    """float32 [P2, D] that varies in coordinate 0 only, k / 256 with 0 <= k < P2, the other coordinates 0.  Against a query whose
+    coordinate 0 is <= 0 the distance grows with k, so: "descending": k = P2 - 1 - j, every candidate is the nearest so far (enters at
+    slot 0 and shifts the whole list); "ascending": k = j, nothing enters once the list is full; "alternating": far, near, far, ...
+    (k = P2 - 1 - j / 2 for even j, (j - 1) / 2 for odd j); "equal": every point the same (k = 3)"""
+    j = np.arange(P2)
+    k = {"descending": P2 - 1 - j, "ascending": j, "alternating": np.where(j % 2 == 0, P2 - 1 - j // 2, (j - 1) // 2),
+         "equal": np.full(P2, 3)}[order]
+    p2 = np.zeros((P2, D), np.float32)
+    p2[:, 0] = k.astype(np.float32) / np.float32(256)
+    return p2
 
 
 def dist_bound(D, dist):
@@ -110,11 +145,13 @@ def knn_backward(p1, p2, lengths1, lengths2, idx, norm, grad_dists):
     for n in range(N):
         n1, k = int(l1[n]), min(K, int(l2[n]))
         for kk in range(k):
-            j = idx[n, :n1, kk]
-            diff = p1[n, :n1] - p2[n, j]
-            t = 2.0 * g[n, :n1, kk, None] * diff if norm == 2 else g[n, :n1, kk, None] * np.where(diff > 0, 1.0, -1.0)
-            g1[n, :n1] += t
-            a1[n, :n1] += np.abs(t)
+            j = np.asarray(idx[n, :n1, kk], np.int64)
+            ok = (j >= 0) & (j < P2)                               # an idx outside [0, P2) is skipped: no term in either gradient
+            rows, j = np.nonzero(ok)[0], j[ok]
+            diff = p1[n, rows] - p2[n, j]
+            t = 2.0 * g[n, rows, kk, None] * diff if norm == 2 else g[n, rows, kk, None] * np.where(diff > 0, 1.0, -1.0)
+            np.add.at(g1[n], rows, t)
+            np.add.at(a1[n], rows, np.abs(t))
             np.add.at(g2[n], j, -t)
             np.add.at(a2[n], j, np.abs(t))
             np.add.at(m2[n], j, 1)

@@ -132,6 +132,58 @@ def test_backward_agrees_with_float64_autograd_of_the_dense_formula(norm):
     assert np.all(np.abs(g2.numpy() - w2.numpy()) <= (m2[..., None] + 3) * R.EPS * s2)
 
 
+@pytest.mark.parametrize("norm", [1, 2])
+@pytest.mark.parametrize("D,K", [(3, 4), (3, 33)])
+def test_cpu_route_clamps_lengths_outside_the_cloud(norm, D, K):
+    """"a value of lengths outside [0, P] is clamped into it": -5, -1, P + 1, 2^40, INT64_MIN and INT64_MAX in both lengths, forward
+    and backward, against the restatement with its np.clip (the GPU twin: test_lengths_outside_the_cloud_are_clamped)"""
+    N, P1, P2 = 16, 70, 7
+    rng = np.random.default_rng(N + K)
+    p1, p2 = R.lattice(rng, (N, P1, D), kmax=8), R.lattice(rng, (N, P2, D), kmax=8)
+    l1, l2 = R.wild_lengths(rng, N, P1), R.wild_lengths(rng, N, P2, at=8)
+    assert {-5, -1, P1 + 1, 2 ** 40, R.I64_MIN, R.I64_MAX} <= set(l1.tolist()) and {-5, -1, P2 + 1, 2 ** 40, R.I64_MIN, R.I64_MAX} <= set(l2.tolist())
+    gd = (2.0 ** rng.integers(-2, 3, size=(N, P1, K))).astype(np.float32)
+    a, b = _t(p1, grad=True), _t(p2, grad=True)
+    res = maths.knn_points(a, b, _t(l1), _t(l2), norm=norm, K=K)
+    idx, d = R.knn_points(p1, p2, l1, l2, norm=norm, K=K)
+    assert idx.any() and np.array_equal(res.idx.numpy(), idx) and np.array_equal(res.dists.detach().numpy(), d)
+    # every wild value is what its clamped value is
+    i2, d2 = R.knn_points(p1, p2, np.clip(l1, 0, P1), np.clip(l2, 0, P2), norm=norm, K=K)
+    assert np.array_equal(i2, idx) and np.array_equal(d2, d)
+    g1, g2 = torch.autograd.grad(res.dists, (a, b), _t(gd))
+    w1, w2 = R.knn_backward(p1, p2, l1, l2, idx, norm, gd)[:2]
+    assert w1.any() and np.array_equal(g1.numpy().astype(np.float64), w1) and np.array_equal(g2.numpy().astype(np.float64), w2)
+
+
+@pytest.mark.parametrize("norm", [1, 2])
+@pytest.mark.parametrize("D,K", [(3, 8), (9, 3)])
+def test_cpu_route_backward_skips_idx_outside_the_cloud(norm, D, K):
+    """"an idx outside [0, P2) is skipped": a tenth of a real forward's idx overwritten by -1, P2, P2 + 7 and 2^40; those (n, i, k)
+    terms are missing from both gradients, the others are as before (the GPU twin: test_backward_skips_idx_outside_the_cloud)"""
+    N, P1, P2 = 2, 300, 5
+    rng = np.random.default_rng(D + K)
+    p1, p2 = R.lattice(rng, (N, P1, D), kmax=8), R.lattice(rng, (N, P2, D), kmax=8)
+    gd = (2.0 ** rng.integers(-2, 3, size=(N, P1, K))).astype(np.float32)
+    for lens in ((None, None), (np.array([299, 120]), np.array([5, 2]))):
+        idx = R.knn_points(p1, p2, lens[0], lens[1], norm, K)[0]
+        bad, hit = R.spoil_idx(rng, idx, P2)
+        assert all((bad == v).any() for v in (-1, P2, P2 + 7, 2 ** 40)) and np.array_equal(bad[~hit], idx[~hit])
+        full = [torch.full((N,), P, dtype=torch.int64) if l is None else _t(l) for l, P in zip(lens, (P1, P2))]
+        g1, g2 = M._knn_torch_backward(_t(p1), _t(p2), *full, _t(bad), norm, _t(gd))
+        w1, w2 = R.knn_backward(p1, p2, lens[0], lens[1], bad, norm, gd)[:2]
+        clean = R.knn_backward(p1, p2, lens[0], lens[1], idx, norm, gd)[:2]
+        assert not np.array_equal(w1, clean[0]) and not np.array_equal(w2, clean[1])
+        assert np.array_equal(g1.numpy().astype(np.float64), w1) and np.array_equal(g2.numpy().astype(np.float64), w2)
+
+
+def test_ref_backward_skips_idx_outside_the_cloud():
+    """the restatement itself, on the 3-4-5 answer of test_ref_known_answers: a spoiled slot takes its term out of both gradients"""
+    p1, p2 = np.zeros((1, 1, 2)), np.array([[[3.0, 4.0], [-1.0, 0.0]]])
+    for j in (-1, 2, 9, 2 ** 40):
+        g1, g2 = R.knn_backward(p1, p2, None, None, np.array([[[1, j]]]), 2, np.array([[[1.0, 0.5]]]))[:2]
+        assert g1.tolist() == [[[2.0, 0.0]]] and g2.tolist() == [[[0.0, 0.0], [-2.0, 0.0]]]
+
+
 def test_knn_gather_edges():
     x = torch.arange(24, dtype=torch.float32).view(2, 4, 3)
     idx = torch.tensor([[[0, 3, 1]], [[2, 0, 0]]])
@@ -159,13 +211,70 @@ def test_empty_clouds():
 def test_header_and_table_have_the_entries():
     from nr3d_lib_amd import _abi
     header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "nr3d_hip.h")).read(), flags=re.S)
-    want = {"nr3d_knn_points": 13, "nr3d_knn_points_backward": 15, "nr3d_knn_fast_path": 2, "nr3d_knn_tile_points": 1}
+    want = {"nr3d_knn_points": 13, "nr3d_knn_points_backward": 15, "nr3d_knn_fast_path": 2, "nr3d_knn_tile_points": 1,
+            "nr3d_knn_launch_plan": 4}
     for name, nargs in want.items():
         assert re.search(r"\bint\s+%s\s*\(" % name, header), name
         ret, args = _abi.SIGNATURES[name]
         assert ret == "int" and len(args) == nargs, (name, args)
     assert _abi.SIGNATURES["nr3d_knn_points"][1][:4] == ["ptr"] * 4 and _abi.SIGNATURES["nr3d_knn_points"][1][4:7] == ["uint64_t"] * 3
+    assert _abi.SIGNATURES["nr3d_knn_launch_plan"][1] == ["uint64_t", "uint64_t", "uint32_t", "uint32_t"]
     assert _abi.ABI_VERSION == 29
+
+
+def test_launch_plan_is_the_documented_rule(hiplib):
+    """launch_plan (the function the launcher calls) against the rule as DESIGN.md 4h words it: the wide variant (R = 4 for KB 1, 2 for
+    KB 4 .. 16, none for KB 32; 256 lanes) when N ceil(P1 / (256 R)) >= 512 workgroups, else R = 1 and the workgroup halved down to
+    one wave while there are fewer than 512; nothing for a (D, K) off the fast kernel.  No device is touched."""
+    from nr3d_lib_amd.bindings import _pytorch3d_knn as B
+
+    def rule(N, P1, K):
+        Rw = 4 if K == 1 else 2 if K <= 16 else 1
+        if Rw > 1 and N * -(-P1 // (256 * Rw)) >= 512:
+            return Rw, 256
+        wg = 256
+        while wg > 64 and N * -(-P1 // wg) < 512:
+            wg //= 2
+        return 1, wg
+
+    seen = set()
+    for N in (1, 2, 3, 255, 256, 257, 300, 511, 512, 513, 1 << 20):
+        for P1 in (1, 64, 65, 128, 129, 200, 256, 257, 300, 512, 513, 1000, 1024, 1025, 2049, 1 << 20):
+            for K in (1, 2, 4, 5, 8, 9, 16, 17, 32):
+                for D in (1, 3, 8):
+                    assert B.launch_plan(N, P1, D, K) == rule(N, P1, K), (N, P1, D, K)
+                seen.add(rule(N, P1, K))
+            assert B.launch_plan(N, P1, 9, 1) is None and B.launch_plan(N, P1, 3, 33) is None and B.launch_plan(N, P1, 0, 1) is None
+    assert seen == {(1, 64), (1, 128), (1, 256), (2, 256), (4, 256)}
+    assert B.launch_plan(2 ** 31 - 1, 2 ** 31 - 1, 3, 1) == (4, 256)
+
+
+def test_every_compiled_kernel_has_a_named_case(hiplib):
+    """tests/test_knn_gpu.py's coverage(): every instantiation of csrc/knn.hip -- k_knn<D, KB, NORM, 1> (80), the wide k_knn<D, KB, NORM,
+    R> (64: R = 4 for KB 1, 2 for KB 4, 8, 16) and k_knn_any<DC> (9) -- is claimed by at least one case; the case exists under that
+    id, and the launcher's own plan for the case's rows is the variant it claims, so a retuned kWantGroups or Wide<KB>::R fails here
+    (and in the case itself) instead of silently moving the coverage"""
+    import test_knn_gpu as G
+    from nr3d_lib_amd.bindings import _pytorch3d_knn as B
+    table = G.coverage()
+    narrow = {("k_knn", D, KB, norm, 1) for D in range(1, 9) for KB in (1, 4, 8, 16, 32) for norm in (1, 2)}
+    wide = {("k_knn", D, KB, norm, 4 if KB == 1 else 2) for D in range(1, 9) for KB in (1, 4, 8, 16) for norm in (1, 2)}
+    generic = {("k_knn_any", DC) for DC in range(9)}
+    assert (len(narrow), len(wide), len(generic)) == (80, 64, 9)
+    assert set(table) == narrow | wide | generic
+    for inst, cases in table.items():
+        assert cases, inst
+        for case, N, P1, D, K in cases:
+            name, params = re.fullmatch(r"(\w+)\[([\d-]+)\]", case).groups()
+            marks = [m for m in getattr(G, name).pytestmark if m.name == "parametrize"]
+            assert len(marks) == 1 and marks[0].args[0] == "D,K,norm" and tuple(int(p) for p in params.split("-")) in marks[0].args[1], case
+            assert (D, K) == tuple(int(p) for p in params.split("-"))[:2]
+            plan = B.launch_plan(N, P1, D, K)
+            if inst[0] == "k_knn":
+                assert B.fast_path(D, K) and D == inst[1] and G.bucket(K) == inst[2] and plan is not None and plan[0] == inst[4], (inst, case)
+                assert inst[3] == int(params.split("-")[2])
+            else:
+                assert plan is None and not B.fast_path(D, K) and inst[1] == (D if D <= 8 else 0), (inst, case)
 
 
 def test_module_surface():
@@ -180,6 +289,7 @@ def test_module_surface():
     assert not M._fused(torch.zeros(1, 4, 3), 1) and not M._fused(torch.zeros(1, 4, 3))      # CPU tensors: the torch route
     from nr3d_lib_amd.bindings import _pytorch3d_knn as B
     assert callable(B.knn_points_idx) and callable(B.knn_points_backward) and callable(B.TILE) and callable(B.fast_path)
+    assert callable(B.launch_plan) and "launch_plan" in B.__all__
 
 
 def test_argument_errors():
