@@ -550,6 +550,25 @@ int nr3d_mlp_half_backward(const nr3d_mlp_desc_t *desc, uint64_t n, const void *
                            const void *dL_dy, int64_t gy_stride, const void *packed, void *dL_dx, int64_t gx_stride,
                            int64_t gx_feature_stride, float *const *dL_dW, float *const *dL_db, void *stream);
 
+/* The weight normalisation of the reference's LipshitzMLP (nr3d_lib/models/blocks/mlp.py:168-249, `normalization`) and its gradient,
+ * ONE launch each for all layers of a network (csrc/mlp_lipschitz.hip; additions, the ABI number stays).  Per layer l and row r:
+ *   sp = softplus(c[l]) (torch's: beta 1, threshold 20),  a = sum_j |W[r, j]|,  den = max(a, sp) (a NaN propagates, as clamp_min),
+ *   normalized[l][r, j] = W[r, j] * (sp / den), rounded once to the weight type; where a < sp that is W[r, j] bit for bit.
+ * The decoder entries above then take `normalized` in place of the weights.  Backward, from grads[l] = dL/d normalized[l] (fp32):
+ *   S = sum_j grads[l][r, j] W[r, j],  pass = a >= sp (a tie sends the gradient through a),
+ *   dL_dW[l][r, j] = grads[l][r, j] sp / den - (pass ? sign(W[r, j]) S (sp / den) / den : 0)      (sign(0) = 0),
+ *   dL_dc[l] = softplus'(c[l]) sum_r S_r / den_r -- both fp32 and WRITTEN (no zero fill, no atomics: a fixed summation order, the same
+ *   bytes run after run).  Inf, NaN, all-zero rows and an sp that underflows to 0 give what IEEE arithmetic gives, as in the torch chain.
+ * rows[l] x cols[l] (HOST arrays, each 1..4096: not restricted to the fused decoder's widths) is the shape of weights[l], row-major and
+ * contiguous; weights / normalized / grads / dL_dW: HOST arrays of n_layers DEVICE pointers, as nr3d_mlp_pack takes them (outputs must
+ * not alias inputs); weights_half != 0: weights and normalized are __half, else float; c: n_layers floats on the device.
+ * n_layers 1..NR3D_MLP_MAX_LAYERS + 1; a zero or too large dimension or a NULL pointer fails with a message. */
+int nr3d_mlp_lipschitz_normalize(uint32_t n_layers, const uint32_t *rows, const uint32_t *cols, const void *const *weights,
+                                 int weights_half, const float *c, void *const *normalized, void *stream);
+int nr3d_mlp_lipschitz_normalize_backward(uint32_t n_layers, const uint32_t *rows, const uint32_t *cols, const void *const *weights,
+                                          int weights_half, const float *c, const float *const *grads, float *const *dL_dW,
+                                          float *dL_dc, void *stream);
+
 /* =================================================================================================
  * pack_ops -- replaces nr3d_lib.bindings._pack_ops  (csrc/pack_ops/pack_ops.h:11-65,
  * csrc/pack_ops/pack_ops.cpp:21-58, kernels csrc/pack_ops/pack_ops_cuda.cu)

@@ -248,6 +248,65 @@ def backward_backward_softplus(desc: MLPDesc, x: torch.Tensor, dL_dy: torch.Tens
 
 
 # ------------------------------------------------------------------------------------------------
+# the weight normalisation of a Lipschitz MLP (nr3d_mlp_lipschitz_normalize*, csrc/mlp_lipschitz.hip): one launch each way for all
+# layers of a network -- W~_l = W_l softplus(c_l) / max(row abs-sum, softplus(c_l)); not restricted to the fused decoder's shapes
+# ------------------------------------------------------------------------------------------------
+LIPSCHITZ_MAX_LAYERS = MAX_LAYERS + 1
+LIPSCHITZ_MAX_DIM = 4096
+
+
+def _lipschitz_args(name, weights, c):
+    """checks -> (contiguous weights, rows[], cols[], sizes, c, half)"""
+    weights = list(weights)
+    H.require_gpu(c, *weights)
+    n = len(weights)
+    if not 1 <= n <= LIPSCHITZ_MAX_LAYERS:
+        raise RuntimeError(f"{name}: {n} layers, expected 1..{LIPSCHITZ_MAX_LAYERS}")
+    dtype, dev = weights[0].dtype, weights[0].device
+    if dtype not in (torch.float32, torch.float16) or any(w.dtype != dtype or w.device != dev for w in weights):
+        raise RuntimeError(f"{name}: the weights must all be float32 or all be float16, on one GPU")
+    if c.dtype != torch.float32 or c.device != dev or tuple(c.shape) != (n,):
+        raise RuntimeError(f"{name}: expected c float32 [{n}] on the weights' device, got {c.dtype} {list(c.shape)}")
+    for l, w in enumerate(weights):
+        if w.dim() != 2 or not (1 <= w.shape[0] <= LIPSCHITZ_MAX_DIM and 1 <= w.shape[1] <= LIPSCHITZ_MAX_DIM):
+            raise RuntimeError(f"{name}: weights[{l}] has shape {list(w.shape)}, expected [rows, cols] with both in 1..{LIPSCHITZ_MAX_DIM}")
+    ws = [w.detach().contiguous() for w in weights]
+    rows = (C.c_uint32 * n)(*[w.shape[0] for w in ws])
+    cols = (C.c_uint32 * n)(*[w.shape[1] for w in ws])
+    return ws, rows, cols, [w.numel() for w in ws], c.detach().contiguous(), dtype == torch.float16
+
+
+def lipschitz_normalize(weights, c):
+    """weights[l] [rows_l, cols_l] (all float32 or all float16, on one GPU), c float32 [n_layers] -> [W~_l] of the weights' dtype: views of
+    ONE allocation, written by one launch"""
+    ws, rows, cols, sizes, c, half = _lipschitz_args("mlp.lipschitz_normalize", weights, c)
+    outs = [o.view_as(w) for o, w in zip(H.empty(sum(sizes), dtype=ws[0].dtype, device=c.device).split(sizes), ws)]
+    with H.on_device(c.device):
+        H.check(H.lib().nr3d_mlp_lipschitz_normalize(len(ws), rows, cols, _ptr_array(ws), int(half), H.ptr(c), _ptr_array(outs),
+                                                     H.stream_of(c)))
+    return outs
+
+
+def lipschitz_normalize_backward(weights, c, grads):
+    """grads[l] = dL/dW~_l (float32, the shapes of the weights) -> ([dL/dW_l float32], dL/dc float32 [n_layers]): views of ONE allocation,
+    written (not accumulated) by one launch in a fixed summation order"""
+    name = "mlp.lipschitz_normalize_backward"
+    ws, rows, cols, sizes, c, half = _lipschitz_args(name, weights, c)
+    grads = list(grads)
+    H.require_gpu(*grads)
+    if len(grads) != len(ws) or any(g.dtype != torch.float32 or g.shape != w.shape or g.device != c.device for g, w in zip(grads, ws)):
+        raise RuntimeError(f"{name}: expected one float32 gradient of each weight's shape, on the weights' device")
+    gs = [g.detach().contiguous() for g in grads]
+    n = len(ws)
+    parts = H.empty(sum(sizes) + n, dtype=torch.float32, device=c.device).split(sizes + [n])
+    dWs = [p.view_as(w) for p, w in zip(parts, ws)]
+    with H.on_device(c.device):
+        H.check(H.lib().nr3d_mlp_lipschitz_normalize_backward(n, rows, cols, _ptr_array(ws), int(half), H.ptr(c), _ptr_array(gs),
+                                                              _ptr_array(dWs), H.ptr(parts[n]), H.stream_of(c)))
+    return dWs, parts[n]
+
+
+# ------------------------------------------------------------------------------------------------
 # half precision on the f16 MFMA (nr3d_mlp_half_*): half x / weights / y, fp32 accumulation inside a layer, activations
 # rounded to half between the layers -- the contract of the reference's tcnn FullyFusedMLP (models/tcnn_adapter.py:37-51)
 # ------------------------------------------------------------------------------------------------

@@ -20,7 +20,11 @@ linear -- the eikonal term does give x and the hidden biases a gradient, and the
 kernel of its own (csrc/mlp_softplus2.hip k_mlp_bwd2_sp, ``desc.softplus_second_order_fusable``; ``desc.second_order_fusable`` stays False for
 it), taken when ``FUSED_SOFTPLUS_SECOND_ORDER`` is on: the nablas are then the fused first backward's dL/dx bit for bit.  With the switch
 off its create_graph backward differentiates the layer-by-layer torch evaluation of the same network -- which is also the route of a
-block with a sigmoid output, whatever its hidden layers: no double backward kernel takes it (both ``..._second_order_fusable`` are False)."""
+block with a sigmoid output, whatever its hidden layers: no double backward kernel takes it (both ``..._second_order_fusable`` are False).
+
+``LipshitzMLP`` (nr3d_lib/models/blocks/mlp.py:168-249) is the same network on weights normalised to a learnable bound per layer: the
+normalisation of all layers is one launch each way (csrc/mlp_lipschitz.hip, ``LipschitzNormalizeFunction``, ``FUSED_LIPSHITZ``), and the
+normalised weights take the routes above in place of the raw ones."""
 from typing import List, Union
 
 import torch
@@ -30,7 +34,8 @@ from nr3d_lib_amd.models.embedders import get_embedder
 from nr3d_lib_amd.models.layers import DenseLayer, get_nonlinearity
 from nr3d_lib_amd.profile import profile
 
-__all__ = ['MLP', 'FCBlock', 'MLPNet', 'FusedMLPFunction', 'FusedMLPHalfFunction', 'FusedMLPBackwardFunction']
+__all__ = ['MLP', 'FCBlock', 'MLPNet', 'LipshitzMLP', 'FusedMLPFunction', 'FusedMLPHalfFunction', 'FusedMLPBackwardFunction',
+           'LipschitzNormalizeFunction']
 
 USE_FUSED = True                       # False: always the layer-by-layer path (A/B measurements, debugging)
 # False: a create_graph backward of a fused block differentiates the layer-by-layer torch evaluation (the route before the fused double
@@ -39,6 +44,9 @@ FUSED_SECOND_ORDER = True
 # True: softplus networks take the fused route above too, through their own double backward kernel (k_mlp_bwd2_sp).  Needs
 # FUSED_SECOND_ORDER.  False: their create_graph backward differentiates the torch evaluation.  DESIGN 7b has the measurements behind the default.
 FUSED_SOFTPLUS_SECOND_ORDER = True
+# True: a LipshitzMLP on the GPU normalises the weights of all its layers in one launch (LipschitzNormalizeFunction) and hands them to the
+# routes of MLP, the fused decoder included.  False: the reference's torch chain, layer by layer.  README has the measurements behind the default.
+FUSED_LIPSHITZ = True
 
 
 def _fused_second_order(desc):
@@ -451,6 +459,135 @@ class MLP(nn.Module):
 
 
 FCBlock = MLP
+
+
+class LipschitzNormalizeFunction(torch.autograd.Function):
+    """(c, W_0 ... W_D) -> (W~_0 ... W~_D), W~_l = W_l softplus(c_l) / max(row abs-sum, softplus(c_l)): ``LipshitzMLP.normalization`` of every
+    layer in ONE launch (nr3d_mlp_lipschitz_normalize), its gradient in one more (nr3d_mlp_lipschitz_normalize_backward: dL/dW_l and dL/dc
+    written in a fixed order, no atomics).  fp32 GPU tensors.  Differentiable once: in an eikonal step the decoder's double backward
+    produces dL/dW~, and the normalisation is differentiated once after it."""
+
+    @staticmethod
+    def forward(ctx, c, *weights):
+        from nr3d_lib_amd.bindings import _mlp
+        ctx.save_for_backward(c, *weights)
+        return tuple(_mlp.lipschitz_normalize(weights, c))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        from nr3d_lib_amd.bindings import _mlp
+        c, *ws = ctx.saved_tensors
+        gs = [torch.zeros_like(w) if g is None else g.float() for g, w in zip(grads, ws)]
+        dWs, dc = _mlp.lipschitz_normalize_backward(ws, c, gs)
+        need = ctx.needs_input_grad
+        return (dc if need[0] else None, *[dW if n else None for dW, n in zip(dWs, need[1:])])
+
+
+class LipshitzMLP(MLP):
+    """``LipshitzMLP`` (nr3d_lib/models/blocks/mlp.py:168-249; https://arxiv.org/abs/2202.08345): an MLP whose layers run on weights
+    normalised to a learnable per-layer bound softplus(c_l) of their inf-norm, c = ``lipshitz_bound_per_layer`` (fp32, initialised to
+    max_r sum_j |W[r, j]| * ``c_init_factor`` per layer).  Same constructor, parameter names and methods as the reference's.
+
+    On the GPU (``FUSED_LIPSHITZ``) the normalised weights of all layers come from one launch (``LipschitzNormalizeFunction``) and are then
+    handed, in place of the raw weights, to the routes of ``MLP``: the fused decoder kernels wherever ``MLP`` would fuse the same network
+    (first and second order, ReLU / softplus hidden layers, sigmoid output, fp32 and half), the layer-by-layer torch evaluation otherwise
+    (``return_last``, shapes outside the kernels, autocast).  CPU tensors, or the switch off, take the reference's torch chain."""
+
+    def __init__(self, in_features: int, out_features: int, *, c_init_factor: float = 1.0, D: int = 4, W: Union[int, List[int]] = 128,
+                 skips: List[int] = [], activation: Union[str, dict] = 'relu', output_activation: Union[str, dict] = None, bias=True,
+                 last_bias: bool = None, weight_norm=False, equal_lr=False, dtype: Union[str, torch.dtype] = None,
+                 device: torch.device = None):
+        assert len(skips) == 0 and not weight_norm and not equal_lr
+        super().__init__(in_features, out_features, D=D, W=W, skips=[], activation=activation, output_activation=output_activation,
+                         bias=bias, last_bias=last_bias, equal_lr=False, weight_norm=False, dtype=dtype, device=device)
+        self.lipshitz_bound_per_layer = nn.Parameter(self.initial_bounds(c_init_factor), requires_grad=True)
+        self._normalized_cache = None
+
+    @torch.no_grad()
+    def initial_bounds(self, c_init_factor: float = 1.0) -> torch.Tensor:
+        """the constructor's value of ``lipshitz_bound_per_layer`` for the present weights: their inf-norm times ``c_init_factor``
+        (2.0 in permuto-SDF, 1.0 in the original Lipschitz regularisation)"""
+        c = [layer.weight.abs().sum(dim=1).max().item() * c_init_factor for layer in self.layers]
+        return torch.tensor(c, dtype=torch.float, device=self.layers[0].weight.device)
+
+    def normalization(self, w: torch.Tensor, softplus_ci: torch.Tensor):
+        absrowsum = w.abs().sum(dim=1)          # inf-norm of the matrix
+        # first clamp, then divide: safe where absrowsum is tiny
+        scale = softplus_ci / absrowsum.clamp_min_(softplus_ci.data)
+        return w * scale[:, None]
+
+    def lipshitz_bound_full(self):
+        return torch.prod(torch.nn.functional.softplus(self.lipshitz_bound_per_layer))
+
+    def get_weight_reg(self, norm_type: float = 2.0):
+        # (without `lipshitz_bound_per_layer`)
+        return torch.stack([p.norm(p=norm_type) for n, p in self.layers.named_parameters()])
+
+    def invalidate_packed(self):
+        self._normalized_cache = None
+        super().invalidate_packed()
+
+    def _normalized_weights(self):
+        """[W~_l] of all layers from one launch.  CACHE_PACKED: reused while no gradient is in play and (W_l, c) are the tensors and versions
+        they were computed from -- an optimiser step on c alone is a new version.  Fresh W~ are new tensors whose addresses the
+        allocator may hand out again, so the packed copy keyed on them (FusedMLPFunction) is dropped whenever they are recomputed."""
+        c, ws = self.lipshitz_bound_per_layer, [layer.weight for layer in self.layers]
+        reuse = CACHE_PACKED and not (torch.is_grad_enabled() and (c.requires_grad or any(w.requires_grad for w in ws)))
+        if reuse:
+            key = tuple((p.data_ptr(), p._version) for p in (c, *ws))
+            if self._normalized_cache is not None and self._normalized_cache[0] == key:
+                return self._normalized_cache[1]
+        self.invalidate_packed()
+        out = list(LipschitzNormalizeFunction.apply(c, *ws))
+        if reuse:
+            self._normalized_cache = (key, out)
+        return out
+
+    def _kernel_ok(self, x):
+        """does the normalisation run through the kernel?  fp32 parameters on x's GPU, within the entry's range"""
+        from nr3d_lib_amd.bindings import _mlp
+        c = self.lipshitz_bound_per_layer
+        return (FUSED_LIPSHITZ and x.is_cuda and c.is_cuda and c.dtype == torch.float32 and len(self.layers) <= _mlp.LIPSCHITZ_MAX_LAYERS
+                and all(l.weight.dtype == torch.float32 and l.weight.device == c.device and max(l.weight.shape) <= _mlp.LIPSCHITZ_MAX_DIM
+                        and min(l.weight.shape) >= 1 for l in self.layers))
+
+    def _fused_ok(self, x, return_last, input_max_channel):
+        desc = super()._fused_ok(x, return_last, input_max_channel)
+        if desc is not None and not self._needs_grad and torch.is_grad_enabled() and self.lipshitz_bound_per_layer.requires_grad:
+            self._needs_grad = True             # the bounds alone ask for a gradient: the normalised weights do
+            half = self.dtype == torch.float16
+            return desc if (desc.half_backward_fusable if half else desc.backward_fusable) else None
+        return desc
+
+    def forward_columns(self, x: torch.Tensor, n_cols: int):
+        return self(x)[..., :int(n_cols)]
+
+    @profile
+    def forward(self, x: torch.Tensor, return_last: bool = False):
+        if not self._kernel_ok(x):
+            weights = [self.normalization(layer.weight, torch.nn.functional.softplus(self.lipshitz_bound_per_layer[i]))
+                       for i, layer in enumerate(self.layers)]
+        else:
+            weights = self._normalized_weights()
+            desc = self._fused_ok(x, return_last, None)
+            if desc is not None:
+                params = []
+                for w, layer in zip(weights, self.layers):
+                    params += [w, layer.bias]
+                fn = FusedMLPHalfFunction if self.dtype == torch.float16 else FusedMLPFunction
+                return fn.apply(desc, self._needs_grad, x, *params)
+        # layer by layer on the normalised weights (the reference's forward; autocast as DenseLayer's)
+        h, last_h = x, None
+        low_precision = self.dtype in (torch.float16, torch.bfloat16)
+        for i, (weight, layer) in enumerate(zip(weights, self.layers)):
+            with torch.autocast(device_type='cuda', dtype=self.dtype, enabled=low_precision):
+                if i == self.D:
+                    last_h = h
+                h = torch.nn.functional.linear(h, weight, layer.bias)
+                if layer.activation is not None:
+                    h = layer.activation(h)
+        return (h, last_h) if return_last else h
 
 
 class MLPNet(MLP):
