@@ -28,7 +28,7 @@ enum { NR3D_F32 = 0, NR3D_F16 = 1, NR3D_F64 = 2, NR3D_I32 = 3, NR3D_I64 = 4, NR3
  * (generated from this header by tools/gen_abi.py at build time) carries the same number next to every entry point's argument types;
  * the loader also refuses a library whose nr3d_abi_version() differs, so a vendored nr3d_lib_amd/ needs this header neither at import
  * nor at run time. */
-#define NR3D_ABI_VERSION 29
+#define NR3D_ABI_VERSION 30
 
 const char *nr3d_last_error(void);
 int nr3d_abi_version(void);
@@ -363,12 +363,13 @@ int nr3d_lotd_forest_bwd_bwd_dx(const nr3d_lotd_meta_t *meta, const void *meta_d
                                 uint32_t batch_data_size, int32_t max_level, float *dL_dx, void *stream);
 
 /* =================================================================================================
- * occ_grid ray marching -- replaces nr3d_lib.bindings._occ_grid
+ * Occupancy-grid ray marching -- replaces nr3d_lib.bindings._occ_grid
  *   csrc/occ_grid/include/occ_grid/cpp_api.h:14-66, csrc/occ_grid/src/ray_marching.cu:136-244,
  *   csrc/occ_grid/src/batched_marching.cu:153-287
+ * and the ATen chains around it.  Every marcher of this section (static, one call, time-sliced, forest) lives in csrc/occ_grid.hip.
  * Two-phase: *_count writes num_steps[n_rays] AND the exclusive scan packed_info[n_rays,2]
- * (= [cumsum - num, num], int32) plus the grand total into total_steps[0] (device int32/int64);
- * the caller reads total_steps back (the single host sync), allocates outputs, calls *_emit.
+ * (= [cumsum - num, num], int32) plus the grand total into totals[0] (device int32/int64);
+ * the caller reads the totals back (the single host sync), allocates outputs, calls *_emit.
  * total_steps / total / totals of the count entry points may be DEVICE memory (then copy it back) or pinned, device-visible HOST
  * memory (hipHostMalloc): the scan's last store lands there and the readback is a stream synchronisation, no copy launch.
  * Optional sample cache (>= nr3d_ray_marching_cache_bytes(n_rays, max_steps) bytes, or NULL): *_count also stores
@@ -379,17 +380,29 @@ int nr3d_lotd_forest_bwd_bwd_dx(const nr3d_lotd_meta_t *meta, const void *meta_d
  * ============================================================================================== */
 enum { NR3D_CONTRACT_AABB = 0, NR3D_CONTRACT_UN_BOUNDED_TANH = 1, NR3D_CONTRACT_UN_BOUNDED_SPHERE = 2 };
 
+/* ---- static grid(s): count | readback | emit ------------------------------------------------------
+ * with_hit_rays == 0: packed_info and totals[0] = S, the number of samples; totals is ONE word, ridx_hit / pack_infos are ignored.
+ * with_hit_rays != 0: the same AND the per-ray post-processing of occgrid_raymarch.py:87-112 (nonzero on the counts, index, .long())
+ * with ONE scan of the counts: the rays with >= 1 sample, ascending, go to ridx_hit int64 [n_rays] / pack_infos int64 [n_rays, 2]
+ * (their first n_hit rows are written; both required when n_rays > 0) and totals int64 [2] = {S, n_hit} (the caller reads n_hit back).
+ * n_rays == 0 zeroes exactly the words of its mode, one or two.  scan_tmp >= nr3d_scan_tmp_bytes(n_rays).
+ * Range of the compacting entry points (with_hit_rays != 0, the one-call and time-sliced marchers below, nr3d_prune_compact_packs):
+ * one scan carries the running sample count (36 bits) and the rank among the non-empty packs (28 bits) -- fewer than 2^28 packs /
+ * rays per call (checked: nonzero status above that), fewer than 2^36 samples in all (more than a 288 GB device can hold). */
 int nr3d_ray_marching_count(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
                             const float *t_max, const float *roi, const int32_t grid_res[3],
                             const uint8_t *grid_binary, int contraction_type, float step_size,
                             float max_step_size, float dt_gamma, uint32_t max_steps, int batched,
                             const int32_t *batch_inds, uint32_t batch_data_size,
-                            int32_t *packed_info /*[n_rays,2]*/, int64_t *total_steps /*[1]*/,
+                            int32_t *packed_info /*[n_rays,2]*/, int64_t *totals /*[1] or [2]*/,
                             void *scan_tmp /* >= nr3d_scan_tmp_bytes(n_rays) bytes */,
-                            void *sample_cache /*or NULL*/, uint64_t sample_cache_bytes, void *stream);
-
-uint64_t nr3d_ray_marching_cache_bytes(uint32_t n_rays, uint32_t max_steps);
-
+                            void *sample_cache /*or NULL*/, uint64_t sample_cache_bytes, int with_hit_rays,
+                            int64_t *ridx_hit /*[n_rays]*/, int64_t *pack_infos /*[n_rays,2]*/, void *stream);
+/* The samples to their packed rows: t_starts / t_ends f32, ridx int32 (/ bidx / gidx int32).  With the sample cache of the count
+ * entry ONE launch, a per-ray copy; without it the second march.  Per-sample post-processing of the same lines, each output optional
+ * (NULL): ridx64 = (int64) ridx, deltas = t_ends - t_starts, samples [S, 3] = fma(rays_d[ridx], t_starts, rays_o[ridx])
+ * (torch.addcmul).  It rides on the cached copy; behind the second march this entry enqueues it as a launch of its own over n_samples
+ * rows (n_samples = S of the readback; read on that route only).  The same values on both routes. */
 int nr3d_ray_marching_emit(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
                            const float *t_max, const float *roi, const int32_t grid_res[3],
                            const uint8_t *grid_binary, int contraction_type, float step_size,
@@ -397,12 +410,76 @@ int nr3d_ray_marching_emit(uint32_t n_rays, const float *rays_o, const float *ra
                            uint32_t batch_data_size, const int32_t *packed_info, float *t_starts,
                            float *t_ends, int32_t *ridx, int32_t *bidx /*NULL unless batched*/,
                            int32_t *gidx /*or NULL*/, const void *sample_cache /*or NULL*/,
-                           uint32_t cache_max_steps, void *stream);
+                           uint32_t cache_max_steps, int64_t *ridx64, float *deltas, float *samples, uint64_t n_samples,
+                           void *stream);
 
-/* forest_ray_marching (csrc/occ_grid/src/forest_marching.cu:16-303): marching through the occupancy grids of the
+/* ---- static grid, configs[2] in ONE call (round 6) ------------------------------------------------
+ * ray_marching (csrc/occ_grid/src/ray_marching.cu:136-244) + the post-processing of
+ * occgrid_raymarch.py:87-112 + alpha = 1 - exp(-sigma * delta) (nerf_utils.py:23-24) + the renderer's composite chain
+ * (nr3d_lib/models/fields/nerf/renderer_mixin.py:298-311), enqueued back to back with NO device->host wait inside:
+ *   count (+ sample cache) -> scan (+ hit rays, totals) -> cached emit (+ ridx64 / deltas / samples) -> composite over ALL rays.
+ * Every per-sample buffer (t_starts, t_ends, ridx, gidx?, ridx64?, deltas, samples?, alphas, vw) has `rows` >= n_rays * max_steps
+ * rows (the bound; checked) and its first S rows are written -- the same values as nr3d_ray_marching_count (with_hit_rays) +
+ * nr3d_ray_marching_emit + nr3d_tau_to_alpha_fwd + nr3d_pack_composite_fwd, vw / mask / depth / rgb_out bit-identical to
+ * them.  sigma [sigma_rows] / rgb [sigma_rows, 3] (rgb optional): the caller's per-sample density / colour; rows beyond sigma_rows
+ * read as density 0 (the caller compares S with sigma_rows after its readback).  mask / depth [n_rays], rgb_out [n_rays, 3] are
+ * FULLY written (rays without samples: zeros -- no fill).  totals (device-visible, normally pinned host memory) = {S, n_hit}: read it
+ * after a stream synchronisation, AFTER this call returned (and after nr3d_march_composite_bwd was enqueued, if wanted).
+ * Needs the sample cache (nr3d_ray_marching_cache_bytes); single grid only (batched / forest marches keep the two-phase calls). */
+int nr3d_march_composite_fwd(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min, const float *t_max,
+                             const float *roi, const int32_t grid_res[3], const uint8_t *grid_binary, int type, float step_size,
+                             float max_step_size, float dt_gamma, uint32_t max_steps, int32_t *packed_info, int64_t *ridx_hit,
+                             int64_t *pack_infos, int64_t *totals, void *scan_tmp, void *sample_cache, uint64_t sample_cache_bytes,
+                             uint64_t rows, float *t_starts, float *t_ends, int32_t *ridx, int32_t *gidx, int64_t *ridx64,
+                             float *deltas, float *samples, const float *sigma, uint64_t sigma_rows, const float *rgb,
+                             float early_stop_eps, float alpha_thre, int normalize_depth, float *alphas, float *vw, float *mask,
+                             float *depth, float *rgb_out, void *stream);
+/* its backward (= nr3d_pack_composite_bwd over all rays of packed_info, no ray_index, no g_vw; the same values): g_mask / g_depth
+ * [n_rays], g_rgb [n_rays, 3] (each may be NULL = zero) -> grad_alphas [S rows written], grad_t / grad_rgb optional; grad_sigma
+ * (optional, needs sigma and deltas) = grad_alphas * exp(-sigma * delta) * delta as nr3d_tau_to_alpha_bwd. */
+int nr3d_march_composite_bwd(uint32_t n_rays, const int32_t *packed_info, const float *alphas, const float *vw, const float *t,
+                             const float *rgb, float early_stop_eps, float alpha_thre, int normalize_depth, const float *mask,
+                             const float *depth, const float *g_mask, const float *g_depth, const float *g_rgb, float *grad_alphas,
+                             float *grad_t, float *grad_rgb, const float *sigma, const float *deltas, uint64_t sigma_rows,
+                             float *grad_sigma, void *stream);
+
+/* ---- dynamic scenes: the march through TIME-SLICED occupancy, every ray with a timestamp ----------
+ * No single reference kernel: replaces the
+ * chain of models/accelerations/occgrid_accel/dynamic.py:117-151, :328-364 and batched_dynamic.py:69-110
+ * (torch_consecutive_nearest1d -> `occ_dynamic | occ_static.expand_as(...)` -> batched march -> ts_keyframes[bidx] -> div / sub).
+ *   grid_dynamic uint8 [n_slices, Rx, Ry, Rz], n_slices = (batch_inds ? n_batches : 1) * T; grid_static uint8 [Rx, Ry, Rz] or NULL
+ *   (a cell is occupied when either byte is nonzero); roi [6]; AABB grids only.  ts_keyframes [T] ascending, rays_ts [n_rays].
+ *   Frame of a ray = torch_consecutive_nearest1d (nr3d_lib/utils.py:675-699), the same float32 operations: i = first index with
+ *   key[i] >= t (NaN: T), clamped to [1, T-1]; frame i-1 if |key[i-1] - t| < |key[i] - t| else i; T == 1: frame 0.
+ *   slice = (batch_inds ? batch_inds[i] : 0) * T + frame -> rays_slice int32 [n_rays]; a ray whose batch index is negative or
+ *   >= n_batches gets slice -1, count 0 and is never probed.  n_slices * Rx*Ry*Rz >= 2^31 is refused (gidx is int32).
+ * _count: packed_info / ridx_hit / pack_infos / totals = {S, n_hit} / scan_tmp as nr3d_ray_marching_count with with_hit_rays != 0;
+ * the sample cache (nr3d_ray_marching_cache_bytes) is required.  _emit (after the caller read totals = {S, n_hit}): per sample t_starts, t_ends,
+ * ridx int64, bidx int64 (= batch_inds of the ray; NULL without batch_inds), ts = ts_keyframes[frame], gidx int32 (cell + slice *
+ * Rx*Ry*Rz; optional), deltas = t_ends - t_starts, samples [S, 3] = rays_o + (rays_d * t_starts) with the product rounded on its own --
+ * torch.addcmul's float32 result on the chain's route (self + value * (t1 * t2)), so the two routes agree bit for bit. */
+int nr3d_dynamic_ray_marching_count(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
+                                    const float *t_max, const float *roi, const int32_t grid_res[3],
+                                    const uint8_t *grid_dynamic, const uint8_t *grid_static, const float *ts_keyframes,
+                                    uint32_t T, const float *rays_ts, const int32_t *batch_inds, uint32_t n_batches,
+                                    float step_size, float max_step_size, float dt_gamma, uint32_t max_steps,
+                                    int32_t *packed_info, int32_t *rays_slice, int64_t *ridx_hit, int64_t *pack_infos,
+                                    int64_t *totals, void *scan_tmp, void *sample_cache, uint64_t sample_cache_bytes,
+                                    void *stream);
+int nr3d_dynamic_ray_marching_emit(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *ts_keyframes,
+                                   uint32_t T, const int32_t *batch_inds, const int32_t *packed_info,
+                                   const int32_t *rays_slice, const void *sample_cache, uint32_t cache_max_steps,
+                                   float *t_starts, float *t_ends, int64_t *ridx, int64_t *bidx, float *ts, int32_t *gidx,
+                                   float *deltas, float *samples, void *stream);
+/* the frame lookup alone: fidx int64 [n] = nearest keyframe of ts [n] (as above) */
+int nr3d_nearest_keyframe(uint64_t n, const float *ts_keyframes, uint32_t T, const float *ts, int64_t *fidx, void *stream);
+
+/* ---- forest of block grids ------------------------------------------------------------------------
+ * forest_ray_marching (csrc/occ_grid/src/forest_marching.cu:16-303): marching through the occupancy grids of the
  * blocks a ray crosses.  The block segments of every ray (seg_block_inds int32 [S], seg_entries / seg_exits f32 [S],
  * packed per ray by seg_pack_infos int32 [n_rays,2]) come from the caller's octree ray trace.
- * grid_binary uint8/bool [n_trees, Rx, Ry, Rz].  Same two-phase contract as nr3d_ray_marching_count/_emit. */
+ * grid_binary uint8/bool [n_trees, Rx, Ry, Rz].  Same two-phase contract as nr3d_ray_marching_count (with_hit_rays == 0) / _emit
+ * (no sample cache: always the second march). */
 int nr3d_forest_ray_marching_count(const nr3d_forest_meta_t *forest, uint32_t n_rays, const float *rays_o,
                                    const float *rays_d, const float *t_min, const float *t_max,
                                    const int32_t *seg_block_inds, const float *seg_entries, const float *seg_exits,
@@ -418,8 +495,18 @@ int nr3d_forest_ray_marching_emit(const nr3d_forest_meta_t *forest, uint32_t n_r
                                   float *t_starts, float *t_ends, int32_t *ridx, int32_t *blidx, int32_t *gidx /*or NULL*/,
                                   void *stream);
 
+/* ---- sizes and the readback ------------------------------------------------------------------------
+ * Bytes of the marchers' sample cache ([n_rays][max_steps] x {t_start, t_end, cell}). */
+uint64_t nr3d_ray_marching_cache_bytes(uint32_t n_rays, uint32_t max_steps);
 /* Scratch bytes needed by the device-wide scans used in two-phase ops (any n). */
 uint64_t nr3d_scan_tmp_bytes(uint64_t n);
+/* Host-side wait for words a kernel writes into device-visible HOST memory (pinned; the `totals` of the two-phase and one-call ops):
+ * spins until none of words[0..n) equals `sentinel` (the caller stores the sentinel before the launch; the kernels store the totals
+ * with system scope) or `timeout_us` passed.  Returns 0 when the words arrived, 1 on timeout (NOT an error: the caller falls back to a
+ * stream synchronisation).  Why: a stream synchronisation returns when EVERYTHING enqueued has drained and costs ~20 us of wake-up
+ * latency; the totals are written by the SECOND of the one-call path's launches, and reading them early lets the host build its views
+ * while the composite kernels still run.  Holds no lock, touches no HIP API. */
+int nr3d_wait_host_words(const int64_t *words, int n, int64_t sentinel, uint32_t timeout_us);
 
 /* Occupancy-value grid maintenance -- replaces torch_scatter.scatter_max in update_occ_val_grid[_idx]_ /
  * update_batched_occ_val_grid[_idx]_ (nr3d_lib/models/accelerations/occgrid/utils.py:80-125):
@@ -692,100 +779,6 @@ int nr3d_pack_composite_bwd(uint32_t P, const float *alphas, const float *vw, co
 int nr3d_tau_to_alpha_fwd(uint64_t S, const float *sigma, const float *delta, float *alpha, void *stream);
 int nr3d_tau_to_alpha_bwd(uint64_t S, const float *sigma, const float *delta, const float *grad_alpha, float *grad_sigma,
                           void *stream);
-/* Post-processing of the marcher's outputs per sample (nr3d_lib/graphics/raymarch/occgrid_raymarch.py:87-112): ridx64 =
- * (int64) ridx, deltas = t_ends - t_starts, samples [S, 3] = fma(rays_d[ridx], t_starts, rays_o[ridx]) (torch.addcmul).  Any
- * output may be NULL. */
-int nr3d_march_finish_samples(uint64_t S, const float *rays_o, const float *rays_d, const int32_t *ridx,
-                              const float *t_starts, const float *t_ends, int64_t *ridx64, float *deltas, float *samples,
-                              void *stream);
-/* nr3d_ray_marching_count AND the per-ray post-processing of the same lines (nonzero on the counts, index, .long()) with ONE
- * scan of the counts: packed_info int32 [n_rays, 2] as nr3d_ray_marching_count -> the rays with >= 1 sample, ascending:
- * ridx_hit int64 [n_rays] / pack_infos int64 [n_rays, 2] (their first n_hit rows are written); totals int64 [2] = {number of
- * samples, n_hit} (the caller reads n_hit back).  scan_tmp >= nr3d_scan_tmp_bytes(n_rays).
- * Range of the compacting entry points (this one, nr3d_prune_compact_packs): one scan carries the running sample count (36
- * bits) and the rank among the non-empty packs (28 bits) -- fewer than 2^28 packs / rays per call (checked: nonzero status
- * above that), fewer than 2^36 samples in all (more than a 288 GB device can hold). */
-int nr3d_ray_marching_count_finished(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
-                                     const float *t_max, const float *roi, const int32_t grid_res[3],
-                                     const uint8_t *grid_binary, int type, float step_size, float max_step_size,
-                                     float dt_gamma, uint32_t max_steps, int batched, const int32_t *batch_inds,
-                                     uint32_t batch_data_size, int32_t *packed_info, int64_t *ridx_hit, int64_t *pack_infos,
-                                     int64_t *totals, void *scan_tmp, void *sample_cache, uint64_t sample_cache_bytes,
-                                     void *stream);
-
-/* configs[2] in ONE call (round 6): ray_marching (csrc/occ_grid/src/ray_marching.cu:136-244) + the post-processing of
- * occgrid_raymarch.py:87-112 + alpha = 1 - exp(-sigma * delta) (nerf_utils.py:23-24) + the renderer's composite chain
- * (nr3d_lib/models/fields/nerf/renderer_mixin.py:298-311), enqueued back to back with NO device->host wait inside:
- *   count (+ sample cache) -> scan (+ hit rays, totals) -> cached emit (+ ridx64 / deltas / samples) -> composite over ALL rays.
- * Every per-sample buffer (t_starts, t_ends, ridx, gidx?, ridx64?, deltas, samples?, alphas, vw) has `rows` >= n_rays * max_steps
- * rows (the bound; checked) and its first S rows are written -- the same values as nr3d_ray_marching_count_finished +
- * nr3d_ray_marching_emit_finished + nr3d_tau_to_alpha_fwd + nr3d_pack_composite_fwd, vw / mask / depth / rgb_out bit-identical to
- * them.  sigma [sigma_rows] / rgb [sigma_rows, 3] (rgb optional): the caller's per-sample density / colour; rows beyond sigma_rows
- * read as density 0 (the caller compares S with sigma_rows after its readback).  mask / depth [n_rays], rgb_out [n_rays, 3] are
- * FULLY written (rays without samples: zeros -- no fill).  totals (device-visible, normally pinned host memory) = {S, n_hit}: read it
- * after a stream synchronisation, AFTER this call returned (and after nr3d_march_composite_bwd was enqueued, if wanted).
- * Needs the sample cache (nr3d_ray_marching_cache_bytes); single grid only (batched / forest marches keep the two-phase calls). */
-int nr3d_march_composite_fwd(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min, const float *t_max,
-                             const float *roi, const int32_t grid_res[3], const uint8_t *grid_binary, int type, float step_size,
-                             float max_step_size, float dt_gamma, uint32_t max_steps, int32_t *packed_info, int64_t *ridx_hit,
-                             int64_t *pack_infos, int64_t *totals, void *scan_tmp, void *sample_cache, uint64_t sample_cache_bytes,
-                             uint64_t rows, float *t_starts, float *t_ends, int32_t *ridx, int32_t *gidx, int64_t *ridx64,
-                             float *deltas, float *samples, const float *sigma, uint64_t sigma_rows, const float *rgb,
-                             float early_stop_eps, float alpha_thre, int normalize_depth, float *alphas, float *vw, float *mask,
-                             float *depth, float *rgb_out, void *stream);
-/* Host-side wait for words a kernel writes into device-visible HOST memory (pinned; the `totals` of the two-phase and one-call ops):
- * spins until none of words[0..n) equals `sentinel` (the caller stores the sentinel before the launch; the kernels store the totals
- * with system scope) or `timeout_us` passed.  Returns 0 when the words arrived, 1 on timeout (NOT an error: the caller falls back to a
- * stream synchronisation).  Why: a stream synchronisation returns when EVERYTHING enqueued has drained and costs ~20 us of wake-up
- * latency; the totals are written by the SECOND of the one-call path's launches, and reading them early lets the host build its views
- * while the composite kernels still run.  Holds no lock, touches no HIP API. */
-int nr3d_wait_host_words(const int64_t *words, int n, int64_t sentinel, uint32_t timeout_us);
-/* its backward (= nr3d_pack_composite_bwd over all rays of packed_info, no ray_index, no g_vw; the same values): g_mask / g_depth
- * [n_rays], g_rgb [n_rays, 3] (each may be NULL = zero) -> grad_alphas [S rows written], grad_t / grad_rgb optional; grad_sigma
- * (optional, needs sigma and deltas) = grad_alphas * exp(-sigma * delta) * delta as nr3d_tau_to_alpha_bwd. */
-int nr3d_march_composite_bwd(uint32_t n_rays, const int32_t *packed_info, const float *alphas, const float *vw, const float *t,
-                             const float *rgb, float early_stop_eps, float alpha_thre, int normalize_depth, const float *mask,
-                             const float *depth, const float *g_mask, const float *g_depth, const float *g_rgb, float *grad_alphas,
-                             float *grad_t, float *grad_rgb, const float *sigma, const float *deltas, uint64_t sigma_rows,
-                             float *grad_sigma, void *stream);
-
-/* nr3d_ray_marching_emit from the sample cache of nr3d_ray_marching_count AND nr3d_march_finish_samples in one launch
- * (the cached emit is a per-ray copy: the epilogue rides on it): t_starts / t_ends / ridx (/ bidx / gidx) as
- * nr3d_ray_marching_emit, ridx64 / deltas / samples (each optional) as nr3d_march_finish_samples -- the same values. */
-int nr3d_ray_marching_emit_finished(uint32_t n_rays, const float *rays_o, const float *rays_d, int batched,
-                                    const int32_t *batch_inds, uint32_t batch_data_size, const int32_t *packed_info,
-                                    const void *sample_cache, uint32_t cache_max_steps, float *t_starts, float *t_ends,
-                                    int32_t *ridx, int32_t *bidx, int32_t *gidx, int64_t *ridx64, float *deltas,
-                                    float *samples, void *stream);
-/* Dynamic scenes: the march through TIME-SLICED occupancy, every ray with a timestamp.  No single reference kernel: replaces the
- * chain of models/accelerations/occgrid_accel/dynamic.py:117-151, :328-364 and batched_dynamic.py:69-110
- * (torch_consecutive_nearest1d -> `occ_dynamic | occ_static.expand_as(...)` -> batched march -> ts_keyframes[bidx] -> div / sub).
- *   grid_dynamic uint8 [n_slices, Rx, Ry, Rz], n_slices = (batch_inds ? n_batches : 1) * T; grid_static uint8 [Rx, Ry, Rz] or NULL
- *   (a cell is occupied when either byte is nonzero); roi [6]; AABB grids only.  ts_keyframes [T] ascending, rays_ts [n_rays].
- *   Frame of a ray = torch_consecutive_nearest1d (nr3d_lib/utils.py:675-699), the same float32 operations: i = first index with
- *   key[i] >= t (NaN: T), clamped to [1, T-1]; frame i-1 if |key[i-1] - t| < |key[i] - t| else i; T == 1: frame 0.
- *   slice = (batch_inds ? batch_inds[i] : 0) * T + frame -> rays_slice int32 [n_rays]; a ray whose batch index is negative or
- *   >= n_batches gets slice -1, count 0 and is never probed.  n_slices * Rx*Ry*Rz >= 2^31 is refused (gidx is int32).
- * _count: packed_info / ridx_hit / pack_infos / totals / scan_tmp as nr3d_ray_marching_count_finished; the sample cache
- * (nr3d_ray_marching_cache_bytes) is required.  _emit (after the caller read totals = {S, n_hit}): per sample t_starts, t_ends,
- * ridx int64, bidx int64 (= batch_inds of the ray; NULL without batch_inds), ts = ts_keyframes[frame], gidx int32 (cell + slice *
- * Rx*Ry*Rz; optional), deltas = t_ends - t_starts, samples [S, 3] = rays_o + (rays_d * t_starts) with the product rounded on its own --
- * torch.addcmul's float32 result on the chain's route (self + value * (t1 * t2)), so the two routes agree bit for bit. */
-int nr3d_dynamic_ray_marching_count(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
-                                    const float *t_max, const float *roi, const int32_t grid_res[3],
-                                    const uint8_t *grid_dynamic, const uint8_t *grid_static, const float *ts_keyframes,
-                                    uint32_t T, const float *rays_ts, const int32_t *batch_inds, uint32_t n_batches,
-                                    float step_size, float max_step_size, float dt_gamma, uint32_t max_steps,
-                                    int32_t *packed_info, int32_t *rays_slice, int64_t *ridx_hit, int64_t *pack_infos,
-                                    int64_t *totals, void *scan_tmp, void *sample_cache, uint64_t sample_cache_bytes,
-                                    void *stream);
-int nr3d_dynamic_ray_marching_emit(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *ts_keyframes,
-                                   uint32_t T, const int32_t *batch_inds, const int32_t *packed_info,
-                                   const int32_t *rays_slice, const void *sample_cache, uint32_t cache_max_steps,
-                                   float *t_starts, float *t_ends, int64_t *ridx, int64_t *bidx, float *ts, int32_t *gidx,
-                                   float *deltas, float *samples, void *stream);
-/* the frame lookup alone: fidx int64 [n] = nearest keyframe of ts [n] (as above) */
-int nr3d_nearest_keyframe(uint64_t n, const float *ts_keyframes, uint32_t T, const float *ts, int64_t *fidx, void *stream);
 /* Visibility pruning (nr3d_lib/graphics/nerf/nerf_utils.py:64-98 packed_volume_render_compression + the index gathers
  * of nerf_ray_query.py:128-137).  counts int64 [P] = kept samples per pack (nr3d_alpha_to_vw_forward's num_steps):
  * begin_all [P] = new begin of EVERY pack; the packs that keep >= 1 sample, ascending: idx_out [P'] (tag[i] if tag is

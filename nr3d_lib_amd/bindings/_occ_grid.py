@@ -93,60 +93,42 @@ def _march(rays_o, rays_d, t_min, t_max, batch_inds, batch_data_size, roi, grid_
     with H.on_device(dev):
         st = H.stream_of(rays_o)
         packed_info = H.empty((n, 2), dtype=torch.int32, device=dev)
-        total = None if finish else H.host_i64(1, dev)      # pinned host word the scan writes into
         tmp = H.empty((_scan_tmp_bytes(n) + 7) // 8, dtype=torch.int64, device=dev)
         # sample cache: the count pass keeps every sample, the emit pass only compacts (no second march)
         cache_bytes = _cache_bytes(n, int(max_steps))
         cache = (H.empty((cache_bytes + 3) // 4, dtype=torch.int32, device=dev)
                  if 0 < cache_bytes <= SAMPLE_CACHE_MAX_BYTES else None)
-        if finish:
-            # the hit rays' compaction only needs the counts: the scan that turns them into packed_info compacts the hit rays
-            # as well, and the readback fetches the number of samples and of hit rays together -- ONE device->host sync
-            ridx_hit = H.empty(n, dtype=torch.int64, device=dev)
-            pack_infos = H.empty((n, 2), dtype=torch.int64, device=dev)
-            totals = H.host_i64(2, dev)
-            H.check(H.lib().nr3d_ray_marching_count_finished(
-                n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_binary), ctype,
-                float(step_size), float(max_step_size), float(dt_gamma), int(max_steps), batched, H.ptr(batch_inds), bds,
-                H.ptr(packed_info), H.ptr(ridx_hit), H.ptr(pack_infos), H.ptr(totals), H.ptr(tmp), H.ptr(cache),
-                cache_bytes if cache is not None else 0, st))
-            S, n_hit = H.wait_i64(totals, dev)
-        else:
-            H.check(H.lib().nr3d_ray_marching_count(
-                n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_binary), ctype,
-                float(step_size), float(max_step_size), float(dt_gamma), int(max_steps), batched, H.ptr(batch_inds), bds,
-                H.ptr(packed_info), H.ptr(total), H.ptr(tmp), H.ptr(cache), cache_bytes if cache is not None else 0, st))
-            S = H.wait_i64(total, dev)[0]  # the single device->host sync of this op
+        # finish: the hit rays' compaction only needs the counts, so the scan that turns them into packed_info compacts the hit rays
+        # as well, and the readback fetches the number of samples and of hit rays together -- ONE device->host sync either way
+        ridx_hit = H.empty(n, dtype=torch.int64, device=dev) if finish else None
+        pack_infos = H.empty((n, 2), dtype=torch.int64, device=dev) if finish else None
+        totals = H.host_i64(2 if finish else 1, dev)        # pinned host words the scan writes into: {S} or {S, n_hit}
+        H.check(H.lib().nr3d_ray_marching_count(
+            n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_binary), ctype,
+            float(step_size), float(max_step_size), float(dt_gamma), int(max_steps), batched, H.ptr(batch_inds), bds,
+            H.ptr(packed_info), H.ptr(totals), H.ptr(tmp), H.ptr(cache), cache_bytes if cache is not None else 0,
+            1 if finish else 0, H.ptr(ridx_hit), H.ptr(pack_infos), st))
+        words = H.wait_i64(totals, dev)    # the single device->host sync of this op
+        S = words[0]
         t_starts = H.empty((S, 1), dtype=torch.float32, device=dev)
         t_ends = H.empty((S, 1), dtype=torch.float32, device=dev)
         ridx = H.empty(S, dtype=torch.int32, device=dev)
         bidx = H.empty(S, dtype=torch.int32, device=dev) if batched else None
         gidx = H.empty(S, dtype=torch.int32, device=dev) if return_gidx else None
-        if finish and cache is not None:
-            # the cached emit is a per-ray copy; the per-sample epilogue rides on it (one launch, one op)
-            ridx64 = H.empty(S, dtype=torch.int64, device=dev)
-            deltas = H.empty(S, dtype=torch.float32, device=dev)
-            samples = H.empty((S, 3), dtype=torch.float32, device=dev)
-            if S > 0:
-                H.check(H.lib().nr3d_ray_marching_emit_finished(
-                    n, H.ptr(rays_o), H.ptr(rays_d), batched, H.ptr(batch_inds), bds, H.ptr(packed_info), H.ptr(cache),
-                    int(max_steps), H.ptr(t_starts), H.ptr(t_ends), H.ptr(ridx), H.ptr(bidx), H.ptr(gidx), H.ptr(ridx64),
-                    H.ptr(deltas), H.ptr(samples), st))
-            return dict(n_hit=n_hit, ridx_hit=ridx_hit[:n_hit], pack_infos=H.mark_ordered(pack_infos[:n_hit], total=S), t_starts=t_starts.view(-1),
-                        t_ends=t_ends.view(-1), ridx=ridx64, deltas=deltas, samples=samples, bidx=bidx, gidx=gidx)
+        # finish: the per-sample epilogue rides on the cached emit (a per-ray copy), or follows the second march in the same call
+        ridx64 = H.empty(S, dtype=torch.int64, device=dev) if finish else None
+        deltas = H.empty(S, dtype=torch.float32, device=dev) if finish else None
+        samples = H.empty((S, 3), dtype=torch.float32, device=dev) if finish else None
         if S > 0:
             H.check(H.lib().nr3d_ray_marching_emit(
                 n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid_binary), ctype,
                 float(step_size), float(max_step_size), float(dt_gamma), batched, H.ptr(batch_inds), bds, H.ptr(packed_info),
-                H.ptr(t_starts), H.ptr(t_ends), H.ptr(ridx), H.ptr(bidx), H.ptr(gidx), H.ptr(cache), int(max_steps), st))
-        if finish:
-            ridx64 = H.empty(S, dtype=torch.int64, device=dev)
-            deltas = H.empty(S, dtype=torch.float32, device=dev)
-            samples = H.empty((S, 3), dtype=torch.float32, device=dev)
-            H.check(H.lib().nr3d_march_finish_samples(S, H.ptr(rays_o), H.ptr(rays_d), H.ptr(ridx), H.ptr(t_starts), H.ptr(t_ends),
-                                                      H.ptr(ridx64), H.ptr(deltas), H.ptr(samples), st))
-            return dict(n_hit=n_hit, ridx_hit=ridx_hit[:n_hit], pack_infos=H.mark_ordered(pack_infos[:n_hit], total=S), t_starts=t_starts.view(-1),
-                        t_ends=t_ends.view(-1), ridx=ridx64, deltas=deltas, samples=samples, bidx=bidx, gidx=gidx)
+                H.ptr(t_starts), H.ptr(t_ends), H.ptr(ridx), H.ptr(bidx), H.ptr(gidx), H.ptr(cache), int(max_steps),
+                H.ptr(ridx64), H.ptr(deltas), H.ptr(samples), S, st))
+    if finish:
+        n_hit = words[1]
+        return dict(n_hit=n_hit, ridx_hit=ridx_hit[:n_hit], pack_infos=H.mark_ordered(pack_infos[:n_hit], total=S), t_starts=t_starts.view(-1),
+                    t_ends=t_ends.view(-1), ridx=ridx64, deltas=deltas, samples=samples, bidx=bidx, gidx=gidx)
     if batched:
         return [packed_info, t_starts, t_ends, ridx, bidx, gidx]
     return [packed_info, t_starts, t_ends, ridx, gidx]
@@ -311,8 +293,7 @@ def forest_ray_marching(forest, rays_o, rays_d, t_min, t_max, seg_block_inds, se
         fc = forest._c()
         packed_info = H.empty((n, 2), dtype=torch.int32, device=dev)
         total = H.host_i64(1, dev)
-        nbytes = int(H.lib().nr3d_scan_tmp_bytes(max(n, 1)))
-        tmp = H.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        tmp = H.empty((_scan_tmp_bytes(n) + 7) // 8, dtype=torch.int64, device=dev)
         common = (H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(seg_block_inds), H.ptr(seg_entries),
                   H.ptr(seg_exits), H.ptr(seg_pack_infos), res, H.ptr(grid_binary), float(step_size),
                   float(max_step_size), float(dt_gamma))

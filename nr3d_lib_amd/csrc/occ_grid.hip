@@ -428,7 +428,7 @@ __global__ __launch_bounds__(256) void k_emit_cached(uint32_t n_rays, uint32_t s
 		ridx[base + j] = (int32_t)i;
 		if (bidx) bidx[base + j] = b;
 		if (gidx) gidx[base + j] = (int32_t)c[3 * j + 2];
-		// the per-sample epilogue of nr3d_march_finish_samples (ray_glue.hip: the same expressions), when asked for
+		// the per-sample epilogue of k_finish_samples (ray_glue.hip: the same expressions), when asked for
 		if (ridx64) ridx64[base + j] = (int64_t)i;
 		if (deltas) deltas[base + j] = e - a;
 		if (samples) {
@@ -590,7 +590,7 @@ __global__ __launch_bounds__(256) void k_emit_dyn(uint32_t n_rays, uint32_t stri
 		deltas[base + j] = e - a;
 		// o + (d * t), the product rounded on its own: ATen's addcmul evaluates self + value * (t1 * t2), so the chain's positions are
 		// rounded twice whatever the compiler contracts; both routes of occgrid_raymarch_dynamic return the same bits.  (k_emit_cached
-		// rounds once: there the fused finish follows the reference's CUDA build instead, see nr3d_march_finish_samples.)
+		// rounds once: there the fused finish follows the reference's CUDA build instead, see k_finish_samples.)
 #pragma unroll
 		for (int k = 0; k < 3; ++k) samples[(size_t)(base + j) * 3 + k] = __fadd_rn(o[k], __fmul_rn(d[k], a));
 	}
@@ -765,87 +765,88 @@ extern "C" int nr3d_occ_apply_max(uint64_t n_voxels, float ema_decay, const floa
 	return 0;
 }
 
-// scratch layout: [ int32 counts[n] (padded to 8 B) | tile sums ]
-extern "C" uint64_t nr3d_scan_tmp_bytes(uint64_t n) { return ((n * sizeof(int64_t) + 7) / 8) * 8 + scan::tmp_bytes(n); }
+// ---------------------------------------------------------------------------------------------------
+// The host plan of every occupancy marcher (static, one call, time-sliced, forest): each rule is stated once, here.
+// ---------------------------------------------------------------------------------------------------
+// scan_tmp = [ per-ray counts: 8 B a ray (the marchers keep int32 there) | tile sums of the scan ]
+struct ScanTmp { int32_t *counts; void *tiles; };
+static inline uint64_t scan_counts_bytes(uint64_t n) { return ((n * sizeof(int64_t) + 7) / 8) * 8; }
+static inline ScanTmp split_scan_tmp(void *scan_tmp, uint64_t n) { return {(int32_t *)scan_tmp, (char *)scan_tmp + scan_counts_bytes(n)}; }
+
+extern "C" uint64_t nr3d_scan_tmp_bytes(uint64_t n) { return scan_counts_bytes(n) + scan::tmp_bytes(n); }
 
 extern "C" uint64_t nr3d_ray_marching_cache_bytes(uint32_t n_rays, uint32_t max_steps) {
 	return (uint64_t)n_rays * max_steps * 12u;
 }
 
-// count pass + the scan of the counts.  ridx_hit == NULL: packed_info and total_steps[0] (nr3d_ray_marching_count); else the
-// same scan also compacts the rays that got samples (ridx_hit and pack_infos of nr3d_ray_marching_count_finished; total_steps is then {S, n_hit})
-static int march_count(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
-                       const float *t_max, const float *roi, const int32_t grid_res[3],
-                       const uint8_t *grid_binary, int type, float step_size, float max_step_size,
-                       float dt_gamma, uint32_t max_steps, int batched, const int32_t *batch_inds,
-                       uint32_t batch_data_size, int32_t *packed_info, int64_t *total_steps,
-                       void *scan_tmp, void *sample_cache, uint64_t sample_cache_bytes, int64_t *ridx_hit,
-                       int64_t *pack_infos64, void *stream) {
-	NR3D_CHECK(total_steps && scan_tmp, "ray_marching: NULL scratch pointer");
-	hipStream_t st = (hipStream_t)stream;
-	if (n_rays == 0) { NR3D_HIP_CHECK(hipMemsetAsync(total_steps, 0, (ridx_hit ? 2 : 1) * sizeof(int64_t), st)); return 0; }
-	NR3D_CHECK(rays_o && rays_d && t_min && t_max && roi && grid_binary && packed_info, "ray_marching: NULL tensor pointer");
-	NR3D_CHECK(type >= 0 && type <= 2, "ray_marching: invalid contraction type %d", type);
-	int32_t *counts = (int32_t *)scan_tmp;
-	void *tiles = (char *)scan_tmp + (((uint64_t)n_rays * sizeof(int64_t) + 7) / 8) * 8;
-	const bool cached = sample_cache && sample_cache_bytes >= nr3d_ray_marching_cache_bytes(n_rays, max_steps);
+// lanes per ray of a count pass: 32 / 16 while that still leaves the chip short of work, else one (NR3D_OPT_MARCH_GROUP = 1 | 16 |
+// 32 | 64 forces).  The lanes of a group share the ray through its sample cache: no cache, one lane.
+static int march_lanes(uint32_t n_rays, bool cached) {
+	if (!cached) return 1;
+	const int64_t v = opt::get(NR3D_OPT_MARCH_GROUP);
+	if (v == 1 || v == 16 || v == 32 || v == 64) return (int)v;
+	return n_rays <= 8192u ? 32 : (n_rays <= 32768u ? 16 : 1);
+}
+
+// the tail of every count entry: counts -> packed_info and totals[0] = S; with ridx_hit the same scan also compacts the rays that
+// got samples (ridx_hit, pack_infos) and totals is {S, n_hit}
+static int packs_from_counts(uint32_t n_rays, const ScanTmp &tmp, int32_t *packed_info, int64_t *ridx_hit, int64_t *pack_infos,
+                             int64_t *totals, hipStream_t st) {
+	if (!ridx_hit) return scan::pack_infos_from_counts<int32_t, int32_t>(n_rays, tmp.counts, packed_info, totals, tmp.tiles, st);
+	glue::PackWriter<int32_t, 1> w{tmp.counts, nullptr, nullptr, ridx_hit, pack_infos, packed_info};
+	return glue::compact_packs<int32_t, 1>(n_rays, w, totals, tmp.tiles, st);
+}
+
+// one launch of k_march, one lane per ray.  Count pass (packed_info NULL): counts, and every sample into `cache` when given.  Emit pass
+// (packed_info given; max_steps unused): the second march, samples to their packed rows.  Outputs a pass does not write are NULL.
+static void launch_march(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min, const float *t_max,
+                         const float *roi, const int32_t grid_res[3], const uint8_t *grid_binary, int type, float step_size,
+                         float max_step_size, float dt_gamma, uint32_t max_steps, int batched, const int32_t *batch_inds,
+                         uint32_t batch_data_size, const int32_t *packed_info, int32_t *counts, float *t_starts, float *t_ends,
+                         int32_t *ridx, int32_t *bidx, int32_t *gidx, uint32_t *cache, hipStream_t st) {
 	auto launch = [&](auto kern) {
-		hipLaunchKernelGGL(kern, dim3(div_up(n_rays, occ::kBlock)), dim3(occ::kBlock), 0, st, n_rays, rays_o, rays_d, t_min,
-		                   t_max, roi, grid_res[0], grid_res[1], grid_res[2], grid_binary, type, step_size, max_step_size,
-		                   dt_gamma, max_steps, batched, batch_inds, batch_data_size, (const int32_t *)nullptr, counts,
-		                   (float *)nullptr, (float *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr,
-		                   (uint32_t *)sample_cache);
+		hipLaunchKernelGGL(kern, dim3(div_up(n_rays, occ::kBlock)), dim3(occ::kBlock), 0, st, n_rays, rays_o, rays_d, t_min, t_max, roi,
+		                   grid_res[0], grid_res[1], grid_res[2], grid_binary, type, step_size, max_step_size, dt_gamma, max_steps, batched,
+		                   batch_inds, batch_data_size, packed_info, counts, t_starts, t_ends, ridx, bidx, gidx, cache);
 	};
-	// lanes per ray: 32 / 16 while that still leaves the chip short of work, else one (NR3D_OPT_MARCH_GROUP = 1 | 16 | 32 | 64 forces)
-	int group = n_rays <= 8192u ? 32 : (n_rays <= 32768u ? 16 : 1);
-	{ const int64_t v = opt::get(NR3D_OPT_MARCH_GROUP); if (v == 1 || v == 16 || v == 32 || v == 64) group = (int)v; }
-	if (!cached) group = 1;
-	auto launch_group = [&](auto kern, int G) {
-		hipLaunchKernelGGL(kern, dim3(div_up((uint64_t)n_rays * G, 256)), dim3(256), 0, st, n_rays, rays_o, rays_d, t_min, t_max, roi,
-		                   grid_res[0], grid_res[1], grid_res[2], grid_binary, type, step_size, max_step_size, dt_gamma, max_steps,
-		                   batched, batch_inds, batch_data_size, counts, (uint32_t *)sample_cache);
-	};
-	{
-		prof::Scope ps(NR3D_PROF_MARCH, st);
-		if (group == 64) launch_group(occ::k_march_group<64>, 64);
-		else if (group == 32) launch_group(occ::k_march_group<32>, 32);
-		else if (group == 16) launch_group(occ::k_march_group<16>, 16);
-		else if (cached) launch(occ::k_march<false, true>);
-		else launch(occ::k_march<false, false>);
-	}
-	NR3D_LAUNCH_CHECK();
-	if (ridx_hit) {
-		NR3D_CHECK(pack_infos64 != nullptr, "ray_marching_count_finished: NULL output pointer");
-		glue::PackWriter<int32_t, 1> w{counts, nullptr, nullptr, ridx_hit, pack_infos64, packed_info};
-		return glue::compact_packs<int32_t, 1>(n_rays, w, total_steps, tiles, st);
-	}
-	return scan::pack_infos_from_counts<int32_t, int32_t>(n_rays, counts, packed_info, total_steps, tiles, st);
+	if (packed_info) launch(occ::k_march<true, false>);
+	else if (cache) launch(occ::k_march<false, true>);
+	else launch(occ::k_march<false, false>);
 }
 
 extern "C" int nr3d_ray_marching_count(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
                                        const float *t_max, const float *roi, const int32_t grid_res[3],
                                        const uint8_t *grid_binary, int type, float step_size, float max_step_size,
                                        float dt_gamma, uint32_t max_steps, int batched, const int32_t *batch_inds,
-                                       uint32_t batch_data_size, int32_t *packed_info, int64_t *total_steps,
-                                       void *scan_tmp, void *sample_cache, uint64_t sample_cache_bytes,
-                                       void *stream) {
-	return march_count(n_rays, rays_o, rays_d, t_min, t_max, roi, grid_res, grid_binary, type, step_size, max_step_size, dt_gamma,
-	                   max_steps, batched, batch_inds, batch_data_size, packed_info, total_steps, scan_tmp, sample_cache,
-	                   sample_cache_bytes, nullptr, nullptr, stream);
-}
-
-extern "C" int nr3d_ray_marching_count_finished(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
-                                                const float *t_max, const float *roi, const int32_t grid_res[3],
-                                                const uint8_t *grid_binary, int type, float step_size, float max_step_size,
-                                                float dt_gamma, uint32_t max_steps, int batched, const int32_t *batch_inds,
-                                                uint32_t batch_data_size, int32_t *packed_info, int64_t *ridx_hit,
-                                                int64_t *pack_infos, int64_t *totals, void *scan_tmp, void *sample_cache,
-                                                uint64_t sample_cache_bytes, void *stream) {
-	NR3D_CHECK(n_rays == 0 || (ridx_hit && pack_infos), "ray_marching_count_finished: NULL output pointer");
-	static int64_t dummy;       // n_rays == 0: only the totals are touched
-	return march_count(n_rays, rays_o, rays_d, t_min, t_max, roi, grid_res, grid_binary, type, step_size, max_step_size, dt_gamma,
-	                   max_steps, batched, batch_inds, batch_data_size, packed_info, totals, scan_tmp, sample_cache,
-	                   sample_cache_bytes, ridx_hit ? ridx_hit : &dummy, pack_infos, stream);
+                                       uint32_t batch_data_size, int32_t *packed_info, int64_t *totals, void *scan_tmp,
+                                       void *sample_cache, uint64_t sample_cache_bytes, int with_hit_rays, int64_t *ridx_hit,
+                                       int64_t *pack_infos, void *stream) {
+	NR3D_CHECK(totals && scan_tmp, "ray_marching: NULL scratch pointer");
+	hipStream_t st = (hipStream_t)stream;
+	if (n_rays == 0) { NR3D_HIP_CHECK(hipMemsetAsync(totals, 0, (with_hit_rays ? 2 : 1) * sizeof(int64_t), st)); return 0; }
+	NR3D_CHECK(rays_o && rays_d && t_min && t_max && roi && grid_binary && packed_info, "ray_marching: NULL tensor pointer");
+	NR3D_CHECK(!with_hit_rays || (ridx_hit && pack_infos), "ray_marching_count: with_hit_rays needs ridx_hit and pack_infos");
+	NR3D_CHECK(type >= 0 && type <= 2, "ray_marching: invalid contraction type %d", type);
+	const ScanTmp tmp = split_scan_tmp(scan_tmp, n_rays);
+	const bool cached = sample_cache && sample_cache_bytes >= nr3d_ray_marching_cache_bytes(n_rays, max_steps);
+	uint32_t *cache = cached ? (uint32_t *)sample_cache : nullptr;
+	auto launch_group = [&](auto kern, int G) {
+		hipLaunchKernelGGL(kern, dim3(div_up((uint64_t)n_rays * G, 256)), dim3(256), 0, st, n_rays, rays_o, rays_d, t_min, t_max, roi,
+		                   grid_res[0], grid_res[1], grid_res[2], grid_binary, type, step_size, max_step_size, dt_gamma, max_steps,
+		                   batched, batch_inds, batch_data_size, tmp.counts, cache);
+	};
+	{
+		prof::Scope ps(NR3D_PROF_MARCH, st);
+		const int group = march_lanes(n_rays, cached);
+		if (group == 64) launch_group(occ::k_march_group<64>, 64);
+		else if (group == 32) launch_group(occ::k_march_group<32>, 32);
+		else if (group == 16) launch_group(occ::k_march_group<16>, 16);
+		else launch_march(n_rays, rays_o, rays_d, t_min, t_max, roi, grid_res, grid_binary, type, step_size, max_step_size, dt_gamma,
+		                  max_steps, batched, batch_inds, batch_data_size, nullptr, tmp.counts, nullptr, nullptr, nullptr, nullptr, nullptr,
+		                  cache, st);
+	}
+	NR3D_LAUNCH_CHECK();
+	return packs_from_counts(n_rays, tmp, packed_info, with_hit_rays ? ridx_hit : nullptr, pack_infos, totals, st);
 }
 
 extern "C" int nr3d_ray_marching_emit(uint32_t n_rays, const float *rays_o, const float *rays_d, const float *t_min,
@@ -853,41 +854,27 @@ extern "C" int nr3d_ray_marching_emit(uint32_t n_rays, const float *rays_o, cons
                                       const uint8_t *grid_binary, int type, float step_size, float max_step_size,
                                       float dt_gamma, int batched, const int32_t *batch_inds, uint32_t batch_data_size,
                                       const int32_t *packed_info, float *t_starts, float *t_ends, int32_t *ridx,
-                                      int32_t *bidx, int32_t *gidx, const void *sample_cache,
-                                      uint32_t cache_max_steps, void *stream) {
+                                      int32_t *bidx, int32_t *gidx, const void *sample_cache, uint32_t cache_max_steps,
+                                      int64_t *ridx64, float *deltas, float *samples, uint64_t n_samples, void *stream) {
 	if (n_rays == 0) return 0;
-	NR3D_CHECK(rays_o && rays_d && t_min && t_max && roi && grid_binary && packed_info, "ray_marching: NULL tensor pointer");
+	NR3D_CHECK(packed_info && (sample_cache || (rays_o && rays_d && t_min && t_max && roi && grid_binary)),
+	           "ray_marching: NULL tensor pointer");
 	NR3D_CHECK(t_starts && t_ends && ridx, "ray_marching: NULL output pointer");
-	prof::Scope ps(NR3D_PROF_MARCH, (hipStream_t)stream);
-	if (sample_cache) {   // filled by nr3d_ray_marching_count with the same rays and max_steps == cache_max_steps
-		hipLaunchKernelGGL(occ::k_emit_cached, dim3(div_up(n_rays, 4)), dim3(256), 0, (hipStream_t)stream, n_rays,
-		                   cache_max_steps, batched, batch_inds, batch_data_size, packed_info, (const uint32_t *)sample_cache,
-		                   t_starts, t_ends, ridx, bidx, gidx, (const float *)nullptr, (const float *)nullptr, (int64_t *)nullptr,
-		                   (float *)nullptr, (float *)nullptr);
-		NR3D_LAUNCH_CHECK();
-		return 0;
+	NR3D_CHECK(!samples || (rays_o && rays_d), "ray_marching_emit: samples need rays_o / rays_d");
+	hipStream_t st = (hipStream_t)stream;
+	{
+		prof::Scope ps(NR3D_PROF_MARCH, st);
+		if (sample_cache)   // filled by nr3d_ray_marching_count with the same rays and max_steps == cache_max_steps: a per-ray copy, the epilogue rides on it
+			hipLaunchKernelGGL(occ::k_emit_cached, dim3(div_up(n_rays, 4)), dim3(256), 0, st, n_rays, cache_max_steps, batched, batch_inds,
+			                   batch_data_size, packed_info, (const uint32_t *)sample_cache, t_starts, t_ends, ridx, bidx, gidx, rays_o, rays_d,
+			                   ridx64, deltas, samples);
+		else
+			launch_march(n_rays, rays_o, rays_d, t_min, t_max, roi, grid_res, grid_binary, type, step_size, max_step_size, dt_gamma, 0u,
+			             batched, batch_inds, batch_data_size, packed_info, nullptr, t_starts, t_ends, ridx, bidx, gidx, nullptr, st);
 	}
-	hipLaunchKernelGGL((occ::k_march<true, false>), dim3(div_up(n_rays, occ::kBlock)), dim3(occ::kBlock), 0, (hipStream_t)stream,
-	                   n_rays, rays_o, rays_d, t_min, t_max, roi, grid_res[0], grid_res[1], grid_res[2], grid_binary,
-	                   type, step_size, max_step_size, dt_gamma, 0u, batched, batch_inds, batch_data_size, packed_info,
-	                   (int32_t *)nullptr, t_starts, t_ends, ridx, bidx, gidx, (uint32_t *)nullptr);
 	NR3D_LAUNCH_CHECK();
-	return 0;
-}
-
-extern "C" int nr3d_ray_marching_emit_finished(uint32_t n_rays, const float *rays_o, const float *rays_d, int batched,
-                                               const int32_t *batch_inds, uint32_t batch_data_size, const int32_t *packed_info,
-                                               const void *sample_cache, uint32_t cache_max_steps, float *t_starts,
-                                               float *t_ends, int32_t *ridx, int32_t *bidx, int32_t *gidx, int64_t *ridx64,
-                                               float *deltas, float *samples, void *stream) {
-	if (n_rays == 0) return 0;
-	NR3D_CHECK(packed_info && sample_cache && t_starts && t_ends && ridx, "ray_marching_emit_finished: NULL tensor pointer");
-	NR3D_CHECK(!samples || (rays_o && rays_d), "ray_marching_emit_finished: samples need rays_o / rays_d");
-	prof::Scope ps(NR3D_PROF_MARCH, (hipStream_t)stream);
-	hipLaunchKernelGGL(occ::k_emit_cached, dim3(div_up(n_rays, 4)), dim3(256), 0, (hipStream_t)stream, n_rays, cache_max_steps,
-	                   batched, batch_inds, batch_data_size, packed_info, (const uint32_t *)sample_cache, t_starts, t_ends, ridx,
-	                   bidx, gidx, rays_o, rays_d, ridx64, deltas, samples);
-	NR3D_LAUNCH_CHECK();
+	if (!sample_cache && (ridx64 || deltas || samples))   // the second march writes the marcher's own outputs only: the epilogue follows it
+		return glue::launch_finish_samples(n_samples, rays_o, rays_d, ridx, t_starts, t_ends, ridx64, deltas, samples, st);
 	return 0;
 }
 
@@ -929,16 +916,13 @@ extern "C" int nr3d_dynamic_ray_marching_count(uint32_t n_rays, const float *ray
 	           (unsigned long long)n_slices, (unsigned long long)vol);
 	NR3D_CHECK(sample_cache && sample_cache_bytes >= nr3d_ray_marching_cache_bytes(n_rays, max_steps),
 	           "dynamic_ray_marching: needs the sample cache (nr3d_ray_marching_cache_bytes)");
-	int32_t *counts = (int32_t *)scan_tmp;
-	void *tiles = (char *)scan_tmp + (((uint64_t)n_rays * sizeof(int64_t) + 7) / 8) * 8;
-	// lanes per ray as in march_count (NR3D_OPT_MARCH_GROUP forces)
-	int group = n_rays <= 8192u ? 32 : (n_rays <= 32768u ? 16 : 1);
-	{ const int64_t v = opt::get(NR3D_OPT_MARCH_GROUP); if (v == 1 || v == 16 || v == 32 || v == 64) group = (int)v; }
+	const ScanTmp tmp = split_scan_tmp(scan_tmp, n_rays);
+	const int group = march_lanes(n_rays, true);
 	auto launch = [&](auto kern, int G) {
 		const dim3 grid = G == 1 ? dim3(div_up(n_rays, occ::kBlock)) : dim3((unsigned)div_up((uint64_t)n_rays * G, 256));
 		hipLaunchKernelGGL(kern, grid, dim3(G == 1 ? occ::kBlock : 256), 0, st, n_rays, rays_o, rays_d, t_min, t_max, roi, grid_res[0],
 		                   grid_res[1], grid_res[2], grid_dynamic, grid_static, ts_keyframes, (int)T, rays_ts, batch_inds, n_batches,
-		                   step_size, max_step_size, dt_gamma, max_steps, counts, rays_slice, (uint32_t *)sample_cache);
+		                   step_size, max_step_size, dt_gamma, max_steps, tmp.counts, rays_slice, (uint32_t *)sample_cache);
 	};
 	{
 		prof::Scope ps(NR3D_PROF_MARCH, st);
@@ -955,8 +939,7 @@ extern "C" int nr3d_dynamic_ray_marching_count(uint32_t n_rays, const float *ray
 		}
 	}
 	NR3D_LAUNCH_CHECK();
-	glue::PackWriter<int32_t, 1> w{counts, nullptr, nullptr, ridx_hit, pack_infos, packed_info};
-	return glue::compact_packs<int32_t, 1>(n_rays, w, totals, tiles, st);
+	return packs_from_counts(n_rays, tmp, packed_info, ridx_hit, pack_infos, totals, st);
 }
 
 extern "C" int nr3d_dynamic_ray_marching_emit(uint32_t n_rays, const float *rays_o, const float *rays_d,
@@ -1005,10 +988,9 @@ extern "C" int nr3d_march_composite_fwd(uint32_t n_rays, const float *rays_o, co
 	           "march_composite_fwd: needs the sample cache (nr3d_ray_marching_cache_bytes)");
 	NR3D_CHECK(packed_info && ridx_hit && pack_infos && t_starts && t_ends && ridx && deltas, "march_composite_fwd: NULL march output");
 	NR3D_CHECK(sigma && alphas && vw && mask && depth && (!rgb || rgb_out), "march_composite_fwd: NULL composite tensor");
-	if (int rc = march_count(n_rays, rays_o, rays_d, t_min, t_max, roi, grid_res, grid_binary, type, step_size, max_step_size, dt_gamma,
-	                         max_steps, 0, nullptr, 0u, packed_info, totals, scan_tmp, sample_cache, sample_cache_bytes, ridx_hit,
-	                         pack_infos, stream))
-		return rc;
+	NR3D_TRY(nr3d_ray_marching_count(n_rays, rays_o, rays_d, t_min, t_max, roi, grid_res, grid_binary, type, step_size, max_step_size, dt_gamma,
+	                                 max_steps, 0, nullptr, 0u, packed_info, totals, scan_tmp, sample_cache, sample_cache_bytes, 1, ridx_hit,
+	                                 pack_infos, stream));
 	return pk::launch_emit_composite_rays_fwd(n_rays, packed_info, sample_cache, max_steps, rays_o, rays_d, t_starts, t_ends, ridx, gidx, ridx64,
 	                                          deltas, samples, sigma, sigma_rows, rgb, early_stop_eps, alpha_thre, normalize_depth, alphas, vw,
 	                                          mask, depth, rgb_out, st);
@@ -1028,11 +1010,27 @@ extern "C" int nr3d_march_composite_bwd(uint32_t n_rays, const int32_t *packed_i
 	                                     grad_sigma, (hipStream_t)stream);
 }
 
-static int forest_march_check(const nr3d_forest_meta_t *forest, const void *a, const void *b, const void *c, const void *d,
-                              const void *e, const void *f, const void *g, const void *h, const void *grid) {
+// one launch of k_forest_march after the argument checks both passes share.  Count pass (packed_info NULL): counts.  Emit pass (packed_info
+// given; max_steps unused): the samples to their packed rows.  Outputs a pass does not write are NULL.
+static int launch_forest_march(const nr3d_forest_meta_t *forest, uint32_t n_rays, const float *rays_o, const float *rays_d,
+                               const float *t_min, const float *t_max, const int32_t *seg_block_inds, const float *seg_entries,
+                               const float *seg_exits, const int32_t *seg_pack_infos, const int32_t grid_res[3],
+                               const uint8_t *grid_binary, float step_size, float max_step_size, float dt_gamma, uint32_t max_steps,
+                               const int32_t *packed_info, int32_t *counts, float *t_starts, float *t_ends, int32_t *ridx,
+                               int32_t *blidx, int32_t *gidx, hipStream_t st) {
 	NR3D_CHECK(forest && forest->block_ks, "forest_ray_marching: forest meta or block_ks is NULL");
-	NR3D_CHECK(a && b && c && d && h && grid, "forest_ray_marching: NULL tensor pointer");
-	(void)e; (void)f; (void)g;       // segment arrays may be empty (NULL) when no ray crosses a block
+	// the segment arrays may be empty (NULL) when no ray crosses a block
+	NR3D_CHECK(rays_o && rays_d && t_min && t_max && seg_pack_infos && grid_binary, "forest_ray_marching: NULL tensor pointer");
+	const occ::f3 wo = {forest->world_origin[0], forest->world_origin[1], forest->world_origin[2]};
+	const occ::f3 wb = {forest->world_block_size[0], forest->world_block_size[1], forest->world_block_size[2]};
+	auto launch = [&](auto kern) {
+		hipLaunchKernelGGL(kern, dim3(div_up(n_rays, occ::kBlock)), dim3(occ::kBlock), 0, st, forest->block_ks, wo, wb, n_rays, rays_o, rays_d,
+		                   t_min, t_max, seg_block_inds, seg_entries, seg_exits, seg_pack_infos, grid_res[0], grid_res[1], grid_res[2],
+		                   grid_binary, step_size, max_step_size, dt_gamma, max_steps, packed_info, counts, t_starts, t_ends, ridx, blidx, gidx);
+	};
+	if (packed_info) launch(occ::k_forest_march<true>);
+	else launch(occ::k_forest_march<false>);
+	NR3D_LAUNCH_CHECK();
 	return 0;
 }
 
@@ -1046,20 +1044,12 @@ extern "C" int nr3d_forest_ray_marching_count(const nr3d_forest_meta_t *forest, 
 	NR3D_CHECK(total_steps && scan_tmp, "forest_ray_marching: NULL scratch pointer");
 	hipStream_t st = (hipStream_t)stream;
 	if (n_rays == 0) { NR3D_HIP_CHECK(hipMemsetAsync(total_steps, 0, sizeof(int64_t), st)); return 0; }
-	if (int rc = forest_march_check(forest, rays_o, rays_d, t_min, t_max, seg_block_inds, seg_entries, seg_exits,
-	                                seg_pack_infos, grid_binary)) return rc;
 	NR3D_CHECK(packed_info, "forest_ray_marching: NULL packed_info");
-	int32_t *counts = (int32_t *)scan_tmp;
-	void *tiles = (char *)scan_tmp + (((uint64_t)n_rays * sizeof(int64_t) + 7) / 8) * 8;
-	const occ::f3 wo = {forest->world_origin[0], forest->world_origin[1], forest->world_origin[2]};
-	const occ::f3 wb = {forest->world_block_size[0], forest->world_block_size[1], forest->world_block_size[2]};
-	hipLaunchKernelGGL((occ::k_forest_march<false>), dim3(div_up(n_rays, occ::kBlock)), dim3(occ::kBlock), 0, st, forest->block_ks,
-	                   wo, wb, n_rays, rays_o, rays_d, t_min, t_max, seg_block_inds, seg_entries, seg_exits, seg_pack_infos,
-	                   grid_res[0], grid_res[1], grid_res[2], grid_binary, step_size, max_step_size, dt_gamma, max_steps,
-	                   (const int32_t *)nullptr, counts, (float *)nullptr, (float *)nullptr, (int32_t *)nullptr,
-	                   (int32_t *)nullptr, (int32_t *)nullptr);
-	NR3D_LAUNCH_CHECK();
-	return scan::pack_infos_from_counts<int32_t, int32_t>(n_rays, counts, packed_info, total_steps, tiles, st);
+	const ScanTmp tmp = split_scan_tmp(scan_tmp, n_rays);
+	NR3D_TRY(launch_forest_march(forest, n_rays, rays_o, rays_d, t_min, t_max, seg_block_inds, seg_entries, seg_exits, seg_pack_infos, grid_res,
+	                             grid_binary, step_size, max_step_size, dt_gamma, max_steps, nullptr, tmp.counts, nullptr, nullptr, nullptr,
+	                             nullptr, nullptr, st));
+	return packs_from_counts(n_rays, tmp, packed_info, nullptr, nullptr, total_steps, st);
 }
 
 extern "C" int nr3d_forest_ray_marching_emit(const nr3d_forest_meta_t *forest, uint32_t n_rays, const float *rays_o,
@@ -1071,15 +1061,8 @@ extern "C" int nr3d_forest_ray_marching_emit(const nr3d_forest_meta_t *forest, u
                                              float *t_starts, float *t_ends, int32_t *ridx, int32_t *blidx, int32_t *gidx,
                                              void *stream) {
 	if (n_rays == 0) return 0;
-	if (int rc = forest_march_check(forest, rays_o, rays_d, t_min, t_max, seg_block_inds, seg_entries, seg_exits,
-	                                seg_pack_infos, grid_binary)) return rc;
 	NR3D_CHECK(packed_info && t_starts && t_ends && ridx && blidx, "forest_ray_marching: NULL output pointer");
-	const occ::f3 wo = {forest->world_origin[0], forest->world_origin[1], forest->world_origin[2]};
-	const occ::f3 wb = {forest->world_block_size[0], forest->world_block_size[1], forest->world_block_size[2]};
-	hipLaunchKernelGGL((occ::k_forest_march<true>), dim3(div_up(n_rays, occ::kBlock)), dim3(occ::kBlock), 0, (hipStream_t)stream,
-	                   forest->block_ks, wo, wb, n_rays, rays_o, rays_d, t_min, t_max, seg_block_inds, seg_entries, seg_exits,
-	                   seg_pack_infos, grid_res[0], grid_res[1], grid_res[2], grid_binary, step_size, max_step_size, dt_gamma,
-	                   0u, packed_info, (int32_t *)nullptr, t_starts, t_ends, ridx, blidx, gidx);
-	NR3D_LAUNCH_CHECK();
-	return 0;
+	return launch_forest_march(forest, n_rays, rays_o, rays_d, t_min, t_max, seg_block_inds, seg_entries, seg_exits, seg_pack_infos, grid_res,
+	                           grid_binary, step_size, max_step_size, dt_gamma, 0u, packed_info, nullptr, t_starts, t_ends, ridx, blidx, gidx,
+	                           (hipStream_t)stream);
 }

@@ -1,5 +1,6 @@
-// nr3d_lib_amd/csrc/pack_launch.h -- launchers of pack_ops.hip kernels that another translation unit chains behind its own
-// (occ_grid.hip: nr3d_march_composite_fwd / _bwd enqueue march -> scan -> emit -> composite without the host in between).
+// nr3d_lib_amd/csrc/pack_launch.h -- launchers of kernels that another translation unit chains behind its own, without the host in
+// between.  pack_ops.hip's composites: occ_grid.hip (nr3d_march_composite_fwd / _bwd enqueue march -> scan -> emit -> composite) and
+// neus_composite.hip.  ray_glue.hip's per-sample epilogue: occ_grid.hip (nr3d_ray_marching_emit enqueues it behind its second march).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,4 +37,13 @@ int launch_neus_composite_packs_bwd(uint32_t P, const float *alphas, const float
                                     float *grad_nablas, hipStream_t st);
 
 }  // namespace pk
+
+namespace glue {
+
+// the marcher's per-sample epilogue over S packed rows (occgrid_raymarch.py:87-112): ridx64 = (int64) ridx, deltas = t_ends - t_starts,
+// samples [S, 3] = fma(rays_d[ridx], t_starts, rays_o[ridx]) (torch.addcmul); any output may be NULL
+int launch_finish_samples(uint64_t S, const float *rays_o, const float *rays_d, const int32_t *ridx, const float *t_starts,
+                          const float *t_ends, int64_t *ridx64, float *deltas, float *samples, hipStream_t st);
+
+}  // namespace glue
 }  // namespace nr3d

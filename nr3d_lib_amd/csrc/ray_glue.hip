@@ -5,7 +5,8 @@
 // those chains were ~110 launches and 20 % of the GPU time of an iteration (profiles/r02z_full_loop_kernel_stats.txt);
 // here each chain is one to three launches:
 //   nr3d_tau_to_alpha_fwd / _bwd     alpha = 1 - exp(-sigma * delta) and its gradient: one launch each way
-//   nr3d_march_finish_samples        per sample: int64 ray index, delta = t1 - t0, position o + d * t0
+//   glue::launch_finish_samples      per sample: int64 ray index, delta = t1 - t0, position o + d * t0 (pack_launch.h: enqueued
+//                                    by nr3d_ray_marching_emit behind its second march)
 //   nr3d_prune_compact_packs         kept-sample counts -> new begin of every pack, packs that keep >= 1 sample
 //                                    compacted (index, int64 pack_infos), + both totals
 //   nr3d_prune_compact_samples       kept samples of every pack moved to their compact positions: sample index, depth,
@@ -14,6 +15,7 @@
 #include "common.h"
 #include "scan.h"
 #include "compact.h"
+#include "pack_launch.h"
 #include "../../include/nr3d_hip.h"
 
 namespace nr3d {
@@ -113,13 +115,12 @@ extern "C" int nr3d_tau_to_alpha_bwd(uint64_t S, const float *sigma, const float
 	return 0;
 }
 
-extern "C" int nr3d_march_finish_samples(uint64_t S, const float *rays_o, const float *rays_d, const int32_t *ridx,
-                                         const float *t_starts, const float *t_ends, int64_t *ridx64, float *deltas,
-                                         float *samples, void *stream) {
+int nr3d::glue::launch_finish_samples(uint64_t S, const float *rays_o, const float *rays_d, const int32_t *ridx, const float *t_starts,
+                                      const float *t_ends, int64_t *ridx64, float *deltas, float *samples, hipStream_t st) {
 	if (S == 0) return 0;
-	NR3D_CHECK(ridx && t_starts && (!deltas || t_ends) && (!samples || (rays_o && rays_d)), "march_finish_samples: NULL tensor pointer");
-	hipLaunchKernelGGL(glue::k_finish_samples, dim3((uint32_t)div_up(S, (uint64_t)glue::kBlock)), dim3(glue::kBlock), 0,
-	                   (hipStream_t)stream, S, rays_o, rays_d, ridx, t_starts, t_ends, ridx64, deltas, samples);
+	NR3D_CHECK(ridx && t_starts && (!deltas || t_ends) && (!samples || (rays_o && rays_d)), "ray_marching_emit: NULL tensor pointer");
+	hipLaunchKernelGGL(glue::k_finish_samples, dim3((uint32_t)div_up(S, (uint64_t)glue::kBlock)), dim3(glue::kBlock), 0, st, S, rays_o,
+	                   rays_d, ridx, t_starts, t_ends, ridx64, deltas, samples);
 	NR3D_LAUNCH_CHECK();
 	return 0;
 }

@@ -49,7 +49,7 @@ def test_lookup_modes():
 def test_header_and_abi_table_agree():
     from nr3d_lib_amd import _abi
     header = open(os.path.join(ROOT, "include", "nr3d_hip.h")).read()
-    assert int(re.search(r"#define\s+NR3D_ABI_VERSION\s+(\d+)", header).group(1)) == 29 == _abi.ABI_VERSION
+    assert int(re.search(r"#define\s+NR3D_ABI_VERSION\s+(\d+)", header).group(1)) == 30 == _abi.ABI_VERSION
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import gen_abi

@@ -131,7 +131,7 @@ def test_abi_and_switch():
     from nr3d_lib_amd import _abi
     from nr3d_lib_amd.models.spatial import forest as F
     header = open(os.path.join(ROOT, "include", "nr3d_hip.h")).read()
-    assert int(re.search(r"#define\s+NR3D_ABI_VERSION\s+(\d+)", header).group(1)) == 29 == _abi.ABI_VERSION      # additions keep the number
+    assert int(re.search(r"#define\s+NR3D_ABI_VERSION\s+(\d+)", header).group(1)) == 30 == _abi.ABI_VERSION      # additions keep the number
     head = ["ptr", "uint32_t", "ptr", "ptr", "ptr", "float", "ptr", "float"]
     assert _abi.SIGNATURES["nr3d_forest_ray_test_count"] == ("int", head + ["ptr", "ptr"])
     assert _abi.SIGNATURES["nr3d_forest_ray_test_emit"] == ("int", head + ["ptr", "ptr", "uint64_t", "ptr", "ptr", "ptr", "ptr"])

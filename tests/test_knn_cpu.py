@@ -219,7 +219,7 @@ def test_header_and_table_have_the_entries():
         assert ret == "int" and len(args) == nargs, (name, args)
     assert _abi.SIGNATURES["nr3d_knn_points"][1][:4] == ["ptr"] * 4 and _abi.SIGNATURES["nr3d_knn_points"][1][4:7] == ["uint64_t"] * 3
     assert _abi.SIGNATURES["nr3d_knn_launch_plan"][1] == ["uint64_t", "uint64_t", "uint32_t", "uint32_t"]
-    assert _abi.ABI_VERSION == 29
+    assert _abi.ABI_VERSION == 30
 
 
 def test_launch_plan_is_the_documented_rule(hiplib):

@@ -191,7 +191,7 @@ def test_ply_empty_and_errors(tmp_path):
 def test_header_and_abi():
     from nr3d_lib_amd import _abi
     header = open(os.path.join(ROOT, "include", "nr3d_hip.h")).read()
-    assert int(re.search(r"#define\s+NR3D_ABI_VERSION\s+(\d+)", header).group(1)) == 29 == _abi.ABI_VERSION
+    assert int(re.search(r"#define\s+NR3D_ABI_VERSION\s+(\d+)", header).group(1)) == 30 == _abi.ABI_VERSION
     code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     for name, n_args in (("nr3d_marching_cubes_count", 8), ("nr3d_marching_cubes_emit", 11), ("nr3d_marching_cubes_scratch_bytes", 3)):
         assert re.search(r"\b%s\s*\(" % name, code), name

@@ -134,7 +134,7 @@ def test_restatement_equals_the_torch_expression_on_the_lattice(cols):
 def test_header_and_table_declare_the_entries():
     from nr3d_lib_amd import _abi
     header = open(os.path.join(ROOT, "include", "nr3d_hip.h")).read()
-    assert int(re.search(r"#define\s+NR3D_ABI_VERSION\s+(\d+)", header).group(1)) == 29 == _abi.ABI_VERSION      # additions keep the number
+    assert int(re.search(r"#define\s+NR3D_ABI_VERSION\s+(\d+)", header).group(1)) == 30 == _abi.ABI_VERSION      # additions keep the number
     fwd, bwd = "nr3d_mlp_lipschitz_normalize", "nr3d_mlp_lipschitz_normalize_backward"
     assert re.search(r"\bint\s+" + fwd + r"\s*\(", header) and re.search(r"\bint\s+" + bwd + r"\s*\(", header)
     assert _abi.SIGNATURES[fwd] == ("int", ["uint32_t", "ptr", "ptr", "ptr", "int", "ptr", "ptr", "ptr"])

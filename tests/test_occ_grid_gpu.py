@@ -227,6 +227,101 @@ def test_sample_cache_and_second_march_agree(oracle, dev, monkeypatch):
         assert_equal(b, r, name=f"two-march/{n}")
 
 
+@pytest.mark.parametrize("batched", [False, True], ids=["single", "batched"])
+def test_finished_without_cache_equals_cached(oracle, dev, monkeypatch, batched):
+    """ray_marching_finished with the sample cache (the epilogue rides on the cached emit) and without it (second march, then the
+    per-sample epilogue enqueued by the same library call): every entry of the two dicts is bit-identical -- samples too, both kernels
+    compute fma(d, t0, o) -- and the hit rays are the oracle's.  Batched: rays whose batch index is -1 get no sample on either route."""
+    from nr3d_lib_amd.bindings import _occ_grid
+    o, d, near, far = pinhole_rays(16, seed=5)
+    n = o.shape[0]
+    g = grids((32, 32, 32), 9)
+    grid, roi, bi, skipped = g["shell"], ROI, None, []
+    if batched:
+        grid, roi = np.stack([g["shell"], g["random"]]), np.stack([ROI, ROI])
+        bi = np.repeat(np.array([0, 1], np.int32), n // 2)
+        skipped = [7 * 16 + 8, 8 * 16 + 7, 9 * 16 + 8]                          # central rays, one of grid 0 and two of grid 1
+        full = oracle.ray_marching(o, d, near, far, roi, grid, 0, 0.02, 1e10, 0.0, 128, True, batch_inds=bi.copy(), batch_data_size=None)
+        assert (full[0][skipped, 1] > 0).all(), "the skipped rays would have had samples"
+        bi[skipped] = -1
+    t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    args = (t(o), t(d), t(near), t(far), t(roi), t(grid), _occ_grid.AABB, 0.02, 1e10, 0.0, 128, True)
+    kw = dict(batch_inds=t(bi)) if batched else {}
+    assert 0 < _occ_grid._cache_bytes(n, 128) <= _occ_grid.SAMPLE_CACHE_MAX_BYTES
+    cached = _occ_grid.ray_marching_finished(*args, **kw)
+    monkeypatch.setattr(_occ_grid, "SAMPLE_CACHE_MAX_BYTES", 0)
+    twice = _occ_grid.ray_marching_finished(*args, **kw)
+    assert list(cached) == list(twice) == ["n_hit", "ridx_hit", "pack_infos", "t_starts", "t_ends", "ridx", "deltas", "samples", "bidx", "gidx"]
+    assert cached["n_hit"] == twice["n_hit"] > 0
+    for name in ("ridx_hit", "pack_infos", "t_starts", "t_ends", "ridx", "deltas", "samples", "gidx") + (("bidx",) if batched else ()):
+        x, y = cached[name], twice[name]
+        assert x.dtype == y.dtype and x.shape == y.shape, name
+        assert torch.equal(x, y), name
+    ref = oracle.ray_marching(o, d, near, far, roi, grid, 0, 0.02, 1e10, 0.0, 128, True, batch_inds=bi, batch_data_size=None)
+    hit = np.nonzero(ref[0][:, 1])[0]
+    for out in (cached, twice):
+        assert_equal(out["ridx_hit"], hit, "ridx_hit")
+        assert_equal(out["pack_infos"], ref[0][hit].astype(np.int64), "pack_infos")
+        assert_equal(out["ridx"], ref[3].astype(np.int64), "ridx")
+        if batched:
+            assert not np.isin(skipped, out["ridx_hit"].cpu().numpy()).any() and not np.isin(skipped, out["ridx"].cpu().numpy()).any()
+            assert out["bidx"].dtype == torch.int32 and torch.equal(out["bidx"], t(bi)[out["ridx"]])
+        else:
+            assert out["bidx"] is None
+
+
+@pytest.mark.parametrize("n", [1025, 34817])
+def test_count_entry_modes(dev, n):
+    """nr3d_ray_marching_count called directly in both modes at a size of the single-workgroup scan and one of the three-launch scan: each
+    mode writes the words it owns and no other, both give the same packed_info, n_rays == 0 zeroes the mode's own words, and with_hit_rays
+    without its outputs is refused on the host before anything is launched"""
+    import ctypes as C
+    import scan_ref as R
+    import test_scan_compact_gpu as SC
+    from nr3d_lib_amd import _hip as H
+    from nr3d_lib_amd.bindings import _occ_grid as G
+    rays_o, rays_d, t_min, t_max, roi, grid = SC._march_args(dev, n)
+    res = (C.c_int32 * 3)(*grid.shape)
+    tmp = SC._scan_tmp(n, dev)
+    MARK = SC.MARK
+
+    def count(n_rays, with_hit_rays, hit_outputs=True):
+        packed_info = torch.full((n, 2), MARK, dtype=torch.int32, device=dev)
+        ridx_hit = torch.full((n,), MARK, dtype=torch.int64, device=dev)
+        pack_infos = torch.full((n, 2), MARK, dtype=torch.int64, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, pin_memory=True).fill_(MARK)
+        rc = H.lib().nr3d_ray_marching_count(
+            n_rays, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid), int(G.AABB), SC.MARCH_STEP,
+            SC.MARCH_STEP, 0.0, SC.MARCH_MAX_STEPS, False, None, 0, H.ptr(packed_info), H.ptr(totals), H.ptr(tmp), None, 0, with_hit_rays,
+            H.ptr(ridx_hit) if hit_outputs else None, H.ptr(pack_infos) if hit_outputs else None, H.stream_of(tmp))
+        torch.cuda.synchronize(dev)
+        return rc, packed_info, ridx_hit, pack_infos, totals.tolist()
+
+    rc, pi_hit, ridx_hit, pack_infos, totals = count(n, 1)
+    assert rc == 0
+    counts = pi_hit[:, 1].cpu().numpy().astype(np.int64)
+    SC.assert_mixed(counts)
+    want_begin, want_idx, want_pi, want_tot = R.compact_packs(counts)
+    S, n_hit = want_tot
+    assert tuple(totals) == (S, n_hit) and 0 < n_hit < n
+    SC._eq(ridx_hit[:n_hit], want_idx)
+    SC._eq(pack_infos[:n_hit], want_pi)
+
+    rc, pi_plain, ridx_hit, pack_infos, totals = count(n, 0)
+    assert rc == 0 and totals == [S, MARK]                            # one word: the second is not this mode's
+    assert torch.equal(pi_plain, pi_hit)
+    assert bool((ridx_hit == MARK).all()) and bool((pack_infos == MARK).all())          # ignored
+
+    rc, packed_info, _, _, totals = count(0, 0)
+    assert rc == 0 and totals == [0, MARK] and bool((packed_info == MARK).all())
+    rc, packed_info, _, _, totals = count(0, 1, hit_outputs=False)    # the outputs are required only when there are rays
+    assert rc == 0 and totals == [0, 0] and bool((packed_info == MARK).all())
+
+    rc, packed_info, _, _, totals = count(n, 1, hit_outputs=False)
+    assert rc != 0 and b"ray_marching_count" in H.lib().nr3d_last_error()
+    assert totals == [MARK, MARK] and bool((packed_info == MARK).all())                 # a host-side check: nothing was launched
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # occupancy-value grid maintenance (SURVEY section 8f, rank 2)
 # ---------------------------------------------------------------------------------------------------------------------

@@ -364,8 +364,8 @@ FINISHED_SIZES = [1024, 1025, 4096, 8192, 16384, 32768, 32769, 34817]
 
 @pytest.mark.parametrize("n", FINISHED_SIZES)
 def test_march_finished_compact_i32(dev, n):
-    """compact<int32, 1> with the int32 table: nr3d_ray_marching_count_finished directly (the binding keeps packed_info to itself), then
-    the binding end to end"""
+    """compact<int32, 1> with the int32 table: nr3d_ray_marching_count with with_hit_rays = 1 directly (the binding keeps packed_info to
+    itself), then the binding end to end"""
     from nr3d_lib_amd import _hip as H
     from nr3d_lib_amd.bindings import _occ_grid as G
     rays_o, rays_d, t_min, t_max, roi, grid = args = _march_args(dev, n)
@@ -376,9 +376,9 @@ def test_march_finished_compact_i32(dev, n):
     totals = H.host_i64(2, dev)
     tmp = _scan_tmp(n, dev)
     res = (C.c_int32 * 3)(*grid.shape)
-    H.check(H.lib().nr3d_ray_marching_count_finished(
+    H.check(H.lib().nr3d_ray_marching_count(
         n, H.ptr(rays_o), H.ptr(rays_d), H.ptr(t_min), H.ptr(t_max), H.ptr(roi), res, H.ptr(grid), int(G.AABB), MARCH_STEP, MARCH_STEP, 0.0,
-        MARCH_MAX_STEPS, False, None, 0, H.ptr(packed_info), H.ptr(ridx_hit), H.ptr(pack_infos), H.ptr(totals), H.ptr(tmp), None, 0,
+        MARCH_MAX_STEPS, False, None, 0, H.ptr(packed_info), H.ptr(totals), H.ptr(tmp), None, 0, 1, H.ptr(ridx_hit), H.ptr(pack_infos),
         H.stream_of(tmp)))
     S, n_hit = H.wait_i64(totals, dev)
     torch.cuda.synchronize(dev)
