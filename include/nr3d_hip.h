@@ -1364,6 +1364,64 @@ int nr3d_forest_ray_test_emit(const nr3d_forest_meta_t *forest, uint32_t n_rays,
                               const int64_t *begin_all, uint64_t S, int64_t *seg_block_inds, float *seg_entries, float *seg_exits,
                               void *stream);
 
+/* ---- pixel importance sampling on accumulated error maps (csrc/importance.hip; ErrorMap / ImpSampler of
+ * nr3d_lib/models/importance.py, which runs every step below as a chain of torch ops).  Additions that touch no existing entry: the ABI
+ * number stays.  All arithmetic is float32 with one rounding per operation (no contraction, IEEE division), in the order written here.
+ *
+ * _sample: one launch, one lane per sample s of n_samples.  u_img, u_x, u_y float32 [n_samples] (the caller clamps them to
+ *   [1e-6, 1 - 1e-6]); u_img is read for sampled frames only.  lower(row, len, u) = min(the first k with row[k] >= u, len - 1):
+ *   searchsorted(right=False) with a clamp that no valid CDF reaches and that keeps every read inside its row.
+ *     s <  n_uniform:  i = min(int(u_img * float(n_images)), n_images - 1),  xy = (u_x, u_y)
+ *     s >= n_uniform:  the map is the last of maps[0 .. n_maps) with first <= s (maps[0].first == n_uniform, firsts non-decreasing:
+ *       a map whose segment is empty shares its first with the next one);
+ *       i = lower(cdf_img, n_images, u_img);  h = lower(cdf_y[i], res_y, u_y);  prev = h > 0 ? cdf_y[i, h-1] : 0;
+ *       y = ((u_y - prev) / (cdf_y[i, h] - prev) + float(h)) / float(res_y);  w, x the same way from cdf_x_cond_y[i, h] and u_x.
+ *   frame_mode: _SAMPLED as above; _CONST: i = frame_const for every sample; _TENSOR: i = frame_ind[s] (int64 [n_samples]); negative
+ *     frames count from the end as torch's do, then clamp to [0, n_images).
+ *   out_i int64 [n_samples], out_xy float32 [n_samples, 2] (x first): either may be NULL and is then not computed; fully written.
+ *   maps: a HOST array of n_maps <= NR3D_IMPORTANCE_MAX_MAPS entries (copied into the launch), all maps with n_images images.
+ *
+ * _update: error_map float32 [n_images, res_y, res_x] += the bilinear splat of val float32 [n] at xy float32 [n, 2] of frame frame_ind[s]
+ *   (int64 [n]) or, frame_ind NULL, frame_const.  Per sample: wf = x * float(res_x), w = trunc(wf), w_w = wf - float(w), THEN w is
+ *   clamped to [0, res_x - 2]; the same in y; contributions ((1-w_h)(1-w_w)) val -> (h, w), (w_h (1-w_w)) val -> (h+1, w),
+ *   ((1-w_h) w_w) val -> (h, w+1), (w_h w_w) val -> (h+1, w+1).  Each contribution c, clamped to |c| <= 2^16, is added as
+ *   llrint(double(c) * 2^32) to acc (int64 [n_images, res_y, res_x], ALL ZERO on entry) with a 64-bit integer atomic; a second launch
+ *   takes every touched cell out of acc with an exchange against 0 and adds float(double(sum) * 2^-32) to the map's cell, one writer
+ *   per cell.  acc is all zero again on return; the map's bytes do not depend on the order of arrival.  Dropped without any write: a
+ *   frame outside [0, n_images), a non-finite x, y, val or product with the resolution, val < 0.
+ *   Refused: n > NR3D_IMPORTANCE_UPDATE_CHUNK (the caller splits), res_y < 2 or res_x < 2.
+ *
+ * _construct_cdf: three launches, no atomics.  scan(v [L]): 64-element chunks in order; inside a chunk the Kogge-Stone inclusive scan
+ *   (steps 1, 2, ... 32: v[j] += v[j - step] for j >= step, all j at once), then the carry -- the previous chunk's last result, 0.0f
+ *   before the first -- is added to every element of the chunk.  total = the result at the row's LAST ELEMENT (so norm()'s last value is a, not a ratio of two trees).
+ *   norm(c [L], total) [k] = (a * c[k]) / total + b * (float(k + 1) / float(L)),  a = one_minus_min_pdf, b = min_pdf.
+ *     e = error_map[n, h, :], clamped from above to max_pdf when has_max_pdf (the clamped value is stored back; with `clean` 0 is);
+ *     c = scan(e + 1e-10f): cdf_x_cond_y[n, h] = norm(c, total), pdf_y[n, h] = total;
+ *     cdf_y[n] = norm(scan(pdf_y[n]), total), pdf_img[n] = total;  cdf_img = norm(scan(pdf_img), total).
+ *   pdf_y float32 [n_images, res_y] and pdf_img float32 [n_images] are the caller's workspace; all outputs fully written. */
+#define NR3D_IMPORTANCE_MAX_MAPS 8
+#define NR3D_IMPORTANCE_UPDATE_CHUNK 32768
+#define NR3D_IMPORTANCE_FRAME_SAMPLED 0
+#define NR3D_IMPORTANCE_FRAME_CONST 1
+#define NR3D_IMPORTANCE_FRAME_TENSOR 2
+typedef struct nr3d_importance_map {
+	const float *cdf_img;         /* [n_images] */
+	const float *cdf_y;           /* [n_images, res_y] */
+	const float *cdf_x_cond_y;    /* [n_images, res_y, res_x] */
+	uint32_t res_y;
+	uint32_t res_x;
+	uint32_t first;               /* the first sample of this map's segment */
+	uint32_t reserved;
+} nr3d_importance_map_t;
+int nr3d_importance_sample(uint32_t n_samples, uint32_t n_images, uint32_t n_uniform, int n_maps, const nr3d_importance_map_t *maps,
+                           const float *u_img, const float *u_x, const float *u_y, int frame_mode, int64_t frame_const,
+                           const int64_t *frame_ind, int64_t *out_i, float *out_xy, void *stream);
+int nr3d_importance_update(uint32_t n_samples, uint32_t n_images, uint32_t res_y, uint32_t res_x, int64_t frame_const,
+                           const int64_t *frame_ind, const float *xy, const float *val, float *error_map, int64_t *acc, void *stream);
+int nr3d_importance_construct_cdf(uint32_t n_images, uint32_t res_y, uint32_t res_x, float *error_map, float one_minus_min_pdf,
+                                  float min_pdf, int has_max_pdf, float max_pdf, int clean, float *cdf_x_cond_y, float *cdf_y,
+                                  float *cdf_img, float *pdf_y, float *pdf_img, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
